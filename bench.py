@@ -2,6 +2,14 @@
 """bench.py -- the headline benchmark of the Oriented RepPoints dense-head hot path on MI355X.
 
     python bench.py --gpus N --steps K --warmup W        (N > 1: launched by torch.distributed.run, one rank per GPU)
+    python bench.py ... --full                           (+ every secondary measurement described below)
+    python bench.py ... --dump-outputs DIR               (+ the last timed step's detections as DIR/*.npy)
+
+A plain run measures the headline figure only: set-up, the reproducibility check that picks the library mode, W warm-up
+steps and the K timed steps of the throughput mode (falling back to one replay at a time, then to eager steps, as
+below), then the JSON line.  Everything else in this docstring -- the eager and one-at-a-time loops next to the
+throughput mode, `roofline`, `nms`, `nms_batched_16_images`, `per_op_us`, `cpu_baseline`, `train`, `other_configs` --
+is measured with `--full` only.
 
 Workload (BASELINE.json configs[1]): OrientedRepPoints R-50 FPN inference, 1024x1024 DOTA patch, 15 classes,
 bs = 1 per GPU.  A "step" is one full `simple_test`: stock PyTorch-ROCm ResNet-50 + FPN convolutions (eval BatchNorm +
@@ -610,6 +618,165 @@ def _sync(dev):
         torch.cuda.synchronize()
 
 
+DUMP_LIMIT_BYTES = 64 << 20
+
+
+def dump_outputs(out_dir, results):
+    """What the timed path hands its caller for the last timed step -- per image, per class, the [k, 27] float32 rows of
+    rbbox2result (the nine points, the four min-area-rect corners, the score) -- as out_dir/image<b>_class<cc>.npy."""
+    arrays = {'image%d_class%02d' % (b, c): np.ascontiguousarray(a, dtype=np.float64 if a.dtype == np.float64 else np.float32)
+              for b, per_class in enumerate(results) for c, a in enumerate(per_class)}
+    total = sum(a.nbytes for a in arrays.values())
+    if total > DUMP_LIMIT_BYTES:
+        raise SystemExit('bench.py: --dump-outputs would write %d bytes (limit %d)' % (total, DUMP_LIMIT_BYTES))
+    os.makedirs(out_dir, exist_ok=True)
+    for name, a in arrays.items():
+        np.save(os.path.join(out_dir, name + '.npy'), a)
+
+
+def _detections(res):
+    return int(sum(sum(len(c) for c in r) for r in res))
+
+
+def _all_ranks_ok(ok, dev, dist):
+    """Every rank takes a path, or none does."""
+    if dist is None:
+        return ok
+    flag = torch.tensor([ok], dtype=torch.int32, device=dev)
+    dist.all_reduce(flag, op=dist.ReduceOp.MIN)
+    return int(flag.item())
+
+
+def _timed_loop(dev, dist, run):
+    """The K timed steps (`run()` does all K and returns the last step's results), bracketed by synchronize + barrier;
+    (seconds, MAX over ranks; the last step's results)."""
+    torch.cuda.synchronize()
+    if dist is not None:
+        dist.barrier()
+    t0 = time.perf_counter()
+    last = run()
+    torch.cuda.synchronize()
+    if dist is not None:
+        dist.barrier()
+    elapsed = time.perf_counter() - t0
+    if dist is not None:
+        t = torch.tensor([elapsed], dtype=torch.float64, device=dev)
+        dist.all_reduce(t, op=dist.ReduceOp.MAX)
+        elapsed = float(t.item())
+    return elapsed, last
+
+
+def _config_line(args, world, in_flight):
+    return {'workload': '%s: OrientedRepPoints %s FPN inference, %dx%d patch, 15 classes, '
+                        'bs=%d/GPU, nms_pre=2000, score_thr=0.05, rnms iou_thr=0.4, max_per_img=2000; '
+                        'random-init weights, head biases calibrated to ~%d dets/img'
+                        % ('configs[1]' if (args.model, IMG, args.batch) == ('r50', 1024, 1) else
+                           ('configs[3] per-GPU load' if (args.model, args.batch) == ('r101', 2) else 'variant'),
+                           MODEL_LABEL[args.model], IMG, IMG, args.batch, TARGET_DETS),
+            'global_batch': args.batch * world, 'parallelism': 'replicas x%d (image-parallel, no collective)' % world,
+            'images_in_flight_per_gpu': in_flight}
+
+
+def main_headline(args, model, img, metas, rank, world, dev, dist):
+    """A plain run (no --full): the headline figure and nothing else.  The same choices as the full run -- library mode
+    from the reproducibility check, then the throughput mode, else one replay at a time, else eager steps, each accepted
+    only when its warm-up returns the eager step's detection count -- but only the path that `value` reports is timed."""
+    def step():
+        with torch.no_grad():
+            return model.simple_test_batch(img, metas)
+
+    def same(ra, rb):
+        return all(a.shape == b.shape and np.array_equal(a, b) for r, q in zip(ra, rb) for a, b in zip(r, q))
+
+    model.bbox_head.tower_streams = False                   # the launch sequence of the throughput mode's graphs
+    for _ in range(2):
+        res = step()
+    step_reproducible = all(same(res, step()) for _ in range(3))
+    library_deterministic_mode = False
+    if not step_reproducible:                               # as in the full run: the library's reproducible solvers only
+        torch.backends.cudnn.deterministic = True
+        library_deterministic_mode = True
+        for _ in range(3):
+            res = step()
+        step_reproducible = all(same(res, step()) for _ in range(3))
+    ndet = _detections(res)
+    count_slack = 0 if step_reproducible else max(2, ndet // 200)
+    model.bbox_head.tower_streams = None
+
+    failed = {}
+    elapsed = last = mode = None
+    if args.graph and args.pipeline > 1:
+        ok = 1
+        try:
+            from orientedreppoints_amd.mmdet_models import PipelinedInference
+            pi = PipelinedInference(model, img, metas, depth=args.pipeline)
+            got = [r for r in (pi.submit(img) for _ in range(args.warmup + args.pipeline)) if r is not None] + pi.flush()
+            if any(abs(_detections(g_) - ndet) > count_slack for g_ in got):
+                raise RuntimeError('pipelined replay returned a different detection count')
+        except Exception as e:   # noqa: BLE001  (report, fall back as the full run does)
+            ok = 0
+            failed['pipelined_ms_per_step'] = 'failed: %s' % (str(e)[:200],)
+        if _all_ranks_ok(ok, dev, dist):
+            def run():
+                n_res = sum(pi.submit(img) is not None for _ in range(args.steps))
+                tail = pi.flush()
+                assert n_res + len(tail) == args.steps
+                return tail[-1]
+            elapsed, last = _timed_loop(dev, dist, run)
+            mode = 'hipgraph replay, %d images in flight' % args.pipeline
+        pi = None
+    if mode is None and args.graph:
+        ok = 1
+        try:
+            from orientedreppoints_amd.mmdet_models import GraphedInference
+            gi = GraphedInference(model, img, metas)
+            for _ in range(max(1, args.warmup)):
+                gres = gi(img)
+            if abs(_detections(gres) - ndet) > count_slack:
+                raise RuntimeError('graph replay returned %d detections, eager %d' % (_detections(gres), ndet))
+        except Exception as e:   # noqa: BLE001
+            ok = 0
+            failed['graph_replay_ms'] = 'failed: %s' % (str(e)[:200],)
+        if _all_ranks_ok(ok, dev, dist):
+            def run():
+                for _ in range(args.steps):
+                    r = gi(img)
+                return r
+            elapsed, last = _timed_loop(dev, dist, run)
+            mode = 'hipgraph replay'
+    if mode is None:
+        model.bbox_head.tower_streams = False
+        for _ in range(args.warmup):
+            step()
+
+        def run():
+            for _ in range(args.steps):
+                r = step()
+            return r
+        elapsed, last = _timed_loop(dev, dist, run)
+        mode = 'eager'
+    if rank != 0:
+        return
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, last)
+    ms_per_step = elapsed / args.steps * 1e3
+    out = {
+        'metric': 'images/sec (%dx%d DOTA, %s FPN)' % (IMG, IMG, MODEL_LABEL[args.model]),
+        'value': args.batch * args.steps * world / elapsed, 'unit': 'images/s', 'n_gpus': world,
+        'steps': args.steps, 'warmup': args.warmup, 'ms_per_step': ms_per_step, 'higher_is_better': True,
+        'scaling': 'weak', 'vs_baseline': None, 'dtype': 'f32', 'data': 'synthetic',
+        'config': _config_line(args, world, args.pipeline if mode.endswith('in flight') else 1),
+        'detections_per_step': ndet, 'step_bitwise_reproducible': bool(step_reproducible),
+        'library_deterministic_mode': library_deterministic_mode,
+        'library_build': _lib.lib().orp_version().decode(),
+        'library_path': _lib.LIB_PATH if os.environ.get('ORP_HIP_LIB') else 'in-tree (orientedreppoints_amd/csrc/liborp_hip.so)',
+        'mode': mode,
+        'full': False,
+    }
+    out.update(failed)
+    print(json.dumps(out))
+
+
 def timed_steps(step, args, dev, dist, world):
     """W untimed warm-up steps, then EXACTLY K steps bracketed by barrier + synchronize; MAX over ranks (seconds)."""
     for _ in range(args.warmup):
@@ -828,7 +995,16 @@ def main():
     ap.add_argument('--dtype', choices=('f32', 'fp16', 'bf16'), default='f32',
                     help='--mode train only: f32 (default, the reference\'s arithmetic) or torch.autocast in fp16 (with a '
                          'GradScaler) / bf16: library convolutions in half, hot-path operators on fp32-cast inputs')
+    ap.add_argument('--full', action='store_true',
+                    help='also the secondary measurements (eager and one-at-a-time loops, roofline, NMS stage, per-op table, '
+                         'CPU baselines, train probe, other configurations); off: the headline figure only')
+    ap.add_argument('--dump-outputs', metavar='DIR', default=None,
+                    help='after the timed steps, write the last timed step\'s detections (per image, per class) as DIR/*.npy')
     args = ap.parse_args()
+    if args.steps < 1:
+        raise SystemExit('bench.py: --steps must be at least 1')
+    if args.dump_outputs and (args.mode != 'test' or args.dry):
+        raise SystemExit('bench.py: --dump-outputs writes the inference step\'s detections (--mode test, not --dry)')
     global IMG, TRAIN_SIZES
     size_list = [int(z) for z in str(args.size).split(',')]
     IMG = args.size = size_list[0]
@@ -861,6 +1037,11 @@ def main():
     metas = [dict(img_shape=(IMG, IMG, 3), pad_shape=(IMG, IMG, 3), scale_factor=1.0, flip=False)
              for _ in range(args.batch)]
     calibrate_head(model, img[:1])
+    if not args.full:
+        main_headline(args, model, img, metas, rank, world, dev, dist)
+        if distributed:
+            dist.destroy_process_group()
+        return
 
     def step():
         with torch.no_grad():
@@ -900,7 +1081,7 @@ def main():
     torch.cuda.synchronize()
     t0 = time.perf_counter()
     for _ in range(args.steps):
-        step()
+        last = step()
     torch.cuda.synchronize()
     if distributed:
         dist.barrier()
@@ -942,7 +1123,7 @@ def main():
                 dist.barrier()
             tg = time.perf_counter()
             for _ in range(args.steps):
-                gi(img)
+                last = gi(img)
             torch.cuda.synchronize()
             if distributed:
                 dist.barrier()
@@ -980,7 +1161,8 @@ def main():
                 n_res = 0
                 for _ in range(args.steps):
                     n_res += pi.submit(img) is not None
-                n_res += len(pi.flush())
+                tail = pi.flush()
+                n_res += len(tail)
                 torch.cuda.synchronize()
                 if distributed:
                     dist.barrier()
@@ -992,6 +1174,7 @@ def main():
                     p_elapsed = float(t.item())
                 pipe_ms = p_elapsed / args.steps * 1e3
                 elapsed = p_elapsed
+                last = tail[-1]
 
     prof = {name: read_prof(slot) for name, slot in
             (('nms_mask', 0), ('nms_sweep', 1), ('nms_rank_prepare', 2), ('dcn_fwd', 3), ('minarearect', 4), ('conv_split', 12))}
@@ -999,6 +1182,8 @@ def main():
         if distributed:
             dist.destroy_process_group()
         return
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, last)
 
     total_imgs = args.batch * args.steps * world
     value = total_imgs / elapsed
@@ -1216,14 +1401,7 @@ def main():
         'value_serial': value_serial, 'unit': 'images/s', 'n_gpus': world,
         'steps': args.steps, 'warmup': args.warmup, 'ms_per_step': ms_per_step, 'higher_is_better': True,
         'scaling': 'weak', 'vs_baseline': None, 'dtype': 'f32', 'data': 'synthetic',
-        'config': {'workload': '%s: OrientedRepPoints %s FPN inference, %dx%d patch, 15 classes, '
-                               'bs=%d/GPU, nms_pre=2000, score_thr=0.05, rnms iou_thr=0.4, max_per_img=2000; '
-                               'random-init weights, head biases calibrated to ~%d dets/img'
-                               % ('configs[1]' if (args.model, IMG, args.batch) == ('r50', 1024, 1) else
-                                  ('configs[3] per-GPU load' if (args.model, args.batch) == ('r101', 2) else 'variant'),
-                                  MODEL_LABEL[args.model], IMG, IMG, args.batch, TARGET_DETS),
-                   'global_batch': args.batch * world, 'parallelism': 'replicas x%d (image-parallel, no collective)' % world,
-                   'images_in_flight_per_gpu': args.pipeline if isinstance(pipe_ms, float) else 1},
+        'config': _config_line(args, world, args.pipeline if isinstance(pipe_ms, float) else 1),
         'detections_per_step': ndet, 'step_bitwise_reproducible': bool(step_reproducible), 'library_deterministic_mode': library_deterministic_mode, 'nms_classes_present': int(len(set(cap['labels'].tolist()))) if cap.get('labels') is not None else None,
         'library_build': _lib.lib().orp_version().decode(),
         # (a library swapped in through the environment -- dev aid -- must show in the line)
@@ -1241,6 +1419,7 @@ def main():
         'roofline': roof, 'nms': nms, 'nms_batched_16_images': batched, 'per_op_us': per_op, 'train': train,
         'other_configs': other,
         'cpu_baseline': cpu,
+        'full': True,
     }
     print(json.dumps(out))
     if distributed:

@@ -25,6 +25,24 @@ def golden_dir():
     return os.path.join(ROOT, "tests", "golden")
 
 
+@pytest.fixture(scope="session")
+def reference_configs(golden_dir):
+    """{file name: Config} of the reference's configs/dota/*.py, as Config.fromfile loaded them
+    (tests/golden/make_golden_configs.py -> dota_configs.json)."""
+    import json
+    from orientedreppoints_amd.mmdet_models import Config
+
+    def decode(v):
+        if isinstance(v, dict):
+            return tuple(decode(x) for x in v["__tuple__"]) if set(v) == {"__tuple__"} else {k: decode(x) for k, x in v.items()}
+        if isinstance(v, list):
+            return [decode(x) for x in v]
+        return v
+    with open(os.path.join(golden_dir, "dota_configs.json")) as f:
+        raw = json.load(f)
+    return {name: Config(decode(d), filename=name) for name, d in raw.items()}
+
+
 def pytest_collection_modifyitems(config, items):
     """ORP_TEST_ORDER=reverse runs the collected tests back to front (order-independence check of the GPU suite: no test
     may depend on allocator / cache state left by an earlier one; logs under profiles/r03_gputest_*.log)."""

@@ -42,6 +42,11 @@ def test_bench_single_rank_dry_and_world_size_mismatch():
     # the hot path has no CPU fallback
     r = _run(['--device', 'cpu', '--steps', '1'])
     assert r.returncode != 0
+    # --steps is the number of timed steps: at least one; --dump-outputs belongs to the inference step
+    r = _run(['--device', 'cpu', '--dry', '--steps', '0', '--warmup', '0'])
+    assert r.returncode != 0 and '--steps' in (r.stderr + r.stdout)
+    r = _run(['--device', 'cpu', '--dry', '--steps', '1', '--warmup', '0', '--dump-outputs', 'unused'])
+    assert r.returncode != 0 and '--dump-outputs' in (r.stderr + r.stdout)
 
 
 def test_bench_quotes_counters_only_from_the_running_build(tmp_path, monkeypatch):

@@ -1,21 +1,16 @@
-"""CPU: the reference's configs/dota/*.py load UNCHANGED through the mmcv-free Config and every model `type=` string
-resolves in the registries; orientedreppoints_amd/dota_configs.py carries the same values (skipped without the
-reference tree)."""
-import os
-
+"""CPU: the reference's configs/dota/*.py, as the mmcv-free Config loads them UNCHANGED (recorded by
+tests/golden/make_golden_configs.py into dota_configs.json), build, and every model `type=` string resolves in the registries;
+orientedreppoints_amd/dota_configs.py carries the same values."""
 import pytest
 
-REF_CFG = "/root/reference/configs/dota"
 
-
-@pytest.mark.skipif(not os.path.isdir(REF_CFG), reason="reference tree not present")
-def test_reference_configs_load_unchanged_and_build():
-    from orientedreppoints_amd.mmdet_models import Config, build_detector
+def test_reference_configs_load_unchanged_and_build(reference_configs):
+    from orientedreppoints_amd.mmdet_models import build_detector
     from orientedreppoints_amd import dota_configs
-    names = sorted(os.listdir(REF_CFG))
+    names = sorted(reference_configs)
     assert len(names) == 3
     for f in names:
-        cfg = Config.fromfile(os.path.join(REF_CFG, f))
+        cfg = reference_configs[f]
         assert cfg.model.type == 'OrientedRepPointsDetector'
         assert cfg.test_cfg.nms.type == 'rnms' and cfg.dist_params.backend == 'nccl'
         # every config builds -- ResNet-50 / 101 and Swin-T (its `pretrained` path is a file of the authors' machine: the
@@ -31,7 +26,7 @@ def test_reference_configs_load_unchanged_and_build():
                   # (the Swin config has no extra FPN convolutions: levels 4 and 5 are max-pooled)
                   'neck.fpn_convs.%d.gn.weight' % (4 if cfg.model.backbone.type == 'ResNet' else 2)):
             assert k in keys, k
-    cfg = Config.fromfile(os.path.join(REF_CFG, 'orientedrepoints_r50_demo.py'))
+    cfg = reference_configs['orientedrepoints_r50_demo.py']
     ours = dict(dota_configs.r50_model)
     theirs = dict(cfg.model)
     assert theirs['bbox_head'] == ours['bbox_head']
@@ -39,7 +34,7 @@ def test_reference_configs_load_unchanged_and_build():
     assert {k: v for k, v in theirs['backbone'].items()} == ours['backbone']
     assert dict(cfg.test_cfg) == dota_configs.test_cfg
     assert dict(cfg.train_cfg) == dota_configs.train_cfg
-    cfg = Config.fromfile(os.path.join(REF_CFG, 'orientedrepoints_swin_tiny_demo.py'))
+    cfg = reference_configs['orientedrepoints_swin_tiny_demo.py']
     theirs = dict(cfg.model)
     for part in ('backbone', 'neck', 'bbox_head'):
         assert dict(theirs[part]) == dota_configs.swin_t_model[part], part

@@ -1,19 +1,71 @@
-"""CPU: pin the oracle restatement against the REAL reference code (oracle/_ref/libref_orp.so = the reference's own
-device functions host-compiled by oracle/build_ref.py).  Skipped where the reference tree / prebuilt .so is absent
-(the golden-vector tests cover that case)."""
+"""CPU: pin the oracle restatement against the REAL reference code.  Every call of the reference's own functions (the ref_*
+functions of the oracle module and its use_ref=True legs: the reference's device functions host-compiled into oracle/_ref by
+oracle/build_ref.py) is answered from tests/golden/oracle_vs_ref.npz, recorded from that library on the same seeded inputs by
+tests/golden/make_golden_vs_ref.py; the oracle side is computed here."""
+import os
+
 import numpy as np
 import pytest
 
 from orientedreppoints_amd import synthetic as S
 
+GOLDEN = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "oracle_vs_ref.npz")
+
+
+def _is_ref_call(name, kwargs):
+    return name.startswith("ref_") or bool(kwargs.get("use_ref"))
+
+
+class Recorded(object):
+    """The oracle module with its reference calls answered in order from `golden`, or, with `record` a dict, passed to the
+    real reference library and their results stored into `record` (then `finish()`).  Keys: "<test id>/<call>/n" (-1: one
+    array, else the tuple's length) and "<test id>/<call>/<part>"; scalar results of a test go into "<test id>/scalars"."""
+
+    def __init__(self, oracle, test_id, golden=None, record=None):
+        self._oracle, self._id, self._golden, self._record, self._n = oracle, test_id, golden, record, 0
+        self._scalars = [] if record is not None else list(golden.get(test_id + "/scalars", np.zeros(0)).tolist())
+
+    def finish(self):
+        if self._scalars:
+            self._record[self._id + "/scalars"] = np.array(self._scalars, np.float64)
+
+    def __getattr__(self, name):
+        fn = getattr(self._oracle, name)
+        if not callable(fn) or name.startswith("_"):
+            return fn
+
+        def call(*a, **k):
+            if not _is_ref_call(name, k):
+                return fn(*a, **k)
+            key = "%s/%d" % (self._id, self._n)
+            self._n += 1
+            if self._record is not None:
+                out = fn(*a, **k)
+                if isinstance(out, float):
+                    self._scalars.append(out)
+                    return out
+                parts = out if isinstance(out, tuple) else (out,)
+                self._record[key + "/n"] = np.array(len(parts) if isinstance(out, tuple) else -1)
+                for j, v in enumerate(parts):
+                    self._record["%s/%d" % (key, j)] = np.asarray(v)
+                return out
+            if key + "/n" not in self._golden:
+                return self._scalars.pop(0)
+            n = int(self._golden[key + "/n"])
+            parts = [self._golden["%s/%d" % (key, j)] for j in range(max(n, 1))]
+            return tuple(parts) if n >= 0 else parts[0]
+        return call
+
 
 @pytest.fixture(scope="module")
-def ref(oracle):
-    from oracle import build_ref
-    build_ref.build()
-    if oracle.ref() is None:
-        pytest.skip("oracle/_ref not built (no /root/reference here)")
-    return oracle
+def golden():
+    with np.load(GOLDEN) as g:
+        return {k: g[k] for k in g.files}
+
+
+@pytest.fixture
+def ref(oracle, golden, request):
+    return Recorded(oracle, request.node.name, golden=golden)
 
 
 @pytest.mark.parametrize("seed", [0, 1, 2])

@@ -77,10 +77,10 @@ def test_swin_training_features():
     assert f.layers[1].blocks[0].attn.qkv.weight.requires_grad and not f.layers[0].training and f.layers[1].training
 
 
-@pytest.mark.skipif(not os.path.isdir("/root/reference/configs/dota"), reason="reference tree not present")
-def test_swin_tiny_dota_config_builds_and_feeds_the_neck():
+def test_swin_tiny_dota_config_builds_and_feeds_the_neck(reference_configs):
+    import copy
     from orientedreppoints_amd.mmdet_models import Config, build_detector
-    cfg = Config.fromfile("/root/reference/configs/dota/orientedrepoints_swin_tiny_demo.py")
+    cfg = Config(copy.deepcopy(dict(reference_configs["orientedrepoints_swin_tiny_demo.py"]._cfg_dict)))
     cfg.model.pretrained = None
     m = build_detector(cfg.model, train_cfg=cfg.train_cfg, test_cfg=cfg.test_cfg).eval()
     with torch.no_grad():

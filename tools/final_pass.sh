@@ -11,9 +11,9 @@ python -c "import __graft_entry__ as g; g.smoke(); print('smoke ok')" > $O/${TAG
 bash tools/pmc_all.sh > $O/${TAG}_pmc_all.log 2>&1
 python tools/make_pmc_json.py profiles/${TAG} $O/pmc_fetch $O/pmc_write $O/pmc_sqa $O/pmc_sqb > /dev/null 2>&1
 cp profiles/${TAG}_pmc.json profiles/${TAG}_pmc.txt $O/ 2>/dev/null
-python bench.py > $O/${TAG}_bench.json 2> $O/${TAG}_bench.err
-python bench.py --model r101 --batch 2 --steps 60 --no-cpu-baseline > $O/${TAG}_bench_r101_b2.json 2>/dev/null
-python bench.py --size 1536 --steps 60 --no-cpu-baseline > $O/${TAG}_bench_1536.json 2>/dev/null
+python bench.py --full > $O/${TAG}_bench.json 2> $O/${TAG}_bench.err
+python bench.py --model r101 --batch 2 --steps 60 --no-cpu-baseline --full > $O/${TAG}_bench_r101_b2.json 2>/dev/null
+python bench.py --size 1536 --steps 60 --no-cpu-baseline --full > $O/${TAG}_bench_1536.json 2>/dev/null
 python bench.py --mode train --steps 30 > $O/${TAG}_bench_train.json 2>/dev/null
 python bench.py --mode train --dtype fp16 --steps 30 > $O/${TAG}_bench_train_fp16.json 2>/dev/null
 python bench.py --mode train --dtype bf16 --steps 30 > $O/${TAG}_bench_train_bf16.json 2>/dev/null
@@ -42,8 +42,8 @@ python tests/checks/time_towers.py > $O/${TAG}_towers.log 2>&1
 python tests/checks/time_minarearect.py 2>&1 | grep sets > $O/${TAG}_minarearect.log
 (hipcc --offload-arch=gfx950 -O3 -o /tmp/pk_repro docs/mi355x_pk_mul_f32_next_to_mfma.hip 2>/dev/null && timeout 200 /tmp/pk_repro 100) > $O/${TAG}_pk_mul_reproducer.log 2>&1
 python tests/checks/time_wgrad.py > $O/${TAG}_wgrad.log 2>&1
-ORP_DCN_SPLIT=6 python bench.py --steps 100 --no-cpu-baseline > $O/${TAG}_bench_mode6.json 2>/dev/null
-(cd /tmp && export TMPDIR=/tmp && rocprofv3 --kernel-trace --stats --output-format csv -d $R/$O/${TAG}_prof_bench -- python $R/bench.py --steps 30 --no-cpu-baseline --pipeline 1 > $R/$O/${TAG}_prof_bench.log 2>&1)
+ORP_DCN_SPLIT=6 python bench.py --steps 100 --no-cpu-baseline --full > $O/${TAG}_bench_mode6.json 2>/dev/null
+(cd /tmp && export TMPDIR=/tmp && rocprofv3 --kernel-trace --stats --output-format csv -d $R/$O/${TAG}_prof_bench -- python $R/bench.py --steps 30 --no-cpu-baseline --pipeline 1 --full > $R/$O/${TAG}_prof_bench.log 2>&1)
 (cd /tmp && export TMPDIR=/tmp && rocprofv3 --kernel-trace --stats --output-format csv -d $R/$O/${TAG}_prof_train -- python $R/bench.py --mode train --steps 12 > $R/$O/${TAG}_prof_train.log 2>&1)
 tail -2 $O/${TAG}_smoke.log; tail -c 600 $O/${TAG}_bench.json; echo; tail -c 300 $O/${TAG}_bench_train.json
 # locally afterwards (profiles/ on the GPU box is a scratch copy):
