@@ -17,6 +17,7 @@
 
 #include "../../include/orp_hip.h"
 #include "orp_dcn_split.hpp"
+#include "orp_range.hpp"
 #include "orp_prof.hpp"
 #include "orp_launch.hpp"
 
@@ -50,7 +51,7 @@ to_channels_last_kernel(const TrLevels T, int C) {
     const int c = c0 + r, p = p0 + tx;
     const float v = (c < C && p < HW) ? src[(size_t)c * HW + p] : 0.f;
     tile[r][tx] = v;
-    m = max(m, __float_as_uint(v) & 0x7fffffffu);
+    m = max(m, orp::range_bits(v));
   }
   __syncthreads();
   for (int r = ty; r < 32; r += 8) {
@@ -240,7 +241,7 @@ conv_gn_finish_kernel(const GnFinish F) {
     for (int o = 32; o > 0; o >>= 1) { gm = fmaxf(gm, __shfl_xor(gm, o, 64)); bm = fmaxf(bm, __shfl_xor(bm, o, 64)); }
     if (lane == 0)
       F.bound[(size_t)conv * F.nlev * F.B * F.G + ((size_t)lvl * F.B + b) * F.G + grp] =
-          __float_as_uint(((mx + fabsf(mean)) * rstd * gm + bm) * 1.0001f);
+          orp::range_bound_bits((mx + fabsf(mean)) * rstd * gm + bm);
   }
 }
 

@@ -26,6 +26,7 @@
 #include "../../include/orp_hip.h"
 #include "orp_prof.hpp"
 #include "orp_launch.hpp"
+#include "orp_range.hpp"
 
 #ifndef ORP_WG_ALIGNED
 #define ORP_WG_ALIGNED 1  // X rows: aligned 16-byte loads + one neighbour element instead of 4-byte-aligned 16-byte loads of the shifted octet
@@ -91,12 +92,8 @@ conv_wgrad_split_kernel(const WParams P) {
   const int c_end = min(c_begin + per, P.total_chunks);
 
   // range factors (powers of two): the tensor's largest magnitude lands in [2^14, 2^15)
-  auto scale_of = [](unsigned am) {
-    int k = am == 0u ? 0 : 14 - ((int)((am >> 23) & 0xffu) - 127);
-    k = k < -100 ? -100 : k > 100 ? 100 : k;
-    return __uint_as_float((unsigned)(127 + k) << 23);
-  };
-  const float sx = scale_of(*P.amax_x), sg = scale_of(*P.amax_g);
+  const int kx = orp::range_exp(*P.amax_x), kgo = orp::range_exp(*P.amax_g);
+  const float sx = orp::range_scale(kx), sg = orp::range_scale(kgo);
 
   // this thread's four items of a step: item u = (row r = (tid >> 2) + 128 * u of the 512 rows [G 0..255 | X 256..511],
   // octet q = tid & 3): eight consecutive positions of one channel row
@@ -344,7 +341,7 @@ conv_wgrad_split_kernel(const WParams P) {
     }
   }
 
-  const float osc = 1.f / (sx * sg);
+  const int kxg = kx + kgo;
   float* outp = P.partial + ((size_t)slice * taps + tap) * CH * CH;
 #pragma unroll
   for (int a = 0; a < 2; a++)
@@ -353,7 +350,7 @@ conv_wgrad_split_kernel(const WParams P) {
 #pragma unroll
       for (int r = 0; r < 16; r++) {
         const int o = wo * 64 + a * 32 + (r & 3) + 8 * (r >> 2) + 4 * kg;
-        outp[(size_t)o * CH + wc * 128 + c * 32 + m] = acc[a][c][r] * osc;
+        outp[(size_t)o * CH + wc * 128 + c * 32 + m] = orp::range_unscale(acc[a][c][r], kxg);
       }
 }
 
@@ -381,7 +378,7 @@ wgrad_absmax_kernel(const WAbs A, unsigned* __restrict__ out) {
   const size_t n = A.n[t];
   const int nb = A.bx0[t + 1] - A.bx0[t], b = (int)blockIdx.x - A.bx0[t];
   unsigned mx = 0u;
-  for (size_t i = (size_t)b * 256 + threadIdx.x; i < n; i += (size_t)nb * 256) mx = max(mx, __float_as_uint(x[i]) & 0x7fffffffu);
+  for (size_t i = (size_t)b * 256 + threadIdx.x; i < n; i += (size_t)nb * 256) mx = max(mx, orp::range_bits(x[i]));
 #pragma unroll
   for (int o = 32; o > 0; o >>= 1) mx = max(mx, (unsigned)__shfl_xor((int)mx, o, 64));
   if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = mx;

@@ -46,6 +46,7 @@
 
 #include "../../include/orp_hip.h"
 #include "orp_launch.hpp"
+#include "orp_range.hpp"
 #include "orp_prof.hpp"
 
 #ifndef ORP_BWD_SPLITACC
@@ -158,7 +159,7 @@ __global__ void transpose_set_kernel(const TransposeSet T) {
   for (int k = ty; k < 32; k += 8) {
     const int s = s0 + k, r = r0 + tx;
     const float v = tile[tx][k];
-    vmax = max(vmax, __float_as_uint(v) & 0x7fffffffu);
+    vmax = max(vmax, orp::range_bits(v));
     if (s < S && r < R) {
       const size_t at = plane + (size_t)s * R + r;
       if (T.out_code == 0) reinterpret_cast<float*>(T.out[i])[at] = v;
@@ -219,18 +220,14 @@ __global__ void pack_wT_kernel(const float* __restrict__ w, int taps, float* __r
 // max |w| as float bits (out zeroed by the caller)
 __global__ void __launch_bounds__(256) absmax_w_kernel(const float* __restrict__ w, int n, unsigned* __restrict__ out) {
   unsigned m = 0u;
-  for (int i = blockIdx.x * blockDim.x + threadIdx.x; i < n; i += gridDim.x * blockDim.x) m = max(m, __float_as_uint(w[i]) & 0x7fffffffu);
+  for (int i = blockIdx.x * blockDim.x + threadIdx.x; i < n; i += gridDim.x * blockDim.x) m = max(m, orp::range_bits(w[i]));
 #pragma unroll
   for (int o = 32; o > 0; o >>= 1) m = max(m, (unsigned)__shfl_xor((int)m, o, 64));
   if ((threadIdx.x & 63) == 0 && m > __atomic_load_n(out, __ATOMIC_RELAXED)) atomicMax(out, m);
 }
 // the power of two that puts a tensor's largest magnitude (float bits `am`) into [2^14, 2^15): fp16 pieces then neither overflow
-// nor lose their low piece to the subnormal range (same rule as csrc/orp_dcn_split.hip)
-__device__ __forceinline__ float range_scale(unsigned am) {
-  int k = am == 0u ? 0 : 14 - ((int)((am >> 23) & 0xffu) - 127);
-  k = k < -100 ? -100 : k > 100 ? 100 : k;
-  return __uint_as_float((unsigned)(127 + k) << 23);
-}
+// nor lose their low piece to the subnormal range (csrc/orp_range.hpp)
+__device__ __forceinline__ float range_scale(unsigned am) { return orp::range_scale(orp::range_exp(am)); }
 // w [o][c][tap] -> two fp16 planes [pl][tap][o/16][kh][c][8] of w * 2^k (hi = nearest fp16, lo = the residual: exact in fp32, then rounded):
 // lane (c, kh) of kernel A reads the 8 k-values (output channels) of its MFMA operand as one 16-byte load
 __global__ void pack_wT16_kernel(const float* __restrict__ w, int taps, const unsigned* __restrict__ amax, uint16_t* __restrict__ planes,
@@ -364,8 +361,9 @@ dcn_bwd_input_kernel(const BwdParams P) {
     sCi[e] = ix; sCl[e] = make_float4(fr.x, fr.y, mm, 0.f);
   }
   for (int e = tid; e < 8 * BM2 * MAXT * 3; e += kThreads) sGO[e] = 0.f;
-  float sx = 1.f, osc = 1.f;                                        // F16: grad_out scale 2^k, accumulator scale 1 / (sx * wscale)
-  if (F16) { sx = range_scale(P.go_amax[0]); osc = 1.f / (sx * P.wscale[0]); }
+  float sx = 1.f;                                                   // F16: grad_out scale 2^k, accumulator scale 2^-(k + kw)
+  int kxw = 0;
+  if (F16) { const int k = orp::range_exp(P.go_amax[0]); sx = orp::range_scale(k); kxw = k + orp::range_exp_of(P.wscale[0]); }
   for (int r = wave; r < BM2; r += 8) {
     float4 v = make_float4(0.f, 0.f, 0.f, 0.f);
     if (p0 + r < npos) v = *reinterpret_cast<const float4*>(L.go + (size_t)(p0 + r) * CH + lane * 4);
@@ -477,7 +475,11 @@ dcn_bwd_input_kernel(const BwdParams P) {
 #endif
     if (F16) {
 #pragma unroll
-      for (int mt = 0; mt < MT; mt++) acc[mt] = (acc[mt] + side[mt]) * osc;
+      for (int mt = 0; mt < MT; mt++) {
+        acc[mt] += side[mt];
+#pragma unroll
+        for (int r = 0; r < 16; r++) acc[mt][r] = orp::range_unscale(acc[mt][r], kxw);
+      }
     }
     // ---- consume G_t: scatter into grad_input, coordinate derivatives into the tile's grad_offset ---------------
     if (STORE_G && ORP_BWD_LANEPOS) {
@@ -1079,7 +1081,7 @@ dcn_bwd_weight16_kernel(const BwdParams P, const SampleTab* __restrict__ tab, co
   const int per = (n_active + nsplit - 1) / nsplit;
   const int c_begin = blockIdx.x * per;
   const int c_end = (c_begin + per < n_active) ? c_begin + per : n_active;
-  const float sx = range_scale(*amax_x), sg = range_scale(*P.go_amax);
+  const int kx = orp::range_exp(*amax_x), kgo = orp::range_exp(*P.go_amax);
   const SampleTab* tap_tab = tab + (size_t)tap * P.total_chunks * 32 + px;
   const int c4 = (cz * CX16 + 2 * cp) * (int)sizeof(float);
   const __amdgpu_buffer_rsrc_t rs_g = __builtin_amdgcn_make_buffer_rsrc(const_cast<_Float16*>(go16), 0, P.total_chunks * (int)(kGo16ChunkHalves * sizeof(_Float16)), 0x00020000);
@@ -1222,7 +1224,7 @@ dcn_bwd_weight16_kernel(const BwdParams P, const SampleTab* __restrict__ tab, co
     if (ci < c_end) step(ci, 0, r1, r2);
   }
 
-  const float osc = 1.f / (sx * sg);
+  const int kxg = kx + kgo;
   float* outp = P.partial + ((size_t)blockIdx.x * taps + tap) * CH * CH;
 #pragma unroll
   for (int a = 0; a < 2; a++)
@@ -1231,7 +1233,7 @@ dcn_bwd_weight16_kernel(const BwdParams P, const SampleTab* __restrict__ tab, co
 #pragma unroll
       for (int r = 0; r < 16; r++) {
         const int o = wo * 64 + a * 32 + (r & 3) + 8 * (r >> 2) + 4 * kg;
-        outp[(size_t)o * CH + cz * CX16 + wc * 64 + q * 32 + m] = acc[a][q][r] * osc;
+        outp[(size_t)o * CH + cz * CX16 + wc * 64 + q * 32 + m] = orp::range_unscale(acc[a][q][r], kxg);
       }
 }
 

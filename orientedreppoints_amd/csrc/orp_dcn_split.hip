@@ -36,6 +36,7 @@
 #include <stdlib.h>
 
 #include "orp_dcn_split.hpp"
+#include "orp_range.hpp"
 #include "orp_launch.hpp"
 
 #ifndef ORP_DCNS_DBG
@@ -176,10 +177,9 @@ absmax_kernel(const AbsMaxArgs A, unsigned* __restrict__ out) {
   const size_t n4 = n >> 2;
   for (size_t i = (size_t)b * 256 + threadIdx.x; i < n4; i += (size_t)nb * 256) {
     const float4 v = reinterpret_cast<const float4*>(x)[i];
-    m = max(max(m, __float_as_uint(v.x) & 0x7fffffffu), max(__float_as_uint(v.y) & 0x7fffffffu,
-            max(__float_as_uint(v.z) & 0x7fffffffu, __float_as_uint(v.w) & 0x7fffffffu)));
+    m = max(max(m, orp::range_bits(v.x)), max(orp::range_bits(v.y), max(orp::range_bits(v.z), orp::range_bits(v.w))));
   }
-  if (b == 0 && threadIdx.x < (n & 3)) m = max(m, __float_as_uint(x[(n4 << 2) + threadIdx.x]) & 0x7fffffffu);
+  if (b == 0 && threadIdx.x < (n & 3)) m = max(m, orp::range_bits(x[(n4 << 2) + threadIdx.x]));
 #pragma unroll
   for (int o = 32; o > 0; o >>= 1) m = max(m, (unsigned)__shfl_xor((int)m, o, 64));
   if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = m;
@@ -194,10 +194,7 @@ absmax_kernel(const AbsMaxArgs A, unsigned* __restrict__ out) {
 // largest magnitude lands in [2^14, 2^15); wscale[0] = 2^k
 __global__ void pack_planes16_kernel(const float* __restrict__ w, int cout, int cin, int taps, const unsigned* __restrict__ amax,
                                      uint16_t* __restrict__ planes, float* __restrict__ wscale) {
-  const unsigned am = *amax;
-  int k = am == 0u ? 0 : 14 - ((int)((am >> 23) & 0xffu) - 127);
-  k = k < -100 ? -100 : k > 100 ? 100 : k;
-  const float sc = __uint_as_float((unsigned)(127 + k) << 23);
+  const float sc = orp::range_scale(orp::range_exp(*amax));
   if (blockIdx.x == 0 && threadIdx.x == 0) wscale[0] = sc;
   const long total = (long)cout * cin * taps;
   for (long i = (long)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += (long)gridDim.x * blockDim.x) {
@@ -322,7 +319,8 @@ dcn_fwd_split_kernel(const FwdS P, int total_tiles) {
     plim = p0 + BMS < npos ? p0 + BMS : npos;
   }
   const float* xin = conv ? L.x[1] : L.x[0];
-  float sx = 1.f, osc = 1.f;                                                  // F16: sample scale 2^k, output scale 1 / (sx * sw)
+  float sx = 1.f;                                                             // F16: sample scale 2^k; the output's 2^-(k + kw)
+  int kxw = 0;
   float* sAB = reinterpret_cast<float*>(sCi + BMS * kTapsMax);                 // [2][Cin] the input normalisation's (a[c]) then (b[c]) (coef_in only)
   if (F16) {
     unsigned am = P.amax[conv * P.amax_stride];
@@ -339,11 +337,10 @@ dcn_fwd_split_kernel(const FwdS P, int total_tiles) {
       for (int i = 1; i < kThreadsS / 64; i++) am = max(am, red[i]);
       __syncthreads();                                                          // (before the table build overwrites the scratch)
     }
-    int k = am == 0u ? 0 : 14 - ((int)((am >> 23) & 0xffu) - 127);
-    k = k < -100 ? -100 : k > 100 ? 100 : k;
-    sx = __uint_as_float((unsigned)(127 + k) << 23);
+    const int k = orp::range_exp(am);
+    sx = orp::range_scale(k);
     const float sw = *(L.planes ? L.wscale : conv ? P.wscale[1] : P.wscale[0]);
-    osc = 1.f / (sx * sw);
+    kxw = k + orp::range_exp_of(sw);
     if (P.dbg && tile == 0 && blockIdx.y == 0 && tid == 0) { P.dbg[conv] = am; P.dbg[2 + conv] = __float_as_uint(sw); }
   }
 
@@ -700,7 +697,9 @@ dcn_fwd_split_kernel(const FwdS P, int total_tiles) {
     // image (Chan et al.) in tile order.
     if (F16) {
 #pragma unroll
-      for (int mt = 0; mt < MT; mt++) acc[mt] *= osc;
+      for (int mt = 0; mt < MT; mt++)
+#pragma unroll
+        for (int r = 0; r < 16; r++) acc[mt][r] = orp::range_unscale(acc[mt][r], kxw);
       scaled = true;
     }
     const int cg = P.Cout / P.G, nrow = (int)(plim - p0);
@@ -731,7 +730,7 @@ dcn_fwd_split_kernel(const FwdS P, int total_tiles) {
     if (lane < 32 && (lane & (cg - 1)) == 0)
       P.gn_part[((size_t)conv * total_tiles + tile) * P.G + (n_wave + lane) / cg] = make_float4(mean, m2, mx, cnt);
   }
-  auto finish = [&](float v, int ch) { if (F16 && !scaled) v *= osc; if (bias) v += bias[ch]; return P.relu ? fmaxf(v, 0.f) : v; };
+  auto finish = [&](float v, int ch) { if (F16 && !scaled) v = orp::range_unscale(v, kxw); if (bias) v += bias[ch]; return P.relu ? fmaxf(v, 0.f) : v; };
 #pragma unroll
   for (int mt = 0; mt < MT; mt++) {
     if (OUT_NCHW) {
@@ -843,7 +842,8 @@ dcn_fwd_split_ws_kernel(const FwdS P, int total_tiles) {
     plim = p0 + BMS < npos ? p0 + BMS : npos;
   }
   const float* xin = conv ? L.x[1] : L.x[0];
-  float sx, osc;
+  float sx;
+  int kxw;                                                                    // the output's scale 2^-(k + kw)
   {
     unsigned am = P.amax[conv * P.amax_stride];
     if (P.amax_count > 1) {
@@ -859,11 +859,10 @@ dcn_fwd_split_ws_kernel(const FwdS P, int total_tiles) {
       for (int i = 1; i < kThreadsS / 64; i++) am = max(am, red[i]);
       __syncthreads();
     }
-    int k = am == 0u ? 0 : 14 - ((int)((am >> 23) & 0xffu) - 127);
-    k = k < -100 ? -100 : k > 100 ? 100 : k;
-    sx = __uint_as_float((unsigned)(127 + k) << 23);
+    const int k = orp::range_exp(am);
+    sx = orp::range_scale(k);
     const float sw = *(L.planes ? L.wscale : conv ? P.wscale[1] : P.wscale[0]);
-    osc = 1.f / (sx * sw);
+    kxw = k + orp::range_exp_of(sw);
     if (P.dbg && tile == 0 && blockIdx.y == 0 && tid == 0) { P.dbg[conv] = am; P.dbg[2 + conv] = __float_as_uint(sw); }
   }
 
@@ -1134,7 +1133,9 @@ dcn_fwd_split_ws_kernel(const FwdS P, int total_tiles) {
 #pragma unroll
     for (int mt = 0; mt < MT; mt++)
 #pragma unroll
-      for (int nt = 0; nt < NT; nt++) acc[mt][nt] *= osc;
+      for (int nt = 0; nt < NT; nt++)
+#pragma unroll
+        for (int r = 0; r < 16; r++) acc[mt][nt][r] = orp::range_unscale(acc[mt][nt][r], kxw);
     scaled = true;
     const int cg = P.Cout / P.G, nrow = (int)(plim - p0);
     auto row_ok = [&](int mt, int r) { return mt * 32 + (r & 3) + 8 * (r >> 2) + 4 * (lane >> 5) < nrow; };
@@ -1167,7 +1168,7 @@ dcn_fwd_split_ws_kernel(const FwdS P, int total_tiles) {
         P.gn_part[((size_t)conv * total_tiles + tile) * P.G + (n_wave + nt * 32 + lane) / cg] = make_float4(mean, m2, mx, cnt);
     }
   }
-  auto finish = [&](float v, int ch) { if (!scaled) v *= osc; if (bias) v += bias[ch]; return P.relu ? fmaxf(v, 0.f) : v; };
+  auto finish = [&](float v, int ch) { if (!scaled) v = orp::range_unscale(v, kxw); if (bias) v += bias[ch]; return P.relu ? fmaxf(v, 0.f) : v; };
 #pragma unroll
   for (int mt = 0; mt < MT; mt++)
 #pragma unroll

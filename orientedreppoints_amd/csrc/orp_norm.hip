@@ -23,6 +23,7 @@
 
 #include "../../include/orp_hip.h"
 #include "orp_launch.hpp"
+#include "orp_range.hpp"
 
 namespace {
 
@@ -568,7 +569,7 @@ gn_cl_merge_kernel(const GnClParams P) {
       float gm = 0.f, bm = 0.f;
       for (int c = grp * cg; c < (grp + 1) * cg; c++) { gm = fmaxf(gm, fabsf(L.gamma[c])); bm = fmaxf(bm, fabsf(L.beta[c])); }
       const float bound = (xm + fabsf(mean)) * rstd * gm + bm;
-      atomicMax(P.amax + P.slot[lvl], __float_as_uint(bound * 1.0001f));          // (a hair above the rounding of the bound itself)
+      atomicMax(P.amax + P.slot[lvl], orp::range_bound_bits(bound));                // (NaN / Inf: no bound, 0)
     }
   }
 }

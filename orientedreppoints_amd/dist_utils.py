@@ -19,12 +19,34 @@ def get_dist_info():
     return 0, 1
 
 
+def _loopback_interface():
+    """name of the loopback network interface (IFF_LOOPBACK in its flags), or None"""
+    import os
+    import socket
+    for _, name in socket.if_nameindex():
+        try:
+            with open(os.path.join('/sys/class/net', name, 'flags')) as f:
+                if int(f.read().strip(), 16) & 0x8:
+                    return name
+        except (OSError, ValueError):
+            continue
+    return None
+
+
 def init_dist(backend='nccl', **kwargs):
-    """torch.distributed.run style launch (RANK / LOCAL_RANK / WORLD_SIZE / MASTER_* in the environment)."""
+    """torch.distributed.run style launch (RANK / LOCAL_RANK / WORLD_SIZE / MASTER_* in the environment); `kwargs` go to
+    init_process_group (e.g. another init_method).  A gloo group whose MASTER_ADDR is a loopback address binds gloo to the
+    loopback interface (GLOO_SOCKET_IFNAME, unless it is set): otherwise gloo resolves the machine's host name to pick its
+    interface, which blocks for the resolver's timeouts where that name has no local entry."""
     import os
     rank = int(os.environ['RANK'])
     if torch.cuda.is_available():
         torch.cuda.set_device(int(os.environ.get('LOCAL_RANK', rank % max(torch.cuda.device_count(), 1))))
+    if backend == 'gloo' and 'GLOO_SOCKET_IFNAME' not in os.environ and \
+            os.environ.get('MASTER_ADDR', '') in ('127.0.0.1', 'localhost', '::1'):
+        lo = _loopback_interface()
+        if lo is not None:
+            os.environ['GLOO_SOCKET_IFNAME'] = lo
     dist.init_process_group(backend=backend, **kwargs)
 
 

@@ -5,7 +5,6 @@ single process gets from the rank-averaged gradients (the reference's DDP semant
 mmdet/apis/train.py:137-141; head :441,455).  The HIP operators are replaced by oracle-backed CPU stand-ins
 (tests/cpu_standins.py): what is under test is the host logic around them."""
 import os
-import socket
 import sys
 
 import numpy as np
@@ -15,14 +14,6 @@ import torch.multiprocessing as mp
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 SIZE = 128
-
-
-def _free_port():
-    s = socket.socket()
-    s.bind(('127.0.0.1', 0))
-    p = s.getsockname()[1]
-    s.close()
-    return p
 
 
 def _data(rank):
@@ -47,14 +38,14 @@ def _build():
     return model, opt
 
 
-def _worker(rank, world, port, q):
+def _worker(rank, world, store, q):
     sys.path.insert(0, ROOT)
     sys.path.insert(0, os.path.join(ROOT, 'tests'))
     torch.set_num_threads(2)
     import cpu_standins
     from orientedreppoints_amd import dist_utils as D
-    os.environ.update(MASTER_ADDR='127.0.0.1', MASTER_PORT=str(port), RANK=str(rank), WORLD_SIZE=str(world), LOCAL_RANK=str(rank))
-    D.init_dist(backend='gloo')
+    os.environ.update(MASTER_ADDR='127.0.0.1', RANK=str(rank), WORLD_SIZE=str(world), LOCAL_RANK=str(rank))
+    D.init_dist(backend='gloo', init_method='file://' + store, rank=rank, world_size=world)
     with cpu_standins.installed():
         model, opt = _build()
         hook = D.DistOptimizerHook(grad_clip=dict(max_norm=35, norm_type=2), overlap=True, bucket_size_mb=4)
@@ -92,12 +83,12 @@ def _worker(rank, world, port, q):
     dist.destroy_process_group()
 
 
-def test_detector_train_step_two_ranks_overlapped_reducer():
+def test_detector_train_step_two_ranks_overlapped_reducer(tmp_path):
     world = 2
-    port = _free_port()
+    store = str(tmp_path / 'rendezvous')
     ctx = mp.get_context('spawn')
     q = ctx.Queue()
-    procs = [ctx.Process(target=_worker, args=(r, world, port, q)) for r in range(world)]
+    procs = [ctx.Process(target=_worker, args=(r, world, store, q)) for r in range(world)]
     for p in procs:
         p.start()
     out = sorted(q.get(timeout=900) for _ in range(world))

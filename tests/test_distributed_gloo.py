@@ -1,29 +1,22 @@
 """CPU: the N > 1 path (image-parallel sharding + gradient all-reduce + max-over-ranks timing) with the gloo backend,
-world_size 2, 127.0.0.1 rendezvous."""
+world_size 2, rendezvous through a file store in the test's temporary directory (a TCP store's server looks up the host
+name of every client connection: seconds each where the machine's resolver has no answer), gloo on the loopback interface."""
 import os
-import socket
 
 import torch
 import torch.distributed as dist
 import torch.multiprocessing as mp
 
 
-def _free_port():
-    s = socket.socket()
-    s.bind(('127.0.0.1', 0))
-    p = s.getsockname()[1]
-    s.close()
-    return p
-
-
-def _worker(rank, world, port, q):
+def _worker(rank, world, store, q):
     import sys
     sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
     from orientedreppoints_amd import dist_utils as D
-    os.environ.update(MASTER_ADDR='127.0.0.1', MASTER_PORT=str(port), RANK=str(rank), WORLD_SIZE=str(world),
+    os.environ.update(MASTER_ADDR='127.0.0.1', RANK=str(rank), WORLD_SIZE=str(world),
                       LOCAL_RANK=str(rank))
-    D.init_dist(backend='gloo')
+    D.init_dist(backend='gloo', init_method='file://' + store, rank=rank, world_size=world)
     assert D.get_dist_info() == (rank, world)
+    assert os.environ.get('GLOO_SOCKET_IFNAME'), "a loopback MASTER_ADDR binds gloo to the loopback interface"
     torch.manual_seed(0)                                   # same init on every rank
     model = torch.nn.Sequential(torch.nn.Conv2d(3, 4, 3, padding=1), torch.nn.ReLU(), torch.nn.Conv2d(4, 2, 1))
     opt = torch.optim.SGD(model.parameters(), lr=0.1)
@@ -54,12 +47,12 @@ def _worker(rank, world, port, q):
     dist.destroy_process_group()
 
 
-def test_two_rank_gradient_allreduce_and_sharding():
+def test_two_rank_gradient_allreduce_and_sharding(tmp_path):
     world = 2
-    port = _free_port()
+    store = str(tmp_path / 'rendezvous')
     ctx = mp.get_context('spawn')
     q = ctx.Queue()
-    procs = [ctx.Process(target=_worker, args=(r, world, port, q)) for r in range(world)]
+    procs = [ctx.Process(target=_worker, args=(r, world, store, q)) for r in range(world)]
     for p in procs:
         p.start()
     out = sorted(q.get(timeout=180) for _ in range(world))
@@ -73,13 +66,13 @@ def test_two_rank_gradient_allreduce_and_sharding():
     assert tmax0 == tmax1 == 2.0
 
 
-def _overlap_worker(rank, world, port, q):
+def _overlap_worker(rank, world, store, q):
     import sys
     sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
     from orientedreppoints_amd import dist_utils as D
-    os.environ.update(MASTER_ADDR='127.0.0.1', MASTER_PORT=str(port), RANK=str(rank), WORLD_SIZE=str(world),
+    os.environ.update(MASTER_ADDR='127.0.0.1', RANK=str(rank), WORLD_SIZE=str(world),
                       LOCAL_RANK=str(rank))
-    D.init_dist(backend='gloo')
+    D.init_dist(backend='gloo', init_method='file://' + store, rank=rank, world_size=world)
 
     class Net(torch.nn.Module):                            # a head that only some ranks use: different autograd graphs
         def __init__(self):
@@ -124,15 +117,15 @@ def _overlap_worker(rank, world, port, q):
     dist.destroy_process_group()
 
 
-def test_overlapped_bucketed_allreduce_matches_the_plain_path():
+def test_overlapped_bucketed_allreduce_matches_the_plain_path(tmp_path):
     """OverlappedGradientReducer (async bucketed all-reduce from grad hooks, issued in a fixed order) == the reference-style
     all-reduce after backward, over three SGD steps, with a parameter that never gets a gradient and a head that only one
     rank uses in some iterations (the ranks' autograd graphs differ; the collectives must still match up)."""
     world = 2
-    port = _free_port()
+    store = str(tmp_path / 'rendezvous')
     ctx = mp.get_context('spawn')
     q = ctx.Queue()
-    procs = [ctx.Process(target=_overlap_worker, args=(r, world, port, q)) for r in range(world)]
+    procs = [ctx.Process(target=_overlap_worker, args=(r, world, store, q)) for r in range(world)]
     for p in procs:
         p.start()
     out = sorted(q.get(timeout=180) for _ in range(world))
