@@ -28,15 +28,6 @@
 #include "orp_launch.hpp"
 #include "orp_range.hpp"
 
-#ifndef ORP_WG_ALIGNED
-#define ORP_WG_ALIGNED 1  // X rows: aligned 16-byte loads + one neighbour element instead of 4-byte-aligned 16-byte loads of the shifted octet
-#endif
-#ifndef ORP_WG_PAIRS
-#define ORP_WG_PAIRS 1    // the X fragments of a chunk in two pairs of column blocks, the second pair's LDS reads under the first pair's MFMAs
-#endif
-#ifndef ORP_WG_DBG
-#define ORP_WG_DBG 0      // dev aid (timing only, wrong results): 1 = no fetches after the first, 2 = no MFMA, 4 = no conversion / LDS writes
-#endif
 
 namespace {
 
@@ -132,7 +123,7 @@ conv_wgrad_split_kernel(const WParams P) {
         if (inrow && (hs0 < 0 || hs0 >= L.H)) {                         // ... of a row above / below the map: zeros, no loads
 #pragma unroll
           for (int e = 0; e < 8; e++) it[u].v[e] = 0.f;
-        } else if (ORP_WG_ALIGNED && inrow && (L.W & 3) == 0 && sh_w >= -1 && sh_w <= 1) {
+        } else if (inrow && (L.W & 3) == 0 && sh_w >= -1 && sh_w <= 1) {
           // 16-byte ALIGNED loads of the unshifted octet plus the one neighbour the tap's column shift brings in (zero at the row's
           // end); the shift itself is a renaming under a workgroup-uniform condition
           const float* src = row + hs0 * L.W + w0;
@@ -248,7 +239,6 @@ conv_wgrad_split_kernel(const WParams P) {
       const int cur = (chunk - c_begin) & 1;
       const bool more = chunk + 1 < c_end, more2 = chunk + 2 < c_end;
       const _Float16* sB = sT + (size_t)cur * BUF;
-#if ORP_WG_PAIRS
       // The X fragments in two PAIRS of column blocks: the second pair's LDS reads fly under the first pair's twelve MFMAs, and the first
       // pair of the step's second chunk under the second pair's (its registers are free by then; the G fragments follow when theirs
       // are).  Exposed LDS reads per step and wave: 12 KB instead of 24 -- all eight waves read at once, 1 536 cycles of the CU's LDS
@@ -275,16 +265,19 @@ conv_wgrad_split_kernel(const WParams P) {
           for (int a = 0; a < 2; a++)
 #pragma unroll
             for (int c = c0; c < c0 + 2; c++)
-              if (ORP_WG_DBG & 2) acc[a][c][0] += (float)ga[a][pr == 0 ? 1 : 0][0] * (float)xb[c][pr == 1 ? 1 : 0][0];
-              else acc[a][c] = __builtin_amdgcn_mfma_f32_32x32x16_f16(ga[a][pr == 0 ? 1 : 0], xb[c][pr == 1 ? 1 : 0], acc[a][c], 0, 0, 0);
+              acc[a][c] = __builtin_amdgcn_mfma_f32_32x32x16_f16(ga[a][pr == 0 ? 1 : 0], xb[c][pr == 1 ? 1 : 0], acc[a][c], 0, 0, 0);
       };
       ld_ga(0); ld_xb(0, 0);
 #pragma unroll
       for (int j = 0; j < KS / 16; j++) {
         ld_xb(j, 2);
         __builtin_amdgcn_sched_barrier(0);
-        if (more && !(ORP_WG_DBG & 4)) stash(it, cur ^ 1, 2 * j, 2 * j + 2);
-        if (FAST && !(ORP_WG_DBG & 1)) fetch_fast(min(chunk + 2, c_end - 1), it, 2 * j, 2 * j + 2);
+        // half of the next step's rows per 16-position chunk, converted in the shadow of the chunk's MFMAs.  (Converting first and
+        // re-arming the registers with the step after next right away -- a whole step for the loads to land instead of a barrier --
+        // measured slower: 281 us against 257.)
+        if (more) stash(it, cur ^ 1, 2 * j, 2 * j + 2);
+        // FAST: the two items just converted take the rows of the step after next (past the end: the last step again, dropped)
+        if (FAST) fetch_fast(min(chunk + 2, c_end - 1), it, 2 * j, 2 * j + 2);
         mfma_pair(0);
 #pragma unroll
         for (int i = 0; i < 12; i++) {
@@ -298,45 +291,7 @@ conv_wgrad_split_kernel(const WParams P) {
         __builtin_amdgcn_sched_barrier(0);
         if (j + 1 < KS / 16) ld_ga(j + 1);
       }
-#else
-#pragma unroll
-      for (int j = 0; j < KS / 16; j++) {
-        h8 ga[2][2], xb[4][2];
-#pragma unroll
-        for (int a = 0; a < 2; a++)
-#pragma unroll
-          for (int pl = 0; pl < 2; pl++)
-            ga[a][pl] = *reinterpret_cast<const h8*>(sB + (size_t)pl * PL + (size_t)(wo * 64 + a * 32 + m) * RS + j * 16 + kg * 8);
-#pragma unroll
-        for (int c = 0; c < 4; c++)
-#pragma unroll
-          for (int pl = 0; pl < 2; pl++)
-            xb[c][pl] = *reinterpret_cast<const h8*>(sB + (size_t)(2 + pl) * PL + (size_t)(wc * 128 + c * 32 + m) * RS + j * 16 + kg * 8);
-        __builtin_amdgcn_sched_barrier(0);
-        // half of the next step's rows per 16-position chunk, converted in the shadow of the chunk's MFMAs (1 MFMA : 4 VALU).
-        // (Converting first and re-arming the registers with the step after next right away -- a whole step for the loads to
-        //  land instead of a barrier -- measured slower: 281 us against 257.)
-        if (more && !(ORP_WG_DBG & 4)) stash(it, cur ^ 1, 2 * j, 2 * j + 2);
-        // FAST: the two items just converted take the rows of the step after next (past the end: the last step again, dropped)
-        if (FAST && !(ORP_WG_DBG & 1)) fetch_fast(min(chunk + 2, c_end - 1), it, 2 * j, 2 * j + 2);
-        // smallest products first; eight independent accumulators between two MFMAs into the same one
-#pragma unroll
-        for (int pr = 0; pr < 3; pr++)
-#pragma unroll
-          for (int a = 0; a < 2; a++)
-#pragma unroll
-            for (int c = 0; c < 4; c++)
-              if (ORP_WG_DBG & 2) acc[a][c][0] += (float)ga[a][pr == 0 ? 1 : 0][0] * (float)xb[c][pr == 1 ? 1 : 0][0];
-              else acc[a][c] = __builtin_amdgcn_mfma_f32_32x32x16_f16(ga[a][pr == 0 ? 1 : 0], xb[c][pr == 1 ? 1 : 0], acc[a][c], 0, 0, 0);
-#pragma unroll
-        for (int i = 0; i < 24; i++) {
-          __builtin_amdgcn_sched_group_barrier(0x008, 1, 0);
-          __builtin_amdgcn_sched_group_barrier(0x002, 4, 0);
-        }
-        __builtin_amdgcn_sched_barrier(0);
-      }
-#endif
-      if (!FAST && more2 && !(ORP_WG_DBG & 1)) fetch(chunk + 2, it, 0, 4);  // lands during the next step
+      if (!FAST && more2) fetch(chunk + 2, it, 0, 4);  // lands during the next step
       __syncthreads();
     }
   }

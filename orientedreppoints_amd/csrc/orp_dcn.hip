@@ -31,34 +31,12 @@
 #include "orp_prof.hpp"
 #include "orp_dcn_split.hpp"
 
-#ifndef ORP_DCN_APF_PIN
-#define ORP_DCN_APF_PIN 0    // 1: sched_barrier behind the prefetch reads (measured: 6 spills, 487 vs 483 us)
-#endif
-#ifndef ORP_DCN_IPF
-#define ORP_DCN_IPF 0      // gather pixel indices read from LDS one chunk ahead (measured: no gain on top of APF)
-#endif
-#ifndef ORP_DCN_APF_ALL
-#define ORP_DCN_APF_ALL 1  // ... also in the two-layer instantiation (254 VGPRs, no spill; 494 -> 482 us per pair launch)
-#endif
-#ifndef ORP_DCN_APF
-#define ORP_DCN_APF 1      // A-fragment LDS prefetch one k-step ahead in the single-layer second-generation kernel
-#endif
-#ifndef ORP_DCN_GDIST
-#define ORP_DCN_GDIST 1    // gather-to-combine distance (chunks) of the single-layer second-generation kernel: 1 or 2
-#endif
-#ifndef ORP_DCN_WDIST
-#define ORP_DCN_WDIST 1    // weight prefetch distance (chunks) of the single-layer second-generation kernel: 1 or 2 (2: measured, no gain)
-#endif
-#ifndef ORP_DCN_KS_DBG
-#define ORP_DCN_KS_DBG 0   // dev aid for the tap-granular split (timing only): 1 = no hand-over of the cut tiles at all, 4 = coefficient table built once only
-#endif
-#ifndef ORP_DCN_DBG
-#define ORP_DCN_DBG 0      // dev aid, compile-time (timing only, wrong results): 1 = no A gather, 2 = no weight loads, 4 = no per-tap barriers / LDS refill, 8 = no MFMA
-#endif
-
 namespace {
 
 typedef float floatx16 __attribute__((ext_vector_type(16)));
+
+constexpr int kGatherDist = 1;  // gather-to-combine distance (chunks) of the single-layer second-generation kernel: 1 or 2
+constexpr int kWeightDist = 1;  // weight prefetch distance (chunks) of the single-layer second-generation kernel: 1 or 2 (2: measured, no gain)
 
 constexpr int BM = 32;          // output positions per workgroup
 constexpr int BN = 256;         // output channels per workgroup (4 waves x 64)
@@ -482,7 +460,7 @@ dcn_fwd_mfma2_kernel(const FwdParams P, int total_tiles) {
   }
   if (!first_seg) __syncthreads();                          // every wave is past its last read of the previous segment's A tile / table
   first_seg = false;
-  if (tile != cur_tile && !((ORP_DCN_KS_DBG & 4) && cur_tile >= 0)) {
+  if (tile != cur_tile) {
   cur_tile = tile;
   int lvl = 0;
 #pragma unroll 1
@@ -546,17 +524,6 @@ dcn_fwd_mfma2_kernel(const FwdParams P, int total_tiles) {
     const int tap = phase / ncb, cb = phase - tap * ncb;
     const int4 ix = sCi[m * taps + tap];
     const float* base = xin + cb * CB + lane * 4;
-#if ORP_DCN_DBG & 1
-    g[0] = g[1] = g[2] = g[3] = make_float4(1.f, 1.f, 1.f, 1.f); return;
-#endif
-    g[0] = *reinterpret_cast<const float4*>(base + (size_t)ix.x * Cin);
-    g[1] = *reinterpret_cast<const float4*>(base + (size_t)ix.y * Cin);
-    g[2] = *reinterpret_cast<const float4*>(base + (size_t)ix.z * Cin);
-    g[3] = *reinterpret_cast<const float4*>(base + (size_t)ix.w * Cin);
-  };
-  auto gather_issue_ix = [&](int phase, const int4 ix, float4 (&g)[4]) {      // ... with the pixel indices already in registers
-    const int tap = phase / ncb, cb = phase - tap * ncb;
-    const float* base = xin + cb * CB + lane * 4;
     g[0] = *reinterpret_cast<const float4*>(base + (size_t)ix.x * Cin);
     g[1] = *reinterpret_cast<const float4*>(base + (size_t)ix.y * Cin);
     g[2] = *reinterpret_cast<const float4*>(base + (size_t)ix.z * Cin);
@@ -582,9 +549,6 @@ dcn_fwd_mfma2_kernel(const FwdParams P, int total_tiles) {
     const int tap = phase / ncb, cb = phase - tap * ncb;
     const size_t c4 = (size_t)(tap * Cin + cb * CB + j * KC2 + 4 * kh) >> 2;
     const float* base = w3 + (c4 * Cout + n_wave + mrow) * 4;
-#if ORP_DCN_DBG & 2
-    r[0] = r[1] = make_float4(1.f, 1.f, 1.f, 1.f); return;
-#endif
     if (n_ok) {
       r[0] = *reinterpret_cast<const float4*>(base);
       r[1] = *reinterpret_cast<const float4*>(base + (size_t)8 * Cout);     // channels + 8 -> c4 + 2
@@ -596,12 +560,10 @@ dcn_fwd_mfma2_kernel(const FwdParams P, int total_tiles) {
   // ---- prologue: A tile of phase 0, weight fragments of chunk 0 ------------------------------------------------
   // the weight fragments are fetched WDIST chunks ahead of their use (the single-layer instantiation has the registers for
   // two; measured round 2: 505 us vs 503 us per pair -- the weight latency is not what the matrix pipe waits for)
-  constexpr int WDIST = (NCONV == 1) ? ORP_DCN_WDIST : 1;
+  constexpr int WDIST = (NCONV == 1) ? kWeightDist : 1;
   // a gathered row is combined GDIST chunks after its loads were issued (the single-layer instantiation has the 16
   // registers for a second row in flight; ROWS + GDIST - 1 <= NCHUNK)
-  constexpr int GDIST = (NCONV == 1 && STAGE == 0 && ROWS + 1 <= CB / KC2) ? ORP_DCN_GDIST : 1;
-  constexpr bool APF = (NCONV == 1 || ORP_DCN_APF_ALL) && ORP_DCN_APF;
-  constexpr bool IPF = APF && ORP_DCN_IPF;
+  constexpr int GDIST = (NCONV == 1 && STAGE == 0 && ROWS + 1 <= CB / KC2) ? kGatherDist : 1;
   auto load_lin = [&](int phase, int j, float4 (&r)[2]) {            // chunk (phase, j) with j possibly >= NCHUNK
     const int ph = phase + j / NCHUNK, jj = j % NCHUNK;
     if (ph < nphase) load_bq(ph, jj, r);
@@ -635,13 +597,9 @@ dcn_fwd_mfma2_kernel(const FwdParams P, int total_tiles) {
     const bool next_phase = phase + 1 < ph1;
     float4 hold[ROWS];
     float4 gq[2][4];                                         // gathered rows in flight (GDIST = 2: two)
-    int4 ixn = make_int4(0, 0, 0, 0);                        // IPF: pixel indices of the row gathered in the next chunk
-    if (IPF && next_phase) ixn = sCi[wave * taps + (phase + 1) / ncb];
-    float4 apre[MT];                                         // APF: the A fragments of the next k-step
-    if (APF) {
+    float4 apre[MT];                                         // the A fragments of the next k-step
 #pragma unroll
-      for (int mt = 0; mt < MT; mt++) apre[mt] = *reinterpret_cast<const float4*>(sA + (size_t)(mt * 32 + mrow) * ASTR + 4 * kh);
-    }
+    for (int mt = 0; mt < MT; mt++) apre[mt] = *reinterpret_cast<const float4*>(sA + (size_t)(mt * 32 + mrow) * ASTR + 4 * kh);
 #pragma unroll
     for (int j = 0; j < NCHUNK; j++) {
       // (1) issue the global loads of the next chunk's weight fragments and of one row of the next phase's A tile
@@ -649,62 +607,35 @@ dcn_fwd_mfma2_kernel(const FwdParams P, int total_tiles) {
       load_lin(phase, j + WDIST, bn);
       float4 (&g)[4] = gq[GDIST == 2 ? (j & 1) : 0];
       const bool do_row = next_phase && (j < ROWS);
-      if (do_row) { if (IPF) gather_issue_ix(phase + 1, ixn, g); else gather_issue(phase + 1, j * 8 + wave, g); }
-      // (2) MFMA over the current chunk
-      if (APF) {
-        // the A fragments of the NEXT k-step are read from LDS before the MFMAs of this one are issued (the wave's own
-        // LDS latency is then hidden behind its own matrix work; the tile only changes behind the tap's barriers, so the
-        // chain stops at the last k-step of a tap)
-        const float* arow = sA + (size_t)mrow * ASTR + j * KC2 + 4 * kh;
+      if (do_row) gather_issue(phase + 1, j * 8 + wave, g);
+      // (2) MFMA over the current chunk.  The A fragments of the NEXT k-step are read from LDS before the MFMAs of this one are
+      // issued (the wave's own LDS latency is then hidden behind its own matrix work; the tile only changes behind the tap's
+      // barriers, so the chain stops at the last k-step of a tap).  Also in the two-layer instantiation: 254 VGPRs, no spill,
+      // 494 -> 482 us per pair launch.  Measured and not taken: a sched_barrier behind the prefetch reads (6 spills, 487 vs
+      // 483 us); the gather's pixel indices read from LDS one chunk ahead (no gain on top of the prefetch).
+      const float* arow = sA + (size_t)mrow * ASTR + j * KC2 + 4 * kh;
 #pragma unroll
-        for (int t = 0; t < KC2 / 8; t++) {
-          float4 a4[MT];
+      for (int t = 0; t < KC2 / 8; t++) {
+        float4 a4[MT];
 #pragma unroll
-          for (int mt = 0; mt < MT; mt++) a4[mt] = apre[mt];
-          const bool more = !(j + 1 == NCHUNK && t + 1 == KC2 / 8);
-          if (more) {
-            const float* nrow = (t + 1 < KC2 / 8) ? arow + 8 * (t + 1) : arow + KC2;      // next k-step: same chunk or chunk j + 1
+        for (int mt = 0; mt < MT; mt++) a4[mt] = apre[mt];
+        const bool more = !(j + 1 == NCHUNK && t + 1 == KC2 / 8);
+        if (more) {
+          const float* nrow = (t + 1 < KC2 / 8) ? arow + 8 * (t + 1) : arow + KC2;      // next k-step: same chunk or chunk j + 1
 #pragma unroll
-            for (int mt = 0; mt < MT; mt++) apre[mt] = *reinterpret_cast<const float4*>(nrow + (size_t)mt * 32 * ASTR);
-          }
-#if ORP_DCN_APF_PIN
-          __builtin_amdgcn_sched_barrier(0);                 // keep the reads in FRONT of this k-step's MFMAs (the scheduler sinks them)
-#endif
-#pragma unroll
-          for (int i = 0; i < 4; i++) {
-            const float b0 = (i == 0) ? bq[t].x : (i == 1) ? bq[t].y : (i == 2) ? bq[t].z : bq[t].w;
-#pragma unroll
-            for (int mt = 0; mt < MT; mt++) {
-              const float av = (i == 0) ? a4[mt].x : (i == 1) ? a4[mt].y : (i == 2) ? a4[mt].z : a4[mt].w;
-              if (OUT_NCHW) acc[mt] = __builtin_amdgcn_mfma_f32_32x32x2f32(b0, av, acc[mt], 0, 0, 0);
-              else          acc[mt] = __builtin_amdgcn_mfma_f32_32x32x2f32(av, b0, acc[mt], 0, 0, 0);
-            }
-          }
+          for (int mt = 0; mt < MT; mt++) apre[mt] = *reinterpret_cast<const float4*>(nrow + (size_t)mt * 32 * ASTR);
         }
-      } else {
-        const float* arow = sA + (size_t)mrow * ASTR + j * KC2 + 4 * kh;
 #pragma unroll
-        for (int t = 0; t < KC2 / 8; t++) {
-          float4 a4[MT];
+        for (int i = 0; i < 4; i++) {
+          const float b0 = (i == 0) ? bq[t].x : (i == 1) ? bq[t].y : (i == 2) ? bq[t].z : bq[t].w;
 #pragma unroll
-          for (int mt = 0; mt < MT; mt++) a4[mt] = *reinterpret_cast<const float4*>(arow + (size_t)mt * 32 * ASTR + 8 * t);
-#pragma unroll
-          for (int i = 0; i < 4; i++) {
-            const float b0 = (i == 0) ? bq[t].x : (i == 1) ? bq[t].y : (i == 2) ? bq[t].z : bq[t].w;
-#pragma unroll
-            for (int mt = 0; mt < MT; mt++) {
-              const float av = (i == 0) ? a4[mt].x : (i == 1) ? a4[mt].y : (i == 2) ? a4[mt].z : a4[mt].w;
-#if ORP_DCN_DBG & 8
-              acc[mt][0] += av * b0; continue;
-#endif
-              if (OUT_NCHW) acc[mt] = __builtin_amdgcn_mfma_f32_32x32x2f32(b0, av, acc[mt], 0, 0, 0);   // D[channel][position]
-              else          acc[mt] = __builtin_amdgcn_mfma_f32_32x32x2f32(av, b0, acc[mt], 0, 0, 0);   // D[position][channel]
-            }
+          for (int mt = 0; mt < MT; mt++) {
+            const float av = (i == 0) ? a4[mt].x : (i == 1) ? a4[mt].y : (i == 2) ? a4[mt].z : a4[mt].w;
+            if (OUT_NCHW) acc[mt] = __builtin_amdgcn_mfma_f32_32x32x2f32(b0, av, acc[mt], 0, 0, 0);   // D[channel][position]
+            else          acc[mt] = __builtin_amdgcn_mfma_f32_32x32x2f32(av, b0, acc[mt], 0, 0, 0);   // D[position][channel]
           }
         }
       }
-      if (IPF && next_phase && j + 1 < ROWS)                 // pixel indices of the NEXT row: read now, needed one chunk later
-        ixn = sCi[((j + 1) * 8 + wave) * taps + (phase + 1) / ncb];
       if (GDIST == 1) {
         if (do_row) {
           const float4 v = combine(phase + 1, j * 8 + wave, g);
@@ -718,7 +649,7 @@ dcn_fwd_mfma2_kernel(const FwdParams P, int total_tiles) {
       else { bq[0] = bn[0]; bq[1] = bn[1]; }
     }
     // two barriers per tap: every wave is past its last read of this tap's A tile -> overwrite it with the next tap's rows
-    if (next_phase && !(ORP_DCN_DBG & 4)) {
+    if (next_phase) {
       __syncthreads();
 #pragma unroll
       for (int rr = 0; rr < ROWS; rr++)
@@ -741,7 +672,6 @@ dcn_fwd_mfma2_kernel(const FwdParams P, int total_tiles) {
     const bool waits = t0 > 0, publishes = t1 < taps;
     constexpr size_t kImage = (size_t)MT * 8 * 16 * 64;
     const size_t lane_off = (size_t)wave * 16 * 64 + lane;
-#if !(ORP_DCN_KS_DBG & 1)
     // Every access to the scratch images and flags is an agent-scope atomic (write-through / cache-bypassing per
     // INSTRUCTION): an agent-scope FENCE instead would write back and invalidate the whole L2 of the XCD -- the packed
     // weights every other workgroup streams from it (measured: 575 us with fences vs 520 us without the split).
@@ -776,7 +706,6 @@ dcn_fwd_mfma2_kernel(const FwdParams P, int total_tiles) {
       __syncthreads();                                          // ... and every other wave has drained its own
       if (tid == 0) __hip_atomic_store(P.ks_flags + wg, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
     }
-#endif
     if (publishes) store_out = false;
   }
   if (HEADS) {
@@ -916,9 +845,7 @@ hipError_t launch_mfma2_n(const FwdParams& P, int tiles, int nblk_n, hipStream_t
 }
 template <int MT, bool OUT_NCHW>
 hipError_t launch_mfma2(const FwdParams& P, int tiles, int nblk_n, hipStream_t st) {
-  static const bool pair_as_grid = getenv("ORP_DCN_PAIR_GRID") && atoi(getenv("ORP_DCN_PAIR_GRID")) == 1;   // dev aid
-  return (P.nconv == 2 && !pair_as_grid) ? launch_mfma2_n<MT, OUT_NCHW, 2>(P, tiles, nblk_n, st)
-                                         : launch_mfma2_n<MT, OUT_NCHW, 1>(P, tiles, nblk_n, st);
+  return P.nconv == 2 ? launch_mfma2_n<MT, OUT_NCHW, 2>(P, tiles, nblk_n, st) : launch_mfma2_n<MT, OUT_NCHW, 1>(P, tiles, nblk_n, st);
 }
 
 // ---- direct kernel: every configuration (groups, deformable groups, DCNv2 mask + bias), NCHW in / out -----------
@@ -1183,8 +1110,7 @@ static int dcn_forward_impl(const orp_dcn_level* levels_host, const orp_dcn_leve
   // whenever the ranges are at least three taps long)
   static const int ks_env = getenv("ORP_DCN_KSPLIT") ? atoi(getenv("ORP_DCN_KSPLIT")) : -1;
   bool use_ks = false;
-  if (gen == 2 && MT == 3 && !heads && c_in == 256 && c_out == 256 && ks_env != 0 && workspace &&
-      !(getenv("ORP_DCN_PAIR_GRID") && atoi(getenv("ORP_DCN_PAIR_GRID")) == 1)) {
+  if (gen == 2 && MT == 3 && !heads && c_in == 256 && c_out == 256 && ks_env != 0 && workspace) {
     const int nwg = ks_workgroups(), taps = kh * kw, per = nwg >> 3, nx = 8 / nconv;      // workgroups per XCD, XCDs per layer
     // steps of the busiest workgroup: whole tiles (both layers in one workgroup) vs whole-tile rounds + the split last round
     const long per_old = (long)((tiles + nwg - 1) / nwg) * nconv * taps;

@@ -35,7 +35,7 @@
 // 32-position chunks hold any non-zero value, an ordered compaction turns the flags into the list of ACTIVE chunks, and
 // both kernels walk that list only (dense gradients: the list is the identity).  Deterministic: the list is in chunk order.
 //
-// Measured and rejected for kernel A (round 2, tests/checks/atomic_rate.hip and the ORP_BWD_DBG switches): pre-accumulating
+// Measured and rejected for kernel A (round 2, tests/checks/atomic_rate.hip and timing-only builds): pre-accumulating
 // grad_input in LDS rows found through a per-tile hash table.  An fp32 global atomic costs one L2-channel clock per LANE
 // (313 G lane-atomics/s, agent and workgroup scope alike) -- but ds_add_f32 ran at the same ~310 G lanes/s on this part,
 // and the 112 KB of rows cut the occupancy from three workgroups per CU to one: 2.56 ms vs 1.40 ms without.
@@ -49,25 +49,12 @@
 #include "orp_range.hpp"
 #include "orp_prof.hpp"
 
-#ifndef ORP_BWD_SPLITACC
-#define ORP_BWD_SPLITACC 0   // kernel A: even / odd k-steps into two independent accumulator tiles (measured: 792 vs 791 us, +16 VGPRs: off)
-#endif
-#ifndef ORP_BWD_WDIST
-#define ORP_BWD_WDIST 3      // kernel A: weight fragments fetched this many chunks ahead (ring of WDIST + 1 slots; 1, 3 or 7)
-#endif
-#ifndef ORP_BWD_WDIST16
-#define ORP_BWD_WDIST16 3    // ... of the fp16-pieces contraction (a chunk is 3 MFMAs = 96 cycles there; the other waves of the SIMD cover the rest)
-#endif
-#ifndef ORP_BWD_LANEPOS
-#define ORP_BWD_LANEPOS 1    // kernel A, dense path: accumulator as D[channel][position] (lane = position) and the in-lane derivative sums; 0 = the round-3 lane = channel epilogue
-#endif
-#ifndef ORP_BWD_DBG
-#define ORP_BWD_DBG 0      // dev aid, compile-time (timing only, wrong results): 1 = no grad_input atomics, 2 = no x loads / derivative reduction, 4 = no G store, 8 = no epilogue at all, 16 = scatter kernel without G row reads, 32 = scatter kernel without accumulator updates
-#endif
-
 namespace {
 
 typedef float floatx16 __attribute__((ext_vector_type(16)));
+
+constexpr int kBwdWDist = 3;     // kernel A: weight fragments fetched this many chunks ahead (ring of kBwdWDist + 1 slots; 1, 3 or 7)
+constexpr int kBwdWDist16 = 3;   // ... of the fp16-pieces contraction (a chunk is 3 MFMAs = 96 cycles there; the other waves of the SIMD cover the rest)
 typedef _Float16 h8 __attribute__((ext_vector_type(8)));     // one operand of v_mfma_f32_32x32x16_f16: 8 k-values
 typedef _Float16 h2 __attribute__((ext_vector_type(2)));
 
@@ -399,7 +386,7 @@ dcn_bwd_input_kernel(const BwdParams P) {
   };
   // the weight fragments of chunk (tap, j) are fetched WD chunks ahead of their use: one chunk is 8 MFMAs = 512 cycles
   // of matrix work per wave, an L2 hit takes longer than that (measured: 1 221 vs 1 245 us at WD = 3 vs 1; 7 costs occupancy)
-  constexpr int WD = F16 ? ORP_BWD_WDIST16 : ORP_BWD_WDIST;
+  constexpr int WD = F16 ? kBwdWDist16 : kBwdWDist;
   float4 bqr[WD + 1][2];
 #pragma unroll
   for (int d = 0; d < WD; d++) load_bq(d / (CH / 16), d % (CH / 16), bqr[d]);
@@ -409,11 +396,6 @@ dcn_bwd_input_kernel(const BwdParams P) {
     floatx16 acc[MT], side[MT];                                     // (side: F16 only -- the small partial products)
 #pragma unroll
     for (int mt = 0; mt < MT; mt++) { acc[mt] = floatx16{0}; side[mt] = floatx16{0}; }
-#if ORP_BWD_SPLITACC
-    floatx16 acc_odd[MT];
-#pragma unroll
-    for (int mt = 0; mt < MT; mt++) acc_odd[mt] = floatx16{0};
-#endif
 #pragma unroll
     for (int j = 0; j < CH / 16; j++) {
       // (16 chunks per tap and WD + 1 ring slots: the slot of chunk (tap, j) is j % (WD + 1), a compile-time index because
@@ -433,7 +415,7 @@ dcn_bwd_input_kernel(const BwdParams P) {
         for (int mt = 0; mt < MT; mt++) {
           const h8 g_hi = *reinterpret_cast<const h8*>(ar + (size_t)mt * 32 * ASTRH);
           const h8 g_lo = *reinterpret_cast<const h8*>(ar + (size_t)mt * 32 * ASTRH + BM2 * ASTRH);
-          if (STORE_G && ORP_BWD_LANEPOS) {                            // D[channel][position]: lane = position
+          if (STORE_G) {                                               // D[channel][position]: lane = position
             side[mt] = __builtin_amdgcn_mfma_f32_32x32x16_f16(w_lo, g_hi, side[mt], 0, 0, 0);
             side[mt] = __builtin_amdgcn_mfma_f32_32x32x16_f16(w_hi, g_lo, side[mt], 0, 0, 0);
             acc[mt] = __builtin_amdgcn_mfma_f32_32x32x16_f16(w_hi, g_hi, acc[mt], 0, 0, 0);
@@ -457,11 +439,7 @@ dcn_bwd_input_kernel(const BwdParams P) {
 #pragma unroll
           for (int mt = 0; mt < MT; mt++) {
             const float av = (i == 0) ? a4[mt].x : (i == 1) ? a4[mt].y : (i == 2) ? a4[mt].z : a4[mt].w;
-#if ORP_BWD_SPLITACC
-            if (i & 1) acc_odd[mt] = __builtin_amdgcn_mfma_f32_32x32x2f32(av, b0, acc_odd[mt], 0, 0, 0);
-            else
-#endif
-            if (STORE_G && ORP_BWD_LANEPOS)
+            if (STORE_G)
               acc[mt] = __builtin_amdgcn_mfma_f32_32x32x2f32(b0, av, acc[mt], 0, 0, 0);     // D[channel][position]: lane = position
             else
               acc[mt] = __builtin_amdgcn_mfma_f32_32x32x2f32(av, b0, acc[mt], 0, 0, 0);     // D[position][channel]: lane = channel
@@ -469,10 +447,7 @@ dcn_bwd_input_kernel(const BwdParams P) {
         }
       }
     }
-#if ORP_BWD_SPLITACC
-#pragma unroll
-    for (int mt = 0; mt < MT; mt++) acc[mt] += acc_odd[mt];
-#endif
+    // (even / odd k-steps into two independent accumulator tiles: measured 792 vs 791 us, +16 VGPRs -- not taken)
     if (F16) {
 #pragma unroll
       for (int mt = 0; mt < MT; mt++) {
@@ -482,7 +457,7 @@ dcn_bwd_input_kernel(const BwdParams P) {
       }
     }
     // ---- consume G_t: scatter into grad_input, coordinate derivatives into the tile's grad_offset ---------------
-    if (STORE_G && ORP_BWD_LANEPOS) {
+    if (STORE_G) {
       // Dense gradients, round 4: the accumulator holds D[channel][position] -- lane = position m (lane & 31), register r =
       // channel n_wave + (r & 3) + 8 (r >> 2) + 4 kh.  The sums over channels the coordinate derivatives need
       //     S_k = sum_c G[m, c] * x[corner_k, c],  k = 1 .. 4
@@ -498,20 +473,19 @@ dcn_bwd_input_kernel(const BwdParams P) {
       const bool row_ok = p0 + m < npos;
       // (a) the row G_t[m, :] for kernel A2: 16 channels per lane as four 16-byte stores (the two half-waves interleave
       //     into whole 32-byte sectors; the row's 1 KB is completed by the 8 waves)
-      if (!(ORP_BWD_DBG & 4) && row_ok) {
+      if (row_ok) {
         float* grow = P.G + ((size_t)((long)tile * BM2 + m) * taps + tap) * CH + wave * 32 + 4 * kh;
 #pragma unroll
         for (int q = 0; q < 4; q++)
           *reinterpret_cast<float4*>(grow + 8 * q) = make_float4(acc[0][4 * q], acc[0][4 * q + 1], acc[0][4 * q + 2], acc[0][4 * q + 3]);
       }
       // (b) the derivative sums
-      const bool live = !(ORP_BWD_DBG & 8) && sNZ[m] != 0;             // a zero grad_out row gives G = 0: nothing to add
+      const bool live = sNZ[m] != 0;                                   // a zero grad_out row gives G = 0: nothing to add
       float S[4] = {0.f, 0.f, 0.f, 0.f};
       if (__ballot(live) != 0) {
         const int4 ix = sCi[e];
         const int ixs[4] = {ix.x, ix.y, ix.z, ix.w};
         const float* xb = L.x + wave * 32 + 4 * kh;
-#if !(ORP_BWD_DBG & 2)
         float4 v[4][4];
 #pragma unroll
         for (int k = 0; k < 4; k++) {
@@ -531,7 +505,6 @@ dcn_bwd_input_kernel(const BwdParams P) {
           }
           S[k] = (live && ixs[k] >= 0) ? sk : 0.f;
         }
-#endif
         // the other half-wave holds the other 16 channels of the same position: lanes m and m + 32
 #pragma unroll
         for (int k = 0; k < 4; k++) S[k] += __shfl_xor(S[k], 32, 64);
@@ -546,16 +519,14 @@ dcn_bwd_input_kernel(const BwdParams P) {
       }
       continue;
     }
+    // grad_input by atomics (STORE_G = false): lane = channel
 #pragma unroll
     for (int mt = 0; mt < MT; mt++) {
 #pragma unroll 4
       for (int r = 0; r < 16; r++) {
         const int m = mt * 32 + (r & 3) + 8 * (r >> 2) + 4 * kh;
         const int e = m * taps + tap;
-        const bool live = (ORP_BWD_DBG & 8) ? false : (sNZ[m] != 0);   // a zero grad_out row gives G = 0: nothing to add
-        if (STORE_G && !(ORP_BWD_DBG & 4)) {                        // the row of (position, tap) for kernel A2 (zeros included)
-          if (p0 + m < npos) P.G[((size_t)((long)tile * BM2 + m) * taps + tap) * CH + c] = acc[mt][r];
-        }
+        const bool live = sNZ[m] != 0;                                // a zero grad_out row gives G = 0: nothing to add
         if (__ballot(live) == 0) continue;
         const int4 ix = live ? sCi[e] : make_int4(-1, -1, -1, -1);
         const float4 fr = sCl[e];
@@ -563,21 +534,13 @@ dcn_bwd_input_kernel(const BwdParams P) {
         const float lh = fr.x, lw = fr.y, uh = 1.f - lh, uw = 1.f - lw, mm = fr.z;
         const size_t o1 = (size_t)(ix.x < 0 ? 0 : ix.x) * CH + c, o2 = (size_t)(ix.y < 0 ? 0 : ix.y) * CH + c;
         const size_t o3 = (size_t)(ix.z < 0 ? 0 : ix.z) * CH + c, o4 = (size_t)(ix.w < 0 ? 0 : ix.w) * CH + c;
-#if ORP_BWD_DBG & 2
-        const float v1 = uh, v2 = uw, v3 = lh, v4 = lw;
-#else
         const float v1 = ix.x >= 0 ? L.x[o1] : 0.f, v2 = ix.y >= 0 ? L.x[o2] : 0.f;
         const float v3 = ix.z >= 0 ? L.x[o3] : 0.f, v4 = ix.w >= 0 ? L.x[o4] : 0.f;
-#endif
-#if !(ORP_BWD_DBG & 1)
-        if (!STORE_G) {
-          const float gm = g * mm;
-          if (ix.x >= 0) atomicAdd(L.gx + o1, uh * uw * gm);
-          if (ix.y >= 0) atomicAdd(L.gx + o2, uh * lw * gm);
-          if (ix.z >= 0) atomicAdd(L.gx + o3, lh * uw * gm);
-          if (ix.w >= 0) atomicAdd(L.gx + o4, lh * lw * gm);
-        }
-#endif
+        const float gm = g * mm;
+        if (ix.x >= 0) atomicAdd(L.gx + o1, uh * uw * gm);
+        if (ix.y >= 0) atomicAdd(L.gx + o2, uh * lw * gm);
+        if (ix.z >= 0) atomicAdd(L.gx + o3, lh * uw * gm);
+        if (ix.w >= 0) atomicAdd(L.gx + o4, lh * lw * gm);
         float dh = g * mm * (-uw * v1 - lw * v2 + uw * v3 + lw * v4);
         float dw = g * mm * (-uh * v1 + uh * v2 - lh * v3 + lh * v4);
         dh = half_wave_sum(dh);
@@ -774,9 +737,6 @@ dcn_bwd_scatter_kernel(const BwdParams P, const SampleDesc* __restrict__ desc) {
   for (int l = 0; l < kAccRows; l++) mine[l * CH] = 0.f;
   constexpr int U = 16;                                              // list entries per step (2 x U G rows in flight per thread)
   const float* Gc = P.G + c;
-#if ORP_BWD_DBG & 32
-  float dbg_sum = 0.f;
-#endif
   for (int s0 = l0; s0 < l1; s0 += 64) {
     const SampleDesc cur = nxt;
     if (s0 + 64 < l1) nxt = fetch(s0 + 64);
@@ -787,13 +747,13 @@ dcn_bwd_scatter_kernel(const BwdParams P, const SampleDesc* __restrict__ desc) {
     // G rows of step j0 + U are in flight while the read-modify-writes of step j0 run (double buffer)
     float g[U], gn[U];
 #pragma unroll
-    for (int u = 0; u < U; u++) g[u] = (ORP_BWD_DBG & 16) ? 1.f : Gc[(size_t)(unsigned)__builtin_amdgcn_readlane((int)e, u) * CH];
+    for (int u = 0; u < U; u++) g[u] = Gc[(size_t)(unsigned)__builtin_amdgcn_readlane((int)e, u) * CH];
 #pragma unroll 1
     for (int j0 = 0; j0 < nb; j0 += U) {
       const bool more = j0 + U < nb;                                 // uniform; j0 + U + u < 64 then
       if (more) {
 #pragma unroll
-        for (int u = 0; u < U; u++) gn[u] = (ORP_BWD_DBG & 16) ? 1.f : Gc[(size_t)(unsigned)__builtin_amdgcn_readlane((int)e, j0 + U + u) * CH];
+        for (int u = 0; u < U; u++) gn[u] = Gc[(size_t)(unsigned)__builtin_amdgcn_readlane((int)e, j0 + U + u) * CH];
       }
 #pragma unroll
       for (int u = 0; u < U; u++) {
@@ -805,15 +765,11 @@ dcn_bwd_scatter_kernel(const BwdParams P, const SampleDesc* __restrict__ desc) {
         const float x3 = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(w3), j0 + u));
         // the four corners of a sample are four different pixels (or the dummy row): read all, then write all; the next
         // sample's reads follow these writes in program order and the LDS executes a wave's accesses in order
-#if ORP_BWD_DBG & 32
-        dbg_sum += x0 * g[u] + x1 * g[u] + x2 * g[u] + x3 * g[u] + (float)(q0 + q1 + q2 + q3);
-#else
         const float a0 = mine[q0], a1 = mine[q1], a2 = mine[q2], a3 = mine[q3];
         mine[q0] = a0 + x0 * g[u];
         mine[q1] = a1 + x1 * g[u];
         mine[q2] = a2 + x2 * g[u];
         mine[q3] = a3 + x3 * g[u];
-#endif
       }
       if (more) {
 #pragma unroll
@@ -821,9 +777,6 @@ dcn_bwd_scatter_kernel(const BwdParams P, const SampleDesc* __restrict__ desc) {
       }
     }
   }
-#if ORP_BWD_DBG & 32
-  mine[0] = dbg_sum;
-#endif
   // every pixel of the region is written exactly once (zeros included): no memset, no atomics
   for (int l = 0; l < 64; l++) {
     const int h = rh * 8 + (l >> 3), w = rw * 8 + (l & 7);
@@ -993,7 +946,7 @@ dcn_bwd_weight_kernel(const BwdParams P) {
 // Workgroup = (split, tap, half of the input channels): tile 256 (o) x 128 (c), 64 accumulator registers per wave; the corner values of
 // the chunk after next are requested one load behind every MFMA of the current chunk (two register sets that swap roles from chunk to
 // chunk), the next chunk's are combined and split between the MFMAs.  LDS is double buffered (2 x 60 KB); one barrier per chunk.
-// Measured (2 x 21 824 positions, dense gradient): weight kernel + reduction 542 us (exact fp32) -> 253 us.  Anatomy (ORP_BW16_DBG builds):
+// Measured (2 x 21 824 positions, dense gradient): weight kernel + reduction 542 us (exact fp32) -> 253 us.  Anatomy (timing-only builds):
 // without the MFMAs 239 us, without the gathers 182 us -- the kernel sits on the gathers, and what limits them is the vector memory
 // unit's REQUEST rate, not latency and not bytes: with 4-byte loads per lane (thread = channel) 2.4 GB moved at ~27 B/clk per CU and the
 // same kernel took 300 us, whether 16 or 64 loads per thread were in flight and whether they were issued in a burst or spread between the
@@ -1061,10 +1014,6 @@ __global__ void __launch_bounds__(256) pack_go16_kernel(const BwdParams P, _Floa
   *reinterpret_cast<h8*>(dst) = hi;
   *reinterpret_cast<h8*>(dst + (size_t)4 * CH * 8) = lo;
 }
-
-#ifndef ORP_BW16_DBG
-#define ORP_BW16_DBG 0      // dev aid (timing only, wrong results): 1 = no gathers after the prologue, 2 = no MFMA, 4 = no combine / split / LDS writes
-#endif
 
 __global__ void __launch_bounds__(kThreads)
 dcn_bwd_weight16_kernel(const BwdParams P, const SampleTab* __restrict__ tab, const _Float16* __restrict__ go16,
@@ -1195,9 +1144,9 @@ dcn_bwd_weight16_kernel(const BwdParams P, const SampleTab* __restrict__ tab, co
         __builtin_amdgcn_sched_barrier(0);
         // two chunks ahead: 16 of the 32 corner loads per k-step, a load or two behind every MFMA (issued in one burst they hold every
         // wave of the workgroup at the vector memory unit's door at the same time, with the matrix pipe idle behind them)
-        if (!(ORP_BW16_DBG & 1)) issue_half(nx2, j, rb);
+        issue_half(nx2, j, rb);
         // the next chunk's corner values: half an octet per k-step, between the MFMAs
-        if (!(ORP_BW16_DBG & 4)) convert(nx, j, ra, cv[j]);
+        convert(nx, j, ra, cv[j]);
         // smallest products first; four independent accumulators between two MFMAs into the same one
 #pragma unroll
         for (int pr = 0; pr < 3; pr++)
@@ -1205,8 +1154,7 @@ dcn_bwd_weight16_kernel(const BwdParams P, const SampleTab* __restrict__ tab, co
           for (int a = 0; a < 2; a++)
 #pragma unroll
             for (int q = 0; q < 2; q++)
-              if (ORP_BW16_DBG & 2) acc[a][q][0] += (float)ga[a][pr == 0 ? 1 : 0][0] * (float)xb[q][pr == 1 ? 1 : 0][0];
-              else acc[a][q] = __builtin_amdgcn_mfma_f32_32x32x16_f16(ga[a][pr == 0 ? 1 : 0], xb[q][pr == 1 ? 1 : 0], acc[a][q], 0, 0, 0);
+              acc[a][q] = __builtin_amdgcn_mfma_f32_32x32x16_f16(ga[a][pr == 0 ? 1 : 0], xb[q][pr == 1 ? 1 : 0], acc[a][q], 0, 0, 0);
 #pragma unroll
         for (int i = 0; i < 12; i++) {
           __builtin_amdgcn_sched_group_barrier(0x008, 1, 0);
@@ -1215,7 +1163,7 @@ dcn_bwd_weight16_kernel(const BwdParams P, const SampleTab* __restrict__ tab, co
         }
         __builtin_amdgcn_sched_barrier(0);
       }
-      if (more && !(ORP_BW16_DBG & 4)) { put_x(cur ^ 1, cv[0], cv[1]); put_g(cur ^ 1, g); }
+      if (more) { put_x(cur ^ 1, cv[0], cv[1]); put_g(cur ^ 1, g); }
       __syncthreads();
     };
     int ci = c_begin;

@@ -14,8 +14,8 @@
 //     the next tap right after chunk j has used it (in-place register ring, prefetch distance = one whole tap), and the
 //     gathered rows are combined and written to the single LDS A tile between two barriers at the end of the tap.
 // Round 3: a wave gathers with 16-byte loads (one neighbour of TWO rows per instruction) and combines with packed arithmetic
-// (v_pk_fma_f16; bf16 widened to v_pk_fma_f32): 74 -> 55 us per layer at 1024^2 (21 824 positions).  Decomposition with the
-// ORP_DCNH_DBG switches: without the gathers 42.7 us, without the per-tap weight loads 48.9 us, without both 34.1 us -- of
+// (v_pk_fma_f16; bf16 widened to v_pk_fma_f32): 74 -> 55 us per layer at 1024^2 (21 824 positions).  Decomposition with
+// timing-only builds: without the gathers 42.7 us, without the per-tap weight loads 48.9 us, without both 34.1 us -- of
 // which the matrix work is 11.5 us at the instruction rate; the rest of that floor is the A tile's LDS reads (every one
 // of the 8 waves reads the whole tile: 128 B/clk/CU at full matrix rate, half the LDS's peak), so the next step is a wave
 // tile of 64 output channels (half the LDS reads per MFMA), not more prefetch.  Measured without gain: a second A buffer
@@ -29,10 +29,6 @@
 #include "../../include/orp_hip.h"
 #include "orp_launch.hpp"
 #include "orp_prof.hpp"
-
-#ifndef ORP_DCNH_DBG
-#define ORP_DCNH_DBG 0     // dev aid, compile-time (timing only, wrong results): 1 = no gathers, 2 = no per-tap weight loads, 4 = no MFMA, 8 = no combine
-#endif
 
 namespace {
 
@@ -240,7 +236,6 @@ dcn_fwd_half_kernel(const FwdH P, int total_tiles) {
     const int tap = phase / ncb, cb = phase - tap * ncb;
     const int4 ix = sCi[(m2 + half_id) * taps + tap];
     const T* base = xin + cb * CBH + l8;
-    if (ORP_DCNH_DBG & 1) { g[0] = g[1] = g[2] = g[3] = make_uint4(ix.x, ix.y, ix.z, ix.w); return; }
     g[0] = *reinterpret_cast<const uint4*>(base + (size_t)ix.x * P.Cin);
     g[1] = *reinterpret_cast<const uint4*>(base + (size_t)ix.y * P.Cin);
     g[2] = *reinterpret_cast<const uint4*>(base + (size_t)ix.z * P.Cin);
@@ -249,7 +244,6 @@ dcn_fwd_half_kernel(const FwdH P, int total_tiles) {
   auto combine_store = [&](int phase, int m2, const uint4 (&g)[4]) {
     const int tap = phase / ncb;
     const int m = m2 + half_id;
-    if (ORP_DCNH_DBG & 8) { *reinterpret_cast<uint4*>(sA + (size_t)m * ASTRH + l8) = g[0]; return; }
     *reinterpret_cast<uint4*>(sA + (size_t)m * ASTRH + l8) = Elem<T>::combine8(g, sCw[m * taps + tap]);
   };
   // weight fragment of (phase, chunk j): lane (n = lane & 31, kg = lane >> 5) -> 8 k-values, one 16 B load
@@ -308,11 +302,10 @@ dcn_fwd_half_kernel(const FwdH P, int total_tiles) {
       }
 #pragma unroll
       for (int mt = 0; mt < MT; mt++) {
-        if (ORP_DCNH_DBG & 4) { acc[mt][0] += (float)a[mt][0] * (float)bq[j][0]; continue; }
         if (OUT_NCHW) acc[mt] = Elem<T>::mfma(bq[j], a[mt], acc[mt]);     // D[channel][position]
         else          acc[mt] = Elem<T>::mfma(a[mt], bq[j], acc[mt]);     // D[position][channel]
       }
-      if (next_phase && !(ORP_DCNH_DBG & 2)) bq[j] = load_b(phase + 1, j);
+      if (next_phase) bq[j] = load_b(phase + 1, j);
     }
     // (3) two barriers per tap: every wave is past its last read of the A tile -> overwrite it with the next tap's rows
     //     (a second A buffer with ONE barrier per tap was measured in round 3: 55.4 vs 54.9 us -- the barriers are not what
@@ -357,7 +350,7 @@ dcn_fwd_half_kernel(const FwdH P, int total_tiles) {
 // ---- round 6: the same operator, wave-specialised ---------------------------------------------------------------------------------
 // The kernel above runs every tap as  gathers out -> 16 chunks of MFMAs -> barrier -> combine + LDS writes -> barrier: the matrix pipe
 // idles through the combine, and every one of the 8 waves reads the whole A tile (its own analysis, top of this file: "the next step is
-// a wave tile of 64 output channels").  Here, as in csrc/orp_dcn_split.hip's wave-specialised kernel: 4 CONSUMER waves (one per SIMD;
+// a wave tile of 64 output channels").  Here, as in round 6's wave-specialised split kernel (since removed): 4 CONSUMER waves (one per SIMD;
 // the whole tile height x 64 output channels each = MT x 2 accumulator blocks; A fragments from a DOUBLE-buffered LDS tile, weights L2
 // -> an in-place-refilled register ring of one phase) and 4 PRODUCER waves at s_setprio 3 (the rows of phase + 2 gathered during phase
 // p, packed bilinear combine, one 16-byte LDS write per row piece); phases of 128 input channels of one tap, ONE barrier per phase.

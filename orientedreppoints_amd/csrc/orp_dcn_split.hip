@@ -39,54 +39,6 @@
 #include "orp_range.hpp"
 #include "orp_launch.hpp"
 
-#ifndef ORP_DCNS_DBG
-#define ORP_DCNS_DBG 0     // dev aid, compile-time (timing only, wrong results): 1 = no gathers, 2 = no weight refills, 4 = no MFMA, 8 = no combine / split / LDS write, 16 = no A-fragment LDS reads, 32 = no per-phase barrier
-#endif
-
-#ifndef ORP_DCNS_COMBINE_IN_LAST
-#define ORP_DCNS_COMBINE_IN_LAST 1   // 0: combine + split as a VALU-only tail after the phase's last MFMA (measured: the matrix pipe idles through it)
-#endif
-#ifndef ORP_DCNS_REFILL_LAG
-#define ORP_DCNS_REFILL_LAG 0
-#endif
-#ifndef ORP_DCNS_FENCE
-// 1 (default): a scheduling fence between the MFMAs of a chunk and the in-place refill of the chunk's weight registers -- the
-// MFMAs stay together, the refills go out behind them (measured +3 % on the pair launch against the scheduler's own mix).
-// History: round 4 had an inline-asm v_mov of one accumulator element here ("accumulator drain"), on the hypothesis that the
-// refill's VMEM return could overtake queued MFMAs.  tests/checks/mfma_war.hip settles it: 6.5e9 in-place refills right behind
-// their MFMAs, four waves per SIMD, every accumulator exact -- an issued MFMA has read its A / B operands --, and the v_mov
-// waited for nothing (it read a value two MFMAs old).  The wrong rows it seemed to cure were packed-fp32 VALU instructions of
-// the coefficient-table code miscomputing next to a second workgroup's MFMA loop; the v_mov only shifted that workgroup's timing.
-#define ORP_DCNS_FENCE 1
-#endif
-#ifndef ORP_DCNS_OWN_SIMD
-#define ORP_DCNS_OWN_SIMD 1          // 0: dev aid (the instantiations of tile height 1 / 2 then share their SIMDs with other waves)
-#endif
-#ifndef ORP_DCNS_TABLE_SELECTS
-#define ORP_DCNS_TABLE_SELECTS 0     // dev aid: 1 = the coefficient table's border conditions as selects (round 4; wrong rows under co-residency)
-#endif
-#ifndef ORP_DCNS_TRACE
-#define ORP_DCNS_TRACE 0             // dev aid (tests/checks/split_trace.py): 1 = every workgroup dumps its coefficient table, 2 = also a hash of every A-tile row of every phase, into the orp_debug_amax_log buffer
-#endif
-#ifndef ORP_DCNS_SIDE_ACC
-#define ORP_DCNS_SIDE_ACC 1          // PLAIN instantiation: second accumulator set for the small partial products (see Products)
-#endif
-#ifndef ORP_DCNS_CC
-#define ORP_DCNS_CC 0                // dev aid: number of trailing chunks that carry the combine (0: the rule in the kernel)
-#endif
-#ifndef ORP_DCNS_AHEAD2
-#define ORP_DCNS_AHEAD2 1            // PLAIN instantiation: the rows of phase p + 2 are gathered during phase p (two register sets, the loop unrolled by two phases)
-#endif
-#ifndef ORP_DCNS_EARLYBAR
-#define ORP_DCNS_EARLYBAR 0          // with AHEAD2: the phase's barrier in front of the LAST chunk's MFMAs, the next phase's first A fragments read behind it (measured: 200.4 - 202.5 vs 202.1 - 206.8 us, within the noise: off)
-#endif
-#ifndef ORP_DCNS_PRIO
-#define ORP_DCNS_PRIO 0             // dev aid: bit 0 = s_setprio 2 while the phase's gathers are issued, bit 1 = while a chunk carries the combine
-#endif
-#ifndef ORP_DCNS_INTERLEAVE
-#define ORP_DCNS_INTERLEAVE 4        // VALU instructions of the combine pinned behind every MFMA of the chunk that carries it (0: scheduler's choice)
-#endif
-
 namespace orp_split {
 namespace {
 
@@ -100,6 +52,7 @@ constexpr int CBS = 64;            // input channels per phase
 constexpr int ASTRS = CBS + 8;     // A row stride in bf16 elements (36 dwords: conflict-free ds_read_b128 over 16 rows)
 constexpr int NCH = CBS / 16;      // MFMA chunks (16 channels) per phase
 constexpr int kThreadsS = 512;
+constexpr int kInterleave = 4;     // VALU instructions of the combine pinned behind every MFMA of the chunk that carries it
 
 struct LevelK {
   const float* x[2];
@@ -222,16 +175,8 @@ __device__ __forceinline__ unsigned pack_hi16(float a, float b) {
 __device__ __forceinline__ constexpr int prod_a(int t) { const int tab[9] = {2, 2, 1, 2, 0, 1, 1, 0, 0}; return tab[t]; }
 __device__ __forceinline__ constexpr int prod_b(int t) { const int tab[9] = {2, 1, 2, 0, 2, 1, 0, 1, 0}; return tab[t]; }
 // F16 (two fp16 pieces, 0 = hi, 1 = lo): lo * hi, hi * lo, hi * hi
-#ifndef ORP_DCNS_PROD_ORDER16
-#define ORP_DCNS_PROD_ORDER16 0      // 1: lo*hi, hi*hi, hi*lo -- with SIDE the two chains (side, main) alternate; the bits do not change (each chain keeps its own order)
-#endif
-#if ORP_DCNS_PROD_ORDER16
-__device__ __forceinline__ constexpr int prod_a16(int t) { const int tab[3] = {1, 0, 0}; return tab[t]; }
-__device__ __forceinline__ constexpr int prod_b16(int t) { const int tab[3] = {0, 0, 1}; return tab[t]; }
-#else
 __device__ __forceinline__ constexpr int prod_a16(int t) { const int tab[3] = {1, 0, 0}; return tab[t]; }
 __device__ __forceinline__ constexpr int prod_b16(int t) { const int tab[3] = {0, 1, 0}; return tab[t]; }
-#endif
 
 // SIDE: the small partial products (everything but hi * hi) go to a second accumulator set that is added once in the
 // epilogue -- the main chain then rounds once per 16 channels at the output's magnitude instead of 3 (6, 9) times, and the
@@ -244,7 +189,6 @@ struct Products {
     constexpr bool to_side = SIDE && !(pa == 0 && pb == 0);          // everything but hi * hi
 #pragma unroll
     for (int mt = 0; mt < MT; mt++) {
-      if (ORP_DCNS_DBG & 4) { acc[mt][0] += (float)a[mt][pa][0] * (float)b[pb][0]; continue; }
       floatx16& d = to_side ? side[mt] : acc[mt];
       if (F16) {
         const h8 av = __builtin_bit_cast(h8, a[mt][pa]), bv = __builtin_bit_cast(h8, b[pb]);
@@ -282,12 +226,10 @@ dcn_fwd_split_kernel(const FwdS P, int total_tiles) {
   float4* sCw = reinterpret_cast<float4*>(sA + 2 * NPL * PLANE);              // [BMS * taps] bilinear weights
   int4* sCi = reinterpret_cast<int4*>(sCw + BMS * kTapsMax);                  // [BMS * taps] pixel indices
 
-#if ORP_DCNS_OWN_SIMD
   // the kernel claims the whole register budget of its waves (256 VGPRs: two waves fill a SIMD's file), whatever the tile height
   // needs: no wave of another workgroup -- of this kernel or of any other stream's -- runs on a SIMD beside a wave that is in the
   // MFMA loop (what such neighbours suffered)
   asm volatile("" ::: "v255");
-#endif
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   const int taps = P.kh * P.kw;
   int tile, conv;
@@ -368,23 +310,13 @@ dcn_fwd_split_kernel(const FwdS P, int total_tiles) {
         const int h_low = (int)floorf(h_im), w_low = (int)floorf(w_im);
         const float lh = h_im - (float)h_low, lw = w_im - (float)w_low;
         const float hh = 1.f - lh, hw_ = 1.f - lw;
-#if ORP_DCNS_TABLE_SELECTS
-        // (the first formulation, kept as a dev aid: its lane-mask code is where the wrong rows of round 4 came from -- see below)
-        const int h_high = h_low + 1, w_high = w_low + 1;
-        const bool t_ok = h_low >= 0, b_ok = h_high <= L.H - 1, l_ok = w_low >= 0, r_ok = w_high <= L.W - 1;
-        const int hl = t_ok ? h_low : 0, hhg = b_ok ? h_high : L.H - 1, wl = l_ok ? w_low : 0, whg = r_ok ? w_high : L.W - 1;
-        w.x = (t_ok && l_ok) ? hh * hw_ : 0.f;
-        w.y = (t_ok && r_ok) ? hh * lw : 0.f;
-        w.z = (b_ok && l_ok) ? lh * hw_ : 0.f;
-        w.w = (b_ok && r_ok) ? lh * lw : 0.f;
-#else
         // The four border conditions as 0 / 1 FACTORS and min / max clamps -- no lane masks.  h_low is in [-1, H - 1] here, so
         // t_ok = (h_low >= 0) = min(h_low + 1, 1), b_ok = (h_low + 1 <= H - 1) = min(H - 1 - h_low, 1), likewise l_ok / r_ok; a
         // product times 1.f is the product, times 0.f is +0 (the products are >= 0): the same bits as the selects of the
         // reference (deform_conv_cuda_kernel.cu:84-115).  Why: the compiler turned the selects into v_cmp_*_e64 -> s_and_b64 ->
         // v_cndmask chains between packed-fp32 instructions, and with a second workgroup of this kernel in its K loop on the
         // same CU the mask of w.z arrived with its last lane quarter (lanes 48..63) stale -- w.z = 0 in 16 consecutive table
-        // entries, i.e. three wrong A rows in all channels (tests/checks/split_trace.py, sgpr_mask_probe.hip).
+        // entries, i.e. three wrong A rows in all channels (tests/checks/sgpr_mask_probe.hip).
         const float t_ok = (float)min(h_low + 1, 1), b_ok = (float)min(L.H - 1 - h_low, 1);
         const float l_ok = (float)min(w_low + 1, 1), r_ok = (float)min(L.W - 1 - w_low, 1);
         const int hl = max(h_low, 0), hhg = min(h_low + 1, L.H - 1), wl = max(w_low, 0), whg = min(w_low + 1, L.W - 1);
@@ -392,7 +324,6 @@ dcn_fwd_split_kernel(const FwdS P, int total_tiles) {
         w.y = (hh * lw) * (t_ok * r_ok);
         w.z = (lh * hw_) * (b_ok * l_ok);
         w.w = (lh * lw) * (b_ok * r_ok);
-#endif
         const int base = b * L.H;
         ix.x = (base + hl) * L.W + wl;
         ix.y = (base + hl) * L.W + whg;
@@ -412,16 +343,6 @@ dcn_fwd_split_kernel(const FwdS P, int total_tiles) {
     for (int c = tid; c < P.Cin; c += kThreadsS) { const float2 ab = cf[c]; sAB[c] = ab.x; sAB[P.Cin + c] = ab.y; }
   }
   __syncthreads();
-#if ORP_DCNS_TRACE
-  const int trace_wg = conv * total_tiles + tile;
-  if (P.dbg && !PLAIN)                                    // (the DeformConv instantiation only: a PLAIN neighbour stream does not write)
-    for (int e = tid; e < BMS * taps; e += kThreadsS) {
-      unsigned* t = P.dbg + 16 + ((size_t)trace_wg * BMS * kTapsMax + e) * 8;
-      const float4 w = sCw[e]; const int4 ix = sCi[e];
-      t[0] = __float_as_uint(w.x); t[1] = __float_as_uint(w.y); t[2] = __float_as_uint(w.z); t[3] = __float_as_uint(w.w);
-      t[4] = ix.x; t[5] = ix.y; t[6] = ix.z; t[7] = ix.w;
-    }
-#endif
 
   const int ncb = P.Cin / CBS;
   const int nphase = taps * ncb;
@@ -431,7 +352,6 @@ dcn_fwd_split_kernel(const FwdS P, int total_tiles) {
   auto gather_issue = [&](int tap, int cb, int g, float4 (&v)[4]) {
     const int4 ix = sCi[row_of(g) * taps + tap];
     const float* base = xin + cb * CBS + c4;
-    if (ORP_DCNS_DBG & 1) { v[0] = v[1] = v[2] = v[3] = make_float4((float)ix.x, (float)ix.y, (float)ix.z, (float)ix.w); return; }
     v[0] = *reinterpret_cast<const float4*>(base + (size_t)ix.x * P.Cin);
     if (PLAIN) return;
     v[1] = *reinterpret_cast<const float4*>(base + (size_t)ix.y * P.Cin);
@@ -440,7 +360,6 @@ dcn_fwd_split_kernel(const FwdS P, int total_tiles) {
   };
   auto combine_store = [&](int tap, int cbk, int g, const float4 (&v)[4], int buf) {
     const int m = row_of(g);
-    if (ORP_DCNS_DBG & 8) return;
     const float4 cw = sCw[m * taps + tap];
     // the reference's own float expression, w1*v1 + w2*v2 + w3*v3 + w4*v4 evaluated left to right WITHOUT contraction
     // (deform_conv_cuda_kernel.cu:111-113): the samples are the reference's bits (DCNv1), and the value does not depend on
@@ -516,7 +435,7 @@ dcn_fwd_split_kernel(const FwdS P, int total_tiles) {
   }
   __syncthreads();
 
-  constexpr bool SIDE = PLAIN && ORP_DCNS_SIDE_ACC;
+  constexpr bool SIDE = PLAIN;
   floatx16 acc[MT], side[SIDE ? MT : 1];
 #pragma unroll
   for (int mt = 0; mt < MT; mt++) acc[mt] = floatx16{0};
@@ -531,7 +450,7 @@ dcn_fwd_split_kernel(const FwdS P, int total_tiles) {
   // phase p into the register set phase p - 1 emptied, and are split into the other LDS buffer during phase p + 1.  With one phase of
   // lead the first row group was consumed one chunk (~300 cycles of this wave's matrix work) after its loads went out and the wave sat
   // in s_waitcnt: the timing variants without gathers / without their consumer both ran 40 us of 218 faster (profiles/r05_anatomy.log).
-  constexpr bool AHEAD2 = PLAIN && F16 && ORP_DCNS_AHEAD2;          // (the three-plane modes have no registers left at tile height 3)
+  constexpr bool AHEAD2 = PLAIN && F16;                                      // (the three-plane modes have no registers left at tile height 3)
   int tap_n = 0, cb_n = 0, tap_n2 = 0, cb_n2 = 0;                             // phase + 1, phase + 2 (clamped to the last phase)
   auto step = [&](int& t, int& c, int ph) {
     if (ph + 1 < nphase) { if (++c == ncb) { c = 0; t++; } }
@@ -549,43 +468,13 @@ dcn_fwd_split_kernel(const FwdS P, int total_tiles) {
     for (int mt = 0; mt < MT; mt++)
 #pragma unroll
       for (int pl = 0; pl < NPL; pl++)
-        if (!(ORP_DCNS_DBG & 16)) a[mt][pl] = *reinterpret_cast<const bf8*>(abase + (size_t)pl * PLANE + (size_t)mt * 32 * ASTRS + j * 16);
+        a[mt][pl] = *reinterpret_cast<const bf8*>(abase + (size_t)pl * PLANE + (size_t)mt * 32 * ASTRS + j * 16);
   };
 
-  // EARLYBAR (with AHEAD2: the rows are already in registers when the phase starts): the row groups are split into the other buffer
-  // in the FIRST chunks, the phase's one barrier sits in front of the last chunk's MFMAs, and the first A fragments of the next phase
-  // are read right behind it -- under the last chunk's matrix work instead of in front of the next phase's first MFMA.  Safe: at the
-  // barrier every wave has completed its reads of this phase's buffer (the last chunk's fragments are in registers) and its writes of
-  // the other one; nobody writes this phase's buffer before the next phase's first chunk.
-  constexpr bool EARLYBAR = AHEAD2 && ORP_DCNS_EARLYBAR && !(ORP_DCNS_DBG & 16);
   bf8 a[2][MT][3];
-  if (EARLYBAR) {
-    const uint16_t* ab0 = sA + (size_t)mrow * ASTRS + 8 * kg;
-#pragma unroll
-    for (int mt = 0; mt < MT; mt++)
-#pragma unroll
-      for (int pl = 0; pl < NPL; pl++) a[0][mt][pl] = *reinterpret_cast<const bf8*>(ab0 + (size_t)pl * PLANE + (size_t)mt * 32 * ASTRS);
-  }
   auto phase_body = [&](int phase, float4 (&g)[MT][4], float4 (&gf)[AHEAD2 ? MT : 1][4]) __attribute__((always_inline)) {
     const int cur = phase & 1;
-#if ORP_DCNS_TRACE >= 2
-    if (P.dbg && !PLAIN) {   // hash of every row of the buffer this phase reads, as the readers see it (16 threads per row)
-      const int r = tid >> 4, sub = tid & 15;
-      if (r < BMS) {
-        unsigned h = 0;
-        for (int pl = 0; pl < NPL; pl++) {
-          const uint16_t* src = sA + (size_t)cur * NPL * PLANE + (size_t)pl * PLANE + (size_t)r * ASTRS + sub * 4;
-          for (int i = 0; i < 4; i++) h = h * 0x9E3779B1u + src[i] + 1u;
-        }
-        for (int o = 8; o > 0; o >>= 1) h = h * 31u + (unsigned)__shfl_down((int)h, o, 16);
-        if (sub == 0) P.dbg[16 + (size_t)(1 << 20) + ((size_t)trace_wg * 128 + phase) * BMS + r] = h;
-      }
-    }
-#endif
     // (1) the gathers of the next phase's rows go out first: a whole phase of matrix work to land  (AHEAD2: of the phase after it)
-#if ORP_DCNS_PRIO & 1
-    __builtin_amdgcn_s_setprio(2);
-#endif
     if (AHEAD2) {
 #pragma unroll
       for (int r = 0; r < MT; r++) gather_issue(tap_n2, cb_n2, r, gf[r]);
@@ -596,21 +485,10 @@ dcn_fwd_split_kernel(const FwdS P, int total_tiles) {
     // (the scheduler would otherwise SINK these loads down to their use to save registers -- measured in the ISA: the
     //  gathers ended up between the last MFMAs with s_waitcnt vmcnt(0) right behind them; the barriers pin the pipeline)
     __builtin_amdgcn_sched_barrier(0);
-#if ORP_DCNS_PRIO & 1
-    __builtin_amdgcn_s_setprio(0);
-#endif
     const uint16_t* abase = sA + (size_t)cur * NPL * PLANE + (size_t)mrow * ASTRS + 8 * kg;
     // (2) the phase: the A fragments of chunk j + 1 are read from LDS BEFORE the MFMAs of chunk j are issued (a second
     //     register set), the weight registers of chunk j are refilled for the next phase right after use
-    if (ORP_DCNS_DBG & 16) {
-#pragma unroll
-      for (int i = 0; i < 2; i++)
-#pragma unroll
-        for (int mt = 0; mt < MT; mt++)
-#pragma unroll
-          for (int pl = 0; pl < 3; pl++) a[i][mt][pl] = bq[(i + mt + pl) & 3][pl];
-    }
-    if (!EARLYBAR) load_a(abase, 0, a[0]);
+    load_a(abase, 0, a[0]);
 #pragma unroll
     for (int j = 0; j < NCH; j++) {
       if (j + 1 < NCH) load_a(abase, j + 1, a[(j + 1) & 1]);
@@ -619,56 +497,40 @@ dcn_fwd_split_kernel(const FwdS P, int total_tiles) {
       //     (nobody reads it before the barrier below; everybody finished reading it before the barrier that ended the
       //     previous phase): ~70 VALU per row group that the scheduler can place in the shadow of the region's MFMAs
       //     (a 32-cycle MFMA leaves ~5 issue slots) instead of a VALU-only tail during which the matrix pipe idles
-      //     The row groups ride in the LAST CC chunks, one each (CC = MT).  (All of them in the last chunk, so that the
+      //     The row groups ride in the LAST MT chunks, one each.  (All of them in the last chunk, so that the
       //     gathers have three chunks to land instead of one, measured no faster with fp16 pieces: 211 vs 200 us.)
-      constexpr int CC = (ORP_DCNS_CC > 0) ? (ORP_DCNS_CC < MT ? ORP_DCNS_CC : MT) : MT;
-      const bool with_combine = ORP_DCNS_COMBINE_IN_LAST && (EARLYBAR ? j < CC : j >= NCH - CC);
-      const int jc = EARLYBAR ? j : j - (NCH - CC);
-#if ORP_DCNS_PRIO & 2
-      if (with_combine) __builtin_amdgcn_s_setprio(2);                          // dev aid: the chunks that carry the combine issue ahead of the SIMD's other wave
-      else __builtin_amdgcn_s_setprio(0);
-#endif
+      //     The phase's barrier in front of the last chunk's MFMAs instead, with the row groups in the first chunks and the next
+      //     phase's first A fragments read behind it: measured within the noise (200.4 - 202.5 vs 202.1 - 206.8 us), not taken.
+      const bool with_combine = j >= NCH - MT;
+      const int jc = j - (NCH - MT);
       if (with_combine) {
 #pragma unroll
         for (int r = 0; r < MT; r++)
-          if (r * CC / MT == jc) combine_store(tap_n, cb_n, r, g[r], cur ^ 1);
-      }
-      if (EARLYBAR && j == NCH - 1) {
-        if (!(ORP_DCNS_DBG & 32)) __syncthreads();
-        load_a(sA + (size_t)(cur ^ 1) * NPL * PLANE + (size_t)mrow * ASTRS + 8 * kg, 0, a[0]);
-        __builtin_amdgcn_sched_barrier(0);
+          if (r == jc) combine_store(tap_n, cb_n, r, g[r], cur ^ 1);
       }
       Products<F16 ? 0 : 9 - NPROD, F16 ? 3 : 9, MT, OUT_NCHW, SIDE, F16>::run(acc, side, a[j & 1], bq[j]);
-#if ORP_DCNS_FENCE
-      __builtin_amdgcn_sched_barrier(0);                  // the chunk's MFMAs stay together, its refills behind them
-#endif
-#if ORP_DCNS_REFILL_LAG
-      // the registers of chunk j - 1 are refilled one chunk LATER, behind the MFMAs of chunk j (chunk NCH - 1: after the loop)
-      if (!(ORP_DCNS_DBG & 2) && j > 0) load_b(tap_n, cb_n, j - 1, bq[j - 1]);
-#else
-      if (!(ORP_DCNS_DBG & 2)) load_b(tap_n, cb_n, j, bq[j]);
-#endif
-      if (with_combine && ORP_DCNS_INTERLEAVE > 0) {
+      // A scheduling fence between the MFMAs of a chunk and the in-place refill of the chunk's weight registers: the MFMAs stay
+      // together, the refills go out behind them (measured +3 % on the pair launch against the scheduler's own mix).
+      // History: round 4 had an inline-asm v_mov of one accumulator element here ("accumulator drain"), on the hypothesis that the
+      // refill's VMEM return could overtake queued MFMAs.  tests/checks/mfma_war.hip settles it: 6.5e9 in-place refills right behind
+      // their MFMAs, four waves per SIMD, every accumulator exact -- an issued MFMA has read its A / B operands --, and the v_mov
+      // waited for nothing (it read a value two MFMAs old).  The wrong rows it seemed to cure were packed-fp32 VALU instructions of
+      // the coefficient-table code miscomputing next to a second workgroup's MFMA loop; the v_mov only shifted that workgroup's timing.
+      __builtin_amdgcn_sched_barrier(0);
+      load_b(tap_n, cb_n, j, bq[j]);
+      if (with_combine) {
         // pin the interleave: one MFMA, then the chunk's share of the combine's VALU in its 32-cycle shadow, ...
-        constexpr int kGroups = (MT + CC - 1) / CC;
 #pragma unroll
         for (int i = 0; i < NPROD * MT; i++) {
           __builtin_amdgcn_sched_group_barrier(0x008, 1, 0);
-          __builtin_amdgcn_sched_group_barrier(0x002, ORP_DCNS_INTERLEAVE * kGroups, 0);
+          __builtin_amdgcn_sched_group_barrier(0x002, kInterleave, 0);
         }
       }
       __builtin_amdgcn_sched_barrier(0);
     }
-    if (!ORP_DCNS_COMBINE_IN_LAST) {
-#pragma unroll
-      for (int r = 0; r < MT; r++) combine_store(tap_n, cb_n, r, g[r], cur ^ 1);
-    }
-#if ORP_DCNS_REFILL_LAG
-    if (!(ORP_DCNS_DBG & 2)) load_b(tap_n, cb_n, NCH - 1, bq[NCH - 1]);
-#endif
     step(tap_n, cb_n, phase + 1);
     step(tap_n2, cb_n2, phase + 2);
-    if (!EARLYBAR && !(ORP_DCNS_DBG & 32)) __syncthreads();
+    __syncthreads();
   };
   if constexpr (AHEAD2) {
 #pragma unroll 1
@@ -755,469 +617,15 @@ dcn_fwd_split_kernel(const FwdS P, int total_tiles) {
   }
 }
 
-// ================================================================================================================================
-// Round 6: the same tile, WAVE-SPECIALISED (fp16-pieces mode only; ORP_DCNS_WS=1 -- built, measured, NOT the default).
-//
-// The kernel above gives every wave every job: gather rows, combine / split them into LDS, read A fragments, stream its 32 output
-// channels' weights, issue MFMAs -- and the two waves of a SIMD do the same job at the same time.  Here the 8 waves split into 4
-// CONSUMERS (waves 0-3, one per SIMD: A fragments from LDS, weights from L2, MFMAs, epilogue; each owns the whole tile height x 64
-// output channels = MT x 2 accumulator blocks) and 4 PRODUCERS (waves 4-7, the other wave of each SIMD: row gathers two phases
-// ahead, bilinear combine / GroupNorm-on-the-way-in, fp16 split, LDS writes).  Every A fragment is read by 4 waves instead of 8 (LDS
-// read traffic per phase 196 -> 98 KB), the weight stream is unchanged.  The two roles are two separate loops, so the kernel needs
-// max(consumer, producer) registers; A fragments and weights are refilled in place behind the MFMAs that read them.
-//
-// What the measurements say (profiles/r06_ws_anatomy.log; pair launches at 1024^2, us incl. the range pre-pass and the host's launch
-// gap, symmetric kernel 242 DeformConv / 185 convolution):
-//   * as first written 315 / 232: the producers' VALU starves beside the consumers' MFMAs (issue arbitration is priority, then age).
-//     s_setprio 3 on the producers: 244 / 175.  The DeformConv launch gains nothing -- its producers (349 VALU + 24 row fetches per
-//     wave and phase) take as long as a phase's 72 MFMAs --, the convolution gains 5 %.
-//   * consumers alone 178 / 166, consumers without weight refills 158 / 148, consumers issuing nothing but MFMAs 156 / 146: the tile
-//     structure's floor (2 tiles per CU, 2 592 MFMAs per SIMD and tile at the ~1.4 GHz the part sustains under dense MFMAs, plus
-//     prologue / epilogue) is ~146 us -- the symmetric kernel's 180 us of the bench is within 20 % of it.
-//   * L2: 93 % hits, 132 cycles average read latency, 11 TB/s of 34 (profiles/r06_l2_counters.log): not the bound.
-// Why it is not the default: the convolution instantiation of the symmetric kernel keeps the two small partial products in a second
-// accumulator set (SIDE); a consumer would need 2 x 96 accumulator registers + fragments > 256 (the attempt spills inside the MFMA
-// loop), and without SIDE the error against float64 is 1.28e-6 where tests/test_gpu_conv_split.py admits 1.20e-6 (1.5 x the library's
-// own).  The DeformConv instantiation is bit-identical to the symmetric kernel's (same products, same order, no SIDE there).
-#ifndef ORP_WS_PRIO
-#define ORP_WS_PRIO 0                // dev aid: s_setprio of the consumer waves (0: none)
-#endif
-#ifndef ORP_WS_SIDE
-#define ORP_WS_SIDE 0                // PLAIN: second accumulator set for the small partial products
-#endif
-#ifndef ORP_WS_PPRIO
-#define ORP_WS_PPRIO 3               // s_setprio of the producer waves: without it their VALU starves beside the consumers' MFMAs (pair launch 314 us, with it 243)
-#endif
-#ifndef ORP_WS_ROT
-#define ORP_WS_ROT 0
-#endif
-#ifndef ORP_WS_DBG
-#define ORP_WS_DBG 0                 // dev aid (timing only, wrong results): 1 = producers idle, 2 = consumers issue no MFMA, 4 = no weight refills, 8 = no A-fragment reads, 16 = producers: no gathers, 32 = producers: gathers only (no combine / split / LDS write)
-#endif
-
-template <int MT, bool OUT_NCHW, bool PLAIN>
-__global__ void __launch_bounds__(kThreadsS)
-dcn_fwd_split_ws_kernel(const FwdS P, int total_tiles) {
-  constexpr int BMS = 32 * MT;
-  constexpr int PLANE = BMS * ASTRS;
-  constexpr int NPL = 2, NT = 2;
-  constexpr int RG = 2 * MT;                                                  // row groups (4 rows each) of one producer wave per phase
-  constexpr int NB = PLAIN ? 1 : 4;                                           // neighbours fetched per sample
-  extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
-  uint16_t* sA = reinterpret_cast<uint16_t*>(smem);                           // [2 buffers][2 planes][BMS][ASTRS]
-  float4* sCw = reinterpret_cast<float4*>(sA + 2 * NPL * PLANE);
-  int4* sCi = reinterpret_cast<int4*>(sCw + BMS * kTapsMax);
-  float* sAB = reinterpret_cast<float*>(sCi + BMS * kTapsMax);
-#if ORP_DCNS_OWN_SIMD
-  asm volatile("" ::: "v255");
-#endif
-  const int tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);   // (scalar: the role branch is an s_cbranch)
-  const int taps = P.kh * P.kw;
-  int tile, conv;
-  {
-    const int b = blockIdx.x, xcd = b & 7, slot = b >> 3;
-    const int nx = P.nconv == 2 ? 4 : 8;
-    conv = P.nconv == 2 ? (xcd >> 2) : 0;
-    const int xl = P.nconv == 2 ? (xcd & 3) : xcd;
-    const int per = (total_tiles + nx - 1) / nx;
-    tile = xl * per + slot;
-    if (slot >= per || tile >= total_tiles) return;
-  }
-  int lvl = 0;
-#pragma unroll 1
-  for (int i = 1; i < P.nlev; i++) if (tile >= P.lv[i].tile0) lvl = i;
-  const LevelK L = P.lv[lvl];
-  const int HoWo = L.Ho * L.Wo;
-  const long npos = (long)P.B * HoWo;
-  long p0, plim;
-  int img = 0;
-  if (L.tpi > 0) {
-    const int t_in = tile - L.tile0;
-    img = t_in / L.tpi;
-    const int pin = (t_in - img * L.tpi) * BMS;
-    p0 = (long)img * HoWo + pin;
-    plim = p0 + (HoWo - pin < BMS ? HoWo - pin : BMS);
-  } else {
-    p0 = (long)(tile - L.tile0) * BMS;
-    plim = p0 + BMS < npos ? p0 + BMS : npos;
-  }
-  const float* xin = conv ? L.x[1] : L.x[0];
-  float sx;
-  int kxw;                                                                    // the output's scale 2^-(k + kw)
-  {
-    unsigned am = P.amax[conv * P.amax_stride];
-    if (P.amax_count > 1) {
-      unsigned* red = reinterpret_cast<unsigned*>(sCw);
-      unsigned m_ = 0u;
-      for (int i = tid; i < P.amax_count; i += kThreadsS) m_ = max(m_, P.amax[conv * P.amax_stride + i]);
-#pragma unroll
-      for (int o = 32; o > 0; o >>= 1) m_ = max(m_, (unsigned)__shfl_xor((int)m_, o, 64));
-      if (lane == 0) red[wave] = m_;
-      __syncthreads();
-      am = red[0];
-#pragma unroll
-      for (int i = 1; i < kThreadsS / 64; i++) am = max(am, red[i]);
-      __syncthreads();
-    }
-    const int k = orp::range_exp(am);
-    sx = orp::range_scale(k);
-    const float sw = *(L.planes ? L.wscale : conv ? P.wscale[1] : P.wscale[0]);
-    kxw = k + orp::range_exp_of(sw);
-    if (P.dbg && tile == 0 && blockIdx.y == 0 && tid == 0) { P.dbg[conv] = am; P.dbg[2 + conv] = __float_as_uint(sw); }
-  }
-
-  // ---- coefficient table (same as the symmetric kernel: see there for the border-factor formulation) ----
-  for (int e = tid; e < BMS * taps; e += kThreadsS) {
-    const int m = e / taps, tap = e - m * taps;
-    const long p = p0 + m;
-    float4 w = make_float4(0.f, 0.f, 0.f, 0.f);
-    int4 ix = make_int4(0, 0, 0, 0);
-    if (p < plim) {
-      const int b = (int)(p / HoWo), hw = (int)(p - (long)b * HoWo);
-      const int ho = hw / L.Wo, wo = hw - ho * L.Wo;
-      const int ki = tap / P.kw, kj = tap - ki * P.kw;
-      if (PLAIN) {
-        const int hi = ho * P.sh - P.ph + ki * P.dh, wi = wo * P.sw - P.pw + kj * P.dw;
-        if (hi >= 0 && hi < L.H && wi >= 0 && wi < L.W) { w.x = 1.f; ix.x = (b * L.H + hi) * L.W + wi; }
-        sCw[e] = w; sCi[e] = ix;
-        continue;
-      }
-      const float* ob = L.off + ((size_t)b * 2 * taps + 2 * tap) * HoWo + hw;
-      const float h_im = (float)(ho * P.sh - P.ph + ki * P.dh) + ob[0];
-      const float w_im = (float)(wo * P.sw - P.pw + kj * P.dw) + ob[HoWo];
-      if (h_im > -1.f && w_im > -1.f && h_im < (float)L.H && w_im < (float)L.W) {
-        const int h_low = (int)floorf(h_im), w_low = (int)floorf(w_im);
-        const float lh = h_im - (float)h_low, lw = w_im - (float)w_low;
-        const float hh = 1.f - lh, hw_ = 1.f - lw;
-        const float t_ok = (float)min(h_low + 1, 1), b_ok = (float)min(L.H - 1 - h_low, 1);
-        const float l_ok = (float)min(w_low + 1, 1), r_ok = (float)min(L.W - 1 - w_low, 1);
-        const int hl = max(h_low, 0), hhg = min(h_low + 1, L.H - 1), wl = max(w_low, 0), whg = min(w_low + 1, L.W - 1);
-        w.x = (hh * hw_) * (t_ok * l_ok);
-        w.y = (hh * lw) * (t_ok * r_ok);
-        w.z = (lh * hw_) * (b_ok * l_ok);
-        w.w = (lh * lw) * (b_ok * r_ok);
-        const int base = b * L.H;
-        ix.x = (base + hl) * L.W + wl;
-        ix.y = (base + hl) * L.W + whg;
-        ix.z = (base + hhg) * L.W + wl;
-        ix.w = (base + hhg) * L.W + whg;
-        if (L.mask) {
-          const float mm = L.mask[((size_t)b * taps + tap) * HoWo + hw];
-          w.x *= mm; w.y *= mm; w.z *= mm; w.w *= mm;
-        }
-      }
-    }
-    sCw[e] = w; sCi[e] = ix;
-  }
-  const bool has_coef = PLAIN && P.coef_in != nullptr;
-  if (has_coef) {
-    const float2* cf = P.coef_in + ((size_t)(conv * P.nlev + lvl) * P.B + img) * P.Cin;
-    for (int c = tid; c < P.Cin; c += kThreadsS) { const float2 ab = cf[c]; sAB[c] = ab.x; sAB[P.Cin + c] = ab.y; }
-  }
-  __syncthreads();
-
-  const int ncb = P.Cin / CBS;
-  const int nphase = taps * ncb;
-#if ORP_WS_ROT
-  // dev aid (hypothesis test): the workgroups walk the channel blocks in rotated orders, so that at any moment the CUs of an XCD read
-  // different 256-byte columns of the 1 KB input rows (L2 channel = address bits above the 256-byte piece?)
-  const int rot = (tile * ORP_WS_ROT) % ncb;
-  auto phys = [&](int cb) { const int c = cb + rot; return c >= ncb ? c - ncb : c; };
-#else
-  auto phys = [&](int cb) { return cb; };
-#endif
-  const bool consumer = wave < 4;                                              // (waves w and w + 4 share a SIMD: one of each role per SIMD)
-  const int wq = wave & 3;
-
-  // ---- producer side ----------------------------------------------------------------------------------------------------------
-  const int q4 = lane >> 4, c4 = (lane & 15) * 4;
-  auto row_of = [&](int g) { return g * 16 + wq * 4 + q4; };
-  auto gather_issue = [&](int tap, int cb, int g, float4 (&v)[NB]) {
-    const int4 ix = sCi[row_of(g) * taps + tap];
-    const float* base = xin + phys(cb) * CBS + c4;
-    v[0] = *reinterpret_cast<const float4*>(base + (size_t)ix.x * P.Cin);
-    if constexpr (!PLAIN) {
-      v[1] = *reinterpret_cast<const float4*>(base + (size_t)ix.y * P.Cin);
-      v[2] = *reinterpret_cast<const float4*>(base + (size_t)ix.z * P.Cin);
-      v[3] = *reinterpret_cast<const float4*>(base + (size_t)ix.w * P.Cin);
-    }
-  };
-  auto combine_store = [&](int tap, int cbk, int g, const float4 (&v)[NB], int buf) {
-    const int m = row_of(g);
-    const float4 cw = sCw[m * taps + tap];
-    float s[4];
-    if constexpr (PLAIN) {
-      const bool in = cw.x != 0.f;
-      float4 x = v[0];
-      if (has_coef) {
-        const float4 ca = *reinterpret_cast<const float4*>(sAB + phys(cbk) * CBS + c4);
-        const float4 cb_ = *reinterpret_cast<const float4*>(sAB + P.Cin + phys(cbk) * CBS + c4);
-        x.x = fmaf(x.x, ca.x, cb_.x); x.y = fmaf(x.y, ca.y, cb_.y); x.z = fmaf(x.z, ca.z, cb_.z); x.w = fmaf(x.w, ca.w, cb_.w);
-        if (P.relu_in) { x.x = fmaxf(x.x, 0.f); x.y = fmaxf(x.y, 0.f); x.z = fmaxf(x.z, 0.f); x.w = fmaxf(x.w, 0.f); }
-      }
-      s[0] = in ? x.x : 0.f; s[1] = in ? x.y : 0.f; s[2] = in ? x.z : 0.f; s[3] = in ? x.w : 0.f;
-    } else {
-      auto bil = [&](float a, float b, float c, float d) {     // deform_conv_cuda_kernel.cu:111-113, left to right, unfused
-        return __fadd_rn(__fadd_rn(__fadd_rn(__fmul_rn(cw.x, a), __fmul_rn(cw.y, b)), __fmul_rn(cw.z, c)), __fmul_rn(cw.w, d));
-      };
-      s[0] = bil(v[0].x, v[1].x, v[2].x, v[3].x);
-      s[1] = bil(v[0].y, v[1].y, v[2].y, v[3].y);
-      s[2] = bil(v[0].z, v[1].z, v[2].z, v[3].z);
-      s[3] = bil(v[0].w, v[1].w, v[2].w, v[3].w);
-    }
-    uint16_t* dst = sA + (size_t)buf * NPL * PLANE + (size_t)m * ASTRS + c4;
-    _Float16 h[4], l[4];
-#pragma unroll
-    for (int i = 0; i < 4; i++) {
-      const float sv = s[i] * sx;
-      h[i] = (_Float16)sv;
-      l[i] = (_Float16)(sv - (float)h[i]);
-    }
-    const h2 h01 = {h[0], h[1]}, h23 = {h[2], h[3]}, l01 = {l[0], l[1]}, l23 = {l[2], l[3]};
-    *reinterpret_cast<uint2*>(dst) = make_uint2(__builtin_bit_cast(unsigned, h01), __builtin_bit_cast(unsigned, h23));
-    *reinterpret_cast<uint2*>(dst + PLANE) = make_uint2(__builtin_bit_cast(unsigned, l01), __builtin_bit_cast(unsigned, l23));
-  };
-
-  // ---- consumer side ----------------------------------------------------------------------------------------------------------
-  const int n_wave = blockIdx.y * 256 + wq * 64;
-  const int mrow = lane & 31, kg = lane >> 5;
-  const bool live = n_wave < P.Cout;                                           // Cout % 64 == 0
-  const uint16_t* wp = (L.planes ? L.planes : conv ? P.planes[1] : P.planes[0]) + ((size_t)kg * P.Cout + (live ? n_wave : 0) + mrow) * 8;
-  const size_t wblk = (size_t)2 * P.Cout * 8;
-  auto load_b = [&](int tap, int cb, int j, bf8 (&b)[NT][NPL]) {
-    const uint16_t* a = wp + ((size_t)tap * (P.Cin / 16) + phys(cb) * NCH + j) * wblk;
-#pragma unroll
-    for (int nt = 0; nt < NT; nt++)
-#pragma unroll
-      for (int pl = 0; pl < NPL; pl++) b[nt][pl] = *reinterpret_cast<const bf8*>(a + (size_t)pl * P.plane_stride + nt * 32 * 8);
-  };
-
-  int tap_n = 0, cb_n = 0, tap_n2 = 0, cb_n2 = 0;                             // (tap, channel block) of phase + 1 / phase + 2, clamped to the last phase
-  auto step = [&](int& t, int& c, int ph) {
-    if (ph + 1 < nphase) { if (++c == ncb) { c = 0; t++; } }
-  };
-  step(tap_n, cb_n, 0);
-  tap_n2 = tap_n; cb_n2 = cb_n;
-  step(tap_n2, cb_n2, 1);
-
-  // The two roles are two separate loops (not one loop with a branch inside): their register sets are then disjoint live ranges and
-  // the kernel needs max(consumer, producer) registers, not the sum.  Both execute exactly nphase + 1 barriers.
-  if (!consumer) {
-    float4 gA[RG][NB], gB[RG][NB];
-#pragma unroll
-    for (int r = 0; r < RG; r++) gather_issue(0, 0, r, gB[r]);
-#pragma unroll
-    for (int r = 0; r < RG; r++) gather_issue(tap_n, cb_n, r, gA[r]);          // the rows of phase 1
-#pragma unroll
-    for (int r = 0; r < RG; r++) combine_store(0, 0, r, gB[r], 0);
-    __syncthreads();
-#if ORP_WS_PPRIO
-    __builtin_amdgcn_s_setprio(ORP_WS_PPRIO);
-#endif
-    auto produce = [&](int phase, float4 (&g)[RG][NB], float4 (&gf)[RG][NB]) __attribute__((always_inline)) {
-      if (!(ORP_WS_DBG & 1)) {
-        if (!(ORP_WS_DBG & 16)) {
-#pragma unroll
-          for (int r = 0; r < RG; r++) gather_issue(tap_n2, cb_n2, r, gf[r]);  // the rows of phase + 2: a whole phase to land
-        }
-        __builtin_amdgcn_sched_barrier(0);
-        if (!(ORP_WS_DBG & 32)) {
-#pragma unroll
-          for (int r = 0; r < RG; r++) combine_store(tap_n, cb_n, r, g[r], (phase & 1) ^ 1);
-        } else {
-#pragma unroll
-          for (int r = 0; r < RG; r++) asm volatile("" :: "v"(g[r][0].x), "v"(g[r][NB - 1].w));
-        }
-      }
-      step(tap_n, cb_n, phase + 1);
-      step(tap_n2, cb_n2, phase + 2);
-      __syncthreads();
-    };
-#pragma unroll 1
-    for (int phase = 0; phase < nphase; phase += 2) {
-      produce(phase, gA, gB);
-      if (phase + 1 < nphase) produce(phase + 1, gB, gA);
-    }
-    return;
-  }
-
-  // Register plan of a consumer (256 per lane): accumulators MT x NT x 16 = 96; PLAIN: a second set for the two small partial
-  // products (SIDE, as in the symmetric kernel: the main chain then rounds once per 16 channels at the output's magnitude instead of
-  // three times -- the accuracy gate of tests/test_gpu_conv_split.py) = 192.  What is left holds ONE set of A fragments (24) and a weight
-  // ring of BR chunks (16 each).  Both are refilled IN PLACE right behind the MFMAs that read them (an issued MFMA has read its A / B
-  // operands: tests/checks/mfma_war.hip): a chunk's MFMAs run tile row by tile row (mt outer), the A fragments of row mt are re-read
-  // for the next chunk as soon as its 6 MFMAs are out -- 12 MFMAs = 384 cycles before their next use --, the weights of chunk j are
-  // replaced by those of chunk j + BR behind the chunk's last MFMA.
-  constexpr bool SIDE = PLAIN && ORP_WS_SIDE;
-  constexpr int BR = SIDE ? 2 : NCH;                                           // weight ring depth in chunks
-  bf8 bq[BR][NT][NPL];
-  bf8 af[MT][NPL];
-  floatx16 acc[MT][NT], side[SIDE ? MT : 1][SIDE ? NT : 1];
-#pragma unroll
-  for (int mt = 0; mt < MT; mt++)
-#pragma unroll
-    for (int nt = 0; nt < NT; nt++) { acc[mt][nt] = floatx16{0}; if (SIDE) side[SIDE ? mt : 0][SIDE ? nt : 0] = floatx16{0}; }
-#pragma unroll
-  for (int j = 0; j < BR; j++) load_b(0, 0, j, bq[j]);
-  __syncthreads();
-#if ORP_WS_PRIO
-  __builtin_amdgcn_s_setprio(ORP_WS_PRIO);
-#endif
-  int tap_c = 0, cb_c = 0;                                                     // (tap, channel block) of the current phase
-  auto load_a_row = [&](const uint16_t* abase, int j, int mt) {
-#pragma unroll
-    for (int pl = 0; pl < NPL; pl++)
-      if (!(ORP_WS_DBG & 8)) af[mt][pl] = *reinterpret_cast<const bf8*>(abase + (size_t)pl * PLANE + (size_t)mt * 32 * ASTRS + j * 16);
-  };
-  if (ORP_WS_DBG & 8) {
-#pragma unroll
-    for (int mt = 0; mt < MT; mt++)
-#pragma unroll
-      for (int pl = 0; pl < NPL; pl++) af[mt][pl] = bq[mt & (BR - 1)][pl][pl];
-  }
-#pragma unroll 1
-  for (int phase = 0; phase < nphase; phase++) {
-    const uint16_t* abase = sA + (size_t)(phase & 1) * NPL * PLANE + (size_t)mrow * ASTRS + 8 * kg;
-#pragma unroll
-    for (int mt = 0; mt < MT; mt++) load_a_row(abase, 0, mt);
-#pragma unroll
-    for (int j = 0; j < NCH; j++) {
-      __builtin_amdgcn_sched_barrier(0);
-#pragma unroll
-      for (int mt = 0; mt < MT; mt++) {
-        if (!(ORP_WS_DBG & 2)) {
-#pragma unroll
-          for (int t = 0; t < 3; t++) {                                        // lo*hi, hi*lo, hi*hi (smallest first)
-            const int pa = t == 0 ? 1 : 0, pb = t == 1 ? 1 : 0;
-#pragma unroll
-            for (int nt = 0; nt < NT; nt++) {
-              floatx16& d = (SIDE && t < 2) ? side[SIDE ? mt : 0][SIDE ? nt : 0] : acc[mt][nt];
-              const h8 av = __builtin_bit_cast(h8, af[mt][pa]), bv = __builtin_bit_cast(h8, bq[j % BR][nt][pb]);
-              if (OUT_NCHW) d = __builtin_amdgcn_mfma_f32_32x32x16_f16(bv, av, d, 0, 0, 0);
-              else          d = __builtin_amdgcn_mfma_f32_32x32x16_f16(av, bv, d, 0, 0, 0);
-            }
-          }
-        } else {
-          acc[0][0][0] += (float)af[mt][0][0] * (float)bq[j % BR][0][0][0];
-        }
-        __builtin_amdgcn_sched_barrier(0);
-        if (j + 1 < NCH) load_a_row(abase, j + 1, mt);                          // in place, for the next chunk
-        __builtin_amdgcn_sched_barrier(0);
-      }
-      if (!(ORP_WS_DBG & 4)) {                                                 // the ring slot of chunk j takes chunk j + BR (of the next phase when past this one's end)
-        if (j + BR < NCH) load_b(tap_c, cb_c, j + BR, bq[j % BR]);
-        else              load_b(tap_n, cb_n, j + BR - NCH, bq[j % BR]);
-      }
-      __builtin_amdgcn_sched_barrier(0);
-    }
-    tap_c = tap_n; cb_c = cb_n;
-    step(tap_n, cb_n, phase + 1);
-    __syncthreads();
-  }
-  if (SIDE) {
-#pragma unroll
-    for (int mt = 0; mt < MT; mt++)
-#pragma unroll
-      for (int nt = 0; nt < NT; nt++) acc[mt][nt] += side[SIDE ? mt : 0][SIDE ? nt : 0];
-  }
-
-  // ---- epilogue (consumers) ------------------------------------------------------------------------------------------------------
-  if (!live) return;
-#if ORP_WS_PRIO
-  __builtin_amdgcn_s_setprio(0);
-#endif
-  const float* bias = L.planes ? L.bias : conv ? P.bias[1] : P.bias[0];
-  float* outp = conv ? L.out[1] : L.out[0];
-  bool scaled = false;
-  if (PLAIN && !OUT_NCHW && P.gn_part) {
-#pragma unroll
-    for (int mt = 0; mt < MT; mt++)
-#pragma unroll
-      for (int nt = 0; nt < NT; nt++)
-#pragma unroll
-        for (int r = 0; r < 16; r++) acc[mt][nt][r] = orp::range_unscale(acc[mt][nt][r], kxw);
-    scaled = true;
-    const int cg = P.Cout / P.G, nrow = (int)(plim - p0);
-    auto row_ok = [&](int mt, int r) { return mt * 32 + (r & 3) + 8 * (r >> 2) + 4 * (lane >> 5) < nrow; };
-    auto group_sum = [&](float v) {
-      for (int o = 1; o < cg; o <<= 1) v += __shfl_xor(v, o, 64);
-      return v + __shfl_xor(v, 32, 64);
-    };
-    const float cnt = (float)(nrow * cg);
-#pragma unroll
-    for (int nt = 0; nt < NT; nt++) {
-      float sum = 0.f;
-#pragma unroll
-      for (int mt = 0; mt < MT; mt++)
-#pragma unroll
-        for (int r = 0; r < 16; r++) sum += row_ok(mt, r) ? acc[mt][nt][r] : 0.f;
-      const float mean = group_sum(sum) / cnt;
-      float m2 = 0.f, mx = 0.f;
-#pragma unroll
-      for (int mt = 0; mt < MT; mt++)
-#pragma unroll
-        for (int r = 0; r < 16; r++) {
-          const float d = acc[mt][nt][r] - mean;
-          m2 += row_ok(mt, r) ? d * d : 0.f;
-          mx = fmaxf(mx, row_ok(mt, r) ? fabsf(acc[mt][nt][r]) : 0.f);
-        }
-      m2 = group_sum(m2);
-      for (int o = 1; o < cg; o <<= 1) mx = fmaxf(mx, __shfl_xor(mx, o, 64));
-      mx = fmaxf(mx, __shfl_xor(mx, 32, 64));
-      if (lane < 32 && (lane & (cg - 1)) == 0)
-        P.gn_part[((size_t)conv * total_tiles + tile) * P.G + (n_wave + nt * 32 + lane) / cg] = make_float4(mean, m2, mx, cnt);
-    }
-  }
-  auto finish = [&](float v, int ch) { if (!scaled) v = orp::range_unscale(v, kxw); if (bias) v += bias[ch]; return P.relu ? fmaxf(v, 0.f) : v; };
-#pragma unroll
-  for (int mt = 0; mt < MT; mt++)
-#pragma unroll
-    for (int nt = 0; nt < NT; nt++) {
-      const int nb = n_wave + nt * 32;
-      if (OUT_NCHW) {
-        const long p = p0 + mt * 32 + (lane & 31);
-        if (p < plim) {
-          const int b = (int)(p / HoWo), hw = (int)(p - (long)b * HoWo);
-          float* ob = outp + (size_t)b * P.Cout * HoWo + hw;
-#pragma unroll
-          for (int r = 0; r < 16; r++) {
-            const int ch = nb + (r & 3) + 8 * (r >> 2) + 4 * (lane >> 5);
-            ob[(size_t)ch * HoWo] = finish(acc[mt][nt][r], ch);
-          }
-        }
-      } else {
-#pragma unroll
-        for (int r = 0; r < 16; r++) {
-          const int m = (r & 3) + 8 * (r >> 2) + 4 * (lane >> 5);
-          const long p = p0 + mt * 32 + m;
-          if (p < plim) outp[(size_t)p * P.Cout + nb + (lane & 31)] = finish(acc[mt][nt][r], nb + (lane & 31));
-        }
-      }
-    }
-}
-
 constexpr int kCoefCinMax = 512;                                              // orp_conv_split_multi_gn: input channels of a layer that normalises on the way in
 template <int MT, int NPL>
 constexpr size_t split_smem() {
   return (size_t)2 * NPL * 32 * MT * ASTRS * 2 + (sizeof(float4) + sizeof(int4)) * 32 * MT * kTapsMax + sizeof(float) * 2 * kCoefCinMax;
 }
 
-static const int g_ws = getenv("ORP_DCNS_WS") ? atoi(getenv("ORP_DCNS_WS")) : 0;   // 1: the wave-specialised kernel in the fp16-pieces mode (measured, not the default: see its header)
-
 template <int MT, int NPROD, bool OUT_NCHW, bool PLAIN>
 hipError_t launch_one(const FwdS& P, int tiles, int nblk_n, hipStream_t st) {
   constexpr size_t smem = split_smem<MT, NPROD == 3 ? 2 : 3>();
-  if constexpr (NPROD == 3) {
-    if (g_ws) {
-      struct TagW {};
-      hipError_t e = orp::set_max_dynamic_lds_once<TagW>(reinterpret_cast<const void*>(&dcn_fwd_split_ws_kernel<MT, OUT_NCHW, PLAIN>), smem);
-      if (e != hipSuccess) return e;
-      const int nx = P.nconv == 2 ? 4 : 8;
-      const int per = (tiles + nx - 1) / nx;
-      hipLaunchKernelGGL((dcn_fwd_split_ws_kernel<MT, OUT_NCHW, PLAIN>), dim3(per * 8, nblk_n), dim3(kThreadsS), smem, st, P, tiles);
-      return hipGetLastError();
-    }
-  }
   struct Tag {};
   hipError_t e = orp::set_max_dynamic_lds_once<Tag>(reinterpret_cast<const void*>(&dcn_fwd_split_kernel<MT, NPROD, OUT_NCHW, PLAIN>), smem);
   if (e != hipSuccess) return e;
@@ -1324,11 +732,7 @@ int set_amax_log(unsigned* log, int capacity_launches) {
 hipError_t launch(const Args& a, hipStream_t st) {
   FwdS P;
   P.dbg = nullptr;
-#if ORP_DCNS_TRACE
-  P.dbg = g_amax_log;                                     // the trace buffer (>= 16 + 2^20 + 2^20 words), every launch from its start
-#else
   if (a.nprod == 3 && g_amax_log && g_amax_log_next < g_amax_log_cap) P.dbg = g_amax_log + 4 * (g_amax_log_next++);
-#endif
   P.nlev = a.nlev; P.B = a.B; P.Cin = a.Cin; P.Cout = a.Cout;
   P.kh = a.kh; P.kw = a.kw; P.sh = a.sh; P.sw = a.sw; P.ph = a.ph; P.pw = a.pw; P.dh = a.dh; P.dw = a.dw;
   P.planes[0] = a.planes[0]; P.planes[1] = a.planes[1]; P.bias[0] = a.bias[0]; P.bias[1] = a.bias[1];

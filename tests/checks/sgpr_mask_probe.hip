@@ -1,6 +1,6 @@
 // Development aid (GPU box): the instruction sequence behind the wrong rows of the MT = 1 DeformConv split launch, in isolation.
 //
-// tests/checks/split_trace.py showed WHAT goes wrong: in a failing launch the bilinear coefficient table of a workgroup has the third
+// A trace build of the split kernel (round 5) showed WHAT goes wrong: in a failing launch the bilinear coefficient table of a workgroup has the third
 // weight (w.z = lh * hw, kept when b_ok && l_ok) equal to 0 in exactly the entries built by lanes 48..63 of one wave -- every other
 // word of the entry correct.  In the compiler's code for that block (llvm, gfx950, -O3) the select reads VCC = s[10:11] & s[4:5], both
 // written by v_cmp_*_e64 a few instructions earlier, between packed-fp32 instructions:

@@ -5,7 +5,6 @@ same kernel; the comparison runs on the device (no host synchronisation inside t
 configuration is kept and described (which positions, how many channels).
 
   SOAK_N=2000 KINDS=conv,dcn NPRODS=6,3 python tests/checks/soak_split_full.py
-  ORP_HIP_LIB=build_variants/liborp_hip_drain0.so ... (a library built with -DORP_DCNS_DRAIN=0)
 """
 import os
 import sys
