@@ -393,6 +393,33 @@ size_t orp_poly_nms_f64_workspace_bytes(int n);
 int orp_poly_nms_f64(const double* dets_sorted, int n, double iou_thr, int64_t* keep_out, int32_t* num_keep,
                      void* workspace, size_t workspace_bytes, void* stream);
 
+/* Segmented fp64 merge NMS: the merge step of the DOTA evaluation workflow for many (class, scene) segments in ONE launch
+ * sequence.  dets [n_total,9] DOUBLE on device (8 coordinates + score); seg_offsets [nseg+1] int32 (device): segment s is
+ * rows [seg_offsets[s], seg_offsets[s+1]), its size is read ON THE DEVICE; max_seg = host-known upper bound of a segment.
+ *   hbb_prefilter 1: py_cpu_nms_poly_fast (ResultMerge_multi_process.py:60-121): hbb_ovr from the fp64 horizontal boxes
+ *                    (areas with +1, overlap width / height without, the reference's expression and order), polyiou only
+ *                    where hbb_ovr > 0; a pair survives iff ovr <= iou_thr (NaN suppresses).  For iou_thr >= 0 blocks of
+ *                    pairs whose HBB extents do not overlap are skipped without any polyiou; a negative (or NaN) iou_thr
+ *                    is evaluated pair by pair (disjoint pairs then suppress, as in the reference).  The horizontal box is
+ *                    fmin / fmax of the corners: a NaN coordinate is dropped there, where numpy's np.min / np.maximum
+ *                    would propagate it, so boxes with NaN coordinates may be decided differently from the reference.
+ *                 0: py_cpu_nms_poly (ResultMerge.py:18-41): the decisions of orp_poly_nms_f64.
+ *   presorted     0: visiting order = score descending, then row index ascending (stable); -0.0 and +0.0 are one score.
+ *                    Scores are ordered as fp64 values, so they need not be exact fp32.  numpy's unstable
+ *                    `argsort()[::-1]` tie order is not reproduced; callers that need it sort on the host and pass 1.
+ *                 1: every segment's rows are already in visiting order.
+ *   keep_out      [n_total] int64: segment s's kept ORIGINAL (global) row indices in visiting order (the order mergesingle
+ *                 writes them), at keep_out[seg_offsets[s]]; num_keep [nseg] int32 (device) their counts.
+ * Limits: max_seg <= ORP_NMS_MAX_BOXES and nseg <= 65535, else ORP_ETOOBIG (nothing is truncated).  A segment table that
+ * breaks the contract (an entry outside [0, n_total], decreasing, a segment longer than max_seg) is detected on the device
+ * and turned into all-empty segments (num_keep 0), never followed outside the buffers.  Workspace (orp_poly_nms_f64_batched_workspace_bytes), with n = max(n_total, 1) and every part
+ * rounded up to 256 B: 4 (nseg+1) + 4 n + 240 n (box records) + 64 n (horizontal boxes) + 8 n ceil(max_seg/64) (mask) +
+ * 4 nseg + 32 KiB nseg (non-zero mask word lists) + 24 n (sort keys / values) + the radix sort's scratch. */
+size_t orp_poly_nms_f64_batched_workspace_bytes(int n_total, int nseg, int max_seg);
+int orp_poly_nms_f64_batched(const double* dets, int n_total, const int32_t* seg_offsets, int nseg, int max_seg,
+                             double iou_thr, int hbb_prefilter, int presorted, int64_t* keep_out, int32_t* num_keep,
+                             void* workspace, size_t workspace_bytes, void* stream);
+
 /* Detection -> ground-truth matching of the DOTA Task1 evaluation (DOTA_devkit/dota_evaluation_task1.py:160-206, the
  * per-detection python loop of voc_eval): for detection d of image det_image[d], over the ground truths
  * gts[gt_offsets[img] .. gt_offsets[img + 1]) that pass the fp64 horizontal-box pre-filter (`overlaps > 0`, "+ 1." pixel

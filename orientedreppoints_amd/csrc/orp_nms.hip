@@ -27,7 +27,9 @@
 //      block's words only); otherwise the dense pass walks the block rows with the next row's mask words prefetched.
 //      Either way the keep flags are scattered back to original indices and compacted in ascending order (popcount
 //      scan), so the host never sees the mask;
-//   4. fp64 instantiation of the same core for the merge NMS of the DOTA evaluation workflow (orp_poly_nms_f64).
+//   4. fp64 instantiation of the same core for the merge NMS of the DOTA evaluation workflow (orp_poly_nms_f64), and its
+//      segmented form for whole scenes (orp_poly_nms_f64_batched): every (class, scene) segment in one launch sequence,
+//      with the horizontal-box pre-filter of ResultMerge_multi_process.py (py_cpu_nms_poly_fast) or without it.
 // The IoU arithmetic is bit-identical to the reference's fp32 devrIoU / devPolyIoU (see orp_geom.hpp).
 #include <hip/hip_runtime.h>
 #include <hipcub/hipcub.hpp>
@@ -538,6 +540,180 @@ nms_mask_f64_kernel(const orp::QuadPrepT<double>* __restrict__ prep, int n, int 
   }
 }
 
+// ---- segmented fp64 merge NMS (orp_poly_nms_f64_batched): every (class, scene) segment in one launch sequence ----------
+// Stage 1 orders by (score descending, index ascending) with two stable radix sorts (the fp64 score's order-preserving
+// 64-bit image, then the segment id) or takes the caller's order (presorted); the prepare kernel writes the QuadPrep record
+// and the horizontal box of every box at its position.  Stage 2 (below) is the capacity-bounded upper-triangular tile loop
+// of nms_mask_loop_kernel with one pair per lane; stage 3 is nms_sweep_kernel with its sparse side list.
+struct HbbF64 { double x1, y1, x2, y2, area, pad[3]; };   // ResultMerge_multi_process.py:61-67 (+1 in the area)
+
+__device__ __forceinline__ u64 double_flip_desc(double d) {
+  // order-preserving double -> u64 map, inverted so that an ASCENDING radix sort yields scores DESCENDING
+  const u64 u = (u64)__double_as_longlong(d);
+  const u64 mask = (u >> 63) ? ~0ull : 0x8000000000000000ull;
+  return ~(u ^ mask);
+}
+
+// seg_off (caller's, device) -> the workspace copy, checked in parallel by one workgroup so that a broken table cannot
+// address outside the buffers: every entry within [0, n_total], non-decreasing, no segment longer than max_seg.  A table
+// that breaks any of these is replaced by all-empty segments (num_keep 0 everywhere).
+constexpr int kSegCheckThreads = 1024;
+__global__ void __launch_bounds__(kSegCheckThreads)
+seg_check_kernel(const int32_t* __restrict__ src, int nseg, int n_total, int max_seg, int32_t* __restrict__ dst) {
+  __shared__ int bad;
+  if (threadIdx.x == 0) bad = 0;
+  __syncthreads();
+  int my_bad = 0;
+  for (int s = threadIdx.x; s <= nseg; s += kSegCheckThreads) {
+    const int v = src[s];
+    my_bad |= (v < 0) | (v > n_total);
+    if (s > 0) { const int d = v - src[s - 1]; my_bad |= (d < 0) | (d > max_seg); }
+  }
+  if (my_bad) atomicOr(&bad, 1);
+  __syncthreads();
+  for (int s = threadIdx.x; s <= nseg; s += kSegCheckThreads) dst[s] = bad ? 0 : src[s];
+}
+
+__global__ void make_keys_f64_kernel(const double* __restrict__ dets, int n, u64* __restrict__ keys, int32_t* __restrict__ vals) {
+  const int i = blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= n) return;
+  const double s = dets[(size_t)i * 9 + 8];
+  keys[i] = double_flip_desc(s == 0.0 ? 0.0 : s);          // -0.0 ties with +0.0 (index ascending), as the comparison does
+  vals[i] = i;
+}
+
+// keys[k] = 1 + segment of row vals[k] (binary search); rows before the first segment get 0, rows after the last nseg + 1
+__global__ void seg_keys_kernel(const int32_t* __restrict__ vals, int n, const int32_t* __restrict__ seg_off, int nseg,
+                                u64* __restrict__ keys) {
+  const int k = blockIdx.x * blockDim.x + threadIdx.x;
+  if (k >= n) return;
+  const int i = vals[k];
+  if (i < seg_off[0]) { keys[k] = 0ull; return; }
+  if (i >= seg_off[nseg]) { keys[k] = (u64)nseg + 1ull; return; }
+  int lo = 0, hi = nseg;   // seg_off[lo] <= i < seg_off[hi]
+  while (hi - lo > 1) { const int mid = (lo + hi) >> 1; if (seg_off[mid] <= i) lo = mid; else hi = mid; }
+  keys[k] = (u64)lo + 1ull;
+}
+
+__global__ void prep_boxes_f64_seg_kernel(const double* __restrict__ dets, const int32_t* __restrict__ order, int n,
+                                          orp::QuadPrepT<double>* __restrict__ prep, HbbF64* __restrict__ hbb,
+                                          int* __restrict__ nz_count, int nseg) {
+  const int i = blockIdx.x * blockDim.x + threadIdx.x;
+  if (i < nseg) nz_count[i] = 0;
+  if (i >= n) return;
+  const double* d = dets + (size_t)order[i] * 9;
+  double q8[8];
+#pragma unroll
+  for (int k = 0; k < 8; k++) q8[k] = d[k];
+  orp::QuadPrepT<double> p;
+  orp::quad_prepare<double>(q8, p);
+  prep[i] = p;
+  HbbF64 h;
+  h.x1 = fmin(fmin(q8[0], q8[2]), fmin(q8[4], q8[6]));
+  h.y1 = fmin(fmin(q8[1], q8[3]), fmin(q8[5], q8[7]));
+  h.x2 = fmax(fmax(q8[0], q8[2]), fmax(q8[4], q8[6]));
+  h.y2 = fmax(fmax(q8[1], q8[3]), fmax(q8[5], q8[7]));
+  h.area = (h.x2 - h.x1 + 1) * (h.y2 - h.y1 + 1);
+  h.pad[0] = h.pad[1] = h.pad[2] = 0.0;
+  hbb[i] = h;
+}
+
+__device__ __forceinline__ double wave_min_f64(double v) {
+#pragma unroll
+  for (int off = 32; off > 0; off >>= 1) v = fmin(v, __shfl_xor(v, off, 64));
+  return v;
+}
+__device__ __forceinline__ double wave_max_f64(double v) {
+#pragma unroll
+  for (int off = 32; off > 0; off >>= 1) v = fmax(v, __shfl_xor(v, off, 64));
+  return v;
+}
+
+// grid = (bounded tile count, 1, nseg); block = 256.  Workgroup-level loop over the upper-triangular (4R rows x 64 columns)
+// tiles of the segment's ACTUAL size (TileMap); a wave owns R rows of the tile, lane = column.  hbb_prefilter (the fast
+// merge, ResultMerge_multi_process.py:85-113): a pair's polygon IoU is only taken where its HBB overlap ratio is > 0,
+// and for thr >= 0 a wave whose rows' HBB extent does not overlap the columns' extent (all coordinates finite) emits
+// zero words without evaluating any pair: every such pair has hbb_ovr == 0 <= thr and survives.
+__global__ void __launch_bounds__(kMaskThreads)
+nms_mask_f64_seg_kernel(const orp::QuadPrepT<double>* __restrict__ prep, const HbbF64* __restrict__ hbb,
+                        const int32_t* __restrict__ seg_off, int rows_per_wave, int mask_stride, double thr, int hbb_prefilter,
+                        u64* __restrict__ mask, int* __restrict__ nz_count, unsigned* __restrict__ nz_rc) {
+  const int seg = blockIdx.z;
+  const int s0 = seg_off[seg], n = seg_off[seg + 1] - s0;
+  if (n <= 0) return;
+  const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
+  const int rpb = rows_per_wave * (kMaskThreads / 64);
+  TileMap M;
+  M.init(n, rpb);
+  const long total_tiles = M.n_full + M.n_diag;
+  const bool may_skip = hbb_prefilter && (thr >= 0.0);
+  int* my_count = nz_count + seg;
+  unsigned* my_rc = nz_rc + (size_t)seg * kNzCap;
+  for (long k = blockIdx.x; k < total_tiles; k += gridDim.x) {
+    int g, c;
+    M.decode_diag_last(k, g, c);
+    const int r_first = g * rpb + wave * rows_per_wave;          // wave-uniform
+    if (r_first >= n) continue;
+    const int r_last = min(r_first + rows_per_wave, n);
+    const int col = c * 64 + lane;
+    const bool col_ok = col < n;
+    const HbbF64 ch = hbb[s0 + (col_ok ? col : 0)];
+    bool skip = false;
+    if (may_skip) {
+      // this wave's rows (lanes < rows_per_wave) against the tile's columns
+      const int rl = r_first + lane;
+      const bool row_ok = rl < r_last;
+      const HbbF64 rh = hbb[s0 + (row_ok ? rl : r_first)];
+      const double inf = __builtin_huge_val();
+      const bool fin = (!col_ok || (isfinite(ch.x1) && isfinite(ch.y1) && isfinite(ch.x2) && isfinite(ch.y2))) &&
+                       (!row_ok || (isfinite(rh.x1) && isfinite(rh.y1) && isfinite(rh.x2) && isfinite(rh.y2)));
+      const double cx1 = wave_min_f64(col_ok ? ch.x1 : inf), cy1 = wave_min_f64(col_ok ? ch.y1 : inf);
+      const double cx2 = wave_max_f64(col_ok ? ch.x2 : -inf), cy2 = wave_max_f64(col_ok ? ch.y2 : -inf);
+      const double rx1 = wave_min_f64(row_ok ? rh.x1 : inf), ry1 = wave_min_f64(row_ok ? rh.y1 : inf);
+      const double rx2 = wave_max_f64(row_ok ? rh.x2 : -inf), ry2 = wave_max_f64(row_ok ? rh.y2 : -inf);
+      skip = (__ballot(!fin) == 0ull) && ((rx2 <= cx1) || (cx2 <= rx1) || (ry2 <= cy1) || (cy2 <= ry1));
+    }
+    if (skip) {
+      if (lane < r_last - r_first) mask[(size_t)(c) * mask_stride + (s0 + r_first + lane)] = 0ull;
+      continue;
+    }
+    orp::QuadPrepT<double> cp;
+    if (col_ok) {
+      cp = prep[s0 + col];
+    } else {
+#pragma unroll
+      for (int q = 0; q < 4; q++) { cp.ax[q] = cp.ay[q] = cp.bx[q] = cp.by[q] = cp.vx[q] = cp.vy[q] = 0.0; cp.s[q] = 0; }
+      cp.area_abs = 0.0; cp.force_slow = 0; cp.mabs = 0.0; cp.pad0 = 0.0;
+    }
+    for (int r = r_first; r < r_last; r++) {
+      bool hit = false;
+      if (col_ok && col > r) {
+        const HbbF64* rh = hbb + (s0 + r);                       // uniform address -> scalar loads
+        double ovr;
+        if (hbb_prefilter) {
+          // ResultMerge_multi_process.py:85-100, the same operations in the same order (no contraction in this file)
+          const double w = fmax(0.0, fmin(rh->x2, ch.x2) - fmax(rh->x1, ch.x1));
+          const double h = fmax(0.0, fmin(rh->y2, ch.y2) - fmax(rh->y1, ch.y1));
+          const double hi = w * h;
+          ovr = hi / (rh->area + ch.area - hi);
+          if (ovr > 0) ovr = orp::quad_iou_two_phase_t<double, false>(prep + (s0 + r), &cp);
+        } else {
+          ovr = orp::quad_iou_two_phase_t<double, false>(prep + (s0 + r), &cp);
+        }
+        hit = !(ovr <= thr);                                     // `inds = np.where(ovr <= thresh)` survive
+      }
+      const u64 bits = __ballot(hit);
+      if (lane == 0) {
+        mask[(size_t)(c) * mask_stride + (s0 + r)] = bits;
+        if (bits) {                                              // sparse side list of the segment (nms_sweep_kernel)
+          const int pos = atomicAdd(my_count, 1);
+          if (pos < kNzCap) my_rc[pos] = ((unsigned)r << 11) | (unsigned)c;
+        }
+      }
+    }
+  }
+}
+
 // ---- sweep + compaction kernel --------------------------------------------------------------------------------
 // one workgroup per segment.  All LDS is dynamic (16-B aligned carve, cdna guide G17):
 //   [0,8) kept word | [16, 16+4096) scan scratch | removed[cb] u64 | keepbits[cb] u64 | origbits[cb] u64
@@ -1040,6 +1216,110 @@ int launch_nms(const float* dets, int n_total, const int32_t* seg_off_dev, int n
   return e == hipSuccess ? ORP_OK : (int)e;
 }
 
+// ---- segmented fp64 merge NMS: workspace layout and launch sequence ---------------------------------------------------
+struct NmsF64Layout {
+  size_t off_seg, off_order, off_prep, off_hbb, off_mask, off_nzc, off_nzrc, off_keys_a, off_keys_b, off_vals_a, off_vals_b,
+      off_cub, cub_bytes, total;
+};
+
+inline int seg_key_bits(int nseg) {   // keys 0 .. nseg + 1 (seg_keys_kernel)
+  int b = 1;
+  while (b < 63 && (1LL << b) <= (long long)nseg + 1) b++;
+  return b;
+}
+
+NmsF64Layout nms_f64_layout(int n_total, int nseg, int max_seg) {
+  NmsF64Layout L;
+  size_t o = 0;
+  const size_t n = (size_t)(n_total > 0 ? n_total : 1);
+  const size_t ns = (size_t)(nseg > 0 ? nseg : 1);
+  const size_t cb = (size_t)((max_seg + 63) / 64 > 0 ? (max_seg + 63) / 64 : 1);
+  L.off_seg = o; o += align256(sizeof(int32_t) * (ns + 1));
+  L.off_order = o; o += align256(sizeof(int32_t) * n);
+  L.off_prep = o; o += align256(sizeof(orp::QuadPrepT<double>) * n);
+  L.off_hbb = o; o += align256(sizeof(HbbF64) * n);
+  L.off_mask = o; o += align256(sizeof(u64) * n * cb);
+  L.off_nzc = o; o += align256(sizeof(int) * ns);
+  L.off_nzrc = o; o += align256(sizeof(unsigned) * kNzCap * ns);
+  L.off_keys_a = o; o += align256(sizeof(u64) * n);
+  L.off_keys_b = o; o += align256(sizeof(u64) * n);
+  L.off_vals_a = o; o += align256(sizeof(int32_t) * n);
+  L.off_vals_b = o; o += align256(sizeof(int32_t) * n);
+  size_t c1 = 0, c2 = 0;
+  hipcub::DeviceRadixSort::SortPairs((void*)nullptr, c1, (const u64*)nullptr, (u64*)nullptr, (const int32_t*)nullptr,
+                                     (int32_t*)nullptr, (int)n, 0, 64, (hipStream_t)0);
+  hipcub::DeviceRadixSort::SortPairs((void*)nullptr, c2, (const u64*)nullptr, (u64*)nullptr, (const int32_t*)nullptr,
+                                     (int32_t*)nullptr, (int)n, 0, seg_key_bits(nseg), (hipStream_t)0);
+  L.cub_bytes = c1 > c2 ? c1 : c2;
+  L.off_cub = o; o += align256(L.cub_bytes);
+  L.total = o;
+  return L;
+}
+
+int launch_nms_f64(const double* dets, int n_total, const int32_t* seg_off_dev, int nseg, int max_seg, double thr,
+                   int hbb_prefilter, int presorted, int64_t* keep_out, int32_t* num_keep, void* ws, size_t ws_bytes,
+                   hipStream_t st) {
+  if (n_total < 0 || nseg < 0 || max_seg < 0 || (!dets && n_total > 0) || (!seg_off_dev && nseg > 0) || !keep_out || !num_keep)
+    return ORP_EINVAL;
+  if ((hbb_prefilter != 0 && hbb_prefilter != 1) || (presorted != 0 && presorted != 1)) return ORP_EINVAL;
+  if (max_seg > ORP_NMS_MAX_BOXES || nseg > 65535) return ORP_ETOOBIG;
+  if (nseg == 0) return ORP_OK;
+  if (n_total == 0 || max_seg == 0) {
+    hipError_t e = orp::fill_async(num_keep, 0, sizeof(int32_t) * (size_t)nseg, st);
+    return e == hipSuccess ? ORP_OK : (int)e;
+  }
+  const NmsF64Layout L = nms_f64_layout(n_total, nseg, max_seg);
+  if (!ws || ws_bytes < L.total) return ORP_EWORKSPACE;
+  char* base = reinterpret_cast<char*>(ws);
+  int32_t* seg = reinterpret_cast<int32_t*>(base + L.off_seg);
+  int32_t* order = reinterpret_cast<int32_t*>(base + L.off_order);
+  orp::QuadPrepT<double>* prep = reinterpret_cast<orp::QuadPrepT<double>*>(base + L.off_prep);
+  HbbF64* hbb = reinterpret_cast<HbbF64*>(base + L.off_hbb);
+  u64* mask = reinterpret_cast<u64*>(base + L.off_mask);
+  int* nz_count = reinterpret_cast<int*>(base + L.off_nzc);
+  unsigned* nz_rc = reinterpret_cast<unsigned*>(base + L.off_nzrc);
+
+  hipLaunchKernelGGL(seg_check_kernel, dim3(1), dim3(kSegCheckThreads), 0, st, seg_off_dev, nseg, n_total, max_seg, seg);
+  // ---- stage 1: visiting order + per-box records ----------------------------------------------------------------------
+  const int tb = 256;
+  const int nb = ((n_total > nseg ? n_total : nseg) + tb - 1) / tb;
+  if (presorted) {
+    hipLaunchKernelGGL(iota_kernel, dim3(nb), dim3(tb), 0, st, order, n_total);
+  } else {
+    u64* keys_a = reinterpret_cast<u64*>(base + L.off_keys_a);
+    u64* keys_b = reinterpret_cast<u64*>(base + L.off_keys_b);
+    int32_t* vals_a = reinterpret_cast<int32_t*>(base + L.off_vals_a);
+    int32_t* vals_b = reinterpret_cast<int32_t*>(base + L.off_vals_b);
+    hipLaunchKernelGGL(make_keys_f64_kernel, dim3(nb), dim3(tb), 0, st, dets, n_total, keys_a, vals_a);
+    size_t cub_bytes = L.cub_bytes;
+    hipError_t e = hipcub::DeviceRadixSort::SortPairs(base + L.off_cub, cub_bytes, keys_a, keys_b, vals_a, vals_b, n_total,
+                                                      0, 64, st);
+    if (e != hipSuccess) return (int)e;
+    // LSD radix sorts are stable: sorting the score order by segment keeps (score desc, index asc) inside each segment
+    hipLaunchKernelGGL(seg_keys_kernel, dim3(nb), dim3(tb), 0, st, vals_b, n_total, seg, nseg, keys_a);
+    cub_bytes = L.cub_bytes;
+    e = hipcub::DeviceRadixSort::SortPairs(base + L.off_cub, cub_bytes, keys_a, keys_b, vals_b, order, n_total, 0,
+                                           seg_key_bits(nseg), st);
+    if (e != hipSuccess) return (int)e;
+  }
+  hipLaunchKernelGGL(prep_boxes_f64_seg_kernel, dim3(nb), dim3(tb), 0, st, dets, order, n_total, prep, hbb, nz_count, nseg);
+  // ---- stage 2: the suppression mask (16-row tiles, bounded grid over the actual counts, as launch_nms' capacity case) -
+  const int max_cb = (max_seg + 63) / 64;
+  const int R = 4;
+  const int rpb = R * (kMaskThreads / 64);
+  long ntile = ((long)max_cb * ((max_seg + rpb - 1) / rpb)) / 2 + max_cb;
+  const long cap_wg = 4096 / (nseg < 8 ? nseg : 8);
+  if (ntile > cap_wg) ntile = cap_wg;
+  hipLaunchKernelGGL(nms_mask_f64_seg_kernel, dim3((unsigned)ntile, 1, nseg), dim3(kMaskThreads), 0, st, prep, hbb, seg, R,
+                     n_total, thr, hbb_prefilter, mask, nz_count, nz_rc);
+  // ---- stage 3: greedy sweep + compaction, kept original indices in visiting order ---------------------------------------
+  if (sweep_attr() != hipSuccess) return (int)sweep_attr();
+  hipLaunchKernelGGL(nms_sweep_kernel, dim3(nseg), dim3(kSweepThreads), sweep_smem_bytes(max_cb), st, mask, order, seg,
+                     n_total, 1, keep_out, num_keep, nz_count, nz_rc);
+  hipError_t e = hipGetLastError();
+  return e == hipSuccess ? ORP_OK : (int)e;
+}
+
 }  // namespace
 
 extern "C" {
@@ -1155,6 +1435,18 @@ int orp_poly_nms_f64(const double* dets_sorted, int n, double iou_thr, int64_t* 
                      num_keep, (const int*)nullptr, (const unsigned*)nullptr);
   hipError_t e = hipGetLastError();
   return e == hipSuccess ? ORP_OK : (int)e;
+}
+
+// Segmented fp64 merge NMS (include/orp_hip.h): every (class, scene) segment in one launch sequence.
+size_t orp_poly_nms_f64_batched_workspace_bytes(int n_total, int nseg, int max_seg) {
+  return nms_f64_layout(n_total, nseg, max_seg).total;
+}
+
+int orp_poly_nms_f64_batched(const double* dets, int n_total, const int32_t* seg_offsets, int nseg, int max_seg,
+                             double iou_thr, int hbb_prefilter, int presorted, int64_t* keep_out, int32_t* num_keep,
+                             void* workspace, size_t workspace_bytes, void* stream) {
+  return launch_nms_f64(dets, n_total, seg_offsets, nseg, max_seg, iou_thr, hbb_prefilter, presorted, keep_out, num_keep,
+                        workspace, workspace_bytes, (hipStream_t)stream);
 }
 
 }  // extern "C"

@@ -66,6 +66,33 @@ def rnms_batched_device(dets, seg_offsets, max_seg, iou_thr, flavor=0):
     return keep, num[:nseg]
 
 
+def poly_nms_f64_batched_device(dets, seg_offsets, max_seg, iou_thr, hbb_prefilter=True, presorted=False):
+    """fp64 merge NMS of many (class, scene) segments in one launch sequence (`orp_poly_nms_f64_batched`).
+    dets [N,9] float64 CUDA (8 coordinates + score); seg_offsets int32 [S+1]; hbb_prefilter: py_cpu_nms_poly_fast
+    (True) or py_cpu_nms_poly (False) semantics; presorted: rows of every segment already in visiting order, else
+    (score descending, index ascending).  Returns (keep int64 [N] -- segment s's kept global row indices in visiting
+    order at keep[seg_offsets[s]:] --, num_keep int32 [S]), both on the device."""
+    _lib.require_cuda(dets, "dets")
+    if dets.dim() != 2 or dets.size(1) != 9:
+        raise ValueError("dets must be [N, 9] (8 corner coordinates + score)")
+    if int(max_seg) > _lib.ORP_NMS_MAX_BOXES:
+        raise _lib.OrpHipError("poly_nms_f64_batched: a segment of %d boxes exceeds ORP_NMS_MAX_BOXES" % int(max_seg))
+    L = _lib.lib()
+    d = dets.detach().to(torch.float64).contiguous()
+    so = seg_offsets.to(device=d.device, dtype=torch.int32).contiguous()
+    n, nseg = d.size(0), so.numel() - 1
+    keep = torch.empty((max(n, 1),), dtype=torch.long, device=d.device)
+    num = torch.zeros((max(nseg, 1),), dtype=torch.int32, device=d.device)
+    nbytes = L.orp_poly_nms_f64_batched_workspace_bytes(n, nseg, int(max_seg))
+    ws = _lib.workspace(d.device, nbytes)
+    with torch.cuda.device(d.device):
+        rc = L.orp_poly_nms_f64_batched(_lib.ptr(d), n, _lib.ptr(so), nseg, int(max_seg), float(iou_thr),
+                                        int(bool(hbb_prefilter)), int(bool(presorted)), _lib.ptr(keep), _lib.ptr(num),
+                                        _lib.ptr(ws), ws.numel(), _lib.stream_of(d))
+    _lib.check(rc, "orp_poly_nms_f64_batched")
+    return keep[:n], num[:nseg]
+
+
 def rnms(dets, iou_thr, device_id=None):
     """Signature and behaviour of mmdet/ops/nms/nms_wrapper.py:177-199."""
     # convert dets (tensor or numpy array) to tensor
