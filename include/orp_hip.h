@@ -420,6 +420,34 @@ int orp_poly_nms_f64_batched(const double* dets, int n_total, const int32_t* seg
                              double iou_thr, int hbb_prefilter, int presorted, int64_t* keep_out, int32_t* num_keep,
                              void* workspace, size_t workspace_bytes, void* stream);
 
+/* Whole-scene inference: the two device steps between a scene and the per-patch detector (no reference counterpart as
+ * device code: the reference crops patches to files with SplitOnlyImage.py:27-57, normalises each on the host in its test
+ * pipeline and carries patch results to the merge as Task1 text files).
+ *
+ * orp_scene_tiles: tile t of out [num_tiles,3,tile,tile] (contiguous, 16-byte aligned; out_dtype 0 float32, 1 float16,
+ * 2 bfloat16) = the tile x tile crop of scene (uint8 [height,width,3], pixel stride 3, row_stride_bytes between rows) at
+ * origins[t] = (left, up) -- int32 [num_tiles,2] ON THE DEVICE --, channels reversed when to_rgb, each value
+ * (float32(v) - mean[c]) / std[c] in fp32 (IEEE division; mean / std per OUTPUT channel, 3 floats on the host), rounded once
+ * to out_dtype: mmcv.imnormalize bit for bit.  Pixels of a tile outside the scene are written as 0 (Pad after Normalize) and
+ * nothing outside the scene's rows is read.  tile % 4 == 0 (float32) or tile % 8 == 0 (16-bit types), else ORP_EINVAL;
+ * num_tiles <= 65535.
+ *
+ * orp_scene_collect: packed [num_tiles, max_rows + 1, 28] f32 = the per-tile results of the static post-processing (rows of
+ * 18 point coordinates, 8 corners, score, label; last row = count, overflow flag) -> dets [capacity_rows,9] DOUBLE:
+ * x = ((double)x + left) / rate, y = ((double)y + up) / rate (poly2origpoly, ResultMerge_multi_process.py:175-180, on the
+ * exactly widened value), score widened; seg_offsets [num_classes+1] int32: class c's rows are
+ * [seg_offsets[c], seg_offsets[c+1]), inside a class tile ascending, then packed row ascending (deterministic);
+ * src [capacity_rows,2] int32 = (tile, packed row) of every output row; flag[0] != 0 if a tile reported overflow (its rows
+ * are left out).  Rows whose label is outside [0, num_classes) are dropped; rows past capacity_rows are not written
+ * (num_tiles * max_rows always suffices).  num_classes <= 8192. */
+int orp_scene_tiles(const uint8_t* scene, int height, int width, long long row_stride_bytes, const int32_t* origins,
+                    int num_tiles, int tile, const float* mean_host, const float* std_host, int to_rgb, int out_dtype,
+                    void* out, void* stream);
+size_t orp_scene_collect_workspace_bytes(int num_tiles, int num_classes);
+int orp_scene_collect(const float* packed, int num_tiles, int max_rows, const int32_t* origins, double rate, int num_classes,
+                      int capacity_rows, double* dets, int32_t* seg_offsets, int32_t* src, int32_t* flag, void* workspace,
+                      size_t workspace_bytes, void* stream);
+
 /* Detection -> ground-truth matching of the DOTA Task1 evaluation (DOTA_devkit/dota_evaluation_task1.py:160-206, the
  * per-detection python loop of voc_eval): for detection d of image det_image[d], over the ground truths
  * gts[gt_offsets[img] .. gt_offsets[img + 1]) that pass the fp64 horizontal-box pre-filter (`overlaps > 0`, "+ 1." pixel

@@ -38,6 +38,7 @@ SOURCES = [
     ("orp_assign.hip", ["-ffp-contract=off"]),
     ("orp_postproc.hip", ["-ffp-contract=off"]),
     ("orp_soft_rnms.hip", ["-ffp-contract=off"]),
+    ("orp_scene.hip", ["-ffp-contract=off"]),
     ("orp_eval.hip", ["-ffp-contract=off"]),
     ("orp_train.hip", ["-ffp-contract=off"]),
     ("orp_norm.hip", []),

@@ -8,3 +8,4 @@ from . import resnet, swin, fpn, losses, assigners, orientedreppoints_head, dete
 from .orientedreppoints_head import OrientedRepPointsHead  # noqa: F401
 from .detector import OrientedRepPointsDetector  # noqa: F401
 from .graph_inference import GraphedInference, PipelinedInference  # noqa: F401
+from .scene_inference import SceneInference  # noqa: F401

@@ -139,10 +139,9 @@ class PipelinedInference(object):
                 return self.model.simple_test_batch(img, self.metas)
         return results
 
-    def submit(self, img):
-        k = self.count % self.depth
-        out = self._collect(k) if self.pending[k] is not None else None
-        slot, s = self.slots[k], self.streams[k]
+    def _fresh_slot(self, k):
+        """Slot k, captured again first if the model's parameters changed since its capture."""
+        slot = self.slots[k]
         if _param_fingerprint(slot._tensors) != slot._fingerprint:
             head = self.model.bbox_head
             prev, head.tower_streams = getattr(head, 'tower_streams', None), False
@@ -151,6 +150,29 @@ class PipelinedInference(object):
             finally:
                 head.tower_streams = prev
             self.host[k] = [torch.empty(p.shape, dtype=p.dtype, pin_memory=True) for p in slot.packed]
+        return slot
+
+    def submit_device(self, fill, sink):
+        """`submit` for a producer and a consumer that live on the device (`SceneInference`): `fill(static_img)` writes the
+        next slot's input and `sink(packed)` reads its packed results, both on the slot's stream around the replay.  No
+        host copy and nothing pending: stream order alone keeps a slot's replays apart, the host never waits, and the
+        caller makes its own stream wait on `streams` before it uses what `sink` wrote.  Not to be mixed with `submit`
+        while results of that are in flight."""
+        k = self.count % self.depth
+        if self.pending[k] is not None:
+            raise RuntimeError("PipelinedInference.submit_device: results of submit() are still in flight; flush() first")
+        slot, s = self._fresh_slot(k), self.streams[k]
+        s.wait_stream(torch.cuda.current_stream(slot.static_img.device))
+        with torch.cuda.stream(s):
+            fill(slot.static_img)
+            slot.graph.replay()
+            sink(slot.packed)
+        self.count += 1
+
+    def submit(self, img):
+        k = self.count % self.depth
+        out = self._collect(k) if self.pending[k] is not None else None
+        slot, s = self._fresh_slot(k), self.streams[k]
         s.wait_stream(torch.cuda.current_stream(img.device))     # the image may have been produced on the caller's stream
         with torch.cuda.stream(s):
             slot.static_img.copy_(img, non_blocking=True)

@@ -1,0 +1,236 @@
+"""Whole-scene detection: a DOTA scene (thousands of pixels a side) in, merged scene-coordinate detections per class out,
+with the scene uploaded once as uint8 and every later step on the device.
+
+Replaces the reference's chain `DOTA_devkit/SplitOnlyImage.py` (patches to files) -> `tools/test.py` (per-patch pipeline on the
+host, results to a pickle) -> `tools/parse_pkl/parse_pkl_mege_results_for_dota_evaluation.py` (Task1 text files per class) ->
+`DOTA_devkit/ResultMerge_multi_process.py:mergebypoly` (parse, translate, NMS per class):
+
+    tile plan (`dota_devkit.img_split`)  ->  `orp_scene_tiles` straight into a captured graph's input buffer  ->  graph
+    replay (`PipelinedInference`)  ->  packed results stay on the device  ->  `orp_scene_collect`  ->  one
+    `orp_poly_nms_f64_batched`  ->  one gather, one D2H.
+"""
+import os
+
+import numpy as np
+import torch
+import torch.nn.functional as F
+
+from ..dota_devkit.img_split import scaled_size, split_origins
+from ..mmdet_ops.nms_wrapper import poly_nms_f64_batched_device
+from ..mmdet_ops.scene_ops import scene_collect, scene_tiles
+from .graph_inference import PipelinedInference
+
+DOTA_CLASSES = ('plane', 'baseball-diamond', 'bridge', 'ground-track-field', 'small-vehicle', 'large-vehicle', 'ship',
+                'tennis-court', 'basketball-court', 'storage-tank', 'soccer-ball-field', 'roundabout', 'harbor',
+                'swimming-pool', 'helicopter')
+
+
+class _Plan(object):
+    """One scene's work: per rate the (resampled) uint8 scene, the tile origins (host list and padded device tensor) and,
+    once the tiles ran, the packed results [Tpad, m + 1, 28]."""
+
+    def __init__(self):
+        self.rates, self.scenes, self.origins, self.origins_dev, self.packed = [], [], [], [], []
+
+
+class SceneInference(object):
+    """`si = SceneInference(model, subsize=1024, gap=200, rates=(1.0,), batch=1, depth=4); per_class = si(scene)`.
+
+    scene: uint8 [H, W, 3] numpy array or tensor (host or device), BGR as `cv2.imread` gives it.  Returns one float64 [k, 9]
+    array per class (8 scene coordinates + score) in the merge's visiting order -- the lines `mergesingle` would write;
+    `write_task1` writes them.
+
+    * Tiles are those of `SplitSingle` (`img_split.split_origins`: same origins, same order) for every rate; `batch` tiles run
+      per captured graph, `depth` graphs in flight (`PipelinedInference`, whose half-model guard applies).  The last, partly
+      filled batch repeats its last tile; the repeats are not collected.
+    * Patches are fed at scale factor 1: normalised (`imnormalize` with `mean`, `std`, `to_rgb`, bit for bit) and nothing
+      else.  That is the reference's test pipeline for 1024^2 patches under `orientedrepoints_r50_demo.py`
+      (`img_scale=(1333, 1024)`).  The R-101 and Swin-T configs test at `(1333, 960)`: they shrink a 1024^2 patch to 960^2 and
+      scale the boxes back; that per-patch resize is NOT reproduced, those models see the patches at native size here.
+    * rates != 1: the scene is resampled once on the device with torch's bicubic `interpolate` (`align_corners=False`),
+      rounded and clamped to uint8, to `img_split.scaled_size`.  This follows OpenCV's conventions but is NOT checked against
+      cv2's `INTER_CUBIC` pixels.  The rate used in coordinates is `float(str(rate))`, as the patch-name grammar implies.
+    * A tile whose packed result overflowed (`static_capacity`) is re-run, with the tiles of its batch, through
+      `model.simple_test_batch`, and its rows take that tile's place in the order.
+    * One difference from the file route: the reference writes patch results with `str(float32)` (shortest decimal) and
+      parses them back as doubles, which is not the widened fp32 value (up to half an fp32 ulp away).  Here every fp32
+      coordinate and score is widened exactly.  Keep decisions can differ from a files-based run only for pairs whose IoU is
+      within that distance of the threshold.
+
+    Raises ValueError for `subsize % 32 != 0` (the pipeline's `Pad(size_divisor=32)` would change the patch), for a model
+    `GraphedInference` refuses (training mode, no static rnms post-processing), and -- per scene -- for a scaled scene with a
+    side below `subsize` (the reference pipeline would upscale such a patch through `RotateResize(keep_ratio)`; not reproduced).
+    Segments above `ORP_NMS_MAX_BOXES` raise `OrpHipError` in the merge."""
+
+    def __init__(self, model, subsize=1024, gap=200, rates=(1.0,), batch=1, depth=4, nms_thresh=0.1,
+                 mean=(123.675, 116.28, 103.53), std=(58.395, 57.12, 57.375), to_rgb=True):
+        subsize, gap, batch, depth = int(subsize), int(gap), int(batch), int(depth)
+        if subsize <= 0 or subsize % 32 != 0:
+            raise ValueError("SceneInference: subsize (%d) must be a positive multiple of 32, the test pipeline's Pad divisor" % subsize)
+        if not 0 <= gap < subsize:
+            raise ValueError("SceneInference: gap (%d) must be in [0, subsize)" % gap)
+        if batch < 1 or depth < 1 or len(rates) == 0:
+            raise ValueError("SceneInference: batch, depth and the number of rates must be at least 1")
+        if getattr(model, 'training', False):
+            raise ValueError("SceneInference: the model must be in eval mode (GraphedInference refuses a training-mode model)")
+        cfg = model.test_cfg
+        if cfg.nms.get('type', 'rnms') != 'rnms' or not cfg.get('static_postprocess', True):
+            raise ValueError("SceneInference: the model's test_cfg must use the static rnms post-processing (GraphedInference needs it)")
+        self.model, self.subsize, self.gap, self.batch, self.depth = model, subsize, gap, batch, depth
+        self.rates = [(r, float(str(r))) for r in rates]
+        if any(not v > 0 for _, v in self.rates):
+            raise ValueError("SceneInference: rates must be positive")
+        self.nms_thresh = float(nms_thresh)
+        self.mean, self.std, self.to_rgb = np.asarray(mean, np.float32), np.asarray(std, np.float32), bool(to_rgb)
+        self.num_classes = model.bbox_head.num_classes - 1
+        self.metas = [dict(img_shape=(subsize, subsize, 3), pad_shape=(subsize, subsize, 3), scale_factor=1.0, flip=False)
+                      for _ in range(batch)]
+        self.pipe = None
+        self._origins = {}                         # (width, height) of a scaled scene -> (host list, padded device tensor)
+        self.fallback_tiles = 0                    # tiles re-run because their packed result overflowed (all calls)
+
+    # ---- the three stages of a call ------------------------------------------------------------------------------------------
+    def prepare(self, scene):
+        """Upload (if needed), resample per rate, plan the tiles, capture the graphs on first use.  Returns the plan."""
+        if isinstance(scene, np.ndarray):
+            scene = torch.from_numpy(np.ascontiguousarray(scene))
+        if scene.dtype != torch.uint8 or scene.dim() != 3 or scene.size(2) != 3:
+            raise ValueError("SceneInference: scene must be uint8 [H, W, 3]")
+        H, W = int(scene.size(0)), int(scene.size(1))
+        sizes = [(W, H) if v == 1.0 else scaled_size(W, H, v) for _, v in self.rates]
+        for (r, _), (w, h) in zip(self.rates, sizes):
+            if min(w, h) < self.subsize:
+                raise ValueError("SceneInference: the scene at rate %s is %d x %d, smaller than a %d tile (the reference would "
+                                 "upscale such a patch; not reproduced)" % (r, w, h, self.subsize))
+        p = next(self.model.parameters())
+        if not p.is_cuda:
+            raise ValueError("SceneInference: the model must be on a GPU")
+        dev = p.device
+        scene = scene.to(dev)
+        if scene.stride(2) != 1 or scene.stride(1) != 3:
+            scene = scene.contiguous()
+        plan = _Plan()
+        for (r, v), (w, h) in zip(self.rates, sizes):
+            plan.rates.append(v)
+            plan.scenes.append(scene if (w, h) == (W, H) else self._resample(scene, w, h))
+            if (w, h) not in self._origins:
+                if len(self._origins) >= 16:
+                    self._origins.pop(next(iter(self._origins)))
+                host = split_origins(w, h, self.subsize, self.gap)
+                padded = host + [host[-1]] * (-len(host) % self.batch)
+                self._origins[(w, h)] = (host, torch.tensor(padded, dtype=torch.int32).to(dev))
+            host, on_dev = self._origins[(w, h)]
+            plan.origins.append(host)
+            plan.origins_dev.append(on_dev)
+        if self.pipe is None:
+            img = torch.zeros((self.batch, 3, self.subsize, self.subsize), dtype=p.dtype, device=dev)
+            self.pipe = PipelinedInference(self.model, img, self.metas, depth=self.depth)
+        return plan
+
+    @staticmethod
+    def _resample(scene, w, h):
+        x = scene.permute(2, 0, 1)[None].float()
+        y = F.interpolate(x, size=(h, w), mode='bicubic', align_corners=False)
+        return y.round_().clamp_(0, 255).to(torch.uint8)[0].permute(1, 2, 0).contiguous()
+
+    def run_tiles(self, plan):
+        """Every tile of every rate through the captured graphs; the packed results land in plan.packed.  Nothing here waits
+        for the device or copies to the host."""
+        pipe, B = self.pipe, self.batch
+        dev = plan.scenes[0].device
+        rows = pipe.slots[0].packed[0].size(0)
+        plan.packed = []
+        for scene, on_dev in zip(plan.scenes, plan.origins_dev):
+            packed = torch.empty((on_dev.size(0), rows, 28), dtype=torch.float32, device=dev)
+            plan.packed.append(packed)
+            for i in range(0, on_dev.size(0), B):
+                def fill(static_img, i=i):
+                    scene_tiles(scene, on_dev[i:i + B], static_img, self.mean, self.std, self.to_rgb)
+
+                def sink(outs, i=i):
+                    for j, o in enumerate(outs):
+                        packed[i + j].copy_(o, non_blocking=True)
+                pipe.submit_device(fill, sink)
+        cur = torch.cuda.current_stream(dev)
+        for s in pipe.streams:
+            cur.wait_stream(s)
+        return plan
+
+    def merge(self, plan):
+        """collect per rate -> concatenation per class across rates -> one batched merge NMS -> one gather, one D2H."""
+        C = self.num_classes
+        parts = [self._collect(plan, i) for i in range(len(plan.rates))]
+        tables = torch.stack([t for _, t in parts]).cpu().numpy()            # the one D2H of the offsets and flags
+        for i in np.nonzero(tables[:, C + 1])[0]:
+            self._rerun_overflowed(plan, int(i))
+            parts[i] = self._collect(plan, int(i))
+            tables[i] = parts[i][1].cpu().numpy()
+        if len(parts) == 1:
+            n = int(tables[0, C])
+            dets, seg = parts[0][0][:n], parts[0][1][:C + 1]
+            sizes = np.diff(tables[0, :C + 1])
+        else:
+            pieces = [d[int(t[c]):int(t[c + 1])] for c in range(C) for (d, _), t in zip(parts, tables)]
+            dets = torch.cat(pieces)
+            sizes = np.diff(tables[:, :C + 1], axis=1).sum(axis=0)
+            seg = torch.from_numpy(np.concatenate([[0], np.cumsum(sizes)]).astype(np.int32)).to(dets.device)
+        n = int(sizes.sum())
+        if n == 0:
+            return [np.zeros((0, 9), np.float64) for _ in range(C)]
+        keep, num = poly_nms_f64_batched_device(dets, seg, int(sizes.max()), self.nms_thresh, hbb_prefilter=True, presorted=False)
+        # rows past a segment's count are unwritten: clamped, gathered with the rest and dropped on the host
+        out = torch.cat([dets[keep.clamp(0, n - 1)].reshape(-1), num.to(torch.float64)]).cpu().numpy()
+        rows, num = out[:n * 9].reshape(n, 9), out[n * 9:].astype(np.int64)
+        off = np.concatenate([[0], np.cumsum(sizes)])
+        return [rows[off[c]:off[c] + num[c]].copy() for c in range(C)]
+
+    def __call__(self, scene):
+        with torch.no_grad():
+            return self.merge(self.run_tiles(self.prepare(scene)))
+
+    # ---- helpers -------------------------------------------------------------------------------------------------------------
+    def _collect(self, plan, i):
+        T = len(plan.origins[i])
+        dets, table, _ = scene_collect(plan.packed[i][:T], plan.origins_dev[i][:T], plan.rates[i], self.num_classes)
+        return dets, table
+
+    def _rerun_overflowed(self, plan, i):
+        """Rate i has tiles whose packed result overflowed the static capacity: run their batches through
+        `model.simple_test_batch` (which takes the dynamic path for them) and write the rows into the tiles' packed slots."""
+        packed, on_dev, B = plan.packed[i], plan.origins_dev[i], self.batch
+        T, m = len(plan.origins[i]), packed.size(1) - 1
+        over = np.nonzero(packed[:T, m, 1].cpu().numpy())[0]
+        redo = {}
+        img = torch.empty_like(self.pipe.slots[0].static_img)
+        for b in sorted(set(int(t) // B for t in over)):
+            scene_tiles(plan.scenes[i], on_dev[b * B:(b + 1) * B], img, self.mean, self.std, self.to_rgb)
+            with torch.no_grad():
+                results = self.model.simple_test_batch(img, self.metas)
+            for t in over[over // B == b]:
+                per_class = results[int(t) - b * B]
+                rows = np.concatenate([np.concatenate([r[:, -27:], np.full((len(r), 1), c, np.float32)], 1)
+                                       for c, r in enumerate(per_class)]).astype(np.float32)
+                redo[int(t)] = rows
+        self.fallback_tiles += len(redo)
+        need = max([m] + [len(r) for r in redo.values()])
+        if need > m:                                   # static_capacity below max_per_img: the slots grow to the longest result
+            grown = torch.zeros((packed.size(0), need + 1, 28), dtype=torch.float32, device=packed.device)
+            grown[:, :m] = packed[:, :m]
+            grown[:, need] = packed[:, m]
+            plan.packed[i] = packed = grown
+        for t, rows in redo.items():
+            slot = np.zeros((packed.size(1), 28), np.float32)
+            slot[:len(rows)] = rows
+            slot[-1, 0] = len(rows)
+            packed[t].copy_(torch.from_numpy(slot))
+
+    def write_task1(self, dstpath, name, per_class, classes=DOTA_CLASSES):
+        """Append `name score x1 y1 .. x4 y4` lines to dstpath/Task1_<class>.txt, one per kept detection, formatted as
+        `mergesingle` formats them (`str()` of Python floats, score first).  Classes without detections get no file."""
+        os.makedirs(dstpath, exist_ok=True)
+        for cls, rows in zip(classes, per_class):
+            if len(rows) == 0:
+                continue
+            with open(os.path.join(dstpath, 'Task1_' + cls + '.txt'), 'a') as f:
+                for det in np.asarray(rows, np.float64).tolist():
+                    f.write(name + ' ' + str(det[-1]) + ' ' + ' '.join(map(str, det[0:-1])) + '\n')
