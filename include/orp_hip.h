@@ -521,6 +521,28 @@ int orp_groupnorm_act_multi_backward(const orp_norm_level* levels, const float* 
                                      void* workspace, size_t workspace_bytes, void* stream);
 int orp_affine_act(const float* x, const float* residual, const float* scale, const float* shift, float* y, int batch,
                    int channels, int hw, int relu, void* stream);
+/* Glue passes fused away (inference; every entry is kernel launches on `stream` only: no allocation, no synchronisation):
+ * orp_affine2_act: y = relu?((x*scale[c] + shift[c]) + (residual*scale2[c] + shift2[c])) -- the last pass of a stage's first
+ *   bottleneck with the downsample branch's BatchNorm applied while the raw convolution output is read; both affines are
+ *   rounded to fp32 before the add, i.e. the values of orp_affine_act(residual, scale2, shift2) followed by orp_affine_act with
+ *   that residual.  y may alias x.
+ * orp_affine_relu_maxpool: y[B,C,Ho,Wo] = max_pool2d(relu(x*scale[c] + shift[c]), kernel 3, stride 2, padding 1, floor mode) of
+ *   x[B,C,H,W], Ho = (H - 1) / 2 + 1: the ResNet stem behind conv1.  Any H, W; y must not alias x.
+ * orp_fpn_topdown_nhwc: the FPN's top-down path as three launches (chunk statistics, their merge per span, one pass that
+ *   normalises, sums and transposes).  levels[i] = {raw lateral convolution output (NCHW), output (channels-last
+ *   [B, H*W, C]), height, width}, finest level first, every level exactly twice the next in both dimensions, at most 4 levels.
+ *   output i = g_i + up(g_{i+1} + up(...)) with g_j the GroupNorm of lateral j (no activation) and up nearest-neighbour
+ *   upsampling, summed coarsest level first -- the values of orp_groupnorm_act_multi_ex, interpolate + add per level and
+ *   orp_nchw_to_nhwc_multi_amax.  amax_out (or NULL): one word, max |output| over all levels as float bits.  channels % 32 == 0,
+ *   32 % (channels / groups) == 0; workspace: orp_fpn_topdown_workspace_bytes() of the same levels (8-byte aligned). */
+int orp_affine2_act(const float* x, const float* residual, const float* scale, const float* shift, const float* scale2,
+                    const float* shift2, float* y, int batch, int channels, int hw, int relu, void* stream);
+int orp_affine_relu_maxpool(const float* x, const float* scale, const float* shift, float* y, int batch, int channels,
+                            int height, int width, void* stream);
+size_t orp_fpn_topdown_workspace_bytes(const orp_norm_level* levels, int nlevels, int batch, int channels, int groups);
+int orp_fpn_topdown_nhwc(const orp_norm_level* levels, const float* const* gammas_host, const float* const* betas_host,
+                         int nlevels, int batch, int channels, int groups, float eps, uint32_t* amax_out, void* workspace,
+                         size_t workspace_bytes, void* stream);
 
 /* orp_bias_act_multi: y = relu?(x + bias[c] (+ residual)), optionally y2 = y - sub[c], for ALL FPN levels in one launch:
  *   the passes around the head's bias-carrying output convolutions (orientedreppoints_head.py:156-170): conv bias,

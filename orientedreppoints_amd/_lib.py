@@ -111,6 +111,10 @@ _SIGNATURES = {
     "orp_groupnorm_act_multi_backward": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _vp, _vp, _sz, _vp]),
     "orp_voc_best_match_f64": (_i, [_vp, _vp, _i, _vp, _vp, _i, _vp, _vp, _vp]),
     "orp_affine_act": (_i, [_vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _vp]),
+    "orp_affine2_act": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _vp]),
+    "orp_affine_relu_maxpool": (_i, [_vp, _vp, _vp, _vp, _i, _i, _i, _i, _vp]),
+    "orp_fpn_topdown_workspace_bytes": (_sz, [_vp, _i, _i, _i, _i]),
+    "orp_fpn_topdown_nhwc": (_i, [_vp, _vp, _vp, _i, _i, _i, _i, _f, _vp, _vp, _sz, _vp]),
     "orp_bias_act_multi": (_i, [_vp, _i, _i, _i, _vp, _vp, _i, _vp]),
     "orp_conv3x3_small_ok": (_i, [_i, _i]),
     "orp_conv3x3_small_multi": (_i, [_vp, _i, _i, _i, _i, _vp, _vp]),

@@ -15,6 +15,9 @@
 //               then normalises + scales + activates its own chunk with float4 traffic.
 //   orp_affine_act          : y = relu?(x * scale[c] + shift[c] (+ residual)) -- eval-mode BatchNorm folded to a
 //               per-channel affine, fused with the bottleneck's residual add and ReLU; in place allowed.
+//   orp_affine2_act         : the same pass with a second affine on the residual (the downsample branch's BatchNorm);
+//   orp_affine_relu_maxpool : the stem's BatchNorm + ReLU applied inside its 3x3 / stride-2 max-pool, one read of the input;
+//   orp_fpn_topdown_nhwc    : the FPN laterals' GroupNorm + top-down sum + transposition as one pass behind the statistics.
 //   orp_bias_act_multi      : y = relu?(x + bias[c] (+ residual)), y2 = y - sub[c], all FPN levels in one launch -- the
 //               bias / ReLU / `+ pts_out_init` / `- dcn_base_offset` passes around the head's output convolutions.
 #include <hip/hip_runtime.h>
@@ -247,6 +250,153 @@ gn_apply_nhwc_kernel(const GnParams P, const GnNhwc T) {
   }
 }
 
+// The FPN's top-down path as one pass behind its statistics (orp_fpn_topdown_nhwc): level l's output is
+//   g_l + up(g_{l+1} + up(g_{l+2} + ...)),  g_j = GroupNorm(lateral j), up = nearest-neighbour upsampling by exactly 2,
+// written channels-last through the 32 x 33 tile of gn_apply_nhwc_kernel, max |.| of everything written folded into *amax as
+// to_channels_last_kernel does.  The coarser levels' normalised values are recomputed at every fine position (1/4 and 1/16 of
+// the reads) with gn_apply_kernel's statements, and summed innermost level first, each partial sum an fp32: the values the
+// separate normalise / upsample / add launches leave.
+//
+// Statistics: gn_stats_kernel, then gn_merge_kernel -- one workgroup per (level, image, group) span merges the span's partials
+// with gn_apply_kernel's own statements and reduction order into (mean, rstd).  One merge per span instead of one per workgroup
+// of the pass that applies them: the merge is a chain of dependent loads and reductions, and a few thousand workgroups each
+// waiting for it was most of that pass when it was done there (traced at 1024^2: 48 us, against 21 + 5 for the merge kernel).
+constexpr int kTdMaxLevels = 4;
+constexpr int kTdTiles = 8;
+struct TdLevels {
+  float* out[kTdMaxLevels];       // [B, hw, C] per level
+  int width[kTdMaxLevels];
+  int bx0[kTdMaxLevels + 1];      // first blockIdx.x of each level (kTdTiles tiles of 32 positions per workgroup)
+  float2* stats;                  // [nlev][B * G] (mean, rstd)
+  unsigned* amax;                 // nullptr, or one word of float bits, zeroed by gn_merge_kernel
+};
+
+__global__ void __launch_bounds__(kThreads)
+gn_merge_kernel(const GnParams P, const TdLevels T) {
+  __shared__ float red[4];
+  const int bg = blockIdx.x, lvl = blockIdx.y;        // (image, group), level
+  const GnLevel& L = P.lv[lvl];
+  const int span = (P.C / P.G) * L.hw;
+  if (bg == 0 && lvl == 0 && threadIdx.x == 0 && T.amax) *T.amax = 0u;
+  const float2* part = P.partial + L.chunk0 + (size_t)bg * L.cpg;
+  float sm = 0.f;
+  for (int k = threadIdx.x; k < L.cpg; k += kThreads) {
+    const int nk = min(kChunk, span - k * kChunk);
+    sm += (float)nk * part[k].x;
+  }
+  const float mean = block_sum(sm, red) / (float)span;
+  float m2 = 0.f;
+  for (int k = threadIdx.x; k < L.cpg; k += kThreads) {
+    const int nk = min(kChunk, span - k * kChunk);
+    const float2 p = part[k];
+    const float d = p.x - mean;
+    m2 += p.y + (float)nk * d * d;
+  }
+  const float var = block_sum(m2, red) / (float)span;
+  const float rstd = rsqrtf(var + P.eps);
+  if (threadIdx.x == 0) T.stats[(size_t)lvl * P.B * P.G + bg] = make_float2(mean, rstd);
+}
+
+// the tiles of one workgroup, NL = number of levels summed (this one and the coarser ones) as a compile-time constant: every
+// load of a tile is unconditional and issued before the first use; returns the thread's max |.| as range bits
+template <int NL>
+__device__ __forceinline__ unsigned td_tiles(const GnParams& P, const TdLevels& T, int lvl, int b, int c0, int bx, float (*tile)[33],
+                                             const float2 (*sStat)[32]) {
+  const int cg = P.C / P.G;
+  const int tx = threadIdx.x & 31, ty = threadIdx.x >> 5;
+  const int hw = P.lv[lvl].hw;
+  // per (level, channel) coefficients with gn_apply_kernel's statements; this thread's channels are c0 + ty + 8 i
+  float ca[NL][4], cb[NL][4];
+  const float* src[NL];
+#pragma unroll
+  for (int sh = 0; sh < NL; sh++) {
+    const GnLevel& L = P.lv[lvl + sh];
+    src[sh] = L.x + ((size_t)b * P.C + c0 + ty) * L.hw;
+#pragma unroll
+    for (int i = 0; i < 4; i++) {
+      const int r = ty + 8 * i, c = c0 + r;
+      const float2 st = sStat[sh][r / cg];
+      const float a = st.y * L.gamma[c], bb = L.beta[c] - st.x * a;
+      ca[sh][i] = a; cb[sh][i] = bb;
+    }
+  }
+  float* dst = T.out[lvl] + (size_t)b * hw * P.C;
+  unsigned m = 0u;
+#pragma unroll 1
+  for (int it = 0; it < kTdTiles; it++) {
+    const int p0 = (bx * kTdTiles + it) * 32;
+    if (p0 >= hw) break;                            // (block-uniform)
+    const int p = min(p0 + tx, hw - 1);
+    const int h = p / T.width[lvl], w = p - h * T.width[lvl];
+    float x[NL][4];
+#pragma unroll
+    for (int sh = 0; sh < NL; sh++) {
+      const size_t hwj = (size_t)P.lv[lvl + sh].hw;
+      const float* q = src[sh] + (size_t)(h >> sh) * T.width[lvl + sh] + (w >> sh);
+#pragma unroll
+      for (int i = 0; i < 4; i++) x[sh][i] = q[(size_t)(8 * i) * hwj];
+    }
+#pragma unroll
+    for (int i = 0; i < 4; i++) {
+      float t = x[NL - 1][i] * ca[NL - 1][i] + cb[NL - 1][i];           // innermost (coarsest) level first
+#pragma unroll
+      for (int sh = NL - 2; sh >= 0; sh--) {
+        float g = x[sh][i] * ca[sh][i] + cb[sh][i];
+        g += t;
+        t = g;
+      }
+      if (p0 + tx >= hw) t = 0.f;
+      tile[ty + 8 * i][tx] = t;
+      m = max(m, orp::range_bits(t));
+    }
+    __syncthreads();
+#pragma unroll
+    for (int r = ty; r < 32; r += 8) {
+      const int pp = p0 + r, c = c0 + tx;
+      if (pp < hw) dst[(size_t)pp * P.C + c] = tile[tx][r];
+    }
+    __syncthreads();
+  }
+  return m;
+}
+
+__global__ void __launch_bounds__(kThreads)
+fpn_topdown_nhwc_kernel(const GnParams P, const TdLevels T) {
+  __shared__ float tile[32][33];
+  __shared__ float2 sStat[kTdMaxLevels][32];      // (mean, rstd) of the tile's groups, this level and every coarser one
+  int lvl = 0;
+#pragma unroll 1
+  for (int i = 1; i < P.nlev; i++) if ((int)blockIdx.x >= T.bx0[i]) lvl = i;
+  const int cg = P.C / P.G;
+  const int b = blockIdx.z, c0 = blockIdx.y * 32, bx = (int)blockIdx.x - T.bx0[lvl];
+  const int ngrp = 32 / cg;                         // groups of this channel tile (cg | 32, 32 | C)
+  const int nl = P.nlev - lvl;
+  if ((int)threadIdx.x < nl * ngrp) {
+    const int sh = threadIdx.x / ngrp, gi = threadIdx.x - sh * ngrp;
+    sStat[sh][gi] = T.stats[(size_t)(lvl + sh) * P.B * P.G + b * P.G + c0 / cg + gi];
+  }
+  __syncthreads();
+  unsigned m;
+  switch (nl) {                                     // (block-uniform)
+    case 1: m = td_tiles<1>(P, T, lvl, b, c0, bx, tile, sStat); break;
+    case 2: m = td_tiles<2>(P, T, lvl, b, c0, bx, tile, sStat); break;
+    case 3: m = td_tiles<3>(P, T, lvl, b, c0, bx, tile, sStat); break;
+    default: m = td_tiles<4>(P, T, lvl, b, c0, bx, tile, sStat); break;
+  }
+  if (T.amax) {
+    __shared__ unsigned redm[4];
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) m = max(m, (unsigned)__shfl_xor((int)m, o, 64));
+    if ((threadIdx.x & 63) == 0) redm[threadIdx.x >> 6] = m;
+    __syncthreads();
+    if (threadIdx.x == 0) {
+      // one address, thousands of workgroups: the atomic only where it would raise the value (see to_channels_last_kernel)
+      const unsigned mx = max(max(redm[0], redm[1]), max(redm[2], redm[3]));
+      if (mx > __atomic_load_n(T.amax, __ATOMIC_RELAXED)) atomicMax(T.amax, mx);
+    }
+  }
+}
+
 // y = act(x * scale[c] + shift[c] (+ residual)), NCHW.  grid.y = (image, channel) plane, so the per-channel constants are
 // block-uniform scalars and no integer division sits in the element loop; float4 traffic when HW % 4 == 0.
 __global__ void __launch_bounds__(kThreads)
@@ -274,6 +424,108 @@ affine_act_kernel(const float* __restrict__ x, const float* __restrict__ res, co
       if (res) t += res[base + i];
       if (relu) t = fmaxf(t, 0.f);
       y[base + i] = t;
+    }
+  }
+}
+
+// y = act((x * scale[c] + shift[c]) + (res * scale2[c] + shift2[c])): the last pass of a stage's FIRST bottleneck, whose identity
+// branch is conv -> BatchNorm.  The second affine is the downsample BatchNorm, applied while the raw convolution output is read
+// instead of in a read-modify-write pass of its own; it is rounded to fp32 before the add, which is the value that pass stored.
+__global__ void __launch_bounds__(kThreads)
+affine2_act_kernel(const float* __restrict__ x, const float* __restrict__ res, const float* __restrict__ scale,
+                   const float* __restrict__ shift, const float* __restrict__ scale2, const float* __restrict__ shift2,
+                   float* __restrict__ y, int C, int hw, int relu) {
+  const int plane = blockIdx.y;                       // b * C + c
+  const int c = plane % C;
+  const float a = scale[c], b = shift[c];
+  const float a2 = scale2[c], b2 = shift2[c];
+  const size_t base = (size_t)plane * hw;
+  if ((hw & 3) == 0) {
+    const int hw4 = hw >> 2;
+    const float4* x4 = reinterpret_cast<const float4*>(x + base);
+    const float4* r4 = reinterpret_cast<const float4*>(res + base);
+    float4* y4 = reinterpret_cast<float4*>(y + base);
+    for (int i = blockIdx.x * blockDim.x + threadIdx.x; i < hw4; i += gridDim.x * blockDim.x) {
+      float4 t = x4[i];
+      float4 r = r4[i];
+      t.x = t.x * a + b; t.y = t.y * a + b; t.z = t.z * a + b; t.w = t.w * a + b;
+      r.x = r.x * a2 + b2; r.y = r.y * a2 + b2; r.z = r.z * a2 + b2; r.w = r.w * a2 + b2;
+      t.x += r.x; t.y += r.y; t.z += r.z; t.w += r.w;
+      if (relu) { t.x = fmaxf(t.x, 0.f); t.y = fmaxf(t.y, 0.f); t.z = fmaxf(t.z, 0.f); t.w = fmaxf(t.w, 0.f); }
+      y4[i] = t;
+    }
+  } else {
+    for (int i = blockIdx.x * blockDim.x + threadIdx.x; i < hw; i += gridDim.x * blockDim.x) {
+      float t = x[base + i] * a + b;
+      float r = res[base + i] * a2 + b2;
+      t += r;
+      if (relu) t = fmaxf(t, 0.f);
+      y[base + i] = t;
+    }
+  }
+}
+
+// The stem: y = maxpool3x3/s2/p1(relu(x * scale[c] + shift[c])), NCHW -> a new [B, C, Ho, Wo] tensor.  grid.y = (image, channel)
+// plane as in affine_act_kernel.  A thread owns four input columns (two outputs) of kPoolRows output rows: it walks down its
+// 2 * kPoolRows + 1 input rows once, the activated odd row carried over as the next window's top row, so inside a strip every
+// element is loaded once (16-byte loads when W % 4 == 0; the column left of the quad is a 4-byte load of a line that is in
+// the L1 anyway) and only the row between two strips is read twice.
+// relu(.) is fmaxf(., 0): +0 or larger, never NaN (the pass this replaces had the same fmaxf in front of the pooling), so the
+// maximum of a window is one bit pattern whatever the order, and a padded position can stand in as +0 -- every window holds at
+// least one real element.
+constexpr int kPoolRows = 4;
+template <bool kVec>
+__global__ void __launch_bounds__(kThreads)
+affine_relu_maxpool_kernel(const float* __restrict__ x, const float* __restrict__ scale, const float* __restrict__ shift,
+                           float* __restrict__ y, int C, int H, int W, int Ho, int Wo, int nq, int nitems) {
+  const int plane = blockIdx.y;                       // b * C + c
+  const int c = plane % C;
+  const float a = scale[c], b = shift[c];
+  const float* src = x + (size_t)plane * H * W;
+  float* dst = y + (size_t)plane * Ho * Wo;
+  for (int it = blockIdx.x * blockDim.x + threadIdx.x; it < nitems; it += gridDim.x * blockDim.x) {
+    const int s = it / nq, q = it - s * nq;
+    const int col = 4 * q;                            // input columns col - 1 .. col + 3 -> outputs 2q, 2q + 1
+    const int ho0 = s * kPoolRows;
+    // the activated values of one input row at the five columns (+0 outside the image)
+    auto load_row = [&](int row, float (&v)[5]) {
+      if (row < 0 || row >= H) { v[0] = v[1] = v[2] = v[3] = v[4] = 0.f; return; }
+      const float* p = src + (size_t)row * W + col;
+      float t0, t1, t2, t3, t4;
+      if (kVec) {
+        const float4 f = *reinterpret_cast<const float4*>(p);
+        t1 = f.x; t2 = f.y; t3 = f.z; t4 = f.w;
+      } else {
+        t1 = p[0];
+        t2 = (col + 1 < W) ? p[1] : 0.f; t3 = (col + 2 < W) ? p[2] : 0.f; t4 = (col + 3 < W) ? p[3] : 0.f;
+      }
+      t0 = (col > 0) ? p[-1] : 0.f;
+      v[0] = fmaxf(t0 * a + b, 0.f); v[1] = fmaxf(t1 * a + b, 0.f); v[2] = fmaxf(t2 * a + b, 0.f);
+      v[3] = fmaxf(t3 * a + b, 0.f); v[4] = fmaxf(t4 * a + b, 0.f);
+      if (col == 0) v[0] = 0.f;
+      if (!kVec) { if (col + 1 >= W) v[2] = 0.f; if (col + 2 >= W) v[3] = 0.f; if (col + 3 >= W) v[4] = 0.f; }
+    };
+    float top[5];
+    load_row(2 * ho0 - 1, top);
+#pragma unroll
+    for (int k = 0; k < kPoolRows; k++) {
+      const int ho = ho0 + k;
+      if (ho < Ho) {
+        float mid[5], bot[5];
+        load_row(2 * ho, mid);
+        load_row(2 * ho + 1, bot);
+        float m[5];
+#pragma unroll
+        for (int u = 0; u < 5; u++) { m[u] = fmaxf(fmaxf(top[u], mid[u]), bot[u]); top[u] = bot[u]; }
+        const float o0 = fmaxf(fmaxf(m[0], m[1]), m[2]), o1 = fmaxf(fmaxf(m[2], m[3]), m[4]);
+        float* d = dst + (size_t)ho * Wo + 2 * q;
+        if (kVec) {
+          *reinterpret_cast<float2*>(d) = make_float2(o0, o1);
+        } else {
+          d[0] = o0;
+          if (2 * q + 1 < Wo) d[1] = o1;
+        }
+      }
     }
   }
 }
@@ -911,6 +1163,90 @@ int orp_affine_act(const float* x, const float* residual, const float* scale, co
   if (bx > 64) bx = 64;
   hipLaunchKernelGGL(affine_act_kernel, dim3(bx, batch * channels), dim3(kThreads), 0, (hipStream_t)stream, x, residual,
                      scale, shift, y, channels, hw, relu);
+  hipError_t e = hipGetLastError();
+  return e == hipSuccess ? ORP_OK : (int)e;
+}
+
+int orp_affine2_act(const float* x, const float* residual, const float* scale, const float* shift, const float* scale2,
+                    const float* shift2, float* y, int batch, int channels, int hw, int relu, void* stream) {
+  if (!x || !residual || !scale || !shift || !scale2 || !shift2 || !y || batch <= 0 || channels <= 0 || hw <= 0) return ORP_EINVAL;
+  if ((long)batch * channels > 65535L * 1024) return ORP_ETOOBIG;
+  const int per = ((hw & 3) == 0) ? (hw >> 2) : hw;                 // work items per plane
+  int bx = (per + kThreads * 4 - 1) / (kThreads * 4);               // ~4 items per thread
+  if (bx < 1) bx = 1;
+  if (bx > 64) bx = 64;
+  hipLaunchKernelGGL(affine2_act_kernel, dim3(bx, batch * channels), dim3(kThreads), 0, (hipStream_t)stream, x, residual,
+                     scale, shift, scale2, shift2, y, channels, hw, relu);
+  hipError_t e = hipGetLastError();
+  return e == hipSuccess ? ORP_OK : (int)e;
+}
+
+int orp_affine_relu_maxpool(const float* x, const float* scale, const float* shift, float* y, int batch, int channels,
+                            int height, int width, void* stream) {
+  if (!x || !scale || !shift || !y || x == y || batch <= 0 || channels <= 0 || height <= 0 || width <= 0) return ORP_EINVAL;
+  if ((long)batch * channels > 65535L || (long)height * width >= (1L << 31)) return ORP_ETOOBIG;
+  const int ho = (height - 1) / 2 + 1, wo = (width - 1) / 2 + 1;   // kernel 3, stride 2, padding 1, floor mode
+  const int nq = (wo + 1) / 2;                                      // column quads: two outputs each
+  const long items = (long)nq * ((ho + kPoolRows - 1) / kPoolRows);
+  long bx = (items + kThreads - 1) / kThreads;
+  if (bx > 65535) bx = 65535;                                       // (the kernel strides over the rest)
+  const bool vec = (width & 3) == 0 && ((uintptr_t)x & 15) == 0 && ((uintptr_t)y & 7) == 0;
+  const dim3 grid((unsigned)bx, batch * channels);
+  if (vec)
+    hipLaunchKernelGGL(affine_relu_maxpool_kernel<true>, grid, dim3(kThreads), 0, (hipStream_t)stream, x, scale, shift, y, channels,
+                       height, width, ho, wo, nq, (int)items);
+  else
+    hipLaunchKernelGGL(affine_relu_maxpool_kernel<false>, grid, dim3(kThreads), 0, (hipStream_t)stream, x, scale, shift, y, channels,
+                       height, width, ho, wo, nq, (int)items);
+  hipError_t e = hipGetLastError();
+  return e == hipSuccess ? ORP_OK : (int)e;
+}
+
+// workspace of orp_fpn_topdown_nhwc: chunk partials | (mean, rstd) per (level, image, group)
+static size_t td_stats_offset(size_t chunks) { return (sizeof(float2) * chunks + 255) & ~(size_t)255; }
+
+size_t orp_fpn_topdown_workspace_bytes(const orp_norm_level* levels, int nlevels, int batch, int channels, int groups) {
+  GnParams P;
+  const int chunks = fill(levels, nlevels, batch, channels, groups, P);
+  if (chunks <= 0) return 256;
+  return td_stats_offset(chunks) + sizeof(float2) * (size_t)nlevels * batch * groups;
+}
+
+int orp_fpn_topdown_nhwc(const orp_norm_level* levels, const float* const* gammas_host, const float* const* betas_host,
+                         int nlevels, int batch, int channels, int groups, float eps, uint32_t* amax_out, void* workspace,
+                         size_t workspace_bytes, void* stream) {
+  GnParams P;
+  if (!levels || nlevels <= 0 || nlevels > kTdMaxLevels) return ORP_EINVAL;
+  const int chunks = fill(levels, nlevels, batch, channels, groups, P);
+  if (chunks == -2) return ORP_ETOOBIG;
+  if (chunks <= 0 || !gammas_host || !betas_host) return ORP_EINVAL;
+  if (channels % 32 != 0 || 32 % (channels / groups) != 0 || batch > 65535) return ORP_EINVAL;
+  const size_t nspan = (size_t)nlevels * batch * groups;
+  const size_t stat_off = td_stats_offset(chunks);
+  if (!workspace || ((uintptr_t)workspace & 7) != 0 || workspace_bytes < stat_off + sizeof(float2) * nspan) return ORP_EWORKSPACE;
+  TdLevels T;
+  int bx = 0;
+  for (int i = 0; i < nlevels; i++) {
+    if (!gammas_host[i] || !betas_host[i] || levels[i].output == levels[i].input) return ORP_EINVAL;
+    // every level exactly twice the next in both dimensions: what makes nearest-neighbour upsampling an index shift
+    if (i + 1 < nlevels && (levels[i].height != 2 * levels[i + 1].height || levels[i].width != 2 * levels[i + 1].width))
+      return ORP_EINVAL;
+    P.lv[i].gamma = gammas_host[i]; P.lv[i].beta = betas_host[i];
+    T.out[i] = levels[i].output; T.width[i] = levels[i].width;
+    T.bx0[i] = bx;
+    bx += (P.lv[i].hw + 32 * kTdTiles - 1) / (32 * kTdTiles);
+  }
+  for (int i = nlevels; i <= kTdMaxLevels; i++) T.bx0[i] = 0x7fffffff;
+  for (int i = nlevels; i < kTdMaxLevels; i++) { T.out[i] = T.out[0]; T.width[i] = T.width[0]; }
+  T.stats = reinterpret_cast<float2*>(reinterpret_cast<char*>(workspace) + stat_off);
+  T.amax = amax_out;
+  P.eps = eps; P.relu = 0;
+  P.partial = reinterpret_cast<float2*>(workspace);
+  P.stats = nullptr;
+  hipStream_t st = (hipStream_t)stream;
+  hipLaunchKernelGGL(gn_stats_kernel, dim3(chunks), dim3(kThreads), 0, st, P);
+  hipLaunchKernelGGL(gn_merge_kernel, dim3(batch * groups, nlevels), dim3(kThreads), 0, st, P, T);
+  hipLaunchKernelGGL(fpn_topdown_nhwc_kernel, dim3(bx, channels / 32, batch), dim3(kThreads), 0, st, P, T);
   hipError_t e = hipGetLastError();
   return e == hipSuccess ? ORP_OK : (int)e;
 }

@@ -90,11 +90,23 @@ class FPN(nn.Module):
         C, G = c0.weight.size(0), self.fpn_convs[0].norm.num_groups
         return 1024 % C == 0 and C % G == 0 and (C // G) % 4 == 0 and min(min(t.size(2), t.size(3)) for t in laterals) > 1
 
+    def _topdown_ok(self, raw):
+        """The lateral normalisation, the top-down sum and the transposition run as one pass (`fpn_topdown_cl`): not switched
+        off (`fuse_topdown` attribute, or ORP_FPN_TOPDOWN_FUSE=0 for A/B timing), the output convolutions take the channels-last
+        path -- only there are the NCHW laterals not needed afterwards -- and every level is exactly twice the next."""
+        from .. import switches
+        from ..mmdet_ops.fused_norm import fpn_topdown_ok
+        on = getattr(self, 'fuse_topdown', None)
+        if on is None:
+            on = switches.FPN_TOPDOWN_FUSE
+        return bool(on) and fpn_topdown_ok(raw, [lc.norm for lc in self.lateral_convs]) and self._split_ok(raw)
+
     def forward(self, inputs):
         assert len(inputs) == len(self.in_channels)
         used = len(self.lateral_convs)
         fused = self._fused_ok(inputs)
         split_amax = None
+        topdown_cl = False
         train = fused and torch.is_grad_enabled()     # autograd: the same launch pairs as one node per normalisation layer
         if train:
             from ..mmdet_ops.fused_norm import group_norm_act_train
@@ -103,14 +115,18 @@ class FPN(nn.Module):
                                             [lc.norm for lc in self.lateral_convs], relu=False)
         elif fused:
             from ..mmdet_ops.fused_norm import conv3x3_multi, group_norm_act_multi
-            laterals = group_norm_act_multi([lc.conv(inputs[i + self.start_level])
-                                             for i, lc in enumerate(self.lateral_convs)],
-                                            [lc.norm for lc in self.lateral_convs], relu=False, inplace=True)
+            laterals = [lc.conv(inputs[i + self.start_level]) for i, lc in enumerate(self.lateral_convs)]
+            # the channels-last branch below is the only consumer of the summed laterals: there the normalisation, the top-down
+            # sum and the transposition are ONE pass behind the statistics, straight from the raw convolution outputs
+            topdown_cl = self._topdown_ok(laterals)
+            if not topdown_cl:
+                laterals = group_norm_act_multi(laterals, [lc.norm for lc in self.lateral_convs], relu=False, inplace=True)
         else:
             laterals = [lc(inputs[i + self.start_level]) for i, lc in enumerate(self.lateral_convs)]
-        for i in range(used - 1, 0, -1):
-            laterals[i - 1] = laterals[i - 1] + F.interpolate(laterals[i], size=laterals[i - 1].shape[2:],
-                                                              mode='nearest')
+        if not topdown_cl:
+            for i in range(used - 1, 0, -1):
+                laterals[i - 1] = laterals[i - 1] + F.interpolate(laterals[i], size=laterals[i - 1].shape[2:],
+                                                                  mode='nearest')
         if train:
             from ..mmdet_ops.fused_norm import conv_split_train, conv_split_train_ok
             out_convs = [fc.conv for fc in self.fpn_convs[:used]]
@@ -126,7 +142,11 @@ class FPN(nn.Module):
             from ..mmdet_ops.fused_norm import Amax, conv_split_multi, group_norm_act_multi_cl, to_channels_last_multi
             # (ranges for the fp16-pieces arithmetic ride along on the device: the transposition leaves max |x| of the
             #  laterals, the normalisation a bound of its outputs' for the head's first tower layer -- FpnOutputs.orp_amax)
-            cl, bits = to_channels_last_multi(laterals, amax_slots=[0] * used)
+            if topdown_cl:
+                from ..mmdet_ops.fused_norm import fpn_topdown_cl
+                cl, bits = fpn_topdown_cl(laterals, [lc.norm for lc in self.lateral_convs])
+            else:
+                cl, bits = to_channels_last_multi(laterals, amax_slots=[0] * used)
             conv = conv_split_multi(cl, [fc.conv for fc in self.fpn_convs[:used]], amax=Amax(bits, 0) if bits is not None else None)
             outs, split_amax = group_norm_act_multi_cl(conv, [fc.norm for fc in self.fpn_convs[:used]], relu=False,
                                                        amax_slots=[0] * used)

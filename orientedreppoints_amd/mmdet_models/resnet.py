@@ -52,11 +52,25 @@ class Bottleneck(nn.Module):
         return (not torch.is_grad_enabled()) and x.is_cuda and x.dtype == torch.float32 and \
             isinstance(self.bn1, nn.BatchNorm2d) and not self.bn1.training and not self.bn3.training
 
+    def _downsample_norm_fusable(self):
+        """the identity branch is exactly Sequential(Conv2d, eval-mode BatchNorm2d) and the fusion is not switched off
+        (`fuse_downsample_norm` attribute, or ORP_BN_DOWNSAMPLE_FUSE=0 for A/B timing)"""
+        from .. import switches
+        on = getattr(self, 'fuse_downsample_norm', None)
+        if on is None:
+            on = switches.BN_DOWNSAMPLE_FUSE
+        ds = self.downsample
+        return bool(on) and isinstance(ds, nn.Sequential) and len(ds) == 2 and isinstance(ds[0], nn.Conv2d) and \
+            isinstance(ds[1], nn.BatchNorm2d) and not ds[1].training
+
     def _forward_fused(self, x):
         from ..mmdet_ops.fused_norm import bn_act
         out = bn_act(self.conv1(x).contiguous(), self.bn1, relu=True)
         out = bn_act(self.conv2(out).contiguous(), self.bn2, relu=True)
         out = self.conv3(out).contiguous()
+        if self._downsample_norm_fusable():
+            # the downsample BatchNorm rides in the block's last pass: no read-modify-write pass of its own over the identity
+            return bn_act(out, self.bn3, residual=self.downsample[0](x).contiguous(), residual_bn=self.downsample[1], relu=True)
         if self.downsample is not None:
             identity = bn_act(self.downsample[0](x).contiguous(), self.downsample[1], relu=False)
         else:
@@ -177,11 +191,28 @@ class ResNet(nn.Module):
                 if isinstance(m, Bottleneck):
                     constant_init(m.bn3, 0)
 
+    def _stem_pool_fusable(self):
+        """`maxpool` is exactly MaxPool2d(3, 2, 1) -- dilation 1, floor mode, no indices -- and the fusion is not switched off
+        (`fuse_stem_pool` attribute, or ORP_STEM_POOL_FUSE=0 for A/B timing)"""
+        from .. import switches
+        on = getattr(self, 'fuse_stem_pool', None)
+        if on is None:
+            on = switches.STEM_POOL_FUSE
+
+        def pair(v):
+            return tuple(v) if isinstance(v, (tuple, list)) else (v, v)
+        mp = self.maxpool
+        return bool(on) and type(mp) is nn.MaxPool2d and pair(mp.kernel_size) == (3, 3) and pair(mp.stride) == (2, 2) and \
+            pair(mp.padding) == (1, 1) and pair(mp.dilation) == (1, 1) and not mp.ceil_mode and not mp.return_indices
+
     def forward(self, x):
         if (not torch.is_grad_enabled()) and x.is_cuda and x.dtype == torch.float32 and \
                 isinstance(self.bn1, nn.BatchNorm2d) and not self.bn1.training:
-            from ..mmdet_ops.fused_norm import bn_act
-            x = self.maxpool(bn_act(self.conv1(x).contiguous(), self.bn1, relu=True))
+            from ..mmdet_ops.fused_norm import bn_act, bn_relu_maxpool
+            if self._stem_pool_fusable():
+                x = bn_relu_maxpool(self.conv1(x).contiguous(), self.bn1)      # BatchNorm + ReLU applied while pooling
+            else:
+                x = self.maxpool(bn_act(self.conv1(x).contiguous(), self.bn1, relu=True))
         else:
             x = self.maxpool(self.relu(self.bn1(self.conv1(x))))
         outs = []

@@ -91,20 +91,97 @@ def _bn_affine(bn):
     return _lib.keep_for_graph(hit[0]), _lib.keep_for_graph(hit[1])
 
 
-def bn_act(x, bn, residual=None, relu=True):
-    """relu?(BatchNorm_eval(x) (+ residual)) in ONE pass, in place on x ([B,C,H,W] fp32 CUDA, contiguous)."""
+def bn_act(x, bn, residual=None, relu=True, residual_bn=None):
+    """relu?(BatchNorm_eval(x) (+ residual)) in ONE pass, in place on x ([B,C,H,W] fp32 CUDA, contiguous).
+    residual_bn: the residual is a RAW convolution output and this eval-mode BatchNorm is applied to it while it is read
+    (`orp_affine2_act`: the downsample branch of a stage's first bottleneck) -- the values of bn_act(residual, residual_bn,
+    relu=False) followed by this call, without that pass over memory."""
     if not (x.is_cuda and x.dtype == torch.float32 and x.dim() == 4 and x.is_contiguous()):
         raise ValueError("bn_act expects a contiguous fp32 CUDA [B,C,H,W] tensor")
     if residual is not None and not (residual.shape == x.shape and residual.is_contiguous()
                                      and residual.dtype == torch.float32):
         raise ValueError("bn_act: residual must match x")
+    if residual_bn is not None and residual is None:
+        raise ValueError("bn_act: residual_bn without a residual")
     scale, shift = _bn_affine(bn)
     B, C, H, W = x.shape
+    if residual_bn is not None:
+        scale2, shift2 = _bn_affine(residual_bn)
+        with torch.cuda.device(x.device):
+            rc = _lib.lib().orp_affine2_act(_lib.ptr(x), _lib.ptr(residual), _lib.ptr(scale), _lib.ptr(shift), _lib.ptr(scale2),
+                                            _lib.ptr(shift2), _lib.ptr(x), B, C, H * W, 1 if relu else 0, _lib.stream_of(x))
+        _lib.check(rc, "orp_affine2_act")
+        return x
     with torch.cuda.device(x.device):
         rc = _lib.lib().orp_affine_act(_lib.ptr(x), _lib.ptr(residual), _lib.ptr(scale), _lib.ptr(shift), _lib.ptr(x),
                                        B, C, H * W, 1 if relu else 0, _lib.stream_of(x))
     _lib.check(rc, "orp_affine_act")
     return x
+
+
+def bn_relu_maxpool(x, bn):
+    """max_pool2d(relu(BatchNorm_eval(x)), kernel 3, stride 2, padding 1) as ONE kernel (`orp_affine_relu_maxpool`, the ResNet
+    stem): x [B,C,H,W] fp32 CUDA, contiguous, left as it is; returns a new [B,C,(H-1)//2+1,(W-1)//2+1] tensor."""
+    if not (x.is_cuda and x.dtype == torch.float32 and x.dim() == 4 and x.is_contiguous()):
+        raise ValueError("bn_relu_maxpool expects a contiguous fp32 CUDA [B,C,H,W] tensor")
+    scale, shift = _bn_affine(bn)
+    B, C, H, W = x.shape
+    y = torch.empty((B, C, (H - 1) // 2 + 1, (W - 1) // 2 + 1), dtype=torch.float32, device=x.device)
+    with torch.cuda.device(x.device):
+        rc = _lib.lib().orp_affine_relu_maxpool(_lib.ptr(x), _lib.ptr(scale), _lib.ptr(shift), _lib.ptr(y), B, C, H, W,
+                                                _lib.stream_of(x))
+    _lib.check(rc, "orp_affine_relu_maxpool")
+    return y
+
+
+def fpn_topdown_ok(xs, gns):
+    """the laterals (raw convolution outputs, finest first) and their GroupNorms are what `fpn_topdown_cl` takes: at most four
+    fp32 CUDA [B,C,H,W] tensors, each exactly twice the next in H and W, channel tiles of 32 that hold whole groups"""
+    x0, g0 = xs[0], gns[0]
+    B, C = x0.size(0), x0.size(1)
+    if not (1 <= len(xs) <= 4 and len(gns) == len(xs) and C % 32 == 0 and C % g0.num_groups == 0 and 32 % (C // g0.num_groups) == 0):
+        return False
+    for i, (x, g) in enumerate(zip(xs, gns)):
+        if not (x.is_cuda and x.dtype == torch.float32 and x.dim() == 4 and x.size(0) == B and x.size(1) == C and
+                isinstance(g, torch.nn.GroupNorm) and g.affine and g.num_groups == g0.num_groups and g.eps == g0.eps):
+            return False
+        if i and (xs[i - 1].size(2) != 2 * x.size(2) or xs[i - 1].size(3) != 2 * x.size(3)):
+            return False
+    return True
+
+
+def fpn_topdown_cl(xs, gns, amax=True):
+    """The FPN's top-down path from the RAW lateral convolution outputs xs (finest level first) as ONE pass over the laterals
+    behind their statistics (`orp_fpn_topdown_nhwc`: chunk statistics, their merge, the pass): outs[i] = GN_i(xs[i]) + up2(outs[i + 1]) in channels-last memory -- the values of
+    group_norm_act_multi, `a + F.interpolate(b, size=a.shape[2:], mode='nearest')` per level and to_channels_last_multi.
+    Returns (outs, bits): bits = a one-element int32 tensor with max |out| over all levels as float bits when the library's
+    arithmetic reads ranges (as to_channels_last_multi(amax_slots=[0] * n)), else None."""
+    if not fpn_topdown_ok(xs, gns):
+        raise ValueError("fpn_topdown_cl: see fpn_topdown_ok")
+    L = _lib.lib()
+    x0 = xs[0]
+    B, C = x0.size(0), x0.size(1)
+    n = len(xs)
+    levels = (_NormLevel * n)()
+    gam = (ctypes.c_void_p * n)()
+    bet = (ctypes.c_void_p * n)()
+    outs, keep = [], []
+    for i, x in enumerate(xs):
+        x = x.detach().contiguous()
+        y = torch.empty(x.shape, dtype=torch.float32, device=x.device, memory_format=torch.channels_last)
+        g_ = gns[i].weight.detach().float().contiguous()
+        b_ = gns[i].bias.detach().float().contiguous()
+        keep += [x, g_, b_]; outs.append(y)
+        levels[i] = _NormLevel(x.data_ptr(), y.data_ptr(), x.size(2), x.size(3))
+        gam[i], bet[i] = g_.data_ptr(), b_.data_ptr()
+    bits = torch.empty(1, dtype=torch.int32, device=x0.device) if (amax and _ranges_wanted()) else None
+    nbytes = L.orp_fpn_topdown_workspace_bytes(levels, n, B, C, gns[0].num_groups)
+    ws = _lib.workspace(x0.device, nbytes)
+    with torch.cuda.device(x0.device):
+        rc = L.orp_fpn_topdown_nhwc(levels, gam, bet, n, B, C, gns[0].num_groups, float(gns[0].eps),
+                                    bits.data_ptr() if bits is not None else None, _lib.ptr(ws), ws.numel(), _lib.stream_of(x0))
+    _lib.check(rc, "orp_fpn_topdown_nhwc")
+    return outs, bits
 
 
 class _BiasLevel(ctypes.Structure):

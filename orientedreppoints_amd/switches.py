@@ -16,5 +16,8 @@ def _on(name, default='1'):
 TOWER_SPLIT = _on('ORP_TOWER_SPLIT')          # head towers on the split matrix-pipe kernel (head.split_towers overrides)
 FPN_SPLIT = _on('ORP_FPN_SPLIT')              # FPN output convolutions on it (neck.split_convs overrides)
 TOWER_GN_FUSE = _on('ORP_TOWER_GN_FUSE')      # GroupNorm fused around the tower convolutions (head.fuse_tower_norm overrides)
+BN_DOWNSAMPLE_FUSE = _on('ORP_BN_DOWNSAMPLE_FUSE')  # downsample BatchNorm inside the block-final pass (block.fuse_downsample_norm overrides)
+STEM_POOL_FUSE = _on('ORP_STEM_POOL_FUSE')    # stem BatchNorm + ReLU + max-pool as one kernel (backbone.fuse_stem_pool overrides)
+FPN_TOPDOWN_FUSE = _on('ORP_FPN_TOPDOWN_FUSE')  # FPN lateral GroupNorm + top-down sum + transposition as one pass (neck.fuse_topdown overrides)
 TRAIN_SPLIT = _on('ORP_TRAIN_SPLIT')          # training: tower / FPN convolutions as conv_split_train nodes
 DETERMINISTIC = _on('ORP_DETERMINISTIC', '0')  # training: fixed-order DeformConv backward for both branches (head.deterministic_backward overrides)
