@@ -420,7 +420,7 @@ int orp_poly_nms_f64_batched(const double* dets, int n_total, const int32_t* seg
                              double iou_thr, int hbb_prefilter, int presorted, int64_t* keep_out, int32_t* num_keep,
                              void* workspace, size_t workspace_bytes, void* stream);
 
-/* Whole-scene inference: the two device steps between a scene and the per-patch detector (no reference counterpart as
+/* Whole-scene inference: the device steps between a scene and the per-patch detector (no reference counterpart as
  * device code: the reference crops patches to files with SplitOnlyImage.py:27-57, normalises each on the host in its test
  * pipeline and carries patch results to the merge as Task1 text files).
  *
@@ -431,6 +431,18 @@ int orp_poly_nms_f64_batched(const double* dets, int n_total, const int32_t* seg
  * to out_dtype: mmcv.imnormalize bit for bit.  Pixels of a tile outside the scene are written as 0 (Pad after Normalize) and
  * nothing outside the scene's rows is read.  tile % 4 == 0 (float32) or tile % 8 == 0 (16-bit types), else ORP_EINVAL;
  * num_tiles <= 65535.
+ *
+ * orp_scene_tiles_resized: the same with the test pipeline's per-patch resize in front.  Patch t is the src_w x src_h crop of
+ * scene at origins[t] (moved inside the scene if it hangs over: src_w <= width, src_h <= height); it is resampled bilinearly to
+ * new_w x new_h, rounded to uint8, channel-swapped and normalised as above, and written to out [num_tiles,3,pad_h,pad_w] with
+ * zeros outside (new_h, new_w).  The caller passes the axis tables (int32 / float32 ON THE DEVICE, new_w resp. new_h
+ * entries), built in fp32 for output index d of an axis of `in` source and `out` output pixels as
+ *   src = max((float(in) / float(out)) * (d + 0.5f) - 0.5f, 0), i0 = min(int(src), in - 1), w1 = src - i0
+ * (every operation rounded on its own; align_corners=False).  The kernel uses i1 = min(i0 + 1, in - 1), w0 = 1 - w1 and per
+ * pixel and channel top = w0x*a + w1x*b, bot = w0x*c + w1x*d, v = w0y*top + w1y*bot, every product and sum rounded to fp32,
+ * then rint (ties to even), clamp to [0, 255] and the normalisation.  Source pixels are clamped inside the PATCH.  With
+ * new == src the output is orp_scene_tiles' bit for bit.  Table indices outside the patch are clamped into it.
+ * pad_w % 4 == 0 (float32) or pad_w % 8 == 0 (16-bit types), else ORP_EINVAL; num_tiles <= 65535.
  *
  * orp_scene_collect: packed [num_tiles, max_rows + 1, 28] f32 = the per-tile results of the static post-processing (rows of
  * 18 point coordinates, 8 corners, score, label; last row = count, overflow flag) -> dets [capacity_rows,9] DOUBLE:
@@ -443,6 +455,10 @@ int orp_poly_nms_f64_batched(const double* dets, int n_total, const int32_t* seg
 int orp_scene_tiles(const uint8_t* scene, int height, int width, long long row_stride_bytes, const int32_t* origins,
                     int num_tiles, int tile, const float* mean_host, const float* std_host, int to_rgb, int out_dtype,
                     void* out, void* stream);
+int orp_scene_tiles_resized(const uint8_t* scene, int height, int width, long long row_stride_bytes, const int32_t* origins,
+                            int num_tiles, int src_w, int src_h, int new_w, int new_h, int pad_w, int pad_h, const int32_t* x_i0,
+                            const float* x_w1, const int32_t* y_i0, const float* y_w1, const float* mean_host,
+                            const float* std_host, int to_rgb, int out_dtype, void* out, void* stream);
 size_t orp_scene_collect_workspace_bytes(int num_tiles, int num_classes);
 int orp_scene_collect(const float* packed, int num_tiles, int max_rows, const int32_t* origins, double rate, int num_classes,
                       int capacity_rows, double* dets, int32_t* seg_offsets, int32_t* src, int32_t* flag, void* workspace,

@@ -89,6 +89,8 @@ _SIGNATURES = {
     "orp_poly_nms_f64_batched_workspace_bytes": (_sz, [_i, _i, _i]),
     "orp_poly_nms_f64_batched": (_i, [_vp, _i, _vp, _i, _i, ctypes.c_double, _i, _i, _vp, _vp, _vp, _sz, _vp]),
     "orp_scene_tiles": (_i, [_vp, _i, _i, ctypes.c_longlong, _vp, _i, _i, _vp, _vp, _i, _i, _vp, _vp]),
+    "orp_scene_tiles_resized": (_i, [_vp, _i, _i, ctypes.c_longlong, _vp, _i, _i, _i, _i, _i, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp, _i,
+                                     _i, _vp, _vp]),
     "orp_scene_collect_workspace_bytes": (_sz, [_i, _i]),
     "orp_scene_collect": (_i, [_vp, _i, _i, _vp, ctypes.c_double, _i, _i, _vp, _vp, _vp, _vp, _vp, _sz, _vp]),
     "orp_soft_rnms_host": (_i, [_vp, _i, _f, _i, _f, _f, _vp, _vp]),

@@ -1,8 +1,10 @@
-// orp_scene.hip -- the two device steps between a whole DOTA scene and the per-patch detector (gfx950).
+// orp_scene.hip -- the device steps between a whole DOTA scene and the per-patch detector (gfx950).
 //
 //   orp_scene_tiles    crop + channel swap + normalise + type conversion of T tiles of a uint8 HWC scene in one launch: what the
 //                      reference does per patch on the host (SplitOnlyImage's crop, the test pipeline's Normalize + Pad +
 //                      ImageToTensor), written straight into the detector's input buffer.
+//   orp_scene_tiles_resized  the same with the test pipeline's per-patch resize in front (RotateResize(keep_ratio): bilinear,
+//                      align_corners=False, rounded to uint8) and Pad's zeros behind: T patches of any size -> [T, 3, pad_h, pad_w].
 //   orp_scene_collect  the packed per-tile detections of the static post-processing -> per-class segments of scene-coordinate
 //                      fp64 rows, the input of orp_poly_nms_f64_batched; replaces the Task1 text files the reference writes per
 //                      patch and parses back (parse_pkl_mege_results_for_dota_evaluation.py, ResultMerge_multi_process.py:182-223).
@@ -135,6 +137,110 @@ int launch_tiles(const uint8_t* scene, int H, int W, long long stride, const int
   if (blocks > 0x7fffffffLL || T_ > 65535) return ORP_ETOOBIG;
   hipLaunchKernelGGL(scene_tiles_kernel<T>, dim3((unsigned)blocks, (unsigned)T_), dim3(kTileThreads), 0, st, scene, H, W, stride,
                      origins, S, nrm, to_rgb, reinterpret_cast<T*>(out));
+  return done();
+}
+
+// ---- tiles, resampled ------------------------------------------------------------------------------------------------------
+// The test pipeline's RotateResize(keep_ratio) + Normalize + Pad of T patches in one launch.  The lane mapping is the one above
+// (16 bytes of every output plane per lane, the normalisation by LDS table); a block is 64 lanes along a row by 4 rows, twice,
+// so the axis tables of its kResCols columns and kResRows rows sit in LDS next to the normalisation table.  Per pixel and
+// channel: four source bytes, the two horizontal blends, the vertical one -- every product and sum rounded to fp32 on its own
+// (the __f*_rn forms never contract) --, rint, clamp, one table read.  With new == src every weight is 0 or 1 and the value is
+// the source byte: orp_scene_tiles' output.
+
+constexpr int kResRows = 4 * kTileIters;             // output rows per block
+
+template <typename T>
+__global__ void __launch_bounds__(kTileThreads)
+scene_tiles_resized_kernel(const unsigned char* __restrict__ scene, int H, int W, long long row_stride,
+                           const int32_t* __restrict__ origins, int src_w, int src_h, int new_w, int new_h, int pad_w, int pad_h,
+                           const int32_t* __restrict__ x_i0, const float* __restrict__ x_w1, const int32_t* __restrict__ y_i0,
+                           const float* __restrict__ y_w1, Norm3 nrm, int to_rgb, T* __restrict__ out) {
+  constexpr int kPix = 16 / (int)sizeof(T);
+  constexpr int kResCols = 64 * kPix;                // output columns per block
+  __shared__ T lut[3][256];
+  __shared__ __attribute__((aligned(16))) int col_i0[kResCols];
+  __shared__ __attribute__((aligned(16))) float col_w1[kResCols];
+  __shared__ int row_i0[kResRows];
+  __shared__ float row_w1[kResRows];
+  for (int i = threadIdx.x; i < 768; i += kTileThreads) {
+    const int c = i >> 8;
+    lut[c][i & 255] = OutOf<T>::make(__fdiv_rn((float)(i & 255) - nrm.mean[c], nrm.std[c]));
+  }
+  const int col0 = (int)blockIdx.x * kResCols, rowb = (int)blockIdx.y * kResRows;
+  for (int i = threadIdx.x; i < kResCols; i += kTileThreads) {
+    const int x = col0 + i;
+    const bool in = x < new_w;
+    col_i0[i] = in ? min(max(x_i0[x], 0), src_w - 1) : 0;   // (clamped: a wrong table cannot leave the patch)
+    col_w1[i] = in ? x_w1[x] : 0.f;
+  }
+  if (threadIdx.x < kResRows) {
+    const int y = rowb + (int)threadIdx.x;
+    const bool in = y < new_h;
+    row_i0[threadIdx.x] = in ? min(max(y_i0[y], 0), src_h - 1) : 0;
+    row_w1[threadIdx.x] = in ? y_w1[y] : 0.f;
+  }
+  __syncthreads();
+  const int t = blockIdx.z;
+  // the patch is kept inside the scene (src_w <= W and src_h <= H are checked on the host): no read leaves the scene
+  const int left = min(max(origins[2 * t], 0), W - src_w), up = min(max(origins[2 * t + 1], 0), H - src_h);
+  const int lx = (int)(threadIdx.x & 63), ly = (int)(threadIdx.x >> 6);
+  const int x0 = col0 + lx * kPix;
+  const T zero = OutOf<T>::make(0.f);
+  const size_t plane = (size_t)pad_h * pad_w;
+  const unsigned char* patch = scene + (long long)up * row_stride + (long long)left * 3;
+#pragma unroll 1
+  for (int it = 0; it < kTileIters; it++) {
+    const int r = it * 4 + ly;
+    const int y = rowb + r;
+    if ((y >= pad_h) | (x0 >= pad_w)) break;         // (pad_w % kPix == 0: a lane's 16 bytes are inside the row or outside it)
+    Vec16<T, kPix> o[3];
+#pragma unroll
+    for (int c = 0; c < 3; c++)
+#pragma unroll
+      for (int p = 0; p < kPix; p++) o[c].v[p] = zero;
+    if ((y < new_h) & (x0 < new_w)) {
+      const int ya = row_i0[r], yb = min(ya + 1, src_h - 1);
+      const float wy1 = row_w1[r], wy0 = __fsub_rn(1.f, wy1);
+      const unsigned char* top = patch + (long long)ya * row_stride;
+      const unsigned char* bot = patch + (long long)yb * row_stride;
+#pragma unroll
+      for (int p = 0; p < kPix; p++) {
+        if (x0 + p < new_w) {
+          const int xa = col_i0[lx * kPix + p], xb = min(xa + 1, src_w - 1);
+          const float wx1 = col_w1[lx * kPix + p], wx0 = __fsub_rn(1.f, wx1);
+#pragma unroll
+          for (int c = 0; c < 3; c++) {              // c: source channel
+            const float a = (float)top[3 * xa + c], b = (float)top[3 * xb + c];
+            const float e = (float)bot[3 * xa + c], f = (float)bot[3 * xb + c];
+            const float tv = __fadd_rn(__fmul_rn(wx0, a), __fmul_rn(wx1, b));
+            const float bv = __fadd_rn(__fmul_rn(wx0, e), __fmul_rn(wx1, f));
+            const float v = __fadd_rn(__fmul_rn(wy0, tv), __fmul_rn(wy1, bv));
+            const int byte = (int)fminf(fmaxf(rintf(v), 0.f), 255.f);
+            o[c].v[p] = lut[to_rgb ? 2 - c : c][byte];
+          }
+        }
+      }
+    }
+    T* dst = out + (size_t)t * 3 * plane + (size_t)y * pad_w + x0;
+#pragma unroll
+    for (int c = 0; c < 3; c++) *reinterpret_cast<Vec16<T, kPix>*>(dst + (to_rgb ? 2 - c : c) * plane) = o[c];
+  }
+}
+
+struct Axes { const int32_t* x_i0; const float* x_w1; const int32_t* y_i0; const float* y_w1; };
+
+template <typename T>
+int launch_tiles_resized(const uint8_t* scene, int H, int W, long long stride, const int32_t* origins, int T_, int src_w,
+                         int src_h, int new_w, int new_h, int pad_w, int pad_h, const Axes& ax, const Norm3& nrm, int to_rgb,
+                         void* out, hipStream_t st) {
+  constexpr int kPix = 16 / (int)sizeof(T);
+  if (pad_w % kPix != 0) return ORP_EINVAL;
+  const int bx = (pad_w + 64 * kPix - 1) / (64 * kPix), by = (pad_h + kResRows - 1) / kResRows;
+  if (by > 65535 || T_ > 65535) return ORP_ETOOBIG;
+  hipLaunchKernelGGL(scene_tiles_resized_kernel<T>, dim3((unsigned)bx, (unsigned)by, (unsigned)T_), dim3(kTileThreads), 0, st,
+                     scene, H, W, stride, origins, src_w, src_h, new_w, new_h, pad_w, pad_h, ax.x_i0, ax.x_w1, ax.y_i0, ax.y_w1,
+                     nrm, to_rgb, reinterpret_cast<T*>(out));
   return done();
 }
 
@@ -276,6 +382,30 @@ int orp_scene_tiles(const uint8_t* scene, int height, int width, long long row_s
     case 0: return launch_tiles<float>(scene, height, width, row_stride_bytes, origins, num_tiles, tile, nrm, to_rgb != 0, out, st);
     case 1: return launch_tiles<_Float16>(scene, height, width, row_stride_bytes, origins, num_tiles, tile, nrm, to_rgb != 0, out, st);
     case 2: return launch_tiles<bf16_bits>(scene, height, width, row_stride_bytes, origins, num_tiles, tile, nrm, to_rgb != 0, out, st);
+    default: return ORP_EINVAL;
+  }
+}
+
+int orp_scene_tiles_resized(const uint8_t* scene, int height, int width, long long row_stride_bytes, const int32_t* origins,
+                            int num_tiles, int src_w, int src_h, int new_w, int new_h, int pad_w, int pad_h, const int32_t* x_i0,
+                            const float* x_w1, const int32_t* y_i0, const float* y_w1, const float* mean_host,
+                            const float* std_host, int to_rgb, int out_dtype, void* out, void* stream) {
+  if (!scene || !origins || !x_i0 || !x_w1 || !y_i0 || !y_w1 || !mean_host || !std_host || !out || height <= 0 || width <= 0 ||
+      num_tiles < 0 || src_w <= 0 || src_h <= 0 || src_w > width || src_h > height || new_w <= 0 || new_h <= 0 || pad_w < new_w ||
+      pad_h < new_h || row_stride_bytes < (long long)width * 3 || ((uintptr_t)out & 15) != 0)
+    return ORP_EINVAL;
+  if (num_tiles == 0) return ORP_OK;
+  Norm3 nrm;
+  for (int c = 0; c < 3; c++) { nrm.mean[c] = mean_host[c]; nrm.std[c] = std_host[c]; }
+  const Axes ax = {x_i0, x_w1, y_i0, y_w1};
+  hipStream_t st = (hipStream_t)stream;
+  switch (out_dtype) {
+    case 0: return launch_tiles_resized<float>(scene, height, width, row_stride_bytes, origins, num_tiles, src_w, src_h, new_w, new_h,
+                                               pad_w, pad_h, ax, nrm, to_rgb != 0, out, st);
+    case 1: return launch_tiles_resized<_Float16>(scene, height, width, row_stride_bytes, origins, num_tiles, src_w, src_h, new_w,
+                                                  new_h, pad_w, pad_h, ax, nrm, to_rgb != 0, out, st);
+    case 2: return launch_tiles_resized<bf16_bits>(scene, height, width, row_stride_bytes, origins, num_tiles, src_w, src_h, new_w,
+                                                   new_h, pad_w, pad_h, ax, nrm, to_rgb != 0, out, st);
     default: return ORP_EINVAL;
   }
 }

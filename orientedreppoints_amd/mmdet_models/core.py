@@ -194,9 +194,11 @@ def multiclass_rnms_static(multi_bboxes, multi_scores, score_thr, nms_cfg, max_n
     return torch.cat([body, tail], 0)
 
 
-def fused_postprocess(cls_scores, points_preds, strides, cfg, num_points=9):
+def fused_postprocess(cls_scores, points_preds, strides, cfg, num_points=9, scale_factor=None):
     """get_bboxes_single + multiclass_rnms + packing for ONE image on the fused HIP kernels (csrc/orp_postproc.hip):
     cls_scores[l] [C,H,W] logits, points_preds[l] [2*num_points,H,W] refine offsets ((y,x)-interleaved, grid units).
+    scale_factor (a scalar; `rescale=True` of get_bboxes_single): the decoded boxes and rep-points are divided by it in fp32
+    before the selection and the NMS, with the dynamic path's own division (a tensor by a 0-dim device tensor).
     Same detections in the same order as the tensor-op path (`multiclass_rnms_static`); torch keeps the numerically
     sensitive pieces (sigmoid, class max, top-k), everything else is three kernels around min-area-rect and the NMS.
     Returns the packed [max_per_img + 1, 28] tensor of `rbbox2result_packed`."""
@@ -243,6 +245,10 @@ def fused_postprocess(cls_scores, points_preds, strides, cfg, num_points=9):
         _lib.check(L.orp_pp_gather(_lib.ptr(pts_all), _lib.ptr(cand), m0, N, lo, lw, ls, len(sizes), _lib.ptr(pts_xy),
                                    _lib.ptr(centers), _lib.ptr(strd), _lib.ptr(rep), st), "orp_pp_gather")
     boxes = minaerarect_decode(pts_xy, centers, strd)                                # [m0, 8]
+    if scale_factor is not None:
+        scale = scale_scalar(scale_factor, dev)
+        boxes /= scale
+        rep /= scale
     cap = int(min(cfg.get('static_capacity', 8192), m0 * C))
     max_num = int(cfg.max_per_img)
     m = int(min(max_num, cap)) if max_num > 0 else cap
@@ -288,6 +294,26 @@ def select_candidates(sig, offs, nms_pre):
 
 
 _arange_cache = {}
+_scale_cache = {}
+
+
+def is_scalar_scale(scale_factor):
+    """True for the `scale_factor` of `keep_ratio=True` (one number), False for the per-axis 4-vector of `keep_ratio=False`."""
+    return np.ndim(scale_factor) == 0 and not isinstance(scale_factor, torch.Tensor)
+
+
+def scale_scalar(scale_factor, dev):
+    """`boxes.new_tensor(scale_factor)` of get_bboxes_single as a cached 0-dim float32 device tensor (value-keyed).  The first
+    use of a value copies from pageable host memory, which a stream capture and a sync-free loop cannot contain: the warm-up
+    runs of a capture create it, the capture finds it here, and the graph keeps it alive (`keep_for_graph`)."""
+    key = (float(scale_factor), dev)
+    t = _scale_cache.get(key)
+    if t is None:
+        t = torch.tensor(key[0], dtype=torch.float32, device=dev)
+        if len(_scale_cache) >= 256:
+            _scale_cache.pop(next(iter(_scale_cache)))
+        _scale_cache[key] = t
+    return _lib.keep_for_graph(t)
 
 
 def _arange_cached(a, b, dev):

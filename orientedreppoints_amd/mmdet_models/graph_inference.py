@@ -11,7 +11,7 @@ buffer, the replay, one D2H copy of the packed detections per image (`rbbox2resu
 import torch
 
 from .. import _lib
-from .core import rbbox2result_packed
+from .core import is_scalar_scale, rbbox2result_packed
 
 
 def _param_fingerprint(tensors):
@@ -30,14 +30,19 @@ class GraphedInference(object):
     merge NMS growing the shared scratch, the capacity-overflow fallback, a training step, a cache eviction) can free
     or move memory a replay uses.  If the model's parameters change, the next call re-captures."""
 
-    def __init__(self, model, img, img_metas, warmup=3):
+    def __init__(self, model, img, img_metas, warmup=3, rescale=False):
         """model: an eval-mode OrientedRepPointsDetector on a GPU; img [B,3,H,W] (its shape / dtype are captured);
-        img_metas: the B meta dicts used for every later call.  Raises if the path is not capturable."""
+        img_metas: the B meta dicts used for every later call; rescale: as in `simple_test_batch(img, img_metas, rescale)` --
+        boxes and rep-points divided by each meta's `scale_factor` before the NMS, inside the graph.  Raises if the path is
+        not capturable (with rescale: a per-axis `scale_factor`, i.e. `keep_ratio=False`)."""
+        self.model, self.metas, self.rescale = model, list(img_metas), bool(rescale)
+        if self.rescale and not all(is_scalar_scale(m['scale_factor']) for m in self.metas):
+            raise ValueError("GraphedInference: rescale=True needs one scale factor per image (keep_ratio=True); a per-axis "
+                             "scale_factor is left to simple_test_batch")
         if model.training or not img.is_cuda:
             raise ValueError("GraphedInference needs an eval-mode model and a CUDA image")
         if model.test_cfg.nms.get('type', 'rnms') != 'rnms' or not model.test_cfg.get('static_postprocess', True):
             raise ValueError("GraphedInference needs the static rnms post-processing")
-        self.model, self.metas = model, list(img_metas)
         self.num_classes = model.bbox_head.num_classes
         self.static_img = img.clone()
         self.warmup = max(1, warmup)
@@ -47,7 +52,7 @@ class GraphedInference(object):
     def _device_part(self):
         model, head = self.model, self.model.bbox_head
         outs = head(model.extract_feat(self.static_img))
-        return head.get_bboxes(*(tuple(outs) + (self.metas, model.test_cfg, False)), static=True)
+        return head.get_bboxes(*(tuple(outs) + (self.metas, model.test_cfg, self.rescale)), static=True)
 
     def _capture(self):
         dev = self.static_img.device
@@ -79,7 +84,7 @@ class GraphedInference(object):
         self._capture()
 
     def __call__(self, img):
-        """The per-image result lists of `simple_test_batch(img, img_metas)`."""
+        """The per-image result lists of `simple_test_batch(img, img_metas, rescale)`."""
         self.static_img.copy_(img, non_blocking=True)
         self.graph.replay()
         # checked while the replay runs (keeps ~50 us of host work off the critical path): if the weights changed, the
@@ -90,7 +95,7 @@ class GraphedInference(object):
         results = [rbbox2result_packed(p, self.num_classes) for p in self.packed]
         if any(r is None for r in results):               # more pairs above score_thr than the static capacity holds
             with torch.no_grad():
-                return self.model.simple_test_batch(img, self.metas)
+                return self.model.simple_test_batch(img, self.metas, self.rescale)
         return results
 
 
@@ -100,9 +105,10 @@ class PipelinedInference(object):
     queues an image and returns the results of the image submitted `depth` calls earlier (None while the pipe fills);
     `flush()` returns what is still in flight, oldest first.  The tail of one image (decode, NMS: many small kernels
     that leave most CUs idle) then overlaps the backbone of the next one, and the host never waits on the image it has
-    just queued.  Every image still runs the complete step and produces the same detections as `GraphedInference`."""
+    just queued.  Every image still runs the complete step and produces the same detections as `GraphedInference`;
+    `rescale` is passed on to it."""
 
-    def __init__(self, model, img, img_metas, depth=2, warmup=3, _allow_half=False):
+    def __init__(self, model, img, img_metas, depth=2, warmup=3, _allow_half=False, rescale=False):
         dev = img.device
         if (depth > 2 and not _allow_half and torch.backends.cudnn.deterministic
                 and any(p.dtype != torch.float32 for p in model.parameters())):
@@ -113,14 +119,14 @@ class PipelinedInference(object):
             # Refused here rather than hung there.
             raise ValueError("PipelinedInference: with torch.backends.cudnn.deterministic = True a half / bfloat16 model supports at most "
                              "two graphs in flight (depth <= 2); switch the flag off or lower the depth")
-        self.model, self.metas, self.depth = model, list(img_metas), depth
+        self.model, self.metas, self.depth, self.rescale = model, list(img_metas), depth, bool(rescale)
         self.num_classes = model.bbox_head.num_classes
         # with several images in flight the two towers of ONE image need no second stream (measured: 225 vs 218 img/s)
         head = model.bbox_head
         prev = getattr(head, 'tower_streams', None)
         head.tower_streams = False
         try:
-            self.slots = [GraphedInference(model, img, img_metas, warmup) for _ in range(depth)]
+            self.slots = [GraphedInference(model, img, img_metas, warmup, rescale) for _ in range(depth)]
         finally:
             head.tower_streams = prev
         self.streams = [torch.cuda.Stream(device=dev) for _ in range(depth)]
@@ -136,7 +142,7 @@ class PipelinedInference(object):
         results = [rbbox2result_packed(h, self.num_classes) for h in self.host[k]]
         if any(r is None for r in results):               # static capacity overflow: the reference-shaped path, synchronously
             with torch.no_grad():
-                return self.model.simple_test_batch(img, self.metas)
+                return self.model.simple_test_batch(img, self.metas, self.rescale)
         return results
 
     def _fresh_slot(self, k):

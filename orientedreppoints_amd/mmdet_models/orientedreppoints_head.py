@@ -19,7 +19,8 @@ import torch.nn.functional as F
 
 from ..mmdet_ops.deform_conv import DeformConv
 from ..mmdet_ops.minarea_rect import minaerarect_decode
-from .core import PointGenerator, fused_postprocess, multi_apply, multiclass_rnms, multiclass_rnms_static
+from .core import (PointGenerator, fused_postprocess, is_scalar_scale, multi_apply, multiclass_rnms, multiclass_rnms_static,
+                   scale_scalar)
 from .layers import ConvModule, bias_init_with_prob, normal_init
 from .registry import HEADS, build_loss
 
@@ -482,10 +483,12 @@ class OrientedRepPointsHead(nn.Module):
     def get_bboxes_single(self, cls_scores, points_preds, mlvl_points, img_shape, scale_factor, cfg, rescale=False,
                           nms=True, static=False):
         assert len(cls_scores) == len(points_preds) == len(mlvl_points)
-        if nms and static and self.use_sigmoid_cls and not rescale and cfg.nms.get('type', 'rnms') == 'rnms' \
-                and cfg.get('fused_postprocess', True) and cls_scores[0].is_cuda:
+        # (a per-axis scale factor, keep_ratio=False, is not taken by the fused kernels: the tensor-op path below divides by it)
+        if nms and static and self.use_sigmoid_cls and (not rescale or is_scalar_scale(scale_factor)) \
+                and cfg.nms.get('type', 'rnms') == 'rnms' and cfg.get('fused_postprocess', True) and cls_scores[0].is_cuda:
             # decode -> selection -> NMS -> packing on the fused HIP kernels (same detections, same order)
-            return fused_postprocess(cls_scores, points_preds, self.point_strides, cfg, self.num_points)
+            return fused_postprocess(cls_scores, points_preds, self.point_strides, cfg, self.num_points,
+                                     scale_factor=scale_factor if rescale else None)
         lvl_pts, lvl_scores, lvl_centers, lvl_strides = [], [], [], []
         for i_lvl, (cls_score, points_pred, points) in enumerate(zip(cls_scores, points_preds, mlvl_points)):
             assert cls_score.size()[-2:] == points_pred.size()[-2:]
@@ -514,7 +517,11 @@ class OrientedRepPointsHead(nn.Module):
         # one fused kernel for all levels: hull -> min-area rect -> corners * stride + centre  (head :746-749)
         mlvl_bboxes = minaerarect_decode(pts_all, centers, strides)
         mlvl_reppoints = pts_all * strides[:, None] + centers.repeat(1, self.num_points)
-        if rescale:
+        if rescale and static and is_scalar_scale(scale_factor) and mlvl_bboxes.dtype == mlvl_reppoints.dtype == torch.float32:
+            # the same division by a 0-dim tensor; the cached scalar keeps a pageable host copy out of a capture
+            mlvl_bboxes /= scale_scalar(scale_factor, mlvl_bboxes.device)
+            mlvl_reppoints /= scale_scalar(scale_factor, mlvl_bboxes.device)
+        elif rescale:
             mlvl_bboxes /= mlvl_bboxes.new_tensor(scale_factor)
             mlvl_reppoints /= mlvl_reppoints.new_tensor(scale_factor)
         mlvl_scores = torch.cat(lvl_scores)

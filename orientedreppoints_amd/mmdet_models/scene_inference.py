@@ -5,9 +5,9 @@ Replaces the reference's chain `DOTA_devkit/SplitOnlyImage.py` (patches to files
 host, results to a pickle) -> `tools/parse_pkl/parse_pkl_mege_results_for_dota_evaluation.py` (Task1 text files per class) ->
 `DOTA_devkit/ResultMerge_multi_process.py:mergebypoly` (parse, translate, NMS per class):
 
-    tile plan (`dota_devkit.img_split`)  ->  `orp_scene_tiles` straight into a captured graph's input buffer  ->  graph
-    replay (`PipelinedInference`)  ->  packed results stay on the device  ->  `orp_scene_collect`  ->  one
-    `orp_poly_nms_f64_batched`  ->  one gather, one D2H.
+    tile plan (`dota_devkit.img_split`)  ->  `orp_scene_tiles` / `orp_scene_tiles_resized` straight into a captured graph's
+    input buffer  ->  graph replay (`PipelinedInference`)  ->  packed results stay on the device  ->  `orp_scene_collect`
+    ->  one `orp_poly_nms_f64_batched`  ->  one gather, one D2H.
 """
 import os
 
@@ -17,7 +17,8 @@ import torch.nn.functional as F
 
 from ..dota_devkit.img_split import scaled_size, split_origins
 from ..mmdet_ops.nms_wrapper import poly_nms_f64_batched_device
-from ..mmdet_ops.scene_ops import scene_collect, scene_tiles
+from ..mmdet_datasets.imops import rescale_size
+from ..mmdet_ops.scene_ops import resize_tables, scene_collect, scene_tiles, scene_tiles_resized
 from .graph_inference import PipelinedInference
 
 DOTA_CLASSES = ('plane', 'baseball-diamond', 'bridge', 'ground-track-field', 'small-vehicle', 'large-vehicle', 'ship',
@@ -26,15 +27,35 @@ DOTA_CLASSES = ('plane', 'baseball-diamond', 'bridge', 'ground-track-field', 'sm
 
 
 class _Plan(object):
-    """One scene's work: per rate the (resampled) uint8 scene, the tile origins (host list and padded device tensor) and,
-    once the tiles ran, the packed results [Tpad, m + 1, 28]."""
+    """One scene's work: per rate the (resampled) uint8 scene, the tile origins (host list and padded device tensor), the
+    patch shape's entry (`_Shape`; None = the native-size route) and, once the tiles ran, the packed results
+    [Tpad, m + 1, 28]."""
 
     def __init__(self):
-        self.rates, self.scenes, self.origins, self.origins_dev, self.packed = [], [], [], [], []
+        self.rates, self.scenes, self.origins, self.origins_dev, self.packed, self.shapes = [], [], [], [], [], []
+
+
+class _Shape(object):
+    """What the patches of one shape go through under `img_scale`: src = (w, h) of a patch, new = (w, h) after the resize,
+    pad = (w, h) of the detector's input, the scale factor, the metas the host pipeline would set, and (once captured) the
+    graphs of that input shape."""
+
+    def __init__(self, src, img_scale, divisor, batch):
+        self.src = (int(src[0]), int(src[1]))
+        new_w, new_h, self.scale_factor = rescale_size(self.src, img_scale)
+        self.new = (new_w, new_h)
+        self.pad = (-(-new_w // divisor) * divisor, -(-new_h // divisor) * divisor)
+        # an identity resize of a square patch the divisor leaves alone: `orp_scene_tiles`' case
+        self.native = self.new == self.src == self.pad and self.src[0] == self.src[1]
+        self.metas = [dict(img_shape=(new_h, new_w, 3), pad_shape=(self.pad[1], self.pad[0], 3),
+                           scale_factor=self.scale_factor, flip=False) for _ in range(batch)]
+        self.pipe = self.tables = None
 
 
 class SceneInference(object):
-    """`si = SceneInference(model, subsize=1024, gap=200, rates=(1.0,), batch=1, depth=4); per_class = si(scene)`.
+    """`si = SceneInference(model, subsize=1024, gap=200, rates=(1.0,), batch=1, depth=4, img_scale=None); per_class = si(scene)`;
+    `SceneInference.from_config(model, cfg)` takes `img_scale`, the normalisation and the pad divisor from a config's test
+    pipeline.
 
     scene: uint8 [H, W, 3] numpy array or tensor (host or device), BGR as `cv2.imread` gives it.  Returns one float64 [k, 9]
     array per class (8 scene coordinates + score) in the merge's visiting order -- the lines `mergesingle` would write;
@@ -43,10 +64,19 @@ class SceneInference(object):
     * Tiles are those of `SplitSingle` (`img_split.split_origins`: same origins, same order) for every rate; `batch` tiles run
       per captured graph, `depth` graphs in flight (`PipelinedInference`, whose half-model guard applies).  The last, partly
       filled batch repeats its last tile; the repeats are not collected.
-    * Patches are fed at scale factor 1: normalised (`imnormalize` with `mean`, `std`, `to_rgb`, bit for bit) and nothing
-      else.  That is the reference's test pipeline for 1024^2 patches under `orientedrepoints_r50_demo.py`
-      (`img_scale=(1333, 1024)`).  The R-101 and Swin-T configs test at `(1333, 960)`: they shrink a 1024^2 patch to 960^2 and
-      scale the boxes back; that per-patch resize is NOT reproduced, those models see the patches at native size here.
+    * `img_scale=None`: patches are fed at scale factor 1, normalised (`imnormalize` with `mean`, `std`, `to_rgb`, bit for
+      bit) and nothing else.  That is the reference's test pipeline for 1024^2 patches under `orientedrepoints_r50_demo.py`
+      (`img_scale=(1333, 1024)`).
+    * `img_scale=(long edge, short edge)`, e.g. `(1333, 960)` of the R-101 and Swin-T configs: the test pipeline's
+      `RotateResize(keep_ratio=True)` -> `Normalize` -> `Pad(size_divisor)` per patch, on the device.  A patch is
+      `(min(W, subsize), min(H, subsize))` (what `SplitOnlyImage` writes for a small scene: it does not pad); it is resized
+      to `imops.rescale_size(patch, img_scale)` by `orp_scene_tiles_resized` (bilinear, `align_corners=False`, rounded to
+      uint8, in the fp32 arithmetic DESIGN.md fixes: within one grey level of `imops.imresize` on at most 1e-3 of the pixels,
+      the band in which torch's own CPU resize differs between thread counts), padded with zeros to the divisor, and the
+      graphs divide boxes and rep-points by the scale factor before the NMS (`rescale=True`), so their rows are in patch
+      coordinates as the file route's are.  Graphs are kept per patch shape (four shapes, oldest dropped).  A patch
+      whose resize is the identity goes through `orp_scene_tiles`.
+    * Flip and multi-scale test augmentation (`MultiScaleFlipAug` with `flip=True` or several scales) are not built.
     * rates != 1: the scene is resampled once on the device with torch's bicubic `interpolate` (`align_corners=False`),
       rounded and clamped to uint8, to `img_split.scaled_size`.  This follows OpenCV's conventions but is NOT checked against
       cv2's `INTER_CUBIC` pixels.  The rate used in coordinates is `float(str(rate))`, as the patch-name grammar implies.
@@ -58,15 +88,22 @@ class SceneInference(object):
       within that distance of the threshold.
 
     Raises ValueError for `subsize % 32 != 0` (the pipeline's `Pad(size_divisor=32)` would change the patch), for a model
-    `GraphedInference` refuses (training mode, no static rnms post-processing), and -- per scene -- for a scaled scene with a
-    side below `subsize` (the reference pipeline would upscale such a patch through `RotateResize(keep_ratio)`; not reproduced).
-    Segments above `ORP_NMS_MAX_BOXES` raise `OrpHipError` in the merge."""
+    `GraphedInference` refuses (training mode, no static rnms post-processing), and -- per scene, with `img_scale=None` -- for
+    a scaled scene with a side below `subsize` (the reference pipeline would upscale such a patch through
+    `RotateResize(keep_ratio)`: set `img_scale`).  Segments above `ORP_NMS_MAX_BOXES` raise `OrpHipError` in the merge."""
 
     def __init__(self, model, subsize=1024, gap=200, rates=(1.0,), batch=1, depth=4, nms_thresh=0.1,
-                 mean=(123.675, 116.28, 103.53), std=(58.395, 57.12, 57.375), to_rgb=True):
+                 mean=(123.675, 116.28, 103.53), std=(58.395, 57.12, 57.375), to_rgb=True, img_scale=None, size_divisor=32):
         subsize, gap, batch, depth = int(subsize), int(gap), int(batch), int(depth)
         if subsize <= 0 or subsize % 32 != 0:
             raise ValueError("SceneInference: subsize (%d) must be a positive multiple of 32, the test pipeline's Pad divisor" % subsize)
+        if img_scale is not None:
+            img_scale = tuple(int(v) for v in img_scale)
+            if len(img_scale) != 2 or min(img_scale) <= 0:
+                raise ValueError("SceneInference: img_scale must be None or two positive edge bounds, e.g. (1333, 960)")
+        self.img_scale, self.size_divisor = img_scale, int(size_divisor)
+        if self.size_divisor <= 0 or self.size_divisor % 8 != 0:
+            raise ValueError("SceneInference: size_divisor must be a positive multiple of 8 (16 bytes of an output row per lane)")
         if not 0 <= gap < subsize:
             raise ValueError("SceneInference: gap (%d) must be in [0, subsize)" % gap)
         if batch < 1 or depth < 1 or len(rates) == 0:
@@ -85,11 +122,65 @@ class SceneInference(object):
         self.num_classes = model.bbox_head.num_classes - 1
         self.metas = [dict(img_shape=(subsize, subsize, 3), pad_shape=(subsize, subsize, 3), scale_factor=1.0, flip=False)
                       for _ in range(batch)]
-        self.pipe = None
+        self.pipe = None                           # the native-size graphs (img_scale=None)
+        self._shapes = {}                          # (width, height) of a patch -> _Shape (img_scale set; at most 4)
         self._origins = {}                         # (width, height) of a scaled scene -> (host list, padded device tensor)
         self.fallback_tiles = 0                    # tiles re-run because their packed result overflowed (all calls)
 
+    @classmethod
+    def from_config(cls, model, cfg, **kw):
+        """`SceneInference(model, ...)` with `img_scale`, `mean`, `std`, `to_rgb` and `size_divisor` read from
+        `cfg.data.test.pipeline` (`MultiScaleFlipAug` around `RotateResize` / `Normalize` / `Pad`); keywords override.  Raises
+        ValueError for a pipeline this class does not reproduce: `flip=True`, more than one scale, `keep_ratio=False`, an
+        interpolation other than bilinear, a fixed-size `Pad`."""
+        aug = [t for t in cfg.data.test.pipeline if t['type'] == 'MultiScaleFlipAug']
+        if len(aug) != 1:
+            raise ValueError("SceneInference.from_config: the test pipeline must hold one MultiScaleFlipAug")
+        aug = aug[0]
+        scales = aug['img_scale'] if isinstance(aug['img_scale'], list) else [aug['img_scale']]
+        if aug.get('flip', False):
+            raise ValueError("SceneInference.from_config: flip=True (test-time flip augmentation) is not reproduced")
+        if len(scales) != 1:
+            raise ValueError("SceneInference.from_config: %d test scales (multi-scale augmentation) are not reproduced" % len(scales))
+        got = dict(img_scale=tuple(scales[0]))
+        for t in aug['transforms']:
+            if t['type'] in ('RotateResize', 'Resize', 'PolyResize'):
+                if not t.get('keep_ratio', True):
+                    raise ValueError("SceneInference.from_config: keep_ratio=False (a per-axis scale factor) is not reproduced")
+                if t.get('interpolation', 'bilinear') != 'bilinear':
+                    raise ValueError("SceneInference.from_config: interpolation=%r is not reproduced (bilinear only)" % (t['interpolation'],))
+            elif t['type'] == 'Normalize':
+                got.update(mean=tuple(t['mean']), std=tuple(t['std']), to_rgb=t.get('to_rgb', True))
+            elif t['type'] == 'Pad':
+                if t.get('size') is not None or t.get('size_divisor') is None:
+                    raise ValueError("SceneInference.from_config: Pad to a fixed size is not reproduced")
+                got.update(size_divisor=t['size_divisor'])
+        got.update(kw)
+        return cls(model, **got)
+
     # ---- the three stages of a call ------------------------------------------------------------------------------------------
+    def tile_shapes(self, W, H):
+        """Host-side planning of a W x H scene: per rate ((w, h) of the scaled scene, its patches' `_Shape` or None for the
+        native-size route).  Raises the ValueError of a scene smaller than a tile when `img_scale` is None."""
+        out = []
+        for r, v in self.rates:
+            w, h = (W, H) if v == 1.0 else scaled_size(W, H, v)
+            if self.img_scale is None:
+                if min(w, h) < self.subsize:
+                    raise ValueError("SceneInference: the scene at rate %s is %d x %d, smaller than a %d tile (the reference "
+                                     "would upscale such a patch: set img_scale)" % (r, w, h, self.subsize))
+                out.append(((w, h), None))
+                continue
+            if min(w, h) < 1:
+                raise ValueError("SceneInference: the scene at rate %s is empty" % r)
+            src = (min(w, self.subsize), min(h, self.subsize))
+            if src not in self._shapes:
+                if len(self._shapes) >= 4:
+                    self._shapes.pop(next(iter(self._shapes)))
+                self._shapes[src] = _Shape(src, self.img_scale, self.size_divisor, self.batch)
+            out.append(((w, h), self._shapes[src]))
+        return out
+
     def prepare(self, scene):
         """Upload (if needed), resample per rate, plan the tiles, capture the graphs on first use.  Returns the plan."""
         if isinstance(scene, np.ndarray):
@@ -97,11 +188,8 @@ class SceneInference(object):
         if scene.dtype != torch.uint8 or scene.dim() != 3 or scene.size(2) != 3:
             raise ValueError("SceneInference: scene must be uint8 [H, W, 3]")
         H, W = int(scene.size(0)), int(scene.size(1))
-        sizes = [(W, H) if v == 1.0 else scaled_size(W, H, v) for _, v in self.rates]
-        for (r, _), (w, h) in zip(self.rates, sizes):
-            if min(w, h) < self.subsize:
-                raise ValueError("SceneInference: the scene at rate %s is %d x %d, smaller than a %d tile (the reference would "
-                                 "upscale such a patch; not reproduced)" % (r, w, h, self.subsize))
+        planned = self.tile_shapes(W, H)
+        sizes = [size for size, _ in planned]
         p = next(self.model.parameters())
         if not p.is_cuda:
             raise ValueError("SceneInference: the model must be on a GPU")
@@ -122,10 +210,23 @@ class SceneInference(object):
             host, on_dev = self._origins[(w, h)]
             plan.origins.append(host)
             plan.origins_dev.append(on_dev)
-        if self.pipe is None:
-            img = torch.zeros((self.batch, 3, self.subsize, self.subsize), dtype=p.dtype, device=dev)
-            self.pipe = PipelinedInference(self.model, img, self.metas, depth=self.depth)
+        for _, shape in planned:
+            plan.shapes.append(shape)
+            if shape is None and self.pipe is None:
+                img = torch.zeros((self.batch, 3, self.subsize, self.subsize), dtype=p.dtype, device=dev)
+                self.pipe = PipelinedInference(self.model, img, self.metas, depth=self.depth)
+            elif shape is not None and shape.pipe is None:
+                img = torch.zeros((self.batch, 3, shape.pad[1], shape.pad[0]), dtype=p.dtype, device=dev)
+                shape.pipe = PipelinedInference(self.model, img, shape.metas, depth=self.depth, rescale=True)
+            if shape is not None and not shape.native:         # the axis tables' upload happens here, not in the tile loop
+                shape.tables = [resize_tables(a, b, dev) for a, b in zip(shape.src, shape.new)]
         return plan
+
+    def _fill(self, shape, scene, origins, static_img):
+        """The tiles at `origins` of `scene` into a detector input buffer."""
+        if shape is None or shape.native:
+            return scene_tiles(scene, origins, static_img, self.mean, self.std, self.to_rgb)
+        return scene_tiles_resized(scene, origins, shape.src, shape.new, static_img, self.mean, self.std, self.to_rgb)
 
     @staticmethod
     def _resample(scene, w, h):
@@ -136,24 +237,29 @@ class SceneInference(object):
     def run_tiles(self, plan):
         """Every tile of every rate through the captured graphs; the packed results land in plan.packed.  Nothing here waits
         for the device or copies to the host."""
-        pipe, B = self.pipe, self.batch
+        B = self.batch
         dev = plan.scenes[0].device
-        rows = pipe.slots[0].packed[0].size(0)
+        shapes = plan.shapes or [None] * len(plan.scenes)
+        pipes = []
         plan.packed = []
-        for scene, on_dev in zip(plan.scenes, plan.origins_dev):
+        for scene, on_dev, shape in zip(plan.scenes, plan.origins_dev, shapes):
+            pipe = self.pipe if shape is None else shape.pipe
+            pipes.append(pipe)
+            rows = pipe.slots[0].packed[0].size(0)
             packed = torch.empty((on_dev.size(0), rows, 28), dtype=torch.float32, device=dev)
             plan.packed.append(packed)
             for i in range(0, on_dev.size(0), B):
                 def fill(static_img, i=i):
-                    scene_tiles(scene, on_dev[i:i + B], static_img, self.mean, self.std, self.to_rgb)
+                    self._fill(shape, scene, on_dev[i:i + B], static_img)
 
                 def sink(outs, i=i):
                     for j, o in enumerate(outs):
                         packed[i + j].copy_(o, non_blocking=True)
                 pipe.submit_device(fill, sink)
         cur = torch.cuda.current_stream(dev)
-        for s in pipe.streams:
-            cur.wait_stream(s)
+        for pipe in pipes:
+            for s in pipe.streams:
+                cur.wait_stream(s)
         return plan
 
     def merge(self, plan):
@@ -201,11 +307,15 @@ class SceneInference(object):
         T, m = len(plan.origins[i]), packed.size(1) - 1
         over = np.nonzero(packed[:T, m, 1].cpu().numpy())[0]
         redo = {}
-        img = torch.empty_like(self.pipe.slots[0].static_img)
+        shape = plan.shapes[i] if plan.shapes else None
+        img = torch.empty_like((self.pipe if shape is None else shape.pipe).slots[0].static_img)
         for b in sorted(set(int(t) // B for t in over)):
-            scene_tiles(plan.scenes[i], on_dev[b * B:(b + 1) * B], img, self.mean, self.std, self.to_rgb)
+            self._fill(shape, plan.scenes[i], on_dev[b * B:(b + 1) * B], img)
             with torch.no_grad():
-                results = self.model.simple_test_batch(img, self.metas)
+                if shape is None:
+                    results = self.model.simple_test_batch(img, self.metas)
+                else:
+                    results = self.model.simple_test_batch(img, shape.metas, rescale=True)
             for t in over[over // B == b]:
                 per_class = results[int(t) - b * B]
                 rows = np.concatenate([np.concatenate([r[:, -27:], np.full((len(r), 1), c, np.float32)], 1)
