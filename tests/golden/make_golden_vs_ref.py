@@ -1,4 +1,4 @@
-"""Record tests/golden/oracle_vs_ref.npz: every call that tests/test_oracle_vs_ref.py makes of the reference's own functions
+"""Record tests/golden/oracle_vs_ref.npz (and the files the test module's SPLIT names): every call that tests/test_oracle_vs_ref.py makes of the reference's own functions
 (oracle/_ref/libref_orp.so, built by oracle/build_ref.py from the reference's sources), on the test's own seeded inputs.
 Run where the reference tree is (python tests/golden/make_golden_vs_ref.py); the fixture is committed."""
 import importlib.util
@@ -34,8 +34,19 @@ def main():
             rec = t.Recorded(orp_oracle, test_id, record=record)
             fn(ref=rec, **kw)
             rec.finish()
-    np.savez_compressed(os.path.join(HERE, "oracle_vs_ref.npz"), **record)
-    print("%d arrays" % len(record))
+    files = {}
+    for key, v in record.items():
+        files.setdefault(t.golden_file_of(key), {})[key] = v
+    for name, arrays in sorted(files.items()):
+        path = os.path.join(HERE, name)
+        if os.path.exists(path):                      # leave a file alone whose records did not change
+            with np.load(path) as old:
+                if sorted(old.files) == sorted(arrays) and all(
+                        old[k].dtype == np.asarray(arrays[k]).dtype and np.array_equal(old[k], arrays[k], equal_nan=True) for k in arrays):
+                    print("%s: unchanged (%d arrays)" % (name, len(arrays)))
+                    continue
+        np.savez_compressed(path, **arrays)
+        print("%s: %d arrays" % (name, len(arrays)))
 
 
 if __name__ == "__main__":

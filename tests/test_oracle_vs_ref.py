@@ -1,15 +1,27 @@
 """CPU: pin the oracle restatement against the REAL reference code.  Every call of the reference's own functions (the ref_*
 functions of the oracle module and its use_ref=True legs: the reference's device functions host-compiled into oracle/_ref by
 oracle/build_ref.py) is answered from tests/golden/oracle_vs_ref.npz, recorded from that library on the same seeded inputs by
-tests/golden/make_golden_vs_ref.py; the oracle side is computed here."""
+tests/golden/make_golden_vs_ref.py; the oracle side is computed here.  (The convex GIoU families' records are kept in a file
+of their own, oracle_vs_ref_giou.npz: SPLIT.)"""
 import os
+import sys
 
 import numpy as np
 import pytest
 
 from orientedreppoints_amd import synthetic as S
 
-GOLDEN = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "oracle_vs_ref.npz")
+HERE = os.path.dirname(os.path.abspath(__file__))
+GOLDEN = os.path.join(HERE, "golden", "oracle_vs_ref.npz")
+# records of these tests' calls from the given call number on live in the named file next to GOLDEN
+SPLIT = {"test_convex_giou_values_and_gradients": (1, "oracle_vs_ref_giou.npz")}
+
+
+def golden_file_of(key):
+    """File of the record `key` ("<test id>/<call>/...")."""
+    test_id, call = key.split("/")[:2]
+    first, name = SPLIT.get(test_id, (None, None))
+    return name if name and call.isdigit() and int(call) >= first else os.path.basename(GOLDEN)
 
 
 def _is_ref_call(name, kwargs):
@@ -59,8 +71,11 @@ class Recorded(object):
 
 @pytest.fixture(scope="module")
 def golden():
-    with np.load(GOLDEN) as g:
-        return {k: g[k] for k in g.files}
+    out = {}
+    for name in [os.path.basename(GOLDEN)] + sorted(f for _, f in SPLIT.values()):
+        with np.load(os.path.join(os.path.dirname(GOLDEN), name)) as g:
+            out.update({k: g[k] for k in g.files})
+    return out
 
 
 @pytest.fixture
@@ -123,6 +138,36 @@ def test_convex_giou_values_and_gradients(ref):
     a, b = ref.convex_giou(pts, g), ref.ref_convex_giou(pts, g)
     assert a.shape == b.shape == (400, 19)
     assert np.array_equal(a, b, equal_nan=True)
+    # Second block: every input family of tests/giou_float64.py (ties, touching, degenerate, tiny, far, large ...), the
+    # rows of tests/test_giou_gradient_math.py.  Only rows the oracle flags are skipped: the reference overflows its
+    # scratch arrays there and is undefined.  This is the one authority for TOUCHING rows (a hull vertex on a gt vertex or
+    # edge), where the reference's gradient is a convention of its 1E-8 rules and not the derivative of anything, and for
+    # which of several exact copies of a point carries the gradient.
+    # Values: bit for bit.  Gradients: the reference multiplies dense Jacobians of the three cuts, the oracle pulls the
+    # area gradient back vertex by vertex -- the same fp64 terms summed in another order.  Measured on these rows: 13
+    # families bit-equal; near_tie 1.7e-14 and collinear 3.9e-15 of the row's largest component (components that cancel to
+    # ~0: 1e-16 against 1e-17); shared_corners 9.5e-11 (every crossing sits ON a vertex: den = s2 - s1 is tiny, the 2 x 2
+    # Jacobians are ~1 / den and cancel, which multiplies the 1e-16 of the summation order; 6.7e-9 on 5 000 such rows);
+    # rows whose every component is such a residue differ by up to 1.6e-16 absolute.  Bars: 4 x the measured figure --
+    # 4e-10 x row scale in the two families that touch, 7e-14 elsewhere, + 1e-15 absolute.
+    sys.path.insert(0, HERE)
+    import giou_float64 as G
+    worst = {}
+    for name, fam in G.FAMILIES.items():
+        pts, g = G.generate(name, G.SAMPLE_ROWS)
+        a, flags = ref.convex_giou(pts, g, return_flags=True)
+        b = ref.ref_convex_giou(pts, g)
+        ok = flags == 0
+        assert ok.sum() >= 0.9 * ok.size, name
+        a, b = a[ok], b[ok]
+        assert np.isfinite(b).all(), name
+        assert np.array_equal(a[:, 18].view(np.uint32), b[:, 18].view(np.uint32)), name
+        d = np.abs(a[:, :18].astype(np.float64) - b[:, :18]).max(1)
+        scale = np.abs(b[:, :18]).max(1).astype(np.float64)
+        bar = (4e-10 if fam.may_touch else 7e-14) * scale + 1e-15
+        worst[name] = float(np.max(d / (scale + 1e-15)))
+        assert (d <= bar).all(), (name, worst[name])
+    print("oracle vs reference, largest gradient difference / row scale per family: %s" % worst)
 
 
 def test_points_justify(ref):
