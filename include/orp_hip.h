@@ -213,13 +213,21 @@ int orp_dcn_forward_pair_heads(const orp_dcn_level* levels_a, const orp_dcn_leve
                                int in_layout, void* workspace, size_t workspace_bytes, void* stream);
 /* fp16 / bf16 DeformConv forward on v_mfma_f32_32x32x16_{f16,bf16} (the reference dispatches its DCN kernels over float
  * AND half: deform_conv_cuda_kernel.cu:259,353,451,781,813 AT_DISPATCH_FLOATING_TYPES_AND_HALF; BASELINE configs[4]).
- * dtype: 1 = fp16, 2 = bf16 -- inputs, offsets, masks, bias, packed weights and outputs are all of that type; the bilinear
- * combine and the accumulation are fp32.  Requires c_in % 256 == 0, c_out % 64 == 0, groups = deformable_groups = 1
- * (orp_dcn_half_path_ok); other configurations: convert to fp32 and use the entries above.
+ * dtype: 1 = fp16, 2 = bf16 -- inputs, offsets, masks, bias, packed weights and outputs are all of that type; the
+ * accumulation is fp32; the bilinear combine is fp32 rounded once for bf16 and packed half arithmetic for fp16.
+ * Requires c_in % 256 == 0, c_out % 64 == 0, groups = deformable_groups = 1 (orp_dcn_half_path_ok); other
+ * configurations: convert to fp32 and use the entries above.
  * packed weights: c_out * c_in * kh * kw elements, layout [tap][c_in/16][2][c_out][8]. */
 typedef struct { const void* input; const void* offset; void* output; int height; int width; } orp_dcn_level_h;
 int orp_dcn_half_path_ok(int c_in, int c_out, int kh, int kw, int groups, int deformable_groups);
 int orp_dcn_pack_weight_h(const void* weight, int c_out, int c_in, int kh, int kw, void* packed, int dtype, void* stream);
+/* Rows (output positions) per tile that orp_dcn_forward_multi_h uses for a launch over `positions_all_levels` output
+ * positions (batch x Ho x Wo summed over the levels) on `nlevels` levels: 32, 64 or 96.  ORP_EINVAL for non-positive
+ * arguments or nlevels > 8.  Host only; the launcher calls the same function. */
+int orp_dcn_forward_h_tile_rows(long positions_all_levels, int nlevels);
+/* 1 when this process launches the wave-specialised kernel (the default), 0 when ORP_DCNH_WS=0 selected the symmetric
+ * one at load time.  Host only. */
+int orp_dcn_forward_h_wave_specialised(void);
 size_t orp_dcn_forward_h_workspace_bytes(const orp_dcn_level_h* levels_host, int nlevels, int batch, int c_in, int in_layout);
 int orp_dcn_forward_multi_h(const orp_dcn_level_h* levels_host, const void* const* masks_host, int nlevels, int batch, int c_in,
                             int c_out, const void* weight_packed, const void* bias, int relu, int kh, int kw, int stride_h,

@@ -72,6 +72,8 @@ _SIGNATURES = {
     "orp_dcn_forward_pair_heads": (_i, [_vp, _vp, _i, _i, _vp, _vp, _vp] + [_i] * 9 + [_vp, _sz, _vp]),
     "orp_dcn_half_path_ok": (_i, [_i, _i, _i, _i, _i, _i]),
     "orp_dcn_pack_weight_h": (_i, [_vp, _i, _i, _i, _i, _vp, _i, _vp]),
+    "orp_dcn_forward_h_tile_rows": (_i, [ctypes.c_long, _i]),
+    "orp_dcn_forward_h_wave_specialised": (_i, []),
     "orp_dcn_forward_h_workspace_bytes": (_sz, [_vp, _i, _i, _i, _i]),
     "orp_dcn_forward_multi_h": (_i, [_vp, _vp, _i, _i, _i, _i, _vp, _vp] + [_i] * 12 + [_vp, _sz, _vp]),
     "orp_dcn_im2col": (_i, [_vp, _vp, _vp] + [_i] * 13 + [_vp, _vp]),

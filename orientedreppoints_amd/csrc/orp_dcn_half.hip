@@ -6,8 +6,9 @@
 //   * same implicit GEMM as orp_dcn.hip (A = bilinear samples, never written to HBM; all FPN levels in one launch;
 //     NHWC inputs so that a wave fetches one neighbour of one position as a coalesced 512 B row of 256 channels),
 //     on v_mfma_f32_32x32x16_{f16,bf16}: 16 k-values per instruction, 16x the fp32 matrix rate, fp32 accumulation;
-//   * the bilinear combine is done in fp32 on the four gathered neighbours and rounded ONCE to the storage type (the
-//     reference rounds every partial product in half) -- closer to the fp32 result than the reference's own half path;
+//   * the bilinear combine of the four gathered neighbours: bf16 in fp32, rounded ONCE to the storage type; fp16 in packed half
+//     arithmetic since round 3 (Elem<_Float16>::combine8: every product and partial sum rounded to half, as the reference's own
+//     half kernels do).  The coefficient table itself (weights x modulation) is fp32 for both;
 //   * at this matrix rate one kernel tap of MFMA work (16 chunks x 3 instructions x 32 clk) is SHORTER than an L2 round
 //     trip, so the pipeline is organised per TAP, not per chunk: at the top of a tap a wave issues ALL gathers of the
 //     next tap's A rows (12 rows x 4 neighbours, 96 VGPRs in flight), the weight fragment of chunk j is reloaded for
@@ -595,6 +596,20 @@ hipError_t launch_half(const FwdH& P, int tiles, int nblk_n, hipStream_t st) {
   return hipGetLastError();
 }
 
+// tile height (in units of 32 output positions) of one launch: the cheapest of MT = 1, 2, 3 by waves of 256 workgroups x rows per
+// tile, ties towards the taller tile (fewer weight reloads per position).  The ONE place that decides it: the launcher and the
+// exported query orp_dcn_forward_h_tile_rows both call this.
+inline int pick_mt(long npos_all, int nlevels) {
+  int MT = 1;
+  long best = -1;
+  for (int mt = 1; mt <= 3; mt++) {
+    const long t = (npos_all + 32 * mt - 1) / (32 * mt) + nlevels;
+    const long cost = ((t + 255) / 256) * mt * 100 + (mt == 1 ? 40 : mt == 2 ? 10 : 0);
+    if (best < 0 || cost < best) { best = cost; MT = mt; }
+  }
+  return MT;
+}
+
 inline size_t align256(size_t x) { return (x + 255) & ~(size_t)255; }
 inline int out_dim(int in, int pad, int dil, int k, int stride) { return (in + 2 * pad - (dil * (k - 1) + 1)) / stride + 1; }
 
@@ -620,6 +635,13 @@ int orp_dcn_pack_weight_h(const void* weight, int c_out, int c_in, int kh, int k
   return e == hipSuccess ? ORP_OK : (int)e;
 }
 
+int orp_dcn_forward_h_tile_rows(long positions_all_levels, int nlevels) {
+  if (positions_all_levels <= 0 || nlevels <= 0 || nlevels > MAX_LEVELS) return ORP_EINVAL;
+  return 32 * pick_mt(positions_all_levels, nlevels);
+}
+
+int orp_dcn_forward_h_wave_specialised(void) { return g_half_ws ? 1 : 0; }
+
 size_t orp_dcn_forward_h_workspace_bytes(const orp_dcn_level_h* levels_host, int nlevels, int batch, int c_in, int in_layout) {
   if (in_layout == 1 || !levels_host) return 256;
   size_t tot = 0;
@@ -641,13 +663,7 @@ int orp_dcn_forward_multi_h(const orp_dcn_level_h* levels_host, const void* cons
   for (int i = 0; i < nlevels; i++)
     npos_all += (long)batch * out_dim(levels_host[i].height, pad_h, dil_h, kh, stride_h) *
                 out_dim(levels_host[i].width, pad_w, dil_w, kw, stride_w);
-  int MT = 1;
-  long best = -1;
-  for (int mt = 1; mt <= 3; mt++) {
-    const long t = (npos_all + 32 * mt - 1) / (32 * mt) + nlevels;
-    const long cost = ((t + 255) / 256) * mt * 100 + (mt == 1 ? 40 : mt == 2 ? 10 : 0);
-    if (best < 0 || cost < best) { best = cost; MT = mt; }
-  }
+  const int MT = pick_mt(npos_all, nlevels);
   FwdH P;
   P.nlev = nlevels; P.B = batch; P.Cin = c_in; P.Cout = c_out;
   P.kh = kh; P.kw = kw; P.sh = stride_h; P.sw = stride_w; P.ph = pad_h; P.pw = pad_w; P.dh = dil_h; P.dw = dil_w;

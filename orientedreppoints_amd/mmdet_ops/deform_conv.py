@@ -73,7 +73,11 @@ def fast_path_ok(weight, groups, deformable_groups):
 def deform_conv_forward_multi(inputs, offsets, weight, stride, padding, dilation, masks=None, bias=None, relu=False,
                               cache_pack=True):
     """One DeformConv layer over a list of feature maps (same batch / channels) in ONE launch.  fp32, no autograd.
-    masks (list of [B,kh*kw,Ho,Wo], DCNv2 modulation) / bias ([Cout]) / relu (fused max(., 0)) are optional."""
+    masks (list of [B,kh*kw,Ho,Wo], DCNv2 modulation) / bias ([Cout]) / relu (fused max(., 0)) are optional.
+    fp16 / bf16 inputs with a weight of the same dtype that `half_path_ok` admits run the half kernels and return that
+    dtype.  Half tensors it refuses (c_in % 256, c_out % 64, more than 9 taps, mixed dtypes) are converted, computed by
+    the fp32 path and returned as FP32 tensors: the caller casts (DeformConvFunction does).  What `fast_path_ok` refuses
+    too raises OrpHipError (ORP_EINVAL), whatever the dtype.  Pinned by tests/test_gpu_dcn_half.py."""
     if inputs[0].dtype in _HALF_CODES and weight.dtype == inputs[0].dtype and half_path_ok(weight, 1, 1):
         return deform_conv_forward_multi_half(inputs, offsets, weight, stride, padding, dilation, masks, bias, relu,
                                               cache_pack)
@@ -151,11 +155,25 @@ def half_path_ok(weight, groups, deformable_groups):
                                                                                deformable_groups))
 
 
+def half_tile_rows(positions_all_levels, nlevels):
+    """Output positions per tile (32, 64 or 96) that the half forward uses for a launch over `positions_all_levels`
+    positions (batch x Ho x Wo, summed over the levels) on `nlevels` levels: `orp_dcn_forward_h_tile_rows`, the same
+    host function the launcher calls.  For tests that must know which instantiation a case ran."""
+    rows = _lib.lib().orp_dcn_forward_h_tile_rows(int(positions_all_levels), int(nlevels))
+    if rows <= 0:
+        _lib.check(rows, "orp_dcn_forward_h_tile_rows")
+    return rows
+
+
 def deform_conv_forward_multi_half(inputs, offsets, weight, stride, padding, dilation, masks=None, bias=None, relu=False,
                                    cache_pack=True):
     """`deform_conv_forward_multi` for fp16 / bf16 tensors (the reference's AT_DISPATCH_FLOATING_TYPES_AND_HALF
-    branch; BASELINE configs[4]): v_mfma_f32_32x32x16_{f16,bf16}, fp32 bilinear combine and accumulation, outputs in the
-    input dtype.  All tensors (inputs, offsets, masks, bias, weight) must share that dtype."""
+    branch; BASELINE configs[4]): v_mfma_f32_32x32x16_{f16,bf16} with fp32 accumulation, outputs in the input dtype.
+    The bilinear coefficients (and their product with the DCNv2 modulation) are fp32.  The combine of the four
+    neighbours is fp32 rounded once to bf16 for bf16, and PACKED HALF arithmetic for fp16 (coefficients rounded to
+    half, every product and partial sum rounded to half -- what the reference's own half kernels do); bias and ReLU are
+    applied to the fp32 accumulator, which is rounded once.  All tensors (inputs, offsets, masks, bias, weight) must
+    share that dtype."""
     L = _lib.lib()
     stride, padding, dilation = _pair(stride), _pair(padding), _pair(dilation)
     x0 = inputs[0]
