@@ -15,6 +15,7 @@
 
 #include "../../include/orp_hip.h"
 #include "orp_launch.hpp"
+#include "orp_dcn_common.hpp"
 
 namespace {
 
@@ -387,7 +388,6 @@ apaa_select_kernel(const float* __restrict__ q, const int64_t* __restrict__ pos_
 }
 
 inline int done() { hipError_t e = hipGetLastError(); return e == hipSuccess ? ORP_OK : (int)e; }
-inline size_t align256(size_t x) { return (x + 255) & ~(size_t)255; }
 }  // namespace
 
 extern "C" {

@@ -20,6 +20,7 @@
 #include "orp_range.hpp"
 #include "orp_prof.hpp"
 #include "orp_launch.hpp"
+#include "orp_dcn_common.hpp"
 
 namespace {
 
@@ -74,7 +75,6 @@ to_channels_last_kernel(const TrLevels T, int C) {
   }
 }
 
-inline int out_dim(int in, int pad, int dil, int k, int stride) { return (in + 2 * pad - (dil * (k - 1) + 1)) / stride + 1; }
 
 }  // namespace
 

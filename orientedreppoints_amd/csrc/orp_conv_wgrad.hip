@@ -27,6 +27,7 @@
 #include "orp_prof.hpp"
 #include "orp_launch.hpp"
 #include "orp_range.hpp"
+#include "orp_dcn_common.hpp"
 
 
 namespace {
@@ -349,7 +350,6 @@ inline int pick_nsplit(int total_chunks, int taps) {
   if (ns > total_chunks) ns = total_chunks;
   return ns < 1 ? 1 : ns;
 }
-inline size_t align256w(size_t v) { return (v + 255) & ~(size_t)255; }
 
 }  // namespace
 
@@ -362,7 +362,7 @@ size_t orp_conv_wgrad_split_workspace_bytes(const orp_wgrad_level* levels_host, 
   long chunks = 0;
   for (int i = 0; i < nlevels; i++) chunks += (long)batch * (((long)levels_host[i].height * levels_host[i].width + KS - 1) / KS);
   const int ns = pick_nsplit((int)chunks, kh * kw);
-  return 256 + align256w(sizeof(float) * (size_t)ns * kh * kw * CH * CH);
+  return 256 + align256(sizeof(float) * (size_t)ns * kh * kw * CH * CH);
 }
 
 int orp_conv_wgrad_split(const orp_wgrad_level* levels_host, int nlevels, int batch, int c_in, int c_out, int kh, int kw,

@@ -30,6 +30,7 @@
 #include "orp_launch.hpp"
 #include "orp_prof.hpp"
 #include "orp_dcn_split.hpp"
+#include "orp_dcn_common.hpp"
 
 namespace {
 
@@ -43,8 +44,6 @@ constexpr int BN = 256;         // output channels per workgroup (4 waves x 64)
 constexpr int CB = 256;         // input channels per K phase (one tap)
 constexpr int KC = 32;          // input channels per weight chunk
 constexpr int ASTR = CB + 4;    // padded A row stride (floats): conflict-free ds_read_b128 / ds_write_b128
-constexpr int MAX_TAPS = 9;
-constexpr int MAX_LEVELS = 8;
 constexpr int kThreads = 256;
 
 struct LevelDesc {
@@ -80,7 +79,6 @@ struct FwdParams {
   int ks_nwg, ks_total;     // workgroups (all layers), tiles * taps
 };
 constexpr int KH = 20;           // packed output-channel count of a fused 1x1 head
-inline size_t align256_(size_t x) { return (x + 255) & ~(size_t)255; }
 
 // ---- helpers -------------------------------------------------------------------------------------------------
 __global__ void pack_weight_kernel(const float* __restrict__ w, int cout, int cin, int taps, float* __restrict__ w2) {
@@ -104,37 +102,6 @@ __global__ void pack_head_kernel(const float* __restrict__ w, int k, float* __re
   }
 }
 
-// [B][C][HW] -> [B][HW][C] through a 32x33 LDS tile, for every level of one launch: blockIdx.x walks the levels'
-// position tiles back to back
-struct TransposeLevels {               // up to MAX_LEVELS levels of up to two layers
-  const float* in[2 * MAX_LEVELS];
-  float* out[2 * MAX_LEVELS];
-  int hw[2 * MAX_LEVELS];
-  int bx0[2 * MAX_LEVELS + 1];        // first blockIdx.x of each tensor; bx0[nlev] = gridDim.x
-  int nlev;
-};
-__global__ void nchw_to_nhwc_multi_kernel(const TransposeLevels T, int C) {
-  __shared__ float tile[32][33];
-  int l = 0;
-#pragma unroll
-  for (int i = 1; i < 2 * MAX_LEVELS; i++) l = (i < T.nlev && (int)blockIdx.x >= T.bx0[i]) ? i : l;
-  const int HW = T.hw[l];
-  const int b = blockIdx.z;
-  const int c0 = blockIdx.y * 32, p0 = ((int)blockIdx.x - T.bx0[l]) * 32;
-  const int tx = threadIdx.x & 31, ty = threadIdx.x >> 5;   // 256 threads: 8 rows per pass
-  const float* src = T.in[l] + (size_t)b * C * HW;
-  float* dst = T.out[l] + (size_t)b * C * HW;
-  for (int r = ty; r < 32; r += 8) {
-    const int c = c0 + r, p = p0 + tx;
-    tile[r][tx] = (c < C && p < HW) ? src[(size_t)c * HW + p] : 0.f;
-  }
-  __syncthreads();
-  for (int r = ty; r < 32; r += 8) {
-    const int p = p0 + r, c = c0 + tx;
-    if (p < HW && c < C) dst[(size_t)p * C + c] = tile[tx][r];
-  }
-}
-
 // ---- the MFMA implicit-GEMM kernel -------------------------------------------------------------------------------
 template <bool OUT_NCHW>
 __global__ void __launch_bounds__(kThreads)
@@ -147,11 +114,7 @@ dcn_fwd_mfma_kernel(const FwdParams P) {
 
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   const int taps = P.kh * P.kw;
-  // which level does this tile belong to?
-  int lvl = 0;
-#pragma unroll 1
-  for (int i = 1; i < P.nlev; i++) if ((int)blockIdx.x >= P.lv[i].tile0) lvl = i;
-  const LevelDesc L = P.lv[lvl];
+  const LevelDesc L = P.lv[level_of_tile(P.lv, P.nlev, (int)blockIdx.x)];
   const int HoWo = L.Ho * L.Wo;
   const long npos = (long)P.B * HoWo;
   const long p0 = (long)(blockIdx.x - L.tile0) * BM;
@@ -160,40 +123,7 @@ dcn_fwd_mfma_kernel(const FwdParams P) {
   // ---- bilinear coefficient table: one entry per (position, tap), shared by all channels ---------------------
   for (int e = tid; e < BM * taps; e += kThreads) {
     const int m = e / taps, tap = e - m * taps;
-    const long p = p0 + m;
-    float4 w = make_float4(0.f, 0.f, 0.f, 0.f);
-    int4 ix = make_int4(0, 0, 0, 0);
-    if (p < npos) {
-      const int b = (int)(p / HoWo), hw = (int)(p - (long)b * HoWo);
-      const int ho = hw / L.Wo, wo = hw - ho * L.Wo;
-      const int ki = tap / P.kw, kj = tap - ki * P.kw;
-      const float* ob = L.off + ((size_t)b * 2 * taps + 2 * tap) * HoWo + hw;
-      const float off_h = ob[0], off_w = ob[HoWo];
-      const float h_im = (float)(ho * P.sh - P.ph + ki * P.dh) + off_h;
-      const float w_im = (float)(wo * P.sw - P.pw + kj * P.dw) + off_w;
-      if (h_im > -1.f && w_im > -1.f && h_im < (float)L.H && w_im < (float)L.W) {
-        const int h_low = (int)floorf(h_im), w_low = (int)floorf(w_im);
-        const int h_high = h_low + 1, w_high = w_low + 1;
-        const float lh = h_im - (float)h_low, lw = w_im - (float)w_low;
-        const float hh = 1.f - lh, hw_ = 1.f - lw;
-        const bool t_ok = h_low >= 0, b_ok = h_high <= L.H - 1, l_ok = w_low >= 0, r_ok = w_high <= L.W - 1;
-        const int hl = t_ok ? h_low : 0, hhg = b_ok ? h_high : L.H - 1, wl = l_ok ? w_low : 0, whg = r_ok ? w_high : L.W - 1;
-        w.x = (t_ok && l_ok) ? hh * hw_ : 0.f;
-        w.y = (t_ok && r_ok) ? hh * lw : 0.f;
-        w.z = (b_ok && l_ok) ? lh * hw_ : 0.f;
-        w.w = (b_ok && r_ok) ? lh * lw : 0.f;
-        const int base = b * L.H;
-        ix.x = (base + hl) * L.W + wl;
-        ix.y = (base + hl) * L.W + whg;
-        ix.z = (base + hhg) * L.W + wl;
-        ix.w = (base + hhg) * L.W + whg;
-        if (L.mask) {                                     // DCNv2: the sample is scaled by its modulation scalar
-          const float mm = L.mask[((size_t)b * taps + tap) * HoWo + hw];
-          w.x *= mm; w.y *= mm; w.z *= mm; w.w *= mm;
-        }
-      }
-    }
-    sCw[e] = w; sCi[e] = ix;
+    sample_entry(P, L, L.off, L.mask, p0 + m, npos, tap, taps, HoWo, sCw[e], sCi[e]);
   }
   __syncthreads();
 
@@ -420,8 +350,7 @@ dcn_fwd_mfma2_kernel(const FwdParams P, int total_tiles) {
     ks_rs = (int)(((long)ks_i * rem * taps) / ks_per);
     ks_re = (int)(((long)(ks_i + 1) * rem * taps) / ks_per);
   } else {
-    const int b = blockIdx.x, per = (total_tiles + 7) >> 3;
-    tile = (b & 7) * per + (b >> 3);
+    tile = xcd_slab_index(blockIdx.x, total_tiles);
     if (tile >= total_tiles) return;                                         // whole workgroup leaves together
   }
   const int nb = blockIdx.y;
@@ -462,50 +391,14 @@ dcn_fwd_mfma2_kernel(const FwdParams P, int total_tiles) {
   first_seg = false;
   if (tile != cur_tile) {
   cur_tile = tile;
-  int lvl = 0;
-#pragma unroll 1
-  for (int i = 1; i < P.nlev; i++) if (tile >= P.lv[i].tile0) lvl = i;
-  L = P.lv[lvl];
+  L = P.lv[level_of_tile(P.lv, P.nlev, tile)];
   HoWo = L.Ho * L.Wo;
   npos = (long)P.B * HoWo;
   p0 = (long)(tile - L.tile0) * BM2;
 
   for (int e = tid; e < BM2 * taps; e += kThreads2) {
     const int m = e / taps, tap = e - m * taps;
-    const long p = p0 + m;
-    float4 w = make_float4(0.f, 0.f, 0.f, 0.f);
-    int4 ix = make_int4(0, 0, 0, 0);
-    if (p < npos) {
-      const int b = (int)(p / HoWo), hw = (int)(p - (long)b * HoWo);
-      const int ho = hw / L.Wo, wo = hw - ho * L.Wo;
-      const int ki = tap / P.kw, kj = tap - ki * P.kw;
-      const float* ob = L.off + ((size_t)b * 2 * taps + 2 * tap) * HoWo + hw;
-      const float off_h = ob[0], off_w = ob[HoWo];
-      const float h_im = (float)(ho * P.sh - P.ph + ki * P.dh) + off_h;
-      const float w_im = (float)(wo * P.sw - P.pw + kj * P.dw) + off_w;
-      if (h_im > -1.f && w_im > -1.f && h_im < (float)L.H && w_im < (float)L.W) {
-        const int h_low = (int)floorf(h_im), w_low = (int)floorf(w_im);
-        const int h_high = h_low + 1, w_high = w_low + 1;
-        const float lh = h_im - (float)h_low, lw = w_im - (float)w_low;
-        const float hh = 1.f - lh, hw_ = 1.f - lw;
-        const bool t_ok = h_low >= 0, b_ok = h_high <= L.H - 1, l_ok = w_low >= 0, r_ok = w_high <= L.W - 1;
-        const int hl = t_ok ? h_low : 0, hhg = b_ok ? h_high : L.H - 1, wl = l_ok ? w_low : 0, whg = r_ok ? w_high : L.W - 1;
-        w.x = (t_ok && l_ok) ? hh * hw_ : 0.f;
-        w.y = (t_ok && r_ok) ? hh * lw : 0.f;
-        w.z = (b_ok && l_ok) ? lh * hw_ : 0.f;
-        w.w = (b_ok && r_ok) ? lh * lw : 0.f;
-        const int base = b * L.H;
-        ix.x = (base + hl) * L.W + wl;
-        ix.y = (base + hl) * L.W + whg;
-        ix.z = (base + hhg) * L.W + wl;
-        ix.w = (base + hhg) * L.W + whg;
-        if (L.mask) {                                     // DCNv2: the sample is scaled by its modulation scalar
-          const float mm = L.mask[((size_t)b * taps + tap) * HoWo + hw];
-          w.x *= mm; w.y *= mm; w.z *= mm; w.w *= mm;
-        }
-      }
-    }
-    sCw[e] = w; sCi[e] = ix;
+    sample_entry(P, L, L.off, L.mask, p0 + m, npos, tap, taps, HoWo, sCw[e], sCi[e]);
   }
   __syncthreads();
   }   // coefficient table of `tile`
@@ -836,7 +729,7 @@ inline int ks_workgroups() {                                            // one w
   }();
   return n;
 }
-inline size_t ks_bytes() { return align256_((size_t)ks_workgroups() * kKsSlotBytes) + align256_(sizeof(int) * 1024); }
+inline size_t ks_bytes() { return align256((size_t)ks_workgroups() * kKsSlotBytes) + align256(sizeof(int) * 1024); }
 
 template <int MT, bool OUT_NCHW, int NCONV>
 hipError_t launch_mfma2_n(const FwdParams& P, int tiles, int nblk_n, hipStream_t st) {
@@ -894,9 +787,6 @@ __global__ void dcn_fwd_direct_kernel(const float* __restrict__ x, const float* 
     out[idx] = acc;
   }
 }
-
-inline size_t align256(size_t x) { return (x + 255) & ~(size_t)255; }
-inline int out_dim(int in, int pad, int dil, int k, int stride) { return (in + 2 * pad - (dil * (k - 1) + 1)) / stride + 1; }
 
 }  // namespace
 
@@ -1000,20 +890,14 @@ static int dcn_forward_impl(const orp_dcn_level* levels_host, const orp_dcn_leve
   static const int force_mt = getenv("ORP_DCN_MT") ? atoi(getenv("ORP_DCN_MT")) : -1;   // 0 = first-generation kernel
   int gen = (c_in % CB == 0) ? 2 : 1;
   if (nconv == 2 && gen != 2) return ORP_EINVAL;
-  // tile height: MT*32 positions per workgroup, chosen to minimise rounds x tile height on 256 CUs (B=1, 1024x1024:
-  // MT = 3 -> 228 tiles, one round)
+  // tile height: MT*32 positions per workgroup (pick_tile_rows), then this launcher's own overrides
   int MT = 0;
   if (gen >= 2) {
     long npos_all = 0;
     for (int i = 0; i < nlevels; i++)
       npos_all += (long)batch * out_dim(levels_host[i].height, pad_h, dil_h, kh, stride_h) *
                   out_dim(levels_host[i].width, pad_w, dil_w, kw, stride_w);
-    long best = -1;
-    for (int mt = 1; mt <= 3; mt++) {
-      const long t = (npos_all + 32 * mt - 1) / (32 * mt) + nlevels;     // upper bound incl. per-level remainders
-      const long cost = ((t + 255) / 256) * mt * 100 + (mt == 1 ? 40 : mt == 2 ? 10 : 0);   // small bias to taller tiles
-      if (best < 0 || cost < best) { best = cost; MT = mt; }
-    }
+    MT = pick_tile_rows(npos_all, nlevels);
     if (force_mt >= 1 && force_mt <= 3) MT = force_mt;
     if (heads && MT < 2) MT = 2;
     if (force_mt == 0 && nconv == 1) { gen = 1; MT = 0; }
@@ -1029,7 +913,7 @@ static int dcn_forward_impl(const orp_dcn_level* levels_host, const orp_dcn_leve
   P.w3b = weight2_packed ? weight2_packed + w3_off : P.w3;
   P.bias2 = bias2;
   TransposeLevels TL;
-  int tbx = 0, ntl = 0;
+  TL.n = 0;
   for (int i = 0; i < nlevels; i++) {
     const orp_dcn_level& lv = levels_host[i];
     if (!lv.input || !lv.offset || (!lv.output && !heads) || lv.height <= 0 || lv.width <= 0) return ORP_EINVAL;
@@ -1052,13 +936,10 @@ static int dcn_forward_impl(const orp_dcn_level* levels_host, const orp_dcn_leve
     for (int cv = 0; cv < nconv; cv++) {
       const float* src = cv ? levels2_host[i].input : lv.input;
       if (in_layout == 0) {
-        if (ntl >= 2 * MAX_LEVELS) return ORP_EINVAL;
+        if (TL.n >= 2 * MAX_LEVELS) return ORP_EINVAL;
         float* nhwc = reinterpret_cast<float*>(wsp);
-        const int HW = lv.height * lv.width;
-        wsp += align256(sizeof(float) * (size_t)batch * c_in * HW);
-        TL.in[ntl] = src; TL.out[ntl] = nhwc; TL.hw[ntl] = HW; TL.bx0[ntl] = tbx;
-        tbx += (HW + 31) / 32;
-        ntl++;
+        wsp += align256(sizeof(float) * (size_t)batch * c_in * lv.height * lv.width);
+        transpose_append(TL, src, nhwc, lv.height * lv.width);
         src = nhwc;
       }
       if (cv == 0) { D.x = src; D.x2 = src; } else { D.x2 = src; }
@@ -1066,20 +947,15 @@ static int dcn_forward_impl(const orp_dcn_level* levels_host, const orp_dcn_leve
     D.tile0 = tiles;
     tiles += (int)(((long)batch * D.Ho * D.Wo + bm - 1) / bm);
   }
-  for (int i = nlevels; i < MAX_LEVELS; i++) { P.lv[i] = P.lv[0]; P.lv[i].tile0 = 0x7fffffff; }
-  if (in_layout == 0) {                                  // NCHW inputs: one transposition launch for all levels / layers
-    TL.nlev = ntl;
-    for (int i = ntl; i <= 2 * MAX_LEVELS; i++) TL.bx0[i] = tbx;
-    for (int i = ntl; i < 2 * MAX_LEVELS; i++) { TL.in[i] = TL.in[0]; TL.out[i] = TL.out[0]; TL.hw[i] = 0; }
-    hipLaunchKernelGGL(nchw_to_nhwc_multi_kernel, dim3(tbx, (c_in + 31) / 32, batch), dim3(256), 0, st, TL, c_in);
-  }
+  pad_level_slots(P.lv, nlevels);
+  if (in_layout == 0) transpose_launch<float>(TL, c_in, batch, st);   // NCHW inputs: one transposition launch for all levels / layers
   // opt-in: the contraction on the bf16 matrix pipe with every fp32 operand split exactly into three bf16 pieces
   if (split_mode() != 0 && !heads && orp_split::shape_ok(c_in, c_out, kh, kw)) {
     orp_split::Args A;
     A.nlev = nlevels; A.B = batch; A.Cin = c_in; A.Cout = c_out;
     A.kh = kh; A.kw = kw; A.sh = stride_h; A.sw = stride_w; A.ph = pad_h; A.pw = pad_w; A.dh = dil_h; A.dw = dil_w;
     int mode = split_mode();
-    char* scratch = reinterpret_cast<char*>(align256_(reinterpret_cast<size_t>(wsp)));
+    char* scratch = reinterpret_cast<char*>(align256(reinterpret_cast<size_t>(wsp)));
     // (amax_in: the producer of the channels-last inputs left an upper bound of max |x| -- no pre-pass, no scratch; it only
     //  describes the tensors as handed over, so not with in_layout 0 where this call transposes copies of its own)
     const bool have_amax = amax_in && in_layout == 1;
@@ -1122,12 +998,12 @@ static int dcn_forward_impl(const orp_dcn_level* levels_host, const orp_dcn_leve
       if (steps > per_new) per_new = steps;
       if (rem > 0 && (long)rem * taps / per < min_range) min_range = (long)rem * taps / per;
     }
-    wsp = reinterpret_cast<char*>(align256_(reinterpret_cast<size_t>(wsp)));
+    wsp = reinterpret_cast<char*>(align256(reinterpret_cast<size_t>(wsp)));
     // (ranges of fewer than 3 taps would cut a tile into long hand-over chains: whole tiles then)
     if (wsp + ks_bytes() <= ws_end && (long)tiles * taps < (1L << 30) && per >= 1 && min_range >= 3 &&
         (ks_env == 1 || (tiles > nwg && per_new * 100 <= per_old * 95))) {
       P.ks_scratch = reinterpret_cast<float*>(wsp);
-      P.ks_flags = reinterpret_cast<int*>(wsp + align256_((size_t)nwg * kKsSlotBytes));
+      P.ks_flags = reinterpret_cast<int*>(wsp + align256((size_t)nwg * kKsSlotBytes));
       P.ks_nwg = nwg; P.ks_total = tiles * taps;
       const hipError_t me = orp::fill_async(P.ks_flags, 0, sizeof(int) * nwg, st);
       if (me != hipSuccess) return (int)me;

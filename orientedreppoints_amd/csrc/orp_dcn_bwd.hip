@@ -15,6 +15,7 @@
 
 #include "../../include/orp_hip.h"
 #include "orp_prof.hpp"
+#include "orp_dcn_common.hpp"
 
 namespace {
 
@@ -166,7 +167,6 @@ dcn_col2im_nhwc_kernel(const float* __restrict__ gcolT, const float* __restrict_
   }
 }
 
-inline int out_dim(int in, int pad, int dil, int k, int stride) { return (in + 2 * pad - (dil * (k - 1) + 1)) / stride + 1; }
 inline int fill(Geo& g, int B, int C, int H, int W, int kh, int kw, int sh, int sw, int ph, int pw, int dh, int dw, int dg) {
   if (B <= 0 || C <= 0 || H <= 0 || W <= 0 || kh <= 0 || kw <= 0 || dg <= 0 || C % dg) return ORP_EINVAL;
   g.B = B; g.C = C; g.H = H; g.W = W; g.kh = kh; g.kw = kw; g.sh = sh; g.sw = sw; g.ph = ph; g.pw = pw; g.dh = dh; g.dw = dw; g.dg = dg;

@@ -48,6 +48,7 @@
 #include "orp_launch.hpp"
 #include "orp_range.hpp"
 #include "orp_prof.hpp"
+#include "orp_dcn_common.hpp"
 
 namespace {
 
@@ -102,8 +103,6 @@ struct BwdParams {
   const unsigned* sorted_vals;
 };
 
-inline size_t align256(size_t n) { return (n + 255) & ~(size_t)255; }
-inline int out_dim(int in, int pad, int dil, int k, int stride) { return (in + 2 * pad - (dil * (k - 1) + 1)) / stride + 1; }
 
 // ---- batched [B][R][S] -> [B][S][R] for up to 16 tensors in one launch -------------------------------------------
 struct TransposeSet {
@@ -327,14 +326,11 @@ dcn_bwd_input_kernel(const BwdParams P) {
   {
     const int n_active = P.active[P.total_chunks];
     const int b = blockIdx.x, per = (n_active + 7) >> 3;            // XCD x takes the contiguous active tiles [x*per, (x+1)*per)
-    const int idx = (b & 7) * per + (b >> 3);
+    const int idx = xcd_slab_index(b, n_active);
     if ((b >> 3) >= per || idx >= n_active) return;
     tile = P.active[idx];
   }
-  int lvl = 0;
-#pragma unroll 1
-  for (int i = 1; i < P.nlev; i++) if (tile >= P.lv[i].tile0) lvl = i;
-  const BLevel L = P.lv[lvl];
+  const BLevel L = P.lv[level_of_tile(P.lv, P.nlev, tile)];
   const int HoWo = L.Ho * L.Wo;
   const long npos = (long)P.B * HoWo;
   const long p0 = (long)(tile - L.tile0) * BM2;

@@ -21,7 +21,8 @@
 // of the 8 waves reads the whole tile: 128 B/clk/CU at full matrix rate, half the LDS's peak), so the next step is a wave
 // tile of 64 output channels (half the LDS reads per MFMA), not more prefetch.  Measured without gain: a second A buffer
 // with one barrier per tap (55.4 us), the NCHW output staged through LDS into 16-byte stores (56.3 us).
-// Tolerance (tests): |out - fp32 oracle on the same rounded inputs| <= 2e-3 (fp16) / 1.6e-2 (bf16) of the output scale.
+// Tests (tests/test_gpu_dcn_half.py): exact-arithmetic cases BIT FOR BIT against a float64 reference, both kernels, every tile
+// height; on ordinary data |out - fp32 oracle on the same rounded inputs| <= 2e-3 (fp16) / 1.6e-2 (bf16) of the output scale.
 #include <hip/hip_runtime.h>
 #include <hip/hip_fp16.h>
 #include <stdint.h>
@@ -30,6 +31,7 @@
 #include "../../include/orp_hip.h"
 #include "orp_launch.hpp"
 #include "orp_prof.hpp"
+#include "orp_dcn_common.hpp"
 
 namespace {
 
@@ -37,8 +39,6 @@ typedef float floatx16 __attribute__((ext_vector_type(16)));
 typedef _Float16 half8 __attribute__((ext_vector_type(8)));
 typedef __bf16 bf8 __attribute__((ext_vector_type(8)));
 
-constexpr int MAX_TAPS = 9;
-constexpr int MAX_LEVELS = 8;
 constexpr int CBH = 256;          // input channels per tap phase
 constexpr int ASTRH = CBH + 8;    // padded A row stride in ELEMENTS (132 dwords: conflict-free ds_read_b128 / ds_write_b64)
 constexpr int KCH = 16;           // input channels per MFMA
@@ -125,34 +125,25 @@ __global__ void pack_weight_h_kernel(const T* __restrict__ w, int cout, int cin,
   }
 }
 
-// [B][C][HW] -> [B][HW][C] for 2-byte elements, all levels in one launch
-struct TransposeH {
-  const void* in[MAX_LEVELS];
-  void* out[MAX_LEVELS];
-  int hw[MAX_LEVELS];
-  int bx0[MAX_LEVELS + 1];
-  int nlev;
+// what both kernels below start with, once they know their tile: its level, positions and typed pointers
+template <typename T>
+struct TileH {
+  LevelH L;
+  int HoWo;
+  long npos, p0;       // positions of the level (batch x Ho x Wo), first position of the tile
+  const T *xin, *offp, *maskp;
 };
-__global__ void nchw_to_nhwc_h_kernel(const TransposeH T, int C) {
-  __shared__ unsigned short tile[32][33];
-  int l = 0;
-#pragma unroll
-  for (int i = 1; i < MAX_LEVELS; i++) l = (i < T.nlev && (int)blockIdx.x >= T.bx0[i]) ? i : l;
-  const int HW = T.hw[l];
-  const int b = blockIdx.z;
-  const int c0 = blockIdx.y * 32, p0 = ((int)blockIdx.x - T.bx0[l]) * 32;
-  const int tx = threadIdx.x & 31, ty = threadIdx.x >> 5;
-  const unsigned short* src = reinterpret_cast<const unsigned short*>(T.in[l]) + (size_t)b * C * HW;
-  unsigned short* dst = reinterpret_cast<unsigned short*>(T.out[l]) + (size_t)b * C * HW;
-  for (int r = ty; r < 32; r += 8) {
-    const int c = c0 + r, p = p0 + tx;
-    tile[r][tx] = (c < C && p < HW) ? src[(size_t)c * HW + p] : (unsigned short)0;
-  }
-  __syncthreads();
-  for (int r = ty; r < 32; r += 8) {
-    const int p = p0 + r, c = c0 + tx;
-    if (p < HW && c < C) dst[(size_t)p * C + c] = tile[tx][r];
-  }
+template <typename T, int BMH>
+__device__ __forceinline__ TileH<T> tile_of(const FwdH& P, int tile) {
+  TileH<T> t;
+  t.L = P.lv[level_of_tile(P.lv, P.nlev, tile)];
+  t.HoWo = t.L.Ho * t.L.Wo;
+  t.npos = (long)P.B * t.HoWo;
+  t.p0 = (long)(tile - t.L.tile0) * BMH;
+  t.xin = reinterpret_cast<const T*>(t.L.x);
+  t.offp = reinterpret_cast<const T*>(t.L.off);
+  t.maskp = reinterpret_cast<const T*>(t.L.mask);
+  return t;
 }
 
 template <typename T, int MT, bool OUT_NCHW>
@@ -169,61 +160,15 @@ dcn_fwd_half_kernel(const FwdH P, int total_tiles) {
 
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   const int taps = P.kh * P.kw;
-  int tile;
-  {                                                                          // XCD-aware remap: XCD x takes a contiguous slab
-    const int b = blockIdx.x, per = (total_tiles + 7) >> 3;
-    tile = (b & 7) * per + (b >> 3);
-    if (tile >= total_tiles) return;
-  }
-  int lvl = 0;
-#pragma unroll 1
-  for (int i = 1; i < P.nlev; i++) if (tile >= P.lv[i].tile0) lvl = i;
-  const LevelH L = P.lv[lvl];
-  const int HoWo = L.Ho * L.Wo;
-  const long npos = (long)P.B * HoWo;
-  const long p0 = (long)(tile - L.tile0) * BMH;
+  const int tile = xcd_slab_index(blockIdx.x, total_tiles);
+  if (tile >= total_tiles) return;                                           // the grid's padding: the whole workgroup leaves
+  const TileH<T> blk = tile_of<T, BMH>(P, tile);
   const int nb = blockIdx.y;
-  const T* xin = reinterpret_cast<const T*>(L.x);
-  const T* offp = reinterpret_cast<const T*>(L.off);
-  const T* maskp = reinterpret_cast<const T*>(L.mask);
 
   // ---- bilinear coefficient table (fp32), one entry per (position, tap) --------------------------------------------------
   for (int e = tid; e < BMH * taps; e += kThreadsH) {
     const int m = e / taps, tap = e - m * taps;
-    const long p = p0 + m;
-    float4 w = make_float4(0.f, 0.f, 0.f, 0.f);
-    int4 ix = make_int4(0, 0, 0, 0);
-    if (p < npos) {
-      const int b = (int)(p / HoWo), hw = (int)(p - (long)b * HoWo);
-      const int ho = hw / L.Wo, wo = hw - ho * L.Wo;
-      const int ki = tap / P.kw, kj = tap - ki * P.kw;
-      const T* ob = offp + ((size_t)b * 2 * taps + 2 * tap) * HoWo + hw;
-      const float off_h = Elem<T>::to_f(ob[0]), off_w = Elem<T>::to_f(ob[HoWo]);
-      const float h_im = (float)(ho * P.sh - P.ph + ki * P.dh) + off_h;
-      const float w_im = (float)(wo * P.sw - P.pw + kj * P.dw) + off_w;
-      if (h_im > -1.f && w_im > -1.f && h_im < (float)L.H && w_im < (float)L.W) {
-        const int h_low = (int)floorf(h_im), w_low = (int)floorf(w_im);
-        const int h_high = h_low + 1, w_high = w_low + 1;
-        const float lh = h_im - (float)h_low, lw = w_im - (float)w_low;
-        const float hh = 1.f - lh, hw_ = 1.f - lw;
-        const bool t_ok = h_low >= 0, b_ok = h_high <= L.H - 1, l_ok = w_low >= 0, r_ok = w_high <= L.W - 1;
-        const int hl = t_ok ? h_low : 0, hhg = b_ok ? h_high : L.H - 1, wl = l_ok ? w_low : 0, whg = r_ok ? w_high : L.W - 1;
-        w.x = (t_ok && l_ok) ? hh * hw_ : 0.f;
-        w.y = (t_ok && r_ok) ? hh * lw : 0.f;
-        w.z = (b_ok && l_ok) ? lh * hw_ : 0.f;
-        w.w = (b_ok && r_ok) ? lh * lw : 0.f;
-        const int base = b * L.H;
-        ix.x = (base + hl) * L.W + wl;
-        ix.y = (base + hl) * L.W + whg;
-        ix.z = (base + hhg) * L.W + wl;
-        ix.w = (base + hhg) * L.W + whg;
-        if (maskp) {                                      // DCNv2: the sample is scaled by its modulation scalar
-          const float mm = Elem<T>::to_f(maskp[((size_t)b * taps + tap) * HoWo + hw]);
-          w.x *= mm; w.y *= mm; w.z *= mm; w.w *= mm;
-        }
-      }
-    }
-    sCw[e] = w; sCi[e] = ix;
+    sample_entry(P, blk.L, blk.offp, blk.maskp, blk.p0 + m, blk.npos, tap, taps, blk.HoWo, sCw[e], sCi[e]);
   }
   __syncthreads();
 
@@ -236,7 +181,7 @@ dcn_fwd_half_kernel(const FwdH P, int total_tiles) {
   auto gather_issue = [&](int phase, int m2, uint4 (&g)[4]) {          // m2: even row of the pair
     const int tap = phase / ncb, cb = phase - tap * ncb;
     const int4 ix = sCi[(m2 + half_id) * taps + tap];
-    const T* base = xin + cb * CBH + l8;
+    const T* base = blk.xin + cb * CBH + l8;
     g[0] = *reinterpret_cast<const uint4*>(base + (size_t)ix.x * P.Cin);
     g[1] = *reinterpret_cast<const uint4*>(base + (size_t)ix.y * P.Cin);
     g[2] = *reinterpret_cast<const uint4*>(base + (size_t)ix.z * P.Cin);
@@ -320,10 +265,14 @@ dcn_fwd_half_kernel(const FwdH P, int total_tiles) {
   }
 
   // ---- epilogue: fp32 accumulators (+ bias, ReLU) rounded once to the storage type -------------------------------------------
-  const T* biasp = reinterpret_cast<const T*>(P.bias);
-  T* outp = reinterpret_cast<T*>(L.out);
-  auto finish = [&](float v, int ch) { if (biasp) v += Elem<T>::to_f(biasp[ch]); return Elem<T>::from_f(P.relu ? fmaxf(v, 0.f) : v); };
+  // (the wave-specialised kernel below ends with the same code, one loop index more.  As one shared function -- per 32 x 32 block or per
+  // wave, operands by value or by reference -- it cost 20 of the 24 instantiations a VGPR: docs/notebook/round8.md 1)
   if (!live) return;
+  const T* biasp = reinterpret_cast<const T*>(P.bias);
+  T* outp = reinterpret_cast<T*>(blk.L.out);
+  const int HoWo = blk.HoWo;
+  const long npos = blk.npos, p0 = blk.p0;
+  auto finish = [&](float v, int ch) { if (biasp) v += Elem<T>::to_f(biasp[ch]); return Elem<T>::from_f(P.relu ? fmaxf(v, 0.f) : v); };
 #pragma unroll
   for (int mt = 0; mt < MT; mt++) {
     if (OUT_NCHW) {
@@ -375,61 +324,15 @@ dcn_fwd_half_ws_kernel(const FwdH P, int total_tiles) {
 
   const int tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
   const int taps = P.kh * P.kw;
-  int tile;
-  {
-    const int b = blockIdx.x, per = (total_tiles + 7) >> 3;
-    tile = (b & 7) * per + (b >> 3);
-    if (tile >= total_tiles) return;
-  }
-  int lvl = 0;
-#pragma unroll 1
-  for (int i = 1; i < P.nlev; i++) if (tile >= P.lv[i].tile0) lvl = i;
-  const LevelH L = P.lv[lvl];
-  const int HoWo = L.Ho * L.Wo;
-  const long npos = (long)P.B * HoWo;
-  const long p0 = (long)(tile - L.tile0) * BMH;
+  const int tile = xcd_slab_index(blockIdx.x, total_tiles);
+  if (tile >= total_tiles) return;                                           // the grid's padding: the whole workgroup leaves
+  const TileH<T> blk = tile_of<T, BMH>(P, tile);
   const int nb = blockIdx.y;
-  const T* xin = reinterpret_cast<const T*>(L.x);
-  const T* offp = reinterpret_cast<const T*>(L.off);
-  const T* maskp = reinterpret_cast<const T*>(L.mask);
 
-  // ---- bilinear coefficient table (as above) ----
+  // ---- bilinear coefficient table (fp32), one entry per (position, tap) --------------------------------------------------
   for (int e = tid; e < BMH * taps; e += kThreadsH) {
     const int m = e / taps, tap = e - m * taps;
-    const long p = p0 + m;
-    float4 w = make_float4(0.f, 0.f, 0.f, 0.f);
-    int4 ix = make_int4(0, 0, 0, 0);
-    if (p < npos) {
-      const int b = (int)(p / HoWo), hw = (int)(p - (long)b * HoWo);
-      const int ho = hw / L.Wo, wo = hw - ho * L.Wo;
-      const int ki = tap / P.kw, kj = tap - ki * P.kw;
-      const T* ob = offp + ((size_t)b * 2 * taps + 2 * tap) * HoWo + hw;
-      const float off_h = Elem<T>::to_f(ob[0]), off_w = Elem<T>::to_f(ob[HoWo]);
-      const float h_im = (float)(ho * P.sh - P.ph + ki * P.dh) + off_h;
-      const float w_im = (float)(wo * P.sw - P.pw + kj * P.dw) + off_w;
-      if (h_im > -1.f && w_im > -1.f && h_im < (float)L.H && w_im < (float)L.W) {
-        const int h_low = (int)floorf(h_im), w_low = (int)floorf(w_im);
-        const int h_high = h_low + 1, w_high = w_low + 1;
-        const float lh = h_im - (float)h_low, lw = w_im - (float)w_low;
-        const float hh = 1.f - lh, hw_ = 1.f - lw;
-        const bool t_ok = h_low >= 0, b_ok = h_high <= L.H - 1, l_ok = w_low >= 0, r_ok = w_high <= L.W - 1;
-        const int hl = t_ok ? h_low : 0, hhg = b_ok ? h_high : L.H - 1, wl = l_ok ? w_low : 0, whg = r_ok ? w_high : L.W - 1;
-        w.x = (t_ok && l_ok) ? hh * hw_ : 0.f;
-        w.y = (t_ok && r_ok) ? hh * lw : 0.f;
-        w.z = (b_ok && l_ok) ? lh * hw_ : 0.f;
-        w.w = (b_ok && r_ok) ? lh * lw : 0.f;
-        const int base = b * L.H;
-        ix.x = (base + hl) * L.W + wl;
-        ix.y = (base + hl) * L.W + whg;
-        ix.z = (base + hhg) * L.W + wl;
-        ix.w = (base + hhg) * L.W + whg;
-        if (maskp) {
-          const float mm = Elem<T>::to_f(maskp[((size_t)b * taps + tap) * HoWo + hw]);
-          w.x *= mm; w.y *= mm; w.z *= mm; w.w *= mm;
-        }
-      }
-    }
-    sCw[e] = w; sCi[e] = ix;
+    sample_entry(P, blk.L, blk.offp, blk.maskp, blk.p0 + m, blk.npos, tap, taps, blk.HoWo, sCw[e], sCi[e]);
   }
   __syncthreads();
 
@@ -451,7 +354,7 @@ dcn_fwd_half_ws_kernel(const FwdH P, int total_tiles) {
     auto row_of = [&](int g) { return g * 16 + wq * 4 + q4; };
     auto gather_issue = [&](int tap, int cb, int g, uint4 (&v)[4]) {
       const int4 ix = sCi[row_of(g) * taps + tap];
-      const T* base = xin + cb * CBW + l8;
+      const T* base = blk.xin + cb * CBW + l8;
       v[0] = *reinterpret_cast<const uint4*>(base + (size_t)ix.x * P.Cin);
       v[1] = *reinterpret_cast<const uint4*>(base + (size_t)ix.y * P.Cin);
       v[2] = *reinterpret_cast<const uint4*>(base + (size_t)ix.z * P.Cin);
@@ -539,7 +442,9 @@ dcn_fwd_half_ws_kernel(const FwdH P, int total_tiles) {
   // ---- epilogue ----
   if (!live) return;
   const T* biasp = reinterpret_cast<const T*>(P.bias);
-  T* outp = reinterpret_cast<T*>(L.out);
+  T* outp = reinterpret_cast<T*>(blk.L.out);
+  const int HoWo = blk.HoWo;
+  const long npos = blk.npos, p0 = blk.p0;
   auto finish = [&](float v, int ch) { if (biasp) v += Elem<T>::to_f(biasp[ch]); return Elem<T>::from_f(P.relu ? fmaxf(v, 0.f) : v); };
 #pragma unroll
   for (int mt = 0; mt < MT; mt++)
@@ -576,42 +481,21 @@ static const int g_half_ws = getenv("ORP_DCNH_WS") ? atoi(getenv("ORP_DCNH_WS"))
 template <int MT>
 size_t half_smem() { return 2 * ((size_t)32 * MT * ASTRH) + (sizeof(float4) + sizeof(int4)) * 32 * MT * MAX_TAPS; }
 
-template <typename T, int MT, bool OUT_NCHW>
-hipError_t launch_half(const FwdH& P, int tiles, int nblk_n, hipStream_t st) {
-  if (g_half_ws && P.Cin % CBW == 0) {
-    const size_t smem_w = half_ws_smem<MT>();
-    struct TagW {};
-    hipError_t ew = orp::set_max_dynamic_lds_once<TagW>(reinterpret_cast<const void*>(&dcn_fwd_half_ws_kernel<T, MT, OUT_NCHW>), smem_w);
-    if (ew != hipSuccess) return ew;
-    const int per_w = (tiles + 7) >> 3;
-    hipLaunchKernelGGL((dcn_fwd_half_ws_kernel<T, MT, OUT_NCHW>), dim3(per_w * 8, nblk_n), dim3(kThreadsH), smem_w, st, P, tiles);
-    return hipGetLastError();
-  }
-  const size_t smem = half_smem<MT>();
+// one launch body for both kernels: XCD slab grid (a multiple of 8 workgroups), LDS size set once per instantiation
+template <void (*KERNEL)(const FwdH, int)>
+hipError_t launch_tiles(size_t smem, const FwdH& P, int tiles, int nblk_n, hipStream_t st) {
   struct Tag {};
-  hipError_t e = orp::set_max_dynamic_lds_once<Tag>(reinterpret_cast<const void*>(&dcn_fwd_half_kernel<T, MT, OUT_NCHW>), smem);
+  hipError_t e = orp::set_max_dynamic_lds_once<Tag>(reinterpret_cast<const void*>(KERNEL), smem);
   if (e != hipSuccess) return e;
   const int per = (tiles + 7) >> 3;
-  hipLaunchKernelGGL((dcn_fwd_half_kernel<T, MT, OUT_NCHW>), dim3(per * 8, nblk_n), dim3(kThreadsH), smem, st, P, tiles);
+  hipLaunchKernelGGL(KERNEL, dim3(per * 8, nblk_n), dim3(kThreadsH), smem, st, P, tiles);
   return hipGetLastError();
 }
-
-// tile height (in units of 32 output positions) of one launch: the cheapest of MT = 1, 2, 3 by waves of 256 workgroups x rows per
-// tile, ties towards the taller tile (fewer weight reloads per position).  The ONE place that decides it: the launcher and the
-// exported query orp_dcn_forward_h_tile_rows both call this.
-inline int pick_mt(long npos_all, int nlevels) {
-  int MT = 1;
-  long best = -1;
-  for (int mt = 1; mt <= 3; mt++) {
-    const long t = (npos_all + 32 * mt - 1) / (32 * mt) + nlevels;
-    const long cost = ((t + 255) / 256) * mt * 100 + (mt == 1 ? 40 : mt == 2 ? 10 : 0);
-    if (best < 0 || cost < best) { best = cost; MT = mt; }
-  }
-  return MT;
+template <typename T, int MT, bool OUT_NCHW>
+hipError_t launch_half(const FwdH& P, int tiles, int nblk_n, hipStream_t st) {
+  if (g_half_ws && P.Cin % CBW == 0) return launch_tiles<dcn_fwd_half_ws_kernel<T, MT, OUT_NCHW>>(half_ws_smem<MT>(), P, tiles, nblk_n, st);
+  return launch_tiles<dcn_fwd_half_kernel<T, MT, OUT_NCHW>>(half_smem<MT>(), P, tiles, nblk_n, st);
 }
-
-inline size_t align256(size_t x) { return (x + 255) & ~(size_t)255; }
-inline int out_dim(int in, int pad, int dil, int k, int stride) { return (in + 2 * pad - (dil * (k - 1) + 1)) / stride + 1; }
 
 }  // namespace
 
@@ -637,7 +521,7 @@ int orp_dcn_pack_weight_h(const void* weight, int c_out, int c_in, int kh, int k
 
 int orp_dcn_forward_h_tile_rows(long positions_all_levels, int nlevels) {
   if (positions_all_levels <= 0 || nlevels <= 0 || nlevels > MAX_LEVELS) return ORP_EINVAL;
-  return 32 * pick_mt(positions_all_levels, nlevels);
+  return 32 * pick_tile_rows(positions_all_levels, nlevels);
 }
 
 int orp_dcn_forward_h_wave_specialised(void) { return g_half_ws ? 1 : 0; }
@@ -663,13 +547,14 @@ int orp_dcn_forward_multi_h(const orp_dcn_level_h* levels_host, const void* cons
   for (int i = 0; i < nlevels; i++)
     npos_all += (long)batch * out_dim(levels_host[i].height, pad_h, dil_h, kh, stride_h) *
                 out_dim(levels_host[i].width, pad_w, dil_w, kw, stride_w);
-  const int MT = pick_mt(npos_all, nlevels);
+  const int MT = pick_tile_rows(npos_all, nlevels);
   FwdH P;
   P.nlev = nlevels; P.B = batch; P.Cin = c_in; P.Cout = c_out;
   P.kh = kh; P.kw = kw; P.sh = stride_h; P.sw = stride_w; P.ph = pad_h; P.pw = pad_w; P.dh = dil_h; P.dw = dil_w;
   P.wp = weight_packed; P.bias = bias; P.relu = relu ? 1 : 0;
-  TransposeH TL;
-  int tbx = 0, tiles = 0;
+  TransposeLevels TL;
+  TL.n = 0;
+  int tiles = 0;
   const int bm = 32 * MT;
   for (int i = 0; i < nlevels; i++) {
     const orp_dcn_level_h& lv = levels_host[i];
@@ -683,24 +568,17 @@ int orp_dcn_forward_multi_h(const orp_dcn_level_h* levels_host, const void* cons
     D.off = lv.offset; D.out = lv.output;
     D.mask = masks_host ? masks_host[i] : nullptr;
     if (in_layout == 0) {
-      const int HW = lv.height * lv.width;
-      TL.in[i] = lv.input; TL.out[i] = wsp; TL.hw[i] = HW; TL.bx0[i] = tbx;
-      tbx += (HW + 31) / 32;
+      transpose_append(TL, lv.input, wsp, lv.height * lv.width);
       D.x = wsp;
-      wsp += align256((size_t)2 * batch * c_in * HW);
+      wsp += align256((size_t)2 * batch * c_in * lv.height * lv.width);
     } else {
       D.x = lv.input;
     }
     D.tile0 = tiles;
     tiles += (int)(((long)batch * D.Ho * D.Wo + bm - 1) / bm);
   }
-  for (int i = nlevels; i < MAX_LEVELS; i++) { P.lv[i] = P.lv[0]; P.lv[i].tile0 = 0x7fffffff; }
-  if (in_layout == 0) {
-    TL.nlev = nlevels;
-    for (int i = nlevels; i <= MAX_LEVELS; i++) TL.bx0[i] = tbx;
-    for (int i = nlevels; i < MAX_LEVELS; i++) { TL.in[i] = TL.in[0]; TL.out[i] = TL.out[0]; TL.hw[i] = 0; }
-    hipLaunchKernelGGL(nchw_to_nhwc_h_kernel, dim3(tbx, (c_in + 31) / 32, batch), dim3(256), 0, st, TL, c_in);
-  }
+  pad_level_slots(P.lv, nlevels);
+  if (in_layout == 0) transpose_launch<unsigned short>(TL, c_in, batch, st);
   OrpProfScope prof(ORP_PROF_DCN_FWD, st);
   const int nblk_n = (c_out + 255) / 256;
   const bool nchw = out_layout == 0;

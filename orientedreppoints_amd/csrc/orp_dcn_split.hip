@@ -38,6 +38,7 @@
 #include "orp_dcn_split.hpp"
 #include "orp_range.hpp"
 #include "orp_launch.hpp"
+#include "orp_dcn_common.hpp"
 
 namespace orp_split {
 namespace {
@@ -645,8 +646,6 @@ hipError_t launch_m(int MT, const FwdS& P, int tiles, int nblk_n, bool nchw, hip
        : MT == 2 ? launch_l<2, NPROD, PLAIN>(P, tiles, nblk_n, nchw, st) : launch_l<3, NPROD, PLAIN>(P, tiles, nblk_n, nchw, st);
 }
 
-inline int out_dim(int in, int pad, int dil, int k, int stride) { return (in + 2 * pad - (dil * (k - 1) + 1)) / stride + 1; }
-
 }  // namespace
 
 bool shape_ok(int c_in, int c_out, int kh, int kw) {
@@ -756,7 +755,7 @@ hipError_t launch(const Args& a, hipStream_t st) {
     D.planes = a.nconv == 1 ? a.lv[i].planes : nullptr; D.bias = a.lv[i].bias; D.wscale = a.lv[i].wscale;
     D.tile0 = pl.tile0[i]; D.tpi = pl.tpi[i];
   }
-  for (int i = a.nlev; i < kMaxLevels; i++) { P.lv[i] = P.lv[0]; P.lv[i].tile0 = 0x7fffffff; }
+  pad_level_slots(P.lv, a.nlev);
   const int nblk_n = (a.Cout + 255) / 256;
   bool plain = a.lv[0].off == nullptr;                   // no offsets anywhere: the ordinary convolution
   for (int i = 0; i < a.nlev; i++)

@@ -44,6 +44,7 @@
 #include "orp_tile.hpp"
 #include "orp_launch.hpp"
 #include "orp_prof.hpp"
+#include "orp_dcn_common.hpp"
 
 namespace {
 
@@ -1063,7 +1064,6 @@ nms_sweep_kernel(const u64* __restrict__ mask, const int32_t* __restrict__ order
 }
 
 // ---- host-side plumbing ----------------------------------------------------------------------------------------
-inline size_t align256(size_t x) { return (x + 255) & ~(size_t)255; }
 
 struct NmsLayout {
   size_t off_seg, off_keys_in, off_keys_out, off_vals_in, off_order, off_boxes, off_mask, off_nzc, off_nzrc, off_cub,

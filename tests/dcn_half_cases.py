@@ -243,6 +243,18 @@ def reference(case, data, device="cpu"):
     return outs
 
 
+_expected = {}
+
+
+def expected(case, device):
+    """(generate(case), reference(case, data, device)), computed once per case name and process and never modified: the GPU test
+    files that run the same case (half and fp32) share it."""
+    if case.name not in _expected:
+        data = generate(case)
+        _expected[case.name] = (data, reference(case, data, device))
+    return _expected[case.name]
+
+
 SAMPLE_CLASSES = ("inside", "h_low=-1", "h_high=H", "w_low=-1", "w_high=W", "on -1", "on H-1 / W-1", "at or beyond H / W",
                   "at or beyond -1", "strictly beyond -1", "integer coordinates")
 

@@ -37,16 +37,12 @@ def dev():
     return torch.device("cuda:0")
 
 
-_expected_cache = {}
 _family_stats = collections.OrderedDict()          # family -> [cases run, outputs compared, outputs differing, tile heights]
 
 
 def _expected(case, dev):
     """(CPU float64 tensors of the case, float64 reference outputs on the device), computed once per case."""
-    if case.name not in _expected_cache:
-        data = D.generate(case)
-        _expected_cache[case.name] = (data, D.reference(case, data, dev))
-    return _expected_cache[case.name]
+    return D.expected(case, dev)
 
 
 def _launch(case, data, dtype, channels_last, dev):
