@@ -125,7 +125,9 @@ void orc_feature_dissimilarity(const float* f, int p, int C, float* out) {
   free(mean);
 }
 
-/* point_samples_selection core: keep flags over the P positives */
+/* point_samples_selection core: keep flags over the P positives.  Order of the quality values: the float order (+0 == -0), NaN of
+ * either sign above everything (where torch.sort puts it); ties: lower level, then smaller index. */
+static int q_before(float a, float b) { if (a != a) return 0; if (b != b) return 1; return a < b; }
 void orc_apaa_select(const float* q, const int64_t* pos_gt, const int32_t* pos_lvl, int p, int num_gt, int num_level,
                      int per_level_k, double top_ratio, uint8_t* keep) {
   memset(keep, 0, p);
@@ -137,14 +139,14 @@ void orc_apaa_select(const float* q, const int64_t* pos_gt, const int32_t* pos_l
       for (int r = 0; r < per_level_k; r++) {
         int best = -1;
         for (int i = 0; i < p; i++)
-          if (pos_gt[i] == g && pos_lvl[i] == lv && !used[i] && (best < 0 || q[i] < q[best])) best = i;
+          if (pos_gt[i] == g && pos_lvl[i] == lv && !used[i] && (best < 0 || q_before(q[i], q[best]))) best = i;
         if (best < 0) break;
         used[best] = 1; cq[n] = q[best]; ci[n] = best; n++;
       }
     if (n < 2) { for (int a = 0; a < n; a++) keep[ci[a]] = 1; continue; }
     for (int a = 1; a < n; a++) {           /* stable ascending sort */
       float vq = cq[a]; int vi = ci[a]; int b = a - 1;
-      while (b >= 0 && cq[b] > vq) { cq[b + 1] = cq[b]; ci[b + 1] = ci[b]; b--; }
+      while (b >= 0 && q_before(vq, cq[b])) { cq[b + 1] = cq[b]; ci[b + 1] = ci[b]; b--; }
       cq[b + 1] = vq; ci[b + 1] = vi;
     }
     int topk = (int)ceil((double)n * top_ratio);

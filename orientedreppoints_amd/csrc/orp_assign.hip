@@ -20,9 +20,10 @@
 namespace {
 
 typedef unsigned long long u64;
-// Total order of the quality values in the FINAL ranking of orp_apaa_select (both formulations below use it, so a gt with more
-// than kSelCap positives and one with fewer cannot rank a NaN differently -- round-5 advisor): the float order for ordinary values
-// (+0 == -0), NaN above everything (where torch.sort, which the reference ranks with, puts it).
+// Total order of the quality values in EVERY ranking of orp_apaa_select -- the per-level selection and the final order, in both
+// formulations below, so a gt with more than kSelCap positives and one with fewer cannot rank a NaN or a zero differently: the
+// float order for ordinary values (+0 == -0), NaN of either sign above everything (where torch.sort, which the reference ranks
+// with, puts it).
 __device__ __forceinline__ unsigned apaa_rank_key(float v) {
   if (v != v) return 0xffffffffu;
   if (v == 0.f) v = 0.f;
@@ -290,7 +291,7 @@ apaa_select_kernel(const float* __restrict__ q, const int64_t* __restrict__ pos_
   __shared__ float cand_q[64];
   __shared__ int cand_i[64];
   __shared__ int ncand;
-  __shared__ u64 it_key[kSelCap];                // (order-preserving Q bits, index)
+  __shared__ u64 it_key[kSelCap];                // (apaa_rank_key of Q, index)
   __shared__ unsigned char it_lvl[kSelCap];
   __shared__ int nitem, ncand2;
   __shared__ u64 c_key[64];
@@ -304,9 +305,8 @@ apaa_select_kernel(const float* __restrict__ q, const int64_t* __restrict__ pos_
     if (lv < 0 || lv >= num_level) continue;
     const int slot = atomicAdd(&nitem, 1);
     if (slot < kSelCap) {
-      // Q is a sum of non-negative losses; map to an order-preserving unsigned key for any sign anyway
-      unsigned u = __float_as_uint(q[i]); u = (u & 0x80000000u) ? ~u : (u | 0x80000000u);
-      it_key[slot] = ((u64)u << 32) | (u64)(unsigned)i;
+      // Q is a sum of non-negative losses; the key is order-preserving for any sign, zero and NaN anyway
+      it_key[slot] = ((u64)apaa_rank_key(q[i]) << 32) | (u64)(unsigned)i;
       it_lvl[slot] = (unsigned char)lv;
     }
   }
@@ -332,12 +332,11 @@ apaa_select_kernel(const float* __restrict__ q, const int64_t* __restrict__ pos_
         // (2) position in the stable sort by Q of the level-major, key-ascending concatenation = rank under (Q, level, key)
         const u64 ka = c_key[threadIdx.x]; const int la = c_lvl[threadIdx.x];
         const int ia = (int)(unsigned)(ka & 0xffffffffu);
-        const float qa = q[ia];
+        const unsigned oa = (unsigned)(ka >> 32);                 // apaa_rank_key of Q
         int pos = 0;
         for (int b = 0; b < n; b++) {
           const u64 kb = c_key[b]; const int lb = c_lvl[b];
-          const float qb = q[(int)(unsigned)(kb & 0xffffffffu)];
-          const unsigned ob = apaa_rank_key(qb), oa = apaa_rank_key(qa);
+          const unsigned ob = (unsigned)(kb >> 32);
           const bool before = (ob < oa) || (ob == oa && (lb < la || (lb == la && kb < ka)));
           pos += before ? 1 : 0;
         }
@@ -354,9 +353,7 @@ apaa_select_kernel(const float* __restrict__ q, const int64_t* __restrict__ pos_
       u64 mine = ~0ull;
       for (int i = threadIdx.x; i < p; i += kThreads) {
         if (pos_gt[i] != g || pos_lvl[i] != lv) continue;
-        const float v = q[i];
-        unsigned u = __float_as_uint(v); u = (u & 0x80000000u) ? ~u : (u | 0x80000000u);
-        const u64 key = ((u64)u << 32) | (u64)(unsigned)i;
+        const u64 key = ((u64)apaa_rank_key(q[i]) << 32) | (u64)(unsigned)i;
         if ((first || key > last) && key < mine) mine = key;
       }
       const u64 sel = block_min_u64(mine, sbuf);
