@@ -653,7 +653,14 @@ gn_bwd_apply_kernel(const GnParams P) {
     float d = dy[e];
     if (P.relu && !(y[e] > 0.f)) d = 0.f;
     const float xh = (xv - mean) * rstd;
-    dx[e] = rstd * (d * gm - A - xh * Bq);
+    // d * gm rounded on its own, as the terms of A were: contracted into the subtraction (an fma) it keeps the product's low
+    // bits, and a span of ONE element -- where A is that very product and dx is 0 -- got rstd = eps^-1/2 times them
+    float dg;
+    {
+#pragma clang fp contract(off)
+      dg = d * gm;
+    }
+    dx[e] = rstd * (dg - A - xh * Bq);
   }
 }
 
