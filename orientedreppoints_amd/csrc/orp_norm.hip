@@ -20,6 +20,12 @@
 //   orp_fpn_topdown_nhwc    : the FPN laterals' GroupNorm + top-down sum + transposition as one pass behind the statistics.
 //   orp_bias_act_multi      : y = relu?(x + bias[c] (+ residual)), y2 = y - sub[c], all FPN levels in one launch -- the
 //               bias / ReLU / `+ pts_out_init` / `- dcn_base_offset` passes around the head's output convolutions.
+//
+// The GroupNorm routes (NCHW, transposed, top-down, channels-last, training) are held to each other bit for bit by the tests, and
+// they are by construction: each step exists once.  chunk_load_sum / chunk_m2 are the chunk statistics, merge_span is the merge
+// of a span's partials, gn_coef the per-channel coefficients, affine_act / affine_act4 / relu4 the step itself; level_of,
+// block_sum and block_max are the searches and reductions around them.  Host side: fill / fill_cl + fill_status, set_affine,
+// launch_status, plane_blocks; gn_nchw_forward is the one body of the inference and the training forward entry.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include <stdlib.h>
@@ -67,14 +73,113 @@ __device__ __forceinline__ float block_sum(float v, float* red) {
   __syncthreads();
   return red[0] + red[1] + red[2] + red[3];
 }
+// block-wide maximum of a word (range bits, or the bits of non-negative floats: the same order), in every thread
+__device__ __forceinline__ unsigned block_max(unsigned v, unsigned* red) {
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) v = max(v, (unsigned)__shfl_xor((int)v, o, 64));
+  __syncthreads();                       // red may still be read from a previous call
+  if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = v;
+  __syncthreads();
+  return max(max(red[0], red[1]), max(red[2], red[3]));
+}
+
+// the level an id (chunk, or blockIdx.x) belongs to: the last i with id >= first(i); first(0) is 0
+template <class First>
+__device__ __forceinline__ int level_of(First first, int nlev, int id) {
+  int lvl = 0;
+#pragma unroll 1
+  for (int i = 1; i < nlev; i++) if (id >= first(i)) lvl = i;
+  return lvl;
+}
+
+// (mean, var) of a span from its chunk partials (mean_k, M2_k) (Chan et al.): mean = sum n_k mean_k / N,
+// M2 = sum M2_k + n_k (mean_k - mean)^2.  A chunk holds `chunk` units of `unit` elements, the last one what is left of `count`
+// units: unit = 1 for the NCHW spans, C / G with chunks counted in positions for the channels-last ones.  THE merge of this file:
+// every route that normalises goes through these statements and this reduction order, which is why their statistics are the same bits.
+__device__ __forceinline__ float2 merge_span(const float2* part, int nchunks, int chunk, int count, int unit, float* red) {
+  const float total = (float)count * (float)unit;
+  float sm = 0.f;
+  for (int k = threadIdx.x; k < nchunks; k += kThreads) {
+    const int nk = min(chunk, count - k * chunk) * unit;
+    sm += (float)nk * part[k].x;
+  }
+  const float mean = block_sum(sm, red) / total;
+  float m2 = 0.f;
+  for (int k = threadIdx.x; k < nchunks; k += kThreads) {
+    const int nk = min(chunk, count - k * chunk) * unit;
+    const float2 p = part[k];
+    const float d = p.x - mean;
+    m2 += p.y + (float)nk * d * d;
+  }
+  return make_float2(mean, block_sum(m2, red) / total);
+}
+
+// y = relu?(x * a + b) with the GroupNorm's per-channel coefficients (a, b) = (rstd gamma_c, beta_c - mean a).  The expressions
+// are left to the compiler's contraction (this file is built with it on): x * a + b is one fma, as is beta_c - mean * a.
+__device__ __forceinline__ float2 gn_coef(float mean, float rstd, float gamma_c, float beta_c) {
+  const float a = rstd * gamma_c;
+  return make_float2(a, beta_c - mean * a);
+}
+__device__ __forceinline__ void relu4(float4& t) { t.x = fmaxf(t.x, 0.f); t.y = fmaxf(t.y, 0.f); t.z = fmaxf(t.z, 0.f); t.w = fmaxf(t.w, 0.f); }
+__device__ __forceinline__ float affine_act(float x, float a, float b, int relu) {
+  float t = x * a + b;
+  if (relu) t = fmaxf(t, 0.f);
+  return t;
+}
+// one coefficient pair (a, b) per component
+__device__ __forceinline__ void affine_act4(float4& t, float2 k0, float2 k1, float2 k2, float2 k3, int relu) {
+  t.x = t.x * k0.x + k0.y; t.y = t.y * k1.x + k1.y; t.z = t.z * k2.x + k2.y; t.w = t.w * k3.x + k3.y;
+  if (relu) relu4(t);
+}
+__device__ __forceinline__ void affine_act4(float4& t, float a, float b, int relu) {
+  const float2 k = make_float2(a, b);
+  affine_act4(t, k, k, k, k, relu);
+}
+
+// A chunk of n <= 4096 floats held in registers, 16 per thread: as float4s (vec: n % 4 == 0 and src 16-byte aligned) thread t holds
+// elements 4 (t + 256 q) .. + 3, else elements t + 256 q; 0 past the end.  Returns the thread's sum.
+__device__ __forceinline__ float chunk_load_sum(const float* src, int n, bool vec, float (&v)[16]) {
+  if (vec) {
+#pragma unroll
+    for (int q = 0; q < 4; q++) {
+      const int e = (threadIdx.x + q * kThreads) * 4;
+      float4 t = make_float4(0.f, 0.f, 0.f, 0.f);
+      if (e < n) t = *reinterpret_cast<const float4*>(src + e);
+      v[4 * q] = t.x; v[4 * q + 1] = t.y; v[4 * q + 2] = t.z; v[4 * q + 3] = t.w;
+    }
+  } else {
+#pragma unroll
+    for (int q = 0; q < 16; q++) { const int e = threadIdx.x + q * kThreads; v[q] = (e < n) ? src[e] : 0.f; }
+  }
+  float s = 0.f;
+#pragma unroll
+  for (int q = 0; q < 16; q++) s += v[q];
+  return s;
+}
+// the thread's share of the chunk's M2 around `mean`, over the elements that exist
+__device__ __forceinline__ float chunk_m2(const float (&v)[16], int n, bool vec, float mean) {
+  float m2 = 0.f;
+  if (vec) {
+#pragma unroll
+    for (int q = 0; q < 4; q++) {
+      const int e = (threadIdx.x + q * kThreads) * 4;
+      if (e < n) {
+#pragma unroll
+        for (int u = 0; u < 4; u++) { const float d = v[4 * q + u] - mean; m2 += d * d; }
+      }
+    }
+  } else {
+#pragma unroll
+    for (int q = 0; q < 16; q++) { const int e = threadIdx.x + q * kThreads; if (e < n) { const float d = v[q] - mean; m2 += d * d; } }
+  }
+  return m2;
+}
 
 // chunk id -> level, (image, group), chunk-in-span; returns the span geometry
 struct ChunkGeom { int lvl, bg, k, span, n0, n; };
 __device__ __forceinline__ ChunkGeom locate(const GnParams& P, int chunk) {
   ChunkGeom g;
-  g.lvl = 0;
-#pragma unroll 1
-  for (int i = 1; i < P.nlev; i++) if (chunk >= P.lv[i].chunk0) g.lvl = i;
+  g.lvl = level_of([&](int i) { return P.lv[i].chunk0; }, P.nlev, chunk);
   const GnLevel& L = P.lv[g.lvl];
   const int id = chunk - L.chunk0;
   g.bg = id / L.cpg; g.k = id - g.bg * L.cpg;
@@ -91,37 +196,9 @@ gn_stats_kernel(const GnParams P) {
   const float* src = P.lv[g.lvl].x + (size_t)g.bg * g.span + g.n0;
   float v[16];
   const bool vec = ((g.span & 3) == 0);
-  if (vec) {
-#pragma unroll
-    for (int q = 0; q < 4; q++) {
-      const int e = (threadIdx.x + q * kThreads) * 4;
-      float4 t = make_float4(0.f, 0.f, 0.f, 0.f);
-      if (e < g.n) t = *reinterpret_cast<const float4*>(src + e);
-      v[4 * q] = t.x; v[4 * q + 1] = t.y; v[4 * q + 2] = t.z; v[4 * q + 3] = t.w;
-    }
-  } else {
-#pragma unroll
-    for (int q = 0; q < 16; q++) { const int e = threadIdx.x + q * kThreads; v[q] = (e < g.n) ? src[e] : 0.f; }
-  }
-  float s = 0.f;
-#pragma unroll
-  for (int q = 0; q < 16; q++) s += v[q];
+  const float s = chunk_load_sum(src, g.n, vec, v);
   const float mean = block_sum(s, red) / (float)g.n;
-  float m2 = 0.f;
-  if (vec) {
-#pragma unroll
-    for (int q = 0; q < 4; q++) {
-      const int e = (threadIdx.x + q * kThreads) * 4;
-      if (e < g.n) {
-#pragma unroll
-        for (int u = 0; u < 4; u++) { const float d = v[4 * q + u] - mean; m2 += d * d; }
-      }
-    }
-  } else {
-#pragma unroll
-    for (int q = 0; q < 16; q++) { const int e = threadIdx.x + q * kThreads; if (e < g.n) { const float d = v[q] - mean; m2 += d * d; } }
-  }
-  m2 = block_sum(m2, red);
+  const float m2 = block_sum(chunk_m2(v, g.n, vec, mean), red);
   if (threadIdx.x == 0) P.partial[blockIdx.x] = make_float2(mean, m2);
 }
 
@@ -130,23 +207,8 @@ gn_apply_kernel(const GnParams P) {
   __shared__ float red[4];
   const ChunkGeom g = locate(P, blockIdx.x);
   const GnLevel& L = P.lv[g.lvl];
-  // merge this group's partials (Chan et al.): mean = sum n_k mean_k / N ; M2 = sum M2_k + n_k (mean_k - mean)^2
-  const float2* part = P.partial + L.chunk0 + (size_t)g.bg * L.cpg;
-  float sm = 0.f;
-  for (int k = threadIdx.x; k < L.cpg; k += kThreads) {
-    const int nk = min(kChunk, g.span - k * kChunk);
-    sm += (float)nk * part[k].x;
-  }
-  const float mean = block_sum(sm, red) / (float)g.span;
-  float m2 = 0.f;
-  for (int k = threadIdx.x; k < L.cpg; k += kThreads) {
-    const int nk = min(kChunk, g.span - k * kChunk);
-    const float2 p = part[k];
-    const float d = p.x - mean;
-    m2 += p.y + (float)nk * d * d;
-  }
-  const float var = block_sum(m2, red) / (float)g.span;
-  const float rstd = rsqrtf(var + P.eps);
+  const float2 mv = merge_span(P.partial + L.chunk0 + (size_t)g.bg * L.cpg, L.cpg, kChunk, g.span, 1, red);
+  const float mean = mv.x, rstd = rsqrtf(mv.y + P.eps);
   if (P.stats && g.k == 0 && threadIdx.x == 0) P.stats[(size_t)g.lvl * P.B * P.G + g.bg] = make_float2(mean, rstd);
 
   const int cg = P.C / P.G;
@@ -160,10 +222,9 @@ gn_apply_kernel(const GnParams P) {
       const int e = (threadIdx.x + q * kThreads) * 4;
       if (e < g.n) {
         const int c = grp * cg + (g.n0 + e) / L.hw;       // 4 consecutive elements share a channel (hw % 4 == 0)
-        const float a = rstd * L.gamma[c], b = L.beta[c] - mean * a;
+        const float2 k = gn_coef(mean, rstd, L.gamma[c], L.beta[c]);
         float4 t = *reinterpret_cast<const float4*>(src + e);
-        t.x = t.x * a + b; t.y = t.y * a + b; t.z = t.z * a + b; t.w = t.w * a + b;
-        if (P.relu) { t.x = fmaxf(t.x, 0.f); t.y = fmaxf(t.y, 0.f); t.z = fmaxf(t.z, 0.f); t.w = fmaxf(t.w, 0.f); }
+        affine_act4(t, k.x, k.y, P.relu);
         *reinterpret_cast<float4*>(dst + e) = t;
       }
     }
@@ -173,10 +234,8 @@ gn_apply_kernel(const GnParams P) {
       const int e = threadIdx.x + q * kThreads;
       if (e < g.n) {
         const int c = grp * cg + (g.n0 + e) / L.hw;
-        const float a = rstd * L.gamma[c], b = L.beta[c] - mean * a;
-        float t = src[e] * a + b;
-        if (P.relu) t = fmaxf(t, 0.f);
-        dst[e] = t;
+        const float2 k = gn_coef(mean, rstd, L.gamma[c], L.beta[c]);
+        dst[e] = affine_act(src[e], k.x, k.y, P.relu);
       }
     }
   }
@@ -186,7 +245,7 @@ gn_apply_kernel(const GnParams P) {
 // y_nhwc[b, p, c] -- through a 32 x 33 LDS tile (32 channels = 4 groups x 32 positions per workgroup: 128-byte rows on both
 // sides), and optionally also in place / NCHW (the regression tower's last layer feeds a plain convolution AND the
 // DeformConv).  The head's DeformConv reads its input channels-last; this replaces the separate nchw_to_nhwc launch (one
-// more read + write of every tower output per image).  Same arithmetic as gn_apply_kernel: identical values.
+// more read + write of every tower output per image).  merge_span, gn_coef and affine_act as in gn_apply_kernel: identical values.
 struct GnNhwc {
   float* out[kGnMaxLevels];       // [B, hw, C] per level
   float* nchw[kGnMaxLevels];      // nullptr, or the NCHW output (may alias x)
@@ -196,9 +255,7 @@ __global__ void __launch_bounds__(kThreads)
 gn_apply_nhwc_kernel(const GnParams P, const GnNhwc T) {
   __shared__ float tile[32][33];
   __shared__ float2 sStat[32];                    // (mean, rstd) of the tile's groups (32 channels / (C / G) <= 32 groups)
-  int lvl = 0;
-#pragma unroll 1
-  for (int i = 1; i < P.nlev; i++) if ((int)blockIdx.x >= T.bx0[i]) lvl = i;
+  const int lvl = level_of([&](int i) { return T.bx0[i]; }, P.nlev, (int)blockIdx.x);
   const GnLevel& L = P.lv[lvl];
   const int hw = L.hw, cg = P.C / P.G;
   const int b = blockIdx.z, c0 = blockIdx.y * 32, p0 = ((int)blockIdx.x - T.bx0[lvl]) * 32;
@@ -209,23 +266,8 @@ gn_apply_nhwc_kernel(const GnParams P, const GnNhwc T) {
   for (int gi = 0; gi < ngrp; gi++) {
     const int grp = c0 / cg + gi;
     if (grp >= P.G) break;                          // (block-uniform)
-    // merge this group's partials (Chan et al.) with gn_apply_kernel's own statements and reduction order: the same bits
-    const float2* part = P.partial + L.chunk0 + (size_t)(b * P.G + grp) * L.cpg;
-    float sm = 0.f;
-    for (int k = threadIdx.x; k < L.cpg; k += kThreads) {
-      const int nk = min(kChunk, span - k * kChunk);
-      sm += (float)nk * part[k].x;
-    }
-    const float mean = block_sum(sm, red) / (float)span;
-    float m2 = 0.f;
-    for (int k = threadIdx.x; k < L.cpg; k += kThreads) {
-      const int nk = min(kChunk, span - k * kChunk);
-      const float2 pk = part[k];
-      const float d = pk.x - mean;
-      m2 += pk.y + (float)nk * d * d;
-    }
-    const float var = block_sum(m2, red) / (float)span;
-    if (threadIdx.x == 0) sStat[gi] = make_float2(mean, rsqrtf(var + P.eps));
+    const float2 mv = merge_span(P.partial + L.chunk0 + (size_t)(b * P.G + grp) * L.cpg, L.cpg, kChunk, span, 1, red);
+    if (threadIdx.x == 0) sStat[gi] = make_float2(mv.x, rsqrtf(mv.y + P.eps));
   }
   __syncthreads();
   const float* src = L.x + (size_t)b * P.C * hw;
@@ -235,9 +277,8 @@ gn_apply_nhwc_kernel(const GnParams P, const GnNhwc T) {
     float t = 0.f;
     if (c < P.C && p < hw) {
       const float2 st = sStat[r / cg];
-      const float a = st.y * L.gamma[c], bb = L.beta[c] - st.x * a;
-      t = src[(size_t)c * hw + p] * a + bb;
-      if (P.relu) t = fmaxf(t, 0.f);
+      const float2 k = gn_coef(st.x, st.y, L.gamma[c], L.beta[c]);
+      t = affine_act(src[(size_t)c * hw + p], k.x, k.y, P.relu);
       if (nchw) nchw[(size_t)c * hw + p] = t;
     }
     tile[r][tx] = t;
@@ -254,11 +295,11 @@ gn_apply_nhwc_kernel(const GnParams P, const GnNhwc T) {
 //   g_l + up(g_{l+1} + up(g_{l+2} + ...)),  g_j = GroupNorm(lateral j), up = nearest-neighbour upsampling by exactly 2,
 // written channels-last through the 32 x 33 tile of gn_apply_nhwc_kernel, max |.| of everything written folded into *amax as
 // to_channels_last_kernel does.  The coarser levels' normalised values are recomputed at every fine position (1/4 and 1/16 of
-// the reads) with gn_apply_kernel's statements, and summed innermost level first, each partial sum an fp32: the values the
+// the reads) with gn_coef / affine_act, and summed innermost level first, each partial sum an fp32: the values the
 // separate normalise / upsample / add launches leave.
 //
 // Statistics: gn_stats_kernel, then gn_merge_kernel -- one workgroup per (level, image, group) span merges the span's partials
-// with gn_apply_kernel's own statements and reduction order into (mean, rstd).  One merge per span instead of one per workgroup
+// (merge_span) into (mean, rstd).  One merge per span instead of one per workgroup
 // of the pass that applies them: the merge is a chain of dependent loads and reductions, and a few thousand workgroups each
 // waiting for it was most of that pass when it was done there (traced at 1024^2: 48 us, against 21 + 5 for the merge kernel).
 constexpr int kTdMaxLevels = 4;
@@ -278,23 +319,8 @@ gn_merge_kernel(const GnParams P, const TdLevels T) {
   const GnLevel& L = P.lv[lvl];
   const int span = (P.C / P.G) * L.hw;
   if (bg == 0 && lvl == 0 && threadIdx.x == 0 && T.amax) *T.amax = 0u;
-  const float2* part = P.partial + L.chunk0 + (size_t)bg * L.cpg;
-  float sm = 0.f;
-  for (int k = threadIdx.x; k < L.cpg; k += kThreads) {
-    const int nk = min(kChunk, span - k * kChunk);
-    sm += (float)nk * part[k].x;
-  }
-  const float mean = block_sum(sm, red) / (float)span;
-  float m2 = 0.f;
-  for (int k = threadIdx.x; k < L.cpg; k += kThreads) {
-    const int nk = min(kChunk, span - k * kChunk);
-    const float2 p = part[k];
-    const float d = p.x - mean;
-    m2 += p.y + (float)nk * d * d;
-  }
-  const float var = block_sum(m2, red) / (float)span;
-  const float rstd = rsqrtf(var + P.eps);
-  if (threadIdx.x == 0) T.stats[(size_t)lvl * P.B * P.G + bg] = make_float2(mean, rstd);
+  const float2 mv = merge_span(P.partial + L.chunk0 + (size_t)bg * L.cpg, L.cpg, kChunk, span, 1, red);
+  if (threadIdx.x == 0) T.stats[(size_t)lvl * P.B * P.G + bg] = make_float2(mv.x, rsqrtf(mv.y + P.eps));
 }
 
 // the tiles of one workgroup, NL = number of levels summed (this one and the coarser ones) as a compile-time constant: every
@@ -305,7 +331,7 @@ __device__ __forceinline__ unsigned td_tiles(const GnParams& P, const TdLevels& 
   const int cg = P.C / P.G;
   const int tx = threadIdx.x & 31, ty = threadIdx.x >> 5;
   const int hw = P.lv[lvl].hw;
-  // per (level, channel) coefficients with gn_apply_kernel's statements; this thread's channels are c0 + ty + 8 i
+  // per (level, channel) coefficients; this thread's channels are c0 + ty + 8 i
   float ca[NL][4], cb[NL][4];
   const float* src[NL];
 #pragma unroll
@@ -316,8 +342,8 @@ __device__ __forceinline__ unsigned td_tiles(const GnParams& P, const TdLevels& 
     for (int i = 0; i < 4; i++) {
       const int r = ty + 8 * i, c = c0 + r;
       const float2 st = sStat[sh][r / cg];
-      const float a = st.y * L.gamma[c], bb = L.beta[c] - st.x * a;
-      ca[sh][i] = a; cb[sh][i] = bb;
+      const float2 k = gn_coef(st.x, st.y, L.gamma[c], L.beta[c]);
+      ca[sh][i] = k.x; cb[sh][i] = k.y;
     }
   }
   float* dst = T.out[lvl] + (size_t)b * hw * P.C;
@@ -338,10 +364,10 @@ __device__ __forceinline__ unsigned td_tiles(const GnParams& P, const TdLevels& 
     }
 #pragma unroll
     for (int i = 0; i < 4; i++) {
-      float t = x[NL - 1][i] * ca[NL - 1][i] + cb[NL - 1][i];           // innermost (coarsest) level first
+      float t = affine_act(x[NL - 1][i], ca[NL - 1][i], cb[NL - 1][i], 0);           // innermost (coarsest) level first
 #pragma unroll
       for (int sh = NL - 2; sh >= 0; sh--) {
-        float g = x[sh][i] * ca[sh][i] + cb[sh][i];
+        float g = affine_act(x[sh][i], ca[sh][i], cb[sh][i], 0);
         g += t;
         t = g;
       }
@@ -364,9 +390,7 @@ __global__ void __launch_bounds__(kThreads)
 fpn_topdown_nhwc_kernel(const GnParams P, const TdLevels T) {
   __shared__ float tile[32][33];
   __shared__ float2 sStat[kTdMaxLevels][32];      // (mean, rstd) of the tile's groups, this level and every coarser one
-  int lvl = 0;
-#pragma unroll 1
-  for (int i = 1; i < P.nlev; i++) if ((int)blockIdx.x >= T.bx0[i]) lvl = i;
+  const int lvl = level_of([&](int i) { return T.bx0[i]; }, P.nlev, (int)blockIdx.x);
   const int cg = P.C / P.G;
   const int b = blockIdx.z, c0 = blockIdx.y * 32, bx = (int)blockIdx.x - T.bx0[lvl];
   const int ngrp = 32 / cg;                         // groups of this channel tile (cg | 32, 32 | C)
@@ -385,15 +409,9 @@ fpn_topdown_nhwc_kernel(const GnParams P, const TdLevels T) {
   }
   if (T.amax) {
     __shared__ unsigned redm[4];
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) m = max(m, (unsigned)__shfl_xor((int)m, o, 64));
-    if ((threadIdx.x & 63) == 0) redm[threadIdx.x >> 6] = m;
-    __syncthreads();
-    if (threadIdx.x == 0) {
-      // one address, thousands of workgroups: the atomic only where it would raise the value (see to_channels_last_kernel)
-      const unsigned mx = max(max(redm[0], redm[1]), max(redm[2], redm[3]));
-      if (mx > __atomic_load_n(T.amax, __ATOMIC_RELAXED)) atomicMax(T.amax, mx);
-    }
+    const unsigned mx = block_max(m, redm);
+    // one address, thousands of workgroups: the atomic only where it would raise the value (see to_channels_last_kernel)
+    if (threadIdx.x == 0 && mx > __atomic_load_n(T.amax, __ATOMIC_RELAXED)) atomicMax(T.amax, mx);
   }
 }
 
@@ -413,9 +431,9 @@ affine_act_kernel(const float* __restrict__ x, const float* __restrict__ res, co
     float4* y4 = reinterpret_cast<float4*>(y + base);
     for (int i = blockIdx.x * blockDim.x + threadIdx.x; i < hw4; i += gridDim.x * blockDim.x) {
       float4 t = x4[i];
-      t.x = t.x * a + b; t.y = t.y * a + b; t.z = t.z * a + b; t.w = t.w * a + b;
+      affine_act4(t, a, b, 0);
       if (r4) { const float4 r = r4[i]; t.x += r.x; t.y += r.y; t.z += r.z; t.w += r.w; }
-      if (relu) { t.x = fmaxf(t.x, 0.f); t.y = fmaxf(t.y, 0.f); t.z = fmaxf(t.z, 0.f); t.w = fmaxf(t.w, 0.f); }
+      if (relu) relu4(t);
       y4[i] = t;
     }
   } else {
@@ -448,10 +466,10 @@ affine2_act_kernel(const float* __restrict__ x, const float* __restrict__ res, c
     for (int i = blockIdx.x * blockDim.x + threadIdx.x; i < hw4; i += gridDim.x * blockDim.x) {
       float4 t = x4[i];
       float4 r = r4[i];
-      t.x = t.x * a + b; t.y = t.y * a + b; t.z = t.z * a + b; t.w = t.w * a + b;
-      r.x = r.x * a2 + b2; r.y = r.y * a2 + b2; r.z = r.z * a2 + b2; r.w = r.w * a2 + b2;
+      affine_act4(t, a, b, 0);
+      affine_act4(r, a2, b2, 0);
       t.x += r.x; t.y += r.y; t.z += r.z; t.w += r.w;
-      if (relu) { t.x = fmaxf(t.x, 0.f); t.y = fmaxf(t.y, 0.f); t.z = fmaxf(t.z, 0.f); t.w = fmaxf(t.w, 0.f); }
+      if (relu) relu4(t);
       y4[i] = t;
     }
   } else {
@@ -546,7 +564,7 @@ struct BiasParams {
 };
 __global__ void __launch_bounds__(kThreads)
 bias_act_multi_kernel(const BiasParams P) {
-  int l = 0;
+  int l = 0;                                          // level_of, unrolled over all eight slots: the levels stay in scalar registers
 #pragma unroll
   for (int i = 1; i < kMaxLevels; i++) l = (i < P.nlev && (int)blockIdx.x >= P.lv[i].bx0) ? i : l;
   const BiasLevel L = P.lv[l];
@@ -567,7 +585,7 @@ bias_act_multi_kernel(const BiasParams P) {
       float4 t = x4[i];
       t.x += b; t.y += b; t.z += b; t.w += b;
       if (r4) { const float4 r = r4[i]; t.x += r.x; t.y += r.y; t.z += r.z; t.w += r.w; }
-      if (P.relu) { t.x = fmaxf(t.x, 0.f); t.y = fmaxf(t.y, 0.f); t.z = fmaxf(t.z, 0.f); t.w = fmaxf(t.w, 0.f); }
+      if (P.relu) relu4(t);
       y4[i] = t;
       if (z4) { t.x -= sb; t.y -= sb; t.z -= sb; t.w -= sb; z4[i] = t; }
     }
@@ -712,9 +730,7 @@ struct GnClParams {
 struct ClGeom { int lvl, b, p0, np; };
 __device__ __forceinline__ ClGeom cl_locate(const GnClParams& P, int chunk) {
   ClGeom g;
-  g.lvl = 0;
-#pragma unroll 1
-  for (int i = 1; i < P.nlev; i++) if (chunk >= P.lv[i].chunk0) g.lvl = i;
+  g.lvl = level_of([&](int i) { return P.lv[i].chunk0; }, P.nlev, chunk);
   const GnClLevel& L = P.lv[g.lvl];
   const int id = chunk - L.chunk0, ppc = kChunk / P.C;
   g.b = id / L.cpi;
@@ -755,27 +771,9 @@ gn_cl_stats_kernel(const GnClParams P) {
   const int tpc = P.C >> 2, cg = P.C / P.G, tg = cg >> 2;
   const int grp = (threadIdx.x % tpc) / tg;
   float v[16];
-#pragma unroll
-  for (int q = 0; q < 4; q++) {
-    const int e = (threadIdx.x + q * kThreads) * 4;
-    float4 t = make_float4(0.f, 0.f, 0.f, 0.f);
-    if (e < n) t = *reinterpret_cast<const float4*>(src + e);
-    v[4 * q] = t.x; v[4 * q + 1] = t.y; v[4 * q + 2] = t.z; v[4 * q + 3] = t.w;
-  }
-  float s = 0.f;
-#pragma unroll
-  for (int q = 0; q < 16; q++) s += v[q];
+  const float s = chunk_load_sum(src, n, true, v);
   const float mean = group_total(s, sh, tpc, tg, grp) / (float)(g.np * cg);
-  float m2 = 0.f;
-#pragma unroll
-  for (int q = 0; q < 4; q++) {
-    const int e = (threadIdx.x + q * kThreads) * 4;
-    if (e < n) {
-#pragma unroll
-      for (int u = 0; u < 4; u++) { const float d = v[4 * q + u] - mean; m2 += d * d; }
-    }
-  }
-  m2 = group_total(m2, sh, tpc, tg, grp);
+  const float m2 = group_total(chunk_m2(v, n, true, mean), sh, tpc, tg, grp);
   // partials of one (tensor, image, group) are contiguous over the image's chunks: [tensor][image][group][chunk]
   const size_t slot_ = (size_t)L.chunk0 * P.G + ((size_t)g.b * P.G + grp) * L.cpi + g.p0 / (kChunk / P.C);
   if (threadIdx.x < tpc && threadIdx.x % tg == 0) P.partial[slot_] = make_float2(mean, m2);
@@ -795,36 +793,18 @@ gn_cl_merge_kernel(const GnClParams P) {
   const int grp = blockIdx.x, b = blockIdx.y, lvl = blockIdx.z;
   const GnClLevel& L = P.lv[lvl];
   const int ppc = kChunk / P.C, cg = P.C / P.G;
-  const float2* part = P.partial + (size_t)L.chunk0 * P.G + ((size_t)b * P.G + grp) * L.cpi;
-  const float total = (float)L.hw * (float)cg;
-  float sm = 0.f;
-  for (int k = threadIdx.x; k < L.cpi; k += kThreads) {
-    const int nk = min(ppc, L.hw - k * ppc) * cg;
-    sm += (float)nk * part[k].x;
-  }
-  const float mean = block_sum(sm, red) / total;
-  float m2 = 0.f;
-  for (int k = threadIdx.x; k < L.cpi; k += kThreads) {
-    const int nk = min(ppc, L.hw - k * ppc) * cg;
-    const float2 pk = part[k];
-    const float d = pk.x - mean;
-    m2 += pk.y + (float)nk * d * d;
-  }
-  const float var = block_sum(m2, red) / total;
-  const float rstd = rsqrtf(var + P.eps);
+  const float2 mv = merge_span(P.partial + (size_t)L.chunk0 * P.G + ((size_t)b * P.G + grp) * L.cpi, L.cpi, ppc, L.hw, cg, red);
+  const float mean = mv.x, rstd = rsqrtf(mv.y + P.eps);
   if (threadIdx.x == 0) P.stats[((size_t)lvl * P.B + b) * P.G + grp] = make_float2(mean, rstd);
   if (P.pmax) {
     // |y| = |(x - mean) rstd gamma_c + beta_c| <= (max |x| + |mean|) rstd max |gamma| + max |beta| over the group's channels
     const float* pm = P.pmax + (size_t)L.chunk0 * P.G + ((size_t)b * P.G + grp) * L.cpi;
     float xm = 0.f;
     for (int k = threadIdx.x; k < L.cpi; k += kThreads) xm = fmaxf(xm, pm[k]);
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) xm = fmaxf(xm, __shfl_xor(xm, o, 64));
-    __syncthreads();
-    if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = xm;
-    __syncthreads();
+    // the chunk maxima are fmaxf(0, |x|): never negative, never NaN, so their bits order as they do
+    __shared__ unsigned redm[4];
+    xm = __uint_as_float(block_max(__float_as_uint(xm), redm));
     if (threadIdx.x == 0) {
-      xm = fmaxf(fmaxf(red[0], red[1]), fmaxf(red[2], red[3]));
       float gm = 0.f, bm = 0.f;
       for (int c = grp * cg; c < (grp + 1) * cg; c++) { gm = fmaxf(gm, fabsf(L.gamma[c])); bm = fmaxf(bm, fabsf(L.beta[c])); }
       const float bound = (xm + fabsf(mean)) * rstd * gm + bm;
@@ -843,15 +823,14 @@ gn_cl_apply_kernel(const GnClParams P) {
   const int c0 = (threadIdx.x % tpc) * 4;
   const float2 st = P.stats[((size_t)g.lvl * P.B + g.b) * P.G + c0 / cg];
   const float4 ga = *reinterpret_cast<const float4*>(L.gamma + c0), be = *reinterpret_cast<const float4*>(L.beta + c0);
-  const float a0 = st.y * ga.x, a1 = st.y * ga.y, a2 = st.y * ga.z, a3 = st.y * ga.w;
-  const float b0 = be.x - st.x * a0, b1 = be.y - st.x * a1, b2 = be.z - st.x * a2, b3 = be.w - st.x * a3;
+  const float2 k0 = gn_coef(st.x, st.y, ga.x, be.x), k1 = gn_coef(st.x, st.y, ga.y, be.y);
+  const float2 k2 = gn_coef(st.x, st.y, ga.z, be.z), k3 = gn_coef(st.x, st.y, ga.w, be.w);
 #pragma unroll
   for (int q = 0; q < 4; q++) {
     const int e = (threadIdx.x + q * kThreads) * 4;
     if (e < n) {
       float4 t = *reinterpret_cast<const float4*>(L.x + base + e);
-      t.x = t.x * a0 + b0; t.y = t.y * a1 + b1; t.z = t.z * a2 + b2; t.w = t.w * a3 + b3;
-      if (P.relu) { t.x = fmaxf(t.x, 0.f); t.y = fmaxf(t.y, 0.f); t.z = fmaxf(t.z, 0.f); t.w = fmaxf(t.w, 0.f); }
+      affine_act4(t, k0, k1, k2, k3, P.relu);
       *reinterpret_cast<float4*>(L.y + base + e) = t;
     }
   }
@@ -877,7 +856,7 @@ affine_cl_kernel(const GnClParams P, const float2* __restrict__ coef, const unsi
     if (e < n) {
       float4 t = *reinterpret_cast<const float4*>(L.x + base + e);
       t.x = fmaf(t.x, k0.x, k0.y); t.y = fmaf(t.y, k1.x, k1.y); t.z = fmaf(t.z, k2.x, k2.y); t.w = fmaf(t.w, k3.x, k3.y);
-      if (P.relu) { t.x = fmaxf(t.x, 0.f); t.y = fmaxf(t.y, 0.f); t.z = fmaxf(t.z, 0.f); t.w = fmaxf(t.w, 0.f); }
+      if (P.relu) relu4(t);
       *reinterpret_cast<float4*>(L.y + base + e) = t;
     }
   }
@@ -886,12 +865,8 @@ affine_cl_kernel(const GnClParams P, const float2* __restrict__ coef, const unsi
     for (int s_ = 0; s_ < nsets; s_++) {
       unsigned m = 0u;
       for (int i = threadIdx.x; i < per_set; i += kThreads) m = max(m, bound_in[(size_t)s_ * per_set + i]);
-#pragma unroll
-      for (int o = 32; o > 0; o >>= 1) m = max(m, (unsigned)__shfl_xor((int)m, o, 64));
-      __syncthreads();
-      if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = m;
-      __syncthreads();
-      if (threadIdx.x == 0) slot_out[s_] = max(max(red[0], red[1]), max(red[2], red[3]));
+      m = block_max(m, red);
+      if (threadIdx.x == 0) slot_out[s_] = m;
     }
   }
 }
@@ -942,6 +917,50 @@ int fill(const orp_norm_level* levels, int nlevels, int batch, int channels, int
   return chunks;
 }
 
+// what fill / fill_cl's count means to an entry
+int fill_status(int chunks) { return chunks == -2 ? ORP_ETOOBIG : chunks <= 0 ? ORP_EINVAL : ORP_OK; }
+
+// the levels' affine parameters (GnParams / GnClParams); false when one is missing (ORP_EINVAL)
+template <class Params>
+bool set_affine(Params& P, const float* const* gammas, const float* const* betas, int n) {
+  for (int i = 0; i < n; i++) {
+    if (!gammas[i] || !betas[i]) return false;
+    P.lv[i].gamma = gammas[i]; P.lv[i].beta = betas[i];
+  }
+  return true;
+}
+
+int launch_status() {
+  const hipError_t e = hipGetLastError();
+  return e == hipSuccess ? ORP_OK : (int)e;
+}
+
+// grid.x of the per-plane kernels: about 4 work items (float4s when hw % 4 == 0) per thread, between 1 and 64 blocks
+int plane_blocks(int hw) {
+  const int per = ((hw & 3) == 0) ? (hw >> 2) : hw;
+  const int bx = (per + kThreads * 4 - 1) / (kThreads * 4);
+  return bx < 1 ? 1 : bx > 64 ? 64 : bx;
+}
+
+// orp_groupnorm_act_multi_ex and _train: the launch pair, the second one also storing (mean, rstd) per span when asked to
+int gn_nchw_forward(const orp_norm_level* levels, const float* const* gammas_host, const float* const* betas_host, int nlevels,
+                    int batch, int channels, int groups, float eps, int relu, bool train, float* stats, void* workspace,
+                    size_t workspace_bytes, void* stream) {
+  GnParams P;
+  const int chunks = fill(levels, nlevels, batch, channels, groups, P);
+  if (const int rc = fill_status(chunks)) return rc;
+  if (!gammas_host || !betas_host || (train && !stats)) return ORP_EINVAL;
+  if (!workspace || workspace_bytes < sizeof(float2) * (size_t)chunks) return ORP_EWORKSPACE;
+  if (!set_affine(P, gammas_host, betas_host, nlevels)) return ORP_EINVAL;
+  P.eps = eps; P.relu = relu;
+  P.partial = reinterpret_cast<float2*>(workspace);
+  P.stats = train ? reinterpret_cast<float2*>(stats) : nullptr;
+  hipStream_t st = (hipStream_t)stream;
+  hipLaunchKernelGGL(gn_stats_kernel, dim3(chunks), dim3(kThreads), 0, st, P);
+  hipLaunchKernelGGL(gn_apply_kernel, dim3(chunks), dim3(kThreads), 0, st, P);
+  return launch_status();
+}
+
 }  // namespace
 
 extern "C" {
@@ -955,23 +974,8 @@ size_t orp_groupnorm_workspace_bytes(const orp_norm_level* levels, int nlevels, 
 int orp_groupnorm_act_multi_ex(const orp_norm_level* levels, const float* const* gammas_host,
                                const float* const* betas_host, int nlevels, int batch, int channels, int groups,
                                float eps, int relu, void* workspace, size_t workspace_bytes, void* stream) {
-  GnParams P;
-  const int chunks = fill(levels, nlevels, batch, channels, groups, P);
-  if (chunks == -2) return ORP_ETOOBIG;
-  if (chunks <= 0 || !gammas_host || !betas_host) return ORP_EINVAL;
-  if (!workspace || workspace_bytes < sizeof(float2) * (size_t)chunks) return ORP_EWORKSPACE;
-  for (int i = 0; i < nlevels; i++) {
-    if (!gammas_host[i] || !betas_host[i]) return ORP_EINVAL;
-    P.lv[i].gamma = gammas_host[i]; P.lv[i].beta = betas_host[i];
-  }
-  P.eps = eps; P.relu = relu;
-  P.partial = reinterpret_cast<float2*>(workspace);
-  P.stats = nullptr;
-  hipStream_t st = (hipStream_t)stream;
-  hipLaunchKernelGGL(gn_stats_kernel, dim3(chunks), dim3(kThreads), 0, st, P);
-  hipLaunchKernelGGL(gn_apply_kernel, dim3(chunks), dim3(kThreads), 0, st, P);
-  hipError_t e = hipGetLastError();
-  return e == hipSuccess ? ORP_OK : (int)e;
+  return gn_nchw_forward(levels, gammas_host, betas_host, nlevels, batch, channels, groups, eps, relu, false, nullptr, workspace,
+                         workspace_bytes, stream);
 }
 
 int orp_groupnorm_act_multi_nhwc(const orp_norm_level* levels, const float* const* gammas_host,
@@ -983,15 +987,15 @@ int orp_groupnorm_act_multi_nhwc(const orp_norm_level* levels, const float* cons
   orp_norm_level tmp[kGnMaxLevels];
   for (int i = 0; i < nlevels; i++) { tmp[i] = levels[i]; if (!tmp[i].output) tmp[i].output = const_cast<float*>(tmp[i].input); }
   const int chunks = fill(tmp, nlevels, batch, channels, groups, P);
-  if (chunks == -2) return ORP_ETOOBIG;
-  if (chunks <= 0 || !gammas_host || !betas_host || !nhwc_out_host) return ORP_EINVAL;
+  if (const int rc = fill_status(chunks)) return rc;
+  if (!gammas_host || !betas_host || !nhwc_out_host) return ORP_EINVAL;
   if (channels % 32 != 0 || 32 % (channels / groups) != 0 || batch > 65535) return ORP_EINVAL;
   if (!workspace || workspace_bytes < sizeof(float2) * (size_t)chunks) return ORP_EWORKSPACE;
   GnNhwc T;
   int bx = 0;
+  if (!set_affine(P, gammas_host, betas_host, nlevels)) return ORP_EINVAL;
   for (int i = 0; i < nlevels; i++) {
-    if (!gammas_host[i] || !betas_host[i] || !nhwc_out_host[i]) return ORP_EINVAL;
-    P.lv[i].gamma = gammas_host[i]; P.lv[i].beta = betas_host[i];
+    if (!nhwc_out_host[i]) return ORP_EINVAL;
     T.out[i] = nhwc_out_host[i];
     T.nchw[i] = levels[i].output;                       // NULL: the channels-last tensor is the only output
     T.bx0[i] = bx;
@@ -1005,8 +1009,7 @@ int orp_groupnorm_act_multi_nhwc(const orp_norm_level* levels, const float* cons
   hipStream_t st = (hipStream_t)stream;
   hipLaunchKernelGGL(gn_stats_kernel, dim3(chunks), dim3(kThreads), 0, st, P);
   hipLaunchKernelGGL(gn_apply_nhwc_kernel, dim3(bx, channels / 32, batch), dim3(kThreads), 0, st, P, T);
-  hipError_t e = hipGetLastError();
-  return e == hipSuccess ? ORP_OK : (int)e;
+  return launch_status();
 }
 
 static size_t gn_cl_stat_offset(size_t chunks, int groups) { return (sizeof(float2) * chunks * groups + 255) & ~(size_t)255; }
@@ -1025,17 +1028,16 @@ static int gn_cl_impl(const orp_norm_level* levels, const float* const* gammas_h
                       uint32_t* amax_out, int nslots, void* workspace, size_t workspace_bytes, void* stream) {
   GnClParams P;
   const int chunks = fill_cl(levels, nlevels, batch, channels, groups, P);
-  if (chunks == -2) return ORP_ETOOBIG;
-  if (chunks <= 0 || !gammas_host || !betas_host) return ORP_EINVAL;
+  if (const int rc = fill_status(chunks)) return rc;
+  if (!gammas_host || !betas_host) return ORP_EINVAL;
   if (amax_out && (!slots_host || nslots <= 0)) return ORP_EINVAL;
   const size_t stat_off = gn_cl_stat_offset(chunks, groups);
   const size_t pmax_off = (stat_off + sizeof(float2) * (size_t)nlevels * batch * groups + 255) & ~(size_t)255;
   const size_t need = amax_out ? pmax_off + sizeof(float) * (size_t)chunks * groups : pmax_off;
   if (!workspace || workspace_bytes < need) return ORP_EWORKSPACE;
+  if (!set_affine(P, gammas_host, betas_host, nlevels)) return ORP_EINVAL;
   for (int i = 0; i < nlevels; i++) {
-    if (!gammas_host[i] || !betas_host[i]) return ORP_EINVAL;
     if (amax_out && (slots_host[i] < 0 || slots_host[i] >= nslots)) return ORP_EINVAL;
-    P.lv[i].gamma = gammas_host[i]; P.lv[i].beta = betas_host[i];
     P.slot[i] = amax_out ? slots_host[i] : 0;
   }
   for (int i = nlevels; i < kGnMaxLevels; i++) P.slot[i] = 0;
@@ -1052,21 +1054,19 @@ static int gn_cl_impl(const orp_norm_level* levels, const float* const* gammas_h
   hipLaunchKernelGGL(gn_cl_stats_kernel, dim3(chunks), dim3(kThreads), 0, st, P);
   hipLaunchKernelGGL(gn_cl_merge_kernel, dim3(groups, batch, nlevels), dim3(kThreads), 0, st, P);
   hipLaunchKernelGGL(gn_cl_apply_kernel, dim3(chunks), dim3(kThreads), 0, st, P);
-  hipError_t e = hipGetLastError();
-  return e == hipSuccess ? ORP_OK : (int)e;
+  return launch_status();
 }
 
 int orp_affine_act_multi_cl(const orp_norm_level* levels, int nlevels, int batch, int channels, const float* coef, int relu,
                             const uint32_t* bound_in, int nsets, int per_set, uint32_t* slot_out, void* stream) {
   GnClParams P;
   const int chunks = fill_cl(levels, nlevels, batch, channels, 1, P);
-  if (chunks == -2) return ORP_ETOOBIG;
-  if (chunks <= 0 || !coef || (bound_in && (!slot_out || nsets <= 0 || per_set <= 0))) return ORP_EINVAL;
+  if (const int rc = fill_status(chunks)) return rc;
+  if (!coef || (bound_in && (!slot_out || nsets <= 0 || per_set <= 0))) return ORP_EINVAL;
   P.eps = 0.f; P.relu = relu ? 1 : 0; P.partial = nullptr; P.stats = nullptr; P.pmax = nullptr; P.amax = nullptr;
   hipLaunchKernelGGL(affine_cl_kernel, dim3(chunks), dim3(kThreads), 0, (hipStream_t)stream, P, reinterpret_cast<const float2*>(coef),
                      bound_in, slot_out, nsets, per_set);
-  const hipError_t e = hipGetLastError();
-  return e == hipSuccess ? ORP_OK : (int)e;
+  return launch_status();
 }
 
 int orp_groupnorm_act_multi_cl(const orp_norm_level* levels, const float* const* gammas_host, const float* const* betas_host,
@@ -1087,23 +1087,8 @@ int orp_groupnorm_act_multi_cl_amax(const orp_norm_level* levels, const float* c
 int orp_groupnorm_act_multi_train(const orp_norm_level* levels, const float* const* gammas_host,
                                   const float* const* betas_host, int nlevels, int batch, int channels, int groups,
                                   float eps, int relu, float* stats, void* workspace, size_t workspace_bytes, void* stream) {
-  GnParams P;
-  const int chunks = fill(levels, nlevels, batch, channels, groups, P);
-  if (chunks == -2) return ORP_ETOOBIG;
-  if (chunks <= 0 || !gammas_host || !betas_host || !stats) return ORP_EINVAL;
-  if (!workspace || workspace_bytes < sizeof(float2) * (size_t)chunks) return ORP_EWORKSPACE;
-  for (int i = 0; i < nlevels; i++) {
-    if (!gammas_host[i] || !betas_host[i]) return ORP_EINVAL;
-    P.lv[i].gamma = gammas_host[i]; P.lv[i].beta = betas_host[i];
-  }
-  P.eps = eps; P.relu = relu;
-  P.partial = reinterpret_cast<float2*>(workspace);
-  P.stats = reinterpret_cast<float2*>(stats);
-  hipStream_t st = (hipStream_t)stream;
-  hipLaunchKernelGGL(gn_stats_kernel, dim3(chunks), dim3(kThreads), 0, st, P);
-  hipLaunchKernelGGL(gn_apply_kernel, dim3(chunks), dim3(kThreads), 0, st, P);
-  hipError_t e = hipGetLastError();
-  return e == hipSuccess ? ORP_OK : (int)e;
+  return gn_nchw_forward(levels, gammas_host, betas_host, nlevels, batch, channels, groups, eps, relu, true, stats, workspace,
+                         workspace_bytes, stream);
 }
 
 size_t orp_groupnorm_backward_workspace_bytes(const orp_norm_level* levels, int nlevels, int batch, int channels, int groups) {
@@ -1119,15 +1104,15 @@ int orp_groupnorm_act_multi_backward(const orp_norm_level* levels, const float* 
                                      void* workspace, size_t workspace_bytes, void* stream) {
   GnParams P;
   const int chunks = fill(levels, nlevels, batch, channels, groups, P);
-  if (chunks == -2) return ORP_ETOOBIG;
-  if (chunks <= 0 || !grad_outputs_host || !grad_inputs_host || !gammas_host || !betas_host || !dgammas_host ||
+  if (const int rc = fill_status(chunks)) return rc;
+  if (!grad_outputs_host || !grad_inputs_host || !gammas_host || !betas_host || !dgammas_host ||
       !dbetas_host || !stats)
     return ORP_EINVAL;
   const int cg = channels / groups;
   if (!workspace || workspace_bytes < sizeof(float4) * (size_t)chunks * cg) return ORP_EWORKSPACE;
+  if (!set_affine(P, gammas_host, betas_host, nlevels)) return ORP_EINVAL;
   for (int i = 0; i < nlevels; i++) {
-    if (!gammas_host[i] || !betas_host[i] || !grad_outputs_host[i] || !grad_inputs_host[i]) return ORP_EINVAL;
-    P.lv[i].gamma = gammas_host[i]; P.lv[i].beta = betas_host[i];
+    if (!grad_outputs_host[i] || !grad_inputs_host[i]) return ORP_EINVAL;
     P.dy[i] = grad_outputs_host[i]; P.dx[i] = grad_inputs_host[i];
   }
   for (int i = nlevels; i < kGnMaxLevels; i++) { P.dy[i] = nullptr; P.dx[i] = nullptr; }
@@ -1146,8 +1131,7 @@ int orp_groupnorm_act_multi_backward(const orp_norm_level* levels, const float* 
     hipLaunchKernelGGL(gn_bwd_param_kernel, dim3((channels + 255) / 256), dim3(256), 0, st, P, gammas_host[i], dgammas_host[i],
                        dbetas_host[i]);
   }
-  hipError_t e = hipGetLastError();
-  return e == hipSuccess ? ORP_OK : (int)e;
+  return launch_status();
 }
 
 int orp_groupnorm_act_multi(const orp_norm_level* levels, int nlevels, int batch, int channels, int groups,
@@ -1164,28 +1148,18 @@ int orp_affine_act(const float* x, const float* residual, const float* scale, co
                    int channels, int hw, int relu, void* stream) {
   if (!x || !scale || !shift || !y || batch <= 0 || channels <= 0 || hw <= 0) return ORP_EINVAL;
   if ((long)batch * channels > 65535L * 1024) return ORP_ETOOBIG;
-  const int per = ((hw & 3) == 0) ? (hw >> 2) : hw;                 // work items per plane
-  int bx = (per + kThreads * 4 - 1) / (kThreads * 4);               // ~4 items per thread
-  if (bx < 1) bx = 1;
-  if (bx > 64) bx = 64;
-  hipLaunchKernelGGL(affine_act_kernel, dim3(bx, batch * channels), dim3(kThreads), 0, (hipStream_t)stream, x, residual,
+  hipLaunchKernelGGL(affine_act_kernel, dim3(plane_blocks(hw), batch * channels), dim3(kThreads), 0, (hipStream_t)stream, x, residual,
                      scale, shift, y, channels, hw, relu);
-  hipError_t e = hipGetLastError();
-  return e == hipSuccess ? ORP_OK : (int)e;
+  return launch_status();
 }
 
 int orp_affine2_act(const float* x, const float* residual, const float* scale, const float* shift, const float* scale2,
                     const float* shift2, float* y, int batch, int channels, int hw, int relu, void* stream) {
   if (!x || !residual || !scale || !shift || !scale2 || !shift2 || !y || batch <= 0 || channels <= 0 || hw <= 0) return ORP_EINVAL;
   if ((long)batch * channels > 65535L * 1024) return ORP_ETOOBIG;
-  const int per = ((hw & 3) == 0) ? (hw >> 2) : hw;                 // work items per plane
-  int bx = (per + kThreads * 4 - 1) / (kThreads * 4);               // ~4 items per thread
-  if (bx < 1) bx = 1;
-  if (bx > 64) bx = 64;
-  hipLaunchKernelGGL(affine2_act_kernel, dim3(bx, batch * channels), dim3(kThreads), 0, (hipStream_t)stream, x, residual,
+  hipLaunchKernelGGL(affine2_act_kernel, dim3(plane_blocks(hw), batch * channels), dim3(kThreads), 0, (hipStream_t)stream, x, residual,
                      scale, shift, scale2, shift2, y, channels, hw, relu);
-  hipError_t e = hipGetLastError();
-  return e == hipSuccess ? ORP_OK : (int)e;
+  return launch_status();
 }
 
 int orp_affine_relu_maxpool(const float* x, const float* scale, const float* shift, float* y, int batch, int channels,
@@ -1205,8 +1179,7 @@ int orp_affine_relu_maxpool(const float* x, const float* scale, const float* shi
   else
     hipLaunchKernelGGL(affine_relu_maxpool_kernel<false>, grid, dim3(kThreads), 0, (hipStream_t)stream, x, scale, shift, y, channels,
                        height, width, ho, wo, nq, (int)items);
-  hipError_t e = hipGetLastError();
-  return e == hipSuccess ? ORP_OK : (int)e;
+  return launch_status();
 }
 
 // workspace of orp_fpn_topdown_nhwc: chunk partials | (mean, rstd) per (level, image, group)
@@ -1225,20 +1198,20 @@ int orp_fpn_topdown_nhwc(const orp_norm_level* levels, const float* const* gamma
   GnParams P;
   if (!levels || nlevels <= 0 || nlevels > kTdMaxLevels) return ORP_EINVAL;
   const int chunks = fill(levels, nlevels, batch, channels, groups, P);
-  if (chunks == -2) return ORP_ETOOBIG;
-  if (chunks <= 0 || !gammas_host || !betas_host) return ORP_EINVAL;
+  if (const int rc = fill_status(chunks)) return rc;
+  if (!gammas_host || !betas_host) return ORP_EINVAL;
   if (channels % 32 != 0 || 32 % (channels / groups) != 0 || batch > 65535) return ORP_EINVAL;
   const size_t nspan = (size_t)nlevels * batch * groups;
   const size_t stat_off = td_stats_offset(chunks);
   if (!workspace || ((uintptr_t)workspace & 7) != 0 || workspace_bytes < stat_off + sizeof(float2) * nspan) return ORP_EWORKSPACE;
   TdLevels T;
   int bx = 0;
+  if (!set_affine(P, gammas_host, betas_host, nlevels)) return ORP_EINVAL;
   for (int i = 0; i < nlevels; i++) {
-    if (!gammas_host[i] || !betas_host[i] || levels[i].output == levels[i].input) return ORP_EINVAL;
+    if (levels[i].output == levels[i].input) return ORP_EINVAL;
     // every level exactly twice the next in both dimensions: what makes nearest-neighbour upsampling an index shift
     if (i + 1 < nlevels && (levels[i].height != 2 * levels[i + 1].height || levels[i].width != 2 * levels[i + 1].width))
       return ORP_EINVAL;
-    P.lv[i].gamma = gammas_host[i]; P.lv[i].beta = betas_host[i];
     T.out[i] = levels[i].output; T.width[i] = levels[i].width;
     T.bx0[i] = bx;
     bx += (P.lv[i].hw + 32 * kTdTiles - 1) / (32 * kTdTiles);
@@ -1254,8 +1227,7 @@ int orp_fpn_topdown_nhwc(const orp_norm_level* levels, const float* const* gamma
   hipLaunchKernelGGL(gn_stats_kernel, dim3(chunks), dim3(kThreads), 0, st, P);
   hipLaunchKernelGGL(gn_merge_kernel, dim3(batch * groups, nlevels), dim3(kThreads), 0, st, P, T);
   hipLaunchKernelGGL(fpn_topdown_nhwc_kernel, dim3(bx, channels / 32, batch), dim3(kThreads), 0, st, P, T);
-  hipError_t e = hipGetLastError();
-  return e == hipSuccess ? ORP_OK : (int)e;
+  return launch_status();
 }
 
 int orp_bias_act_multi(const orp_bias_level* levels_host, int nlevels, int batch, int channels, const float* bias,
@@ -1272,16 +1244,11 @@ int orp_bias_act_multi(const orp_bias_level* levels_host, int nlevels, int batch
     L.x = lv.input; L.res = lv.residual; L.y = lv.output; L.y2 = lv.output2;
     L.hw = lv.height * lv.width;
     L.bx0 = bx;
-    const int per = ((L.hw & 3) == 0) ? (L.hw >> 2) : L.hw;
-    int nb = (per + kThreads * 4 - 1) / (kThreads * 4);               // ~4 items per thread
-    if (nb < 1) nb = 1;
-    if (nb > 64) nb = 64;
-    bx += nb;
+    bx += plane_blocks(L.hw);
   }
   for (int i = nlevels; i < kMaxLevels; i++) { P.lv[i] = P.lv[0]; P.lv[i].bx0 = 0x7fffffff; }
   hipLaunchKernelGGL(bias_act_multi_kernel, dim3(bx, batch * channels), dim3(kThreads), 0, (hipStream_t)stream, P);
-  hipError_t e = hipGetLastError();
-  return e == hipSuccess ? ORP_OK : (int)e;
+  return launch_status();
 }
 
 }  // extern "C"

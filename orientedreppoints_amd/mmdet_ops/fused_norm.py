@@ -16,6 +16,48 @@ class _NormLevel(ctypes.Structure):
                 ("width", ctypes.c_int)]
 
 
+def _norm_levels(ins, outs):
+    """the `orp_norm_level` array of a launch: logical [B,C,H,W] tensors, outs[i] None = no such output"""
+    levels = (_NormLevel * len(ins))()
+    for i, (x, y) in enumerate(zip(ins, outs)):
+        levels[i] = _NormLevel(x.data_ptr(), y.data_ptr() if y is not None else None, x.size(2), x.size(3))
+    return levels
+
+
+def _gn_modules(gn, n, who):
+    """gn: one nn.GroupNorm for n tensors or a list with one per tensor (modules may repeat) -> (the n modules, the distinct
+    ones in order of first use, owner[i] = index of tensor i's module among the distinct ones)"""
+    gns = list(gn) if isinstance(gn, (list, tuple)) else [gn] * n
+    if len(gns) != n or any(g.num_groups != gns[0].num_groups or g.eps != gns[0].eps for g in gns):
+        raise ValueError(who + ": one GroupNorm per tensor, equal num_groups / eps")
+    index, distinct, owner = {}, [], []
+    for g in gns:
+        if id(g) not in index:
+            index[id(g)] = len(distinct)
+            distinct.append(g)
+        owner.append(index[id(g)])
+    return gns, distinct, owner
+
+
+def _ptrs(tensors, owner=None):
+    """a pointer per launch tensor: tensors[owner[i]] for tensor i (owner None: tensors[i])"""
+    owner = range(len(tensors)) if owner is None else owner
+    return (ctypes.c_void_p * len(owner))(*[tensors[k].data_ptr() for k in owner])
+
+
+def _param_ptrs(weights, biases, owner):
+    """(gamma pointers, beta pointers) per tensor -- tensor i reads parameter set owner[i] -- and the fp32 contiguous parameter
+    tensors themselves, made once per set: the caller keeps them alive until the launch is queued"""
+    gs = [w.detach().float().contiguous() for w in weights]
+    bs = [b.detach().float().contiguous() for b in biases]
+    return _ptrs(gs, owner), _ptrs(bs, owner), gs, bs
+
+
+def _affine_ptrs(mods, owner):
+    """_param_ptrs of the distinct GroupNorm modules `mods`"""
+    return _param_ptrs([m.weight for m in mods], [m.bias for m in mods], owner)
+
+
 def group_norm_act_multi(xs, gn, relu=True, inplace=True, nhwc=None):
     """[GroupNorm(+ReLU)(x) for x in xs] -- xs: list of [B,C,H,W] fp32 CUDA tensors (FPN levels, possibly of several
     towers: up to 16); gn: one nn.GroupNorm for all of them, or a list with one module per tensor (same num_groups and
@@ -26,35 +68,22 @@ def group_norm_act_multi(xs, gn, relu=True, inplace=True, nhwc=None):
     L = _lib.lib()
     x0 = xs[0]
     B, C = x0.size(0), x0.size(1)
-    gns = list(gn) if isinstance(gn, (list, tuple)) else [gn] * len(xs)
-    if len(gns) != len(xs) or any(g.num_groups != gns[0].num_groups or g.eps != gns[0].eps
-                                  for g in {id(g): g for g in gns}.values()):
-        raise ValueError("group_norm_act_multi: one GroupNorm per tensor, equal num_groups / eps")
-    levels = (_NormLevel * len(xs))()
-    gam = (ctypes.c_void_p * len(xs))()
-    bet = (ctypes.c_void_p * len(xs))()
-    ins, outs, keep, seen = [], [], [], {}
-    for i, x in enumerate(xs):
+    gns, mods, owner = _gn_modules(gn, len(xs), "group_norm_act_multi")
+    ins, outs = [], []
+    for x in xs:
         if not (x.is_cuda and x.dtype == torch.float32 and x.dim() == 4 and x.size(0) == B and x.size(1) == C):
             raise ValueError("group_norm_act_multi expects fp32 CUDA [B,C,H,W] tensors with equal B and C")
         x = x.detach().contiguous()
-        y = x if inplace else torch.empty_like(x)
-        ins.append(x); outs.append(y)
-        levels[i] = _NormLevel(x.data_ptr(), y.data_ptr(), x.size(2), x.size(3))
-        ptrs = seen.get(id(gns[i]))
-        if ptrs is None:                                   # once per distinct module, not per tensor
-            g_ = gns[i].weight.detach().float().contiguous()
-            b_ = gns[i].bias.detach().float().contiguous()
-            keep += [g_, b_]
-            ptrs = seen[id(gns[i])] = (g_.data_ptr(), b_.data_ptr())
-        gam[i], bet[i] = ptrs
+        ins.append(x); outs.append(x if inplace else torch.empty_like(x))
+    levels = _norm_levels(ins, outs)
+    gam, bet, _gs, _bs = _affine_ptrs(mods, owner)
     nbytes = L.orp_groupnorm_workspace_bytes(levels, len(xs), B, C, gns[0].num_groups)
     ws = _lib.workspace(x0.device, nbytes)
     if nhwc is not None:
         if nhwc not in ('only', 'both') or C % 32 != 0 or 32 % (C // gns[0].num_groups) != 0:
             raise ValueError("group_norm_act_multi(nhwc=...): 'only' | 'both', channels % 32 == 0, 32 % (channels / groups) == 0")
         cl = [torch.empty(x.shape, dtype=torch.float32, device=x.device, memory_format=torch.channels_last) for x in ins]
-        cl_ptrs = (ctypes.c_void_p * len(xs))(*[t.data_ptr() for t in cl])
+        cl_ptrs = _ptrs(cl)
         if nhwc == 'only':
             for i in range(len(xs)):
                 levels[i].output = None
@@ -68,6 +97,46 @@ def group_norm_act_multi(xs, gn, relu=True, inplace=True, nhwc=None):
                                           1 if relu else 0, _lib.ptr(ws), ws.numel(), _lib.stream_of(x0))
     _lib.check(rc, "orp_groupnorm_act_multi_ex")
     return outs
+
+
+def group_norm_act_multi_cl(xs, gn, relu=True, inplace=True, amax_slots=None):
+    """[GroupNorm(+ReLU)(x) for x in xs] for CHANNELS-LAST fp32 CUDA tensors (logical [B,C,H,W], memory [B,H,W,C]; up to 16:
+    both towers' levels), results channels-last -- `orp_groupnorm_act_multi_cl`, three launches for all tensors.  gn: one
+    nn.GroupNorm or a list with one per tensor (equal num_groups / eps).  amax_slots (a slot index per tensor): returns
+    (outs, int32 tensor of float bits: an upper bound of max |y| per slot, from the statistics pass) for `Amax`."""
+    L = _lib.lib()
+    x0 = xs[0]
+    B, C = x0.size(0), x0.size(1)
+    gns, mods, owner = _gn_modules(gn, len(xs), "group_norm_act_multi_cl")
+    G = gns[0].num_groups
+    if 1024 % C != 0 or C % G != 0 or (C // G) % 4 != 0:
+        raise ValueError("group_norm_act_multi_cl: 1024 % channels == 0 and (channels / groups) % 4 == 0")
+    ins = [x.detach() for x in xs]
+    for x in ins:
+        if not (x.is_cuda and x.dtype == torch.float32 and x.dim() == 4 and x.size(0) == B and x.size(1) == C and _is_cl(x)):
+            raise ValueError("group_norm_act_multi_cl expects channels-last fp32 CUDA [B,C,H,W] tensors with equal B and C")
+    outs = ins if inplace else [torch.empty_like(x, memory_format=torch.channels_last) for x in ins]
+    levels = _norm_levels(ins, outs)
+    gam, bet, _gs, _bs = _affine_ptrs(mods, owner)
+    nbytes = L.orp_groupnorm_cl_workspace_bytes(levels, len(xs), B, C, G)
+    ws = _lib.workspace(x0.device, nbytes)
+    if amax_slots is not None and not _ranges_wanted():
+        amax_slots, no_ranges = None, True
+    else:
+        no_ranges = False
+    if amax_slots is not None:
+        slots = (ctypes.c_int * len(xs))(*[int(v) for v in amax_slots])
+        bits = torch.empty(max(int(v) for v in amax_slots) + 1, dtype=torch.int32, device=x0.device)
+        with torch.cuda.device(x0.device):
+            rc = L.orp_groupnorm_act_multi_cl_amax(levels, gam, bet, len(xs), B, C, G, float(gns[0].eps), 1 if relu else 0, slots,
+                                                   bits.data_ptr(), bits.numel(), _lib.ptr(ws), ws.numel(), _lib.stream_of(x0))
+        _lib.check(rc, "orp_groupnorm_act_multi_cl_amax")
+        return outs, bits
+    with torch.cuda.device(x0.device):
+        rc = L.orp_groupnorm_act_multi_cl(levels, gam, bet, len(xs), B, C, G, float(gns[0].eps), 1 if relu else 0,
+                                          _lib.ptr(ws), ws.numel(), _lib.stream_of(x0))
+    _lib.check(rc, "orp_groupnorm_act_multi_cl")
+    return (outs, None) if no_ranges else outs
 
 
 _affine_cache = _packcache.new_cache("bn_affine")
@@ -162,18 +231,11 @@ def fpn_topdown_cl(xs, gns, amax=True):
     x0 = xs[0]
     B, C = x0.size(0), x0.size(1)
     n = len(xs)
-    levels = (_NormLevel * n)()
-    gam = (ctypes.c_void_p * n)()
-    bet = (ctypes.c_void_p * n)()
-    outs, keep = [], []
-    for i, x in enumerate(xs):
-        x = x.detach().contiguous()
-        y = torch.empty(x.shape, dtype=torch.float32, device=x.device, memory_format=torch.channels_last)
-        g_ = gns[i].weight.detach().float().contiguous()
-        b_ = gns[i].bias.detach().float().contiguous()
-        keep += [x, g_, b_]; outs.append(y)
-        levels[i] = _NormLevel(x.data_ptr(), y.data_ptr(), x.size(2), x.size(3))
-        gam[i], bet[i] = g_.data_ptr(), b_.data_ptr()
+    gns, mods, owner = _gn_modules(gns, n, "fpn_topdown_cl")
+    ins = [x.detach().contiguous() for x in xs]
+    outs = [torch.empty(x.shape, dtype=torch.float32, device=x.device, memory_format=torch.channels_last) for x in ins]
+    levels = _norm_levels(ins, outs)
+    gam, bet, _gs, _bs = _affine_ptrs(mods, owner)
     bits = torch.empty(1, dtype=torch.int32, device=x0.device) if (amax and _ranges_wanted()) else None
     nbytes = L.orp_fpn_topdown_workspace_bytes(levels, n, B, C, gns[0].num_groups)
     ws = _lib.workspace(x0.device, nbytes)
@@ -316,10 +378,9 @@ def conv3x3_multi(xs, conv, split_k=False):
             outs[i] = F.conv2d(x, c.weight, None, c.stride, c.padding, c.dilation, c.groups)
     if small:
         B = xs[small[0]].size(0)
-        levels = (_NormLevel * len(small))()
         wts = (ctypes.c_void_p * len(small))()
         strides = (ctypes.c_int * len(small))()
-        keep, seen = [], {}
+        keep, seen, ins = [], {}, []
         for k, i in enumerate(small):
             x = xs[i].detach().contiguous()
             st = int(convs[i].stride[0])
@@ -330,10 +391,10 @@ def conv3x3_multi(xs, conv, split_k=False):
                 packed = _packed_weight(convs[i].weight)
                 keep.append(packed)
                 wp = seen[id(convs[i])] = packed.data_ptr()
-            keep.append(x); outs[i] = y
-            levels[k] = _NormLevel(x.data_ptr(), y.data_ptr(), x.size(2), x.size(3))
+            ins.append(x); outs[i] = y
             wts[k] = wp
             strides[k] = st
+        levels = _norm_levels(ins, [outs[i] for i in small])
         x0 = xs[small[0]]
         nbytes = L.orp_conv3x3_small_workspace_bytes(levels, strides, len(small), B, cout) if split_k else 0
         ws = _lib.workspace(x0.device, nbytes) if nbytes else None
@@ -356,21 +417,14 @@ class _GroupNormActTrain(torch.autograd.Function):
         L = _lib.lib()
         xs = [t.detach().contiguous() for t in tensors[:n]]
         m = (len(tensors) - n) // 2
-        gammas = [t.detach().float().contiguous() for t in tensors[n:n + m]]
-        betas = [t.detach().float().contiguous() for t in tensors[n + m:]]
+        gam, bet, gammas, betas = _param_ptrs(tensors[n:n + m], tensors[n + m:], owner)
         x0 = xs[0]
         B, C = x0.size(0), x0.size(1)
-        levels = (_NormLevel * n)()
-        gam = (ctypes.c_void_p * n)()
-        bet = (ctypes.c_void_p * n)()
-        ys = []
-        for i, x in enumerate(xs):
+        for x in xs:
             if not (x.is_cuda and x.dtype == torch.float32 and x.dim() == 4 and x.size(0) == B and x.size(1) == C):
                 raise ValueError("group_norm_act_train expects fp32 CUDA [B,C,H,W] tensors with equal B and C")
-            y = torch.empty_like(x)
-            ys.append(y)
-            levels[i] = _NormLevel(x.data_ptr(), y.data_ptr(), x.size(2), x.size(3))
-            gam[i], bet[i] = gammas[owner[i]].data_ptr(), betas[owner[i]].data_ptr()
+        ys = [torch.empty_like(x) for x in xs]
+        levels = _norm_levels(xs, ys)
         stats = torch.empty((n * B * groups, 2), dtype=torch.float32, device=x0.device)
         nbytes = L.orp_groupnorm_workspace_bytes(levels, n, B, C, groups)
         ws = _lib.workspace(x0.device, nbytes)
@@ -392,25 +446,14 @@ class _GroupNormActTrain(torch.autograd.Function):
         ys = saved[1 + n + 2 * m:]
         x0 = xs[0]
         B, C = x0.size(0), x0.size(1)
-        levels = (_NormLevel * n)()
-        dys = (ctypes.c_void_p * n)()
-        dxs = (ctypes.c_void_p * n)()
-        gam = (ctypes.c_void_p * n)()
-        bet = (ctypes.c_void_p * n)()
-        dg = (ctypes.c_void_p * n)()
-        db = (ctypes.c_void_p * n)()
-        keep, gxs = [], []
+        gys = [torch.zeros_like(x) if g is None else g.detach().float().contiguous() for x, g in zip(xs, grads)]
+        gxs = [torch.empty_like(x) for x in xs]
+        dys, dxs = _ptrs(gys), _ptrs(gxs)
+        levels = _norm_levels(xs, ys)
+        gam, bet, _gs, _bs = _param_ptrs(gammas, betas, owner)
         dgam = [torch.empty_like(g) for g in gammas]
         dbet = [torch.empty_like(b) for b in betas]
-        for i, x in enumerate(xs):
-            g = grads[i]
-            g = torch.zeros_like(x) if g is None else g.detach().float().contiguous()
-            gx = torch.empty_like(x)
-            keep.append(g); gxs.append(gx)
-            levels[i] = _NormLevel(x.data_ptr(), ys[i].data_ptr(), x.size(2), x.size(3))
-            dys[i], dxs[i] = g.data_ptr(), gx.data_ptr()
-            gam[i], bet[i] = gammas[owner[i]].data_ptr(), betas[owner[i]].data_ptr()
-            dg[i], db[i] = dgam[owner[i]].data_ptr(), dbet[owner[i]].data_ptr()
+        dg, db = _ptrs(dgam, owner), _ptrs(dbet, owner)
         nbytes = L.orp_groupnorm_backward_workspace_bytes(levels, n, B, C, groups)
         ws = _lib.workspace(x0.device, nbytes)
         with torch.cuda.device(x0.device):
@@ -423,17 +466,7 @@ class _GroupNormActTrain(torch.autograd.Function):
 def group_norm_act_train(xs, gn, relu=True):
     """[relu?(GroupNorm(x)) for x in xs] with autograd, ONE launch pair forward for all tensors (up to 16).  gn: one
     nn.GroupNorm for all of them or a list with one module per tensor (equal num_groups / eps; modules may repeat)."""
-    gns = list(gn) if isinstance(gn, (list, tuple)) else [gn] * len(xs)
-    if len(gns) != len(xs) or any(g.num_groups != gns[0].num_groups or g.eps != gns[0].eps for g in gns):
-        raise ValueError("group_norm_act_train: one GroupNorm per tensor, equal num_groups / eps")
-    distinct, owner = [], []
-    for g in gns:
-        for k, d in enumerate(distinct):
-            if d is g:
-                owner.append(k)
-                break
-        else:
-            owner.append(len(distinct)); distinct.append(g)
+    gns, distinct, owner = _gn_modules(gn, len(xs), "group_norm_act_train")
     outs = _GroupNormActTrain.apply(len(xs), gns[0].num_groups, gns[0].eps, bool(relu), tuple(owner), *xs,
                                     *[d.weight for d in distinct], *[d.bias for d in distinct])
     return list(outs)
@@ -488,16 +521,15 @@ def to_channels_last_multi(xs, amax_slots=None, amax_into=None, force_ranges=Fal
         return (outs, None) if want_amax else outs
     x0 = xs[todo[0]]
     B, C = x0.size(0), x0.size(1)
-    levels = (_NormLevel * len(todo))()
-    keep = []
-    for k, i in enumerate(todo):
+    ins = []
+    for i in todo:
         x = xs[i].detach()
         if not (x.is_cuda and x.dtype == torch.float32 and x.dim() == 4 and x.size(0) == B and x.size(1) == C):
             raise ValueError("to_channels_last_multi expects fp32 CUDA [B,C,H,W] tensors with equal B and C")
         x = x.contiguous()
-        y = torch.empty(x.shape, dtype=torch.float32, device=x.device, memory_format=torch.channels_last)
-        keep.append(x); outs[i] = y
-        levels[k] = _NormLevel(x.data_ptr(), y.data_ptr(), x.size(2), x.size(3))
+        ins.append(x)
+        outs[i] = torch.empty(x.shape, dtype=torch.float32, device=x.device, memory_format=torch.channels_last)
+    levels = _norm_levels(ins, [outs[i] for i in todo])
     if ranges and len(todo) == len(xs):
         if amax_into is not None:
             bits, slots_all, reset = amax_into[0], amax_into[1], 0
@@ -688,22 +720,14 @@ def conv_split_gn(xs_a, conv_a, xs_b, conv_b, gn_a, gn_b, coef_in=None, amax=Non
     ranges = _ranges_wanted()
     per_set = n * B * G
     bound = torch.empty((2, per_set), dtype=torch.int32, device=x0.device) if ranges else None
-    gam = (ctypes.c_void_p * (2 * n))()
-    bet = (ctypes.c_void_p * (2 * n))()
-    for k, g in enumerate((gn_a, gn_b)):
-        g_, b_ = g.weight.detach().float().contiguous(), g.bias.detach().float().contiguous()
-        keep += [g_, b_]
-        for i in range(n):
-            gam[k * n + i], bet[k * n + i] = g_.data_ptr(), b_.data_ptr()
+    gam, bet, _gs, _bs = _affine_ptrs((gn_a, gn_b), [0] * n + [1] * n)
     with torch.cuda.device(x0.device):
         rc = L.orp_conv_split_gn_finish(levels, n, B, cout, G, 2, float(gn_a.eps), gam, bet, _lib.ptr(partials), _lib.ptr(coef),
                                         bound.data_ptr() if bound is not None else None, _lib.stream_of(x0))
     _lib.check(rc, "orp_conv_split_gn_finish")
     if not materialize:
         return outs_a, outs_b, coef, (Amax(bound, per_set, per_set) if bound is not None else None)
-    nl = (_NormLevel * (2 * n))()
-    for i, t in enumerate(outs_a + outs_b):
-        nl[i] = _NormLevel(t.data_ptr(), t.data_ptr(), t.size(2), t.size(3))
+    nl = _norm_levels(outs_a + outs_b, outs_a + outs_b)
     slots = torch.empty((2,), dtype=torch.int32, device=x0.device) if bound is not None else None
     with torch.cuda.device(x0.device):
         rc = L.orp_affine_act_multi_cl(nl, 2 * n, B, cout, _lib.ptr(coef), 1, bound.data_ptr() if bound is not None else None, 2,
@@ -884,57 +908,3 @@ def conv_split_train(xs, convs):
     c0 = mods[0]
     meta = (len(xs), len(mods), tuple(groups), tuple(c0.padding), tuple(c0.dilation))
     return list(_ConvSplitTrain.apply(meta, *[m.weight for m in mods], *xs))
-
-
-def group_norm_act_multi_cl(xs, gn, relu=True, inplace=True, amax_slots=None):
-    """[GroupNorm(+ReLU)(x) for x in xs] for CHANNELS-LAST fp32 CUDA tensors (logical [B,C,H,W], memory [B,H,W,C]; up to 16:
-    both towers' levels), results channels-last -- `orp_groupnorm_act_multi_cl`, three launches for all tensors.  gn: one
-    nn.GroupNorm or a list with one per tensor (equal num_groups / eps).  amax_slots (a slot index per tensor): returns
-    (outs, int32 tensor of float bits: an upper bound of max |y| per slot, from the statistics pass) for `Amax`."""
-    L = _lib.lib()
-    x0 = xs[0]
-    B, C = x0.size(0), x0.size(1)
-    gns = list(gn) if isinstance(gn, (list, tuple)) else [gn] * len(xs)
-    if len(gns) != len(xs) or any(g.num_groups != gns[0].num_groups or g.eps != gns[0].eps
-                                  for g in {id(g): g for g in gns}.values()):
-        raise ValueError("group_norm_act_multi_cl: one GroupNorm per tensor, equal num_groups / eps")
-    G = gns[0].num_groups
-    if 1024 % C != 0 or C % G != 0 or (C // G) % 4 != 0:
-        raise ValueError("group_norm_act_multi_cl: 1024 % channels == 0 and (channels / groups) % 4 == 0")
-    levels = (_NormLevel * len(xs))()
-    gam = (ctypes.c_void_p * len(xs))()
-    bet = (ctypes.c_void_p * len(xs))()
-    outs, keep, seen = [], [], {}
-    for i, x in enumerate(xs):
-        x = x.detach()
-        if not (x.is_cuda and x.dtype == torch.float32 and x.dim() == 4 and x.size(0) == B and x.size(1) == C and _is_cl(x)):
-            raise ValueError("group_norm_act_multi_cl expects channels-last fp32 CUDA [B,C,H,W] tensors with equal B and C")
-        y = x if inplace else torch.empty_like(x, memory_format=torch.channels_last)
-        keep.append(x); outs.append(y)
-        levels[i] = _NormLevel(x.data_ptr(), y.data_ptr(), x.size(2), x.size(3))
-        ptrs = seen.get(id(gns[i]))
-        if ptrs is None:
-            g_ = gns[i].weight.detach().float().contiguous()
-            b_ = gns[i].bias.detach().float().contiguous()
-            keep += [g_, b_]
-            ptrs = seen[id(gns[i])] = (g_.data_ptr(), b_.data_ptr())
-        gam[i], bet[i] = ptrs
-    nbytes = L.orp_groupnorm_cl_workspace_bytes(levels, len(xs), B, C, G)
-    ws = _lib.workspace(x0.device, nbytes)
-    if amax_slots is not None and not _ranges_wanted():
-        amax_slots, no_ranges = None, True
-    else:
-        no_ranges = False
-    if amax_slots is not None:
-        slots = (ctypes.c_int * len(xs))(*[int(v) for v in amax_slots])
-        bits = torch.empty(max(int(v) for v in amax_slots) + 1, dtype=torch.int32, device=x0.device)
-        with torch.cuda.device(x0.device):
-            rc = L.orp_groupnorm_act_multi_cl_amax(levels, gam, bet, len(xs), B, C, G, float(gns[0].eps), 1 if relu else 0, slots,
-                                                   bits.data_ptr(), bits.numel(), _lib.ptr(ws), ws.numel(), _lib.stream_of(x0))
-        _lib.check(rc, "orp_groupnorm_act_multi_cl_amax")
-        return outs, bits
-    with torch.cuda.device(x0.device):
-        rc = L.orp_groupnorm_act_multi_cl(levels, gam, bet, len(xs), B, C, G, float(gns[0].eps), 1 if relu else 0,
-                                          _lib.ptr(ws), ws.numel(), _lib.stream_of(x0))
-    _lib.check(rc, "orp_groupnorm_act_multi_cl")
-    return (outs, None) if no_ranges else outs
