@@ -670,6 +670,17 @@ int orp_conv_split_gn_finish(const orp_conv_level* levels_host, int nlevels, int
                              float* coef_out, uint32_t* bound_out, void* stream);
 int orp_affine_act_multi_cl(const orp_norm_level* levels, int nlevels, int batch, int channels, const float* coef, int relu,
                             const uint32_t* bound_in, int nsets, int per_set, uint32_t* slot_out, void* stream);
+/* The 3x3 / stride 1 / dilation 1 / padding 1 launches of the fp16-pieces mode (nprod = 3) with c_in <= 256 run the HALO kernel:
+ * spatial tiles of th x tw = 96 output positions (6 x 16 on maps at least 16 wide, 12 x 8 on narrower ones) whose input halo is
+ * staged in LDS once instead of once per tap.  Convolution outputs and range words are bit-identical to the linear-tile kernel's;
+ * the GroupNorm partials are taken over other tiles (merged statistics move by roundings).
+ *   orp_conv_split_set_halo   0: the linear-tile kernel everywhere; 1: the halo kernel where it applies; -1: back to the default
+ *       (environment ORP_CONV_HALO, default 1).  A captured graph keeps the kernel it was captured with.
+ *   orp_conv_split_halo_tile  1 and th[i] / tw[i] per level when a launch of these arguments runs the halo kernel now, else 0
+ *       (levels_host: heights / widths only). */
+int orp_conv_split_set_halo(int on);
+int orp_conv_split_halo_tile(const orp_conv_level* levels_host, int nlevels, int batch, int c_in, int c_out, int kh, int kw, int stride,
+                             int pad, int dil, int nprod, int* th, int* tw);
 int orp_nchw_to_nhwc_multi(const orp_norm_level* levels_host, int nlevels, int batch, int channels, void* stream);
 /* ... leaving max |x| of the tensors of every slot (slots_host[i] in [0, nslots)) in amax_out[slot] as float bits, by
  * atomicMax; reset != 0 zeroes amax_out first (0: accumulate into what another producer left there) */

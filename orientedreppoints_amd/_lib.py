@@ -131,6 +131,8 @@ _SIGNATURES = {
     "orp_conv_split_ok": (_i, [_i, _i, _i, _i]),
     "orp_conv_split_multi": (_i, [_vp, _i, _i, _i, _i, _vp, _vp, _vp, _vp] + [_i] * 11 + [_vp, _sz, _vp, _i, _vp]),
     "orp_conv_split_multi_ex": (_i, [_vp, _vp, _vp, _i, _i, _i, _i] + [_i] * 11 + [_vp, _sz, _vp, _vp]),
+    "orp_conv_split_set_halo": (_i, [_i]),
+    "orp_conv_split_halo_tile": (_i, [_vp] + [_i] * 10 + [_vp, _vp]),
     "orp_conv_wgrad_split_ok": (_i, [_i, _i, _i, _i]),
     "orp_conv_wgrad_split_workspace_bytes": (_sz, [_vp, _i, _i, _i, _i]),
     "orp_conv_wgrad_split": (_i, [_vp, _i, _i, _i, _i, _i, _i, _i, _i, _i, _i, _vp, _vp, _vp, _vp, _sz, _vp]),

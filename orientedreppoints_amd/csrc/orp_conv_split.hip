@@ -293,9 +293,19 @@ static int to_cl_impl(const orp_norm_level* levels_host, int nlevels, int batch,
 
 size_t orp_conv_split_gn_partial_floats(const orp_conv_level* levels_host, int nlevels, int batch, int groups, int nlayers) {
   if (!levels_host || nlevels <= 0 || nlevels > orp_split::kMaxLevels || batch <= 0 || groups <= 0 || nlayers < 1 || nlayers > 2) return 0;
-  // (an upper bound that does not depend on the tile height the launch picks: tiles of 32 positions)
+  // (an upper bound that does not depend on what the launch picks: linear tiles of 32 positions, or the halo kernel's spatial tiles --
+  //  more of them than that on a map one or two pixels high -- whichever way its switch stands by then)
+  orp_split::Args A;
+  if (fill_args(A, levels_host, nlevels, batch, 64, 64, nlayers, 3, 3, 1, 1, 1, 1, 1, 1) != ORP_OK) return 0;
+  A.nprod = 3;
+  int th[orp_split::kMaxLevels], tw[orp_split::kMaxLevels];
+  const bool halo = orp_split::halo_tiles(A, 1, th, tw);
   size_t tiles = 0;
-  for (int i = 0; i < nlevels; i++) tiles += (size_t)batch * (((size_t)levels_host[i].height * levels_host[i].width + 31) / 32);
+  for (int i = 0; i < nlevels; i++) {
+    const size_t h = levels_host[i].height, w = levels_host[i].width;
+    const size_t lin = (h * w + 31) / 32, sp = halo ? ((h + th[i] - 1) / th[i]) * ((w + tw[i] - 1) / tw[i]) : 0;
+    tiles += (size_t)batch * (lin > sp ? lin : sp);
+  }
   return (size_t)4 * nlayers * tiles * groups;
 }
 
@@ -328,7 +338,7 @@ int orp_conv_split_gn_finish(const orp_conv_level* levels_host, int nlevels, int
     orp_split::Args A;
     const int rc = fill_args(A, levels_host, nlevels, batch, channels, channels, nlayers, 3, 3, 1, 1, 1, 1, 1, 1);
     if (rc != ORP_OK) return rc;
-    A.per_image = 1;
+    A.per_image = 1; A.nprod = 6;                            // (the linear tiling)
     pl = orp_split::plan(A);
   }
   GnFinish F;
@@ -343,6 +353,25 @@ int orp_conv_split_gn_finish(const orp_conv_level* levels_host, int nlevels, int
   hipLaunchKernelGGL(conv_gn_finish_kernel, dim3(groups, batch, nlayers * nlevels), dim3(64), 0, (hipStream_t)stream, F);
   const hipError_t e = hipGetLastError();
   return e == hipSuccess ? ORP_OK : (int)e;
+}
+
+int orp_conv_split_set_halo(int on) {
+  if (on != 0 && on != 1 && on != -1) return ORP_EINVAL;
+  orp_split::set_halo(on);
+  return ORP_OK;
+}
+
+int orp_conv_split_halo_tile(const orp_conv_level* levels_host, int nlevels, int batch, int c_in, int c_out, int kh, int kw, int stride,
+                             int pad, int dil, int nprod, int* th, int* tw) {
+  if (!levels_host || nlevels <= 0 || nlevels > orp_split::kMaxLevels || batch <= 0 || !th || !tw) return 0;
+  if (!orp_split::shape_ok(c_in, c_out, kh, kw) || stride <= 0 || dil <= 0 || pad < 0) return 0;
+  orp_split::Args A;
+  if (fill_args(A, levels_host, nlevels, batch, c_in, c_out, 1, kh, kw, stride, stride, pad, pad, dil, dil) != ORP_OK) return 0;
+  A.nprod = nprod;
+  int th_[orp_split::kMaxLevels], tw_[orp_split::kMaxLevels];
+  if (!orp_split::halo_tiles(A, orp_split::halo_switch(), th_, tw_)) return 0;
+  for (int i = 0; i < nlevels; i++) { th[i] = th_[i]; tw[i] = tw_[i]; }
+  return 1;
 }
 
 int orp_debug_amax_log(uint32_t* log, int capacity_launches) { return orp_split::set_amax_log(log, capacity_launches); }

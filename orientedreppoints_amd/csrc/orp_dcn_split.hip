@@ -63,6 +63,7 @@ struct LevelK {
   int H, W, Ho, Wo;
   int tile0;
   int tpi;                        // 0: the level's positions of all images tiled back to back; > 0: tiles per IMAGE (no tile spans two images: GroupNorm statistics)
+  int th, tw;                     // halo kernel: the level's spatial tile, th * tw = 96 output positions
   const uint16_t* planes;         // this level's own layer (or nullptr: FwdS::planes / bias / wscale)
   const float* bias;
   const float* wscale;
@@ -208,6 +209,136 @@ struct Products<TEND, TEND, MT, OUT_NCHW, SIDE, F16> {
   static __device__ __forceinline__ void run(floatx16 (&)[MT], floatx16 (&)[SIDE ? MT : 1], const bf8 (&)[MT][3], const bf8 (&)[3]) {}
 };
 
+// ---- pieces the linear-tile kernel and the halo kernel share -------------------------------------------------------------------------
+// XCD-aware map: an XCD takes a contiguous slab of ONE layer's tiles (the layer's weights stay in that XCD's L2); false: no tile
+__device__ __forceinline__ bool tile_of_block(const FwdS& P, int total_tiles, int& tile, int& conv) {
+  const int b = blockIdx.x, xcd = b & 7, slot = b >> 3;
+  const int nx = P.nconv == 2 ? 4 : 8;
+  conv = P.nconv == 2 ? (xcd >> 2) : 0;
+  const int xl = P.nconv == 2 ? (xcd & 3) : xcd;
+  const int per = (total_tiles + nx - 1) / nx;
+  tile = xl * per + slot;
+  return slot < per && tile < total_tiles;
+}
+
+// F16: the sample scale 2^k (sx) from the launch's range words and the exponent the epilogue takes back out (kxw = k + the weights').
+// `red`: kThreadsS / 64 words of LDS that nobody uses yet (no static LDS in front of the dynamic region)
+__device__ __forceinline__ void sample_range(const FwdS& P, const LevelK& L, int conv, int tile, unsigned* red, float& sx, int& kxw) {
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  unsigned am = P.amax[conv * P.amax_stride];
+  if (P.amax_count > 1) {                                                     // (block-uniform) the producer left one bound per (tensor, image, group)
+    unsigned m_ = 0u;
+    for (int i = tid; i < P.amax_count; i += kThreadsS) m_ = max(m_, P.amax[conv * P.amax_stride + i]);
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) m_ = max(m_, (unsigned)__shfl_xor((int)m_, o, 64));
+    if (lane == 0) red[wave] = m_;
+    __syncthreads();
+    am = red[0];
+#pragma unroll
+    for (int i = 1; i < kThreadsS / 64; i++) am = max(am, red[i]);
+    __syncthreads();                                                            // (before the caller overwrites the scratch)
+  }
+  const int k = orp::range_exp(am);
+  sx = orp::range_scale(k);
+  const float sw = *(L.planes ? L.wscale : conv ? P.wscale[1] : P.wscale[0]);
+  kxw = k + orp::range_exp_of(sw);
+  if (P.dbg && tile == 0 && blockIdx.y == 0 && tid == 0) { P.dbg[conv] = am; P.dbg[2 + conv] = __float_as_uint(sw); }
+}
+
+// Which output position an MFMA row m of the tile is: ok(m) (inside the tile's part of the map), pos(m) (index into the level's
+// B * Ho * Wo positions), count() (rows with ok).
+struct LinearRows {                                                           // positions [p0, plim) of the linearised index
+  long p0, plim;
+  __device__ __forceinline__ bool ok(int m) const { return p0 + m < plim; }
+  __device__ __forceinline__ long pos(int m) const { return p0 + m; }
+  __device__ __forceinline__ int count() const { return (int)(plim - p0); }
+};
+// A spatial tile of 96 / tw x tw positions at `origin` (the position index of its top left corner), nh x nw of them inside the map.
+// Row m is tile row m / tw; its column is m % tw ROTATED by `rot` per tile row: with tw = 16 and rot = 2 the halo row of lane i
+// (row stride tw + 2) is i modulo 16 whatever the tile row, which keeps the 16-lane groups of a ds_read_b128 on 16 different rows
+struct HaloRows {
+  long origin;
+  int W, nh, nw, twl, rot;
+  __device__ __forceinline__ int ty(int m) const { return m >> twl; }
+  __device__ __forceinline__ int tx(int m) const { return (m - rot * ty(m)) & ((1 << twl) - 1); }
+  __device__ __forceinline__ bool ok(int m) const { return ty(m) < nh && tx(m) < nw; }
+  __device__ __forceinline__ long pos(int m) const { return origin + ty(m) * W + tx(m); }
+  __device__ __forceinline__ int count() const { return nh * nw; }
+};
+
+// bias / ReLU / range un-scaling, the tile's GroupNorm partials (GN: the PLAIN channels-last instantiations) and the stores
+template <int MT, bool OUT_NCHW, bool F16, bool GN, class Rows>
+__device__ __forceinline__ void split_epilogue(const FwdS& P, const LevelK& L, floatx16 (&acc)[MT], const Rows R, int conv, int tile,
+                                               int total_tiles, int n_wave, int lane, int kxw) {
+  const int HoWo = L.Ho * L.Wo;
+  const float* bias = L.planes ? L.bias : conv ? P.bias[1] : P.bias[0];
+  float* outp = conv ? L.out[1] : L.out[0];
+  bool scaled = false;
+  if (GN && P.gn_part) {
+    // GroupNorm statistics of the tile while it is in registers: lane = channel (n_wave + lane % 32), its 16 * MT values = the
+    // rows (r & 3) + 8 (r >> 2) + 4 (lane >> 5) + 32 mt; a group = Cout / G consecutive channels = consecutive lanes of both
+    // half-waves.  Two passes (mean, then M2 around it), fixed shuffle order; orp_conv_split_gn_finish merges the tiles of an
+    // image (Chan et al.) in tile order.
+    if (F16) {
+#pragma unroll
+      for (int mt = 0; mt < MT; mt++)
+#pragma unroll
+        for (int r = 0; r < 16; r++) acc[mt][r] = orp::range_unscale(acc[mt][r], kxw);
+      scaled = true;
+    }
+    const int cg = P.Cout / P.G, nrow = R.count();
+    auto row_ok = [&](int mt, int r) { return R.ok(mt * 32 + (r & 3) + 8 * (r >> 2) + 4 * (lane >> 5)); };
+    auto group_sum = [&](float v) {
+      for (int o = 1; o < cg; o <<= 1) v += __shfl_xor(v, o, 64);
+      return v + __shfl_xor(v, 32, 64);
+    };
+    float sum = 0.f;
+#pragma unroll
+    for (int mt = 0; mt < MT; mt++)
+#pragma unroll
+      for (int r = 0; r < 16; r++) sum += row_ok(mt, r) ? acc[mt][r] : 0.f;
+    const float cnt = (float)(nrow * cg);
+    const float mean = group_sum(sum) / cnt;
+    float m2 = 0.f, mx = 0.f;
+#pragma unroll
+    for (int mt = 0; mt < MT; mt++)
+#pragma unroll
+      for (int r = 0; r < 16; r++) {
+        const float d = acc[mt][r] - mean;
+        m2 += row_ok(mt, r) ? d * d : 0.f;
+        mx = fmaxf(mx, row_ok(mt, r) ? fabsf(acc[mt][r]) : 0.f);
+      }
+    m2 = group_sum(m2);
+    for (int o = 1; o < cg; o <<= 1) mx = fmaxf(mx, __shfl_xor(mx, o, 64));
+    mx = fmaxf(mx, __shfl_xor(mx, 32, 64));
+    if (lane < 32 && (lane & (cg - 1)) == 0)
+      P.gn_part[((size_t)conv * total_tiles + tile) * P.G + (n_wave + lane) / cg] = make_float4(mean, m2, mx, cnt);
+  }
+  auto finish = [&](float v, int ch) { if (F16 && !scaled) v = orp::range_unscale(v, kxw); if (bias) v += bias[ch]; return P.relu ? fmaxf(v, 0.f) : v; };
+#pragma unroll
+  for (int mt = 0; mt < MT; mt++) {
+    if (OUT_NCHW) {
+      const int m = mt * 32 + (lane & 31);
+      if (R.ok(m)) {
+        const long p = R.pos(m);
+        const int b = (int)(p / HoWo), hw = (int)(p - (long)b * HoWo);
+        float* ob = outp + (size_t)b * P.Cout * HoWo + hw;
+#pragma unroll
+        for (int r = 0; r < 16; r++) {
+          const int ch = n_wave + (r & 3) + 8 * (r >> 2) + 4 * (lane >> 5);
+          ob[(size_t)ch * HoWo] = finish(acc[mt][r], ch);
+        }
+      }
+    } else {
+#pragma unroll
+      for (int r = 0; r < 16; r++) {
+        const int m = mt * 32 + (r & 3) + 8 * (r >> 2) + 4 * (lane >> 5);
+        if (R.ok(m)) outp[(size_t)R.pos(m) * P.Cout + n_wave + (lane & 31)] = finish(acc[mt][r], n_wave + (lane & 31));
+      }
+    }
+  }
+}
+
 // PLAIN: no offsets -- the ordinary convolution (sample = the tap-shifted pixel itself, zero outside the map): one row fetch
 // per sample instead of four, no bilinear combine; everything else (split, planes, MFMA schedule, epilogue) is shared
 template <int MT, int NPROD, bool OUT_NCHW, bool PLAIN>
@@ -234,15 +365,7 @@ dcn_fwd_split_kernel(const FwdS P, int total_tiles) {
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   const int taps = P.kh * P.kw;
   int tile, conv;
-  {   // XCD-aware map: an XCD takes a contiguous slab of ONE layer's tiles (the layer's weights stay in that XCD's L2)
-    const int b = blockIdx.x, xcd = b & 7, slot = b >> 3;
-    const int nx = P.nconv == 2 ? 4 : 8;
-    conv = P.nconv == 2 ? (xcd >> 2) : 0;
-    const int xl = P.nconv == 2 ? (xcd & 3) : xcd;
-    const int per = (total_tiles + nx - 1) / nx;
-    tile = xl * per + slot;
-    if (slot >= per || tile >= total_tiles) return;
-  }
+  if (!tile_of_block(P, total_tiles, tile, conv)) return;
   int lvl = 0;
 #pragma unroll 1
   for (int i = 1; i < P.nlev; i++) if (tile >= P.lv[i].tile0) lvl = i;
@@ -265,27 +388,7 @@ dcn_fwd_split_kernel(const FwdS P, int total_tiles) {
   float sx = 1.f;                                                             // F16: sample scale 2^k; the output's 2^-(k + kw)
   int kxw = 0;
   float* sAB = reinterpret_cast<float*>(sCi + BMS * kTapsMax);                 // [2][Cin] the input normalisation's (a[c]) then (b[c]) (coef_in only)
-  if (F16) {
-    unsigned am = P.amax[conv * P.amax_stride];
-    if (P.amax_count > 1) {                                                   // (block-uniform) the producer left one bound per (tensor, image, group)
-      unsigned* red = reinterpret_cast<unsigned*>(sCw);                         // (the table is built after this; no static LDS in front of the dynamic region)
-      unsigned m_ = 0u;
-      for (int i = tid; i < P.amax_count; i += kThreadsS) m_ = max(m_, P.amax[conv * P.amax_stride + i]);
-#pragma unroll
-      for (int o = 32; o > 0; o >>= 1) m_ = max(m_, (unsigned)__shfl_xor((int)m_, o, 64));
-      if (lane == 0) red[wave] = m_;
-      __syncthreads();
-      am = red[0];
-#pragma unroll
-      for (int i = 1; i < kThreadsS / 64; i++) am = max(am, red[i]);
-      __syncthreads();                                                          // (before the table build overwrites the scratch)
-    }
-    const int k = orp::range_exp(am);
-    sx = orp::range_scale(k);
-    const float sw = *(L.planes ? L.wscale : conv ? P.wscale[1] : P.wscale[0]);
-    kxw = k + orp::range_exp_of(sw);
-    if (P.dbg && tile == 0 && blockIdx.y == 0 && tid == 0) { P.dbg[conv] = am; P.dbg[2 + conv] = __float_as_uint(sw); }
-  }
+  if (F16) sample_range(P, L, conv, tile, reinterpret_cast<unsigned*>(sCw), sx, kxw);   // (the table is built after this)
 
   // ---- bilinear coefficient table, one entry per (position, tap): deformable_im2col_bilinear (:84-115) hoisted out of the
   //      channel loop; a sample outside (-1, H) x (-1, W) has weight 0 (:229); DCNv2 folds the modulation scalar in (:620) ----
@@ -550,75 +653,201 @@ dcn_fwd_split_kernel(const FwdS P, int total_tiles) {
 #pragma unroll
     for (int mt = 0; mt < MT; mt++) acc[mt] += side[mt];
   }
-  const float* bias = L.planes ? L.bias : conv ? P.bias[1] : P.bias[0];
-  float* outp = conv ? L.out[1] : L.out[0];
-  bool scaled = false;
-  if (PLAIN && !OUT_NCHW && P.gn_part) {
-    // GroupNorm statistics of the tile while it is in registers: lane = channel (n_wave + lane % 32), its 16 * MT values = the
-    // rows (r & 3) + 8 (r >> 2) + 4 (lane >> 5) + 32 mt; a group = Cout / G consecutive channels = consecutive lanes of both
-    // half-waves.  Two passes (mean, then M2 around it), fixed shuffle order; orp_conv_split_gn_finish merges the tiles of an
-    // image (Chan et al.) in tile order.
-    if (F16) {
-#pragma unroll
-      for (int mt = 0; mt < MT; mt++)
-#pragma unroll
-        for (int r = 0; r < 16; r++) acc[mt][r] = orp::range_unscale(acc[mt][r], kxw);
-      scaled = true;
-    }
-    const int cg = P.Cout / P.G, nrow = (int)(plim - p0);
-    auto row_ok = [&](int mt, int r) { return mt * 32 + (r & 3) + 8 * (r >> 2) + 4 * (lane >> 5) < nrow; };
-    auto group_sum = [&](float v) {
-      for (int o = 1; o < cg; o <<= 1) v += __shfl_xor(v, o, 64);
-      return v + __shfl_xor(v, 32, 64);
-    };
-    float sum = 0.f;
-#pragma unroll
-    for (int mt = 0; mt < MT; mt++)
-#pragma unroll
-      for (int r = 0; r < 16; r++) sum += row_ok(mt, r) ? acc[mt][r] : 0.f;
-    const float cnt = (float)(nrow * cg);
-    const float mean = group_sum(sum) / cnt;
-    float m2 = 0.f, mx = 0.f;
-#pragma unroll
-    for (int mt = 0; mt < MT; mt++)
-#pragma unroll
-      for (int r = 0; r < 16; r++) {
-        const float d = acc[mt][r] - mean;
-        m2 += row_ok(mt, r) ? d * d : 0.f;
-        mx = fmaxf(mx, row_ok(mt, r) ? fabsf(acc[mt][r]) : 0.f);
-      }
-    m2 = group_sum(m2);
-    for (int o = 1; o < cg; o <<= 1) mx = fmaxf(mx, __shfl_xor(mx, o, 64));
-    mx = fmaxf(mx, __shfl_xor(mx, 32, 64));
-    if (lane < 32 && (lane & (cg - 1)) == 0)
-      P.gn_part[((size_t)conv * total_tiles + tile) * P.G + (n_wave + lane) / cg] = make_float4(mean, m2, mx, cnt);
-  }
-  auto finish = [&](float v, int ch) { if (F16 && !scaled) v = orp::range_unscale(v, kxw); if (bias) v += bias[ch]; return P.relu ? fmaxf(v, 0.f) : v; };
-#pragma unroll
-  for (int mt = 0; mt < MT; mt++) {
-    if (OUT_NCHW) {
-      const long p = p0 + mt * 32 + (lane & 31);
-      if (p < plim) {
-        const int b = (int)(p / HoWo), hw = (int)(p - (long)b * HoWo);
-        float* ob = outp + (size_t)b * P.Cout * HoWo + hw;
-#pragma unroll
-        for (int r = 0; r < 16; r++) {
-          const int ch = n_wave + (r & 3) + 8 * (r >> 2) + 4 * (lane >> 5);
-          ob[(size_t)ch * HoWo] = finish(acc[mt][r], ch);
-        }
-      }
-    } else {
-#pragma unroll
-      for (int r = 0; r < 16; r++) {
-        const int m = (r & 3) + 8 * (r >> 2) + 4 * (lane >> 5);
-        const long p = p0 + mt * 32 + m;
-        if (p < plim) outp[(size_t)p * P.Cout + n_wave + (lane & 31)] = finish(acc[mt][r], n_wave + (lane & 31));
-      }
-    }
-  }
+  split_epilogue<MT, OUT_NCHW, F16, PLAIN && !OUT_NCHW>(P, L, acc, LinearRows{p0, plim}, conv, tile, total_tiles, n_wave, lane, kxw);
 }
 
-constexpr int kCoefCinMax = 512;                                              // orp_conv_split_multi_gn: input channels of a layer that normalises on the way in
+// ---- the halo kernel: the 3x3 / stride 1 / padding 1 convolution in the fp16-pieces mode over SPATIAL tiles -----------------------------
+// The nine taps of a th x tw tile read the same (th + 2) x (tw + 2) input pixels.  The linear-tile kernel above fetches, normalises
+// and splits the tile's 96 rows again in each of its 9 * Cin / 64 phases; here the halo is staged ONCE, all Cin channels, as two fp16
+// planes [kHaloRows][Cin + 8], and a phase reads its A fragments at (lane's halo row + the tap's row offset, channel block): no gathers,
+// no barriers and no double buffer inside the loop.  Every A value, every weight fragment, the order of the MFMAs into each accumulator
+// and the epilogue are the linear kernel's, and an MFMA output row depends on its own A row only: outputs are bit-identical, only the
+// tiles the GroupNorm partials are taken over differ.
+// Staging runs in slices of 64 channels: the phases (tap 0, channel block k) need slice k only, so slice k + 1 is fetched into
+// registers in front of phase k's MFMAs and split into LDS behind them -- Cin / 64 barriers per tile.
+constexpr int kHaloRows = 144;                                                // (6 + 2) * (16 + 2) >= (12 + 2) * (8 + 2)
+constexpr int kHaloCinMax = 256;                                              // 2 planes * 144 rows * 528 B + coefficients = 154,112 B of the CU's 160 KiB
+constexpr int kHaloStage = (kHaloRows + 31) / 32;                             // row groups of a slice per wave (8 waves x 4 rows per instruction)
+static_assert(kHaloRows == (kHaloStage - 1) * 32 + 16, "stage_row: the last group is half a group");
+constexpr size_t halo_smem(int cin) { return (size_t)2 * kHaloRows * (cin + 8) * 2 + sizeof(float) * 2 * cin; }
+
+template <bool OUT_NCHW>
+__global__ void __launch_bounds__(kThreadsS)
+conv_halo_kernel(const FwdS P, int total_tiles) {
+  constexpr int MT = 3;
+  extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
+  const int astr = P.Cin + 8;                                                 // row stride in halves: 36 / 68 / 100 / 132 dwords, all 4 modulo 32
+  const int plane = kHaloRows * astr;
+  uint16_t* sA = reinterpret_cast<uint16_t*>(smem);                           // [2 planes][kHaloRows][Cin + 8]
+  float* sAB = reinterpret_cast<float*>(sA + 2 * plane);                      // [2][Cin] the input normalisation's (a[c]) then (b[c]) (coef_in only)
+
+  asm volatile("" ::: "v255");                                                // (the whole register budget: see the linear kernel)
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  int tile, conv;
+  if (!tile_of_block(P, total_tiles, tile, conv)) return;
+  int lvl = 0;
+#pragma unroll 1
+  for (int i = 1; i < P.nlev; i++) if (tile >= P.lv[i].tile0) lvl = i;
+  const LevelK L = P.lv[lvl];
+  const int t_in = tile - L.tile0, img = t_in / L.tpi, tt = t_in - img * L.tpi;
+  const int tcols = (L.W + L.tw - 1) / L.tw;
+  const int y0 = (tt / tcols) * L.th, x0 = (tt - (tt / tcols) * tcols) * L.tw;
+  const int hw = L.tw + 2;                                                    // halo width; halo row (hy, hx) = pixel (y0 - 1 + hy, x0 - 1 + hx)
+  HaloRows R;
+  R.origin = ((long)img * L.H + y0) * L.W + x0; R.W = L.W;
+  R.nh = min(L.th, L.H - y0); R.nw = min(L.tw, L.W - x0);
+  R.twl = L.tw == 16 ? 4 : 3; R.rot = L.tw == 16 ? 2 : 0;
+  const float* xin = conv ? L.x[1] : L.x[0];
+  float sx;
+  int kxw;
+  sample_range(P, L, conv, tile, reinterpret_cast<unsigned*>(smem), sx, kxw);
+  const bool has_coef = P.coef_in != nullptr;                                 // (block-uniform)
+  if (has_coef) {
+    const float2* cf = P.coef_in + ((size_t)(conv * P.nlev + lvl) * P.B + img) * P.Cin;
+    for (int c = tid; c < P.Cin; c += kThreadsS) { const float2 ab = cf[c]; sAB[c] = ab.x; sAB[P.Cin + c] = ab.y; }
+  }
+
+  // ---- staging: a wave takes the halo rows i * 32 + wave * 4 + lane / 16; 16 lanes x float4 = the 64 channels of a slice ----
+  // The last 16 of the 144 rows are taken by waves 0-3 AND, again, by waves 4-7 (the same values to the same addresses): no lane is
+  // masked and no staging register is consumed under a divergent branch
+  const int q4 = lane >> 4, c4 = (lane & 15) * 4;
+  auto stage_row = [&](int i) { return i < kHaloStage - 1 ? i * 32 + wave * 4 + q4 : (kHaloStage - 1) * 32 + (wave & 3) * 4 + q4; };
+  int pix[kHaloStage];                                                        // the row's pixel, -1: padding (or past the halo's last row)
+#pragma unroll
+  for (int i = 0; i < kHaloStage; i++) {
+    const int h = stage_row(i);
+    const int hy = h / hw, hx = h - hy * hw;
+    const int y = y0 - 1 + hy, x = x0 - 1 + hx;
+    const bool in = hy < L.th + 2 && y >= 0 && y < L.H && x >= 0 && x < L.W;
+    pix[i] = in ? (img * L.H + y) * L.W + x : -1;
+  }
+  auto stage_issue = [&](int k, float4 (&v)[kHaloStage]) {
+#pragma unroll
+    for (int i = 0; i < kHaloStage; i++)
+      v[i] = *reinterpret_cast<const float4*>(xin + (size_t)max(pix[i], 0) * P.Cin + k * CBS + c4);
+  };
+  auto stage_store = [&](int k, const float4 (&v)[kHaloStage]) {
+    float4 ca = make_float4(1.f, 1.f, 1.f, 1.f), cb_ = make_float4(0.f, 0.f, 0.f, 0.f);
+    if (has_coef) {
+      ca = *reinterpret_cast<const float4*>(sAB + k * CBS + c4);
+      cb_ = *reinterpret_cast<const float4*>(sAB + P.Cin + k * CBS + c4);
+    }
+#pragma unroll
+    for (int i = 0; i < kHaloStage; i++) {
+      const int h = stage_row(i);
+      float4 x = v[i];
+      if (has_coef) {                                                         // the previous layer's GroupNorm (+ ReLU) on the way in
+        x.x = fmaf(x.x, ca.x, cb_.x); x.y = fmaf(x.y, ca.y, cb_.y); x.z = fmaf(x.z, ca.z, cb_.z); x.w = fmaf(x.w, ca.w, cb_.w);
+        if (P.relu_in) { x.x = fmaxf(x.x, 0.f); x.y = fmaxf(x.y, 0.f); x.z = fmaxf(x.z, 0.f); x.w = fmaxf(x.w, 0.f); }
+      }
+      const bool in = pix[i] >= 0;
+      const float s[4] = {in ? x.x : 0.f, in ? x.y : 0.f, in ? x.z : 0.f, in ? x.w : 0.f};   // (the padding of the NORMALISED tensor is 0)
+      _Float16 hh[4], ll[4];
+#pragma unroll
+      for (int e = 0; e < 4; e++) {
+        const float sv = s[e] * sx;                                             // exact (power of two)
+        hh[e] = (_Float16)sv;                                                   // round to nearest
+        ll[e] = (_Float16)(sv - (float)hh[e]);                                  // the residual is exact in fp32
+      }
+      const h2 h01 = {hh[0], hh[1]}, h23 = {hh[2], hh[3]}, l01 = {ll[0], ll[1]}, l23 = {ll[2], ll[3]};
+      uint16_t* dst = sA + (size_t)h * astr + k * CBS + c4;
+      *reinterpret_cast<uint2*>(dst) = make_uint2(__builtin_bit_cast(unsigned, h01), __builtin_bit_cast(unsigned, h23));
+      *reinterpret_cast<uint2*>(dst + plane) = make_uint2(__builtin_bit_cast(unsigned, l01), __builtin_bit_cast(unsigned, l23));
+    }
+  };
+
+  // weight fragments: as in the linear kernel
+  const int n_wave = blockIdx.y * 256 + wave * 32;
+  const int mrow = lane & 31, kg = lane >> 5;
+  const bool live = n_wave < P.Cout;
+  const uint16_t* wp = (L.planes ? L.planes : conv ? P.planes[1] : P.planes[0]) + ((size_t)kg * P.Cout + (live ? n_wave : 0) + mrow) * 8;
+  const size_t wblk = (size_t)2 * P.Cout * 8;
+  auto load_b = [&](int tap, int cb, int j, bf8 (&b)[3]) {
+    const uint16_t* a = wp + ((size_t)tap * (P.Cin / 16) + cb * NCH + j) * wblk;
+#pragma unroll
+    for (int pl = 0; pl < 2; pl++) b[pl] = *reinterpret_cast<const bf8*>(a + (size_t)pl * P.plane_stride);
+  };
+  // A fragments: lane (row mrow of block mt, k-group kg) reads 16 B of halo row (tile row + ki, tile column + kj)
+  const uint16_t* abase[MT];
+#pragma unroll
+  for (int mt = 0; mt < MT; mt++) abase[mt] = sA + (size_t)(R.ty(mt * 32 + mrow) * hw + R.tx(mt * 32 + mrow)) * astr + 8 * kg;
+  auto a_off = [&](int tap, int cb) { const int ki = tap / 3; return ((ki * hw + tap - 3 * ki) * astr + cb * CBS); };
+  auto load_a = [&](int off, int j, bf8 (&a)[MT][3]) {
+#pragma unroll
+    for (int mt = 0; mt < MT; mt++)
+#pragma unroll
+      for (int pl = 0; pl < 2; pl++) a[mt][pl] = *reinterpret_cast<const bf8*>(abase[mt] + pl * plane + off + j * 16);
+  };
+
+  // ---- prologue: weight ring of phase 0, slice 0 -----------------------------------------------------------------------------------
+  bf8 bq[NCH][3];
+#pragma unroll
+  for (int j = 0; j < NCH; j++) load_b(0, 0, j, bq[j]);
+  // (the weights go out FIRST: the scheduler moved one of these loads behind the staging loads, where the wait for slice 0 does not
+  //  cover it -- and a load that may still be in flight with nothing younger behind it at the loop's entry makes the compiler open
+  //  EVERY phase with s_waitcnt vmcnt(0), all of the phase's weights landed, instead of the counted waits per chunk)
+  __builtin_amdgcn_sched_barrier(0);
+  float4 sv[kHaloStage];
+  stage_issue(0, sv);
+  __syncthreads();                                                            // (the coefficients; the range scratch is free)
+  stage_store(0, sv);
+  __syncthreads();
+
+  floatx16 acc[MT], side[MT];
+#pragma unroll
+  for (int mt = 0; mt < MT; mt++) { acc[mt] = floatx16{0}; side[mt] = floatx16{0}; }
+  const int ncb = P.Cin / CBS, nphase = 9 * ncb;
+  int tap = 0, cb = 0, tap_n = 0, cb_n = 0;                                   // this phase, the next one (clamped to the last: unconditional loads)
+  auto step = [&](int& t, int& c, int ph) {
+    if (ph + 1 < nphase) { if (++c == ncb) { c = 0; t++; } }
+  };
+  step(tap_n, cb_n, 0);
+  bf8 a[2][MT][3];
+  load_a(a_off(0, 0), 0, a[0]);
+  // one phase: the A fragments of the next chunk -- of the NEXT PHASE's first chunk behind the last one -- are read before the MFMAs of
+  // this one are issued; the weight registers of a chunk are refilled for the next phase right after use
+  auto phase_body = [&]() __attribute__((always_inline)) {
+    const int off = a_off(tap, cb), off_n = a_off(tap_n, cb_n);
+#pragma unroll
+    for (int j = 0; j < NCH; j++) {
+      if (j + 1 < NCH) load_a(off, j + 1, a[(j + 1) & 1]);
+      else             load_a(off_n, 0, a[0]);
+      __builtin_amdgcn_sched_barrier(0);
+      Products<0, 3, MT, OUT_NCHW, true, true>::run(acc, side, a[j & 1], bq[j]);
+      __builtin_amdgcn_sched_barrier(0);
+      load_b(tap_n, cb_n, j, bq[j]);
+      __builtin_amdgcn_sched_barrier(0);
+    }
+  };
+  // The phases that stage are a loop of their own: every load of either loop is unconditional, so the compiler's s_waitcnt vmcnt counts
+  // are exact (with the staging loads under a condition inside ONE loop every phase opened with vmcnt(0): all of its weights landed
+  // before its first MFMA)
+  int phase = 0;
+#pragma unroll 1
+  for (; phase + 1 < ncb; phase++) {                                          // tap 0: slice phase + 1 is not in LDS yet
+    stage_issue(phase + 1, sv);
+    __builtin_amdgcn_sched_barrier(0);
+    phase_body();
+    stage_store(phase + 1, sv);
+    __syncthreads();
+    load_a(a_off(tap_n, cb_n), 0, a[0]);                                      // (what the phase read ahead was not written yet)
+    tap = tap_n; cb = cb_n;
+    step(tap_n, cb_n, phase + 1);
+  }
+#pragma unroll 1
+  for (; phase < nphase; phase++) {
+    phase_body();
+    tap = tap_n; cb = cb_n;
+    step(tap_n, cb_n, phase + 1);
+  }
+
+  if (!live) return;
+#pragma unroll
+  for (int mt = 0; mt < MT; mt++) acc[mt] += side[mt];
+  split_epilogue<MT, OUT_NCHW, true, !OUT_NCHW>(P, L, acc, R, conv, tile, total_tiles, n_wave, lane, kxw);
+}
+
+constexpr int kCoefCinMax = 512;                                             // orp_conv_split_multi_gn: input channels of a layer that normalises on the way in
 template <int MT, int NPL>
 constexpr size_t split_smem() {
   return (size_t)2 * NPL * 32 * MT * ASTRS * 2 + (sizeof(float4) + sizeof(int4)) * 32 * MT * kTapsMax + sizeof(float) * 2 * kCoefCinMax;
@@ -633,6 +862,17 @@ hipError_t launch_one(const FwdS& P, int tiles, int nblk_n, hipStream_t st) {
   const int nx = P.nconv == 2 ? 4 : 8;
   const int per = (tiles + nx - 1) / nx;
   hipLaunchKernelGGL((dcn_fwd_split_kernel<MT, NPROD, OUT_NCHW, PLAIN>), dim3(per * 8, nblk_n), dim3(kThreadsS), smem, st, P, tiles);
+  return hipGetLastError();
+}
+
+template <bool OUT_NCHW>
+hipError_t launch_halo(const FwdS& P, int tiles, int nblk_n, hipStream_t st) {
+  struct Tag {};
+  hipError_t e = orp::set_max_dynamic_lds_once<Tag>(reinterpret_cast<const void*>(&conv_halo_kernel<OUT_NCHW>), halo_smem(kHaloCinMax));
+  if (e != hipSuccess) return e;
+  const int nx = P.nconv == 2 ? 4 : 8;
+  const int per = (tiles + nx - 1) / nx;
+  hipLaunchKernelGGL((conv_halo_kernel<OUT_NCHW>), dim3(per * 8, nblk_n), dim3(kThreadsS), halo_smem(P.Cin), st, P, tiles);
   return hipGetLastError();
 }
 
@@ -684,8 +924,43 @@ hipError_t pack_planes(const float* weight, int c_out, int c_in, int taps, uint1
   return hipGetLastError();
 }
 
+// The halo kernel's switch: ORP_CONV_HALO (default 1), orp_conv_split_set_halo() overrides it (-1: back to the environment's choice)
+static int g_halo = -1;
+int halo_switch() {
+  if (g_halo < 0) {
+    const char* e = getenv("ORP_CONV_HALO");
+    g_halo = (e && atoi(e) == 0) ? 0 : 1;
+  }
+  return g_halo;
+}
+void set_halo(int on) { g_halo = on < 0 ? -1 : on ? 1 : 0; }
+
+// THE choice between the two plain kernels, and the halo kernel's tile per level: 6 x 16 where a map is at least 16 wide, 12 x 8 on
+// narrower ones (th * tw = 96 = three MFMA row blocks)
+bool halo_tiles(const Args& a, int on, int* th, int* tw) {
+  bool plain = true;
+  for (int i = 0; i < a.nlev; i++) plain = plain && !a.lv[i].off && !a.lv[i].mask;
+  if (!on || !plain || a.nprod != 3 || a.kh != 3 || a.kw != 3 || a.sh != 1 || a.sw != 1 || a.dh != 1 || a.dw != 1 || a.ph != 1 || a.pw != 1 ||
+      a.Cin % CBS != 0 || a.Cin > kHaloCinMax)
+    return false;
+  for (int i = 0; i < a.nlev; i++) { tw[i] = a.lv[i].W >= 16 ? 16 : 8; th[i] = 96 / tw[i]; }
+  return true;
+}
+
 Plan plan(const Args& a) {
   Plan pl;
+  pl.halo = halo_tiles(a, halo_switch(), pl.th, pl.tw) ? 1 : 0;
+  if (pl.halo) {                                           // spatial tiles, per image whether or not GroupNorm statistics are taken
+    int tiles = 0;
+    for (int i = 0; i < kMaxLevels; i++) { pl.tile0[i] = 0x7fffffff; pl.tpi[i] = 0; }
+    for (int i = 0; i < a.nlev; i++) {
+      pl.tile0[i] = tiles;
+      pl.tpi[i] = ((a.lv[i].Ho + pl.th[i] - 1) / pl.th[i]) * ((a.lv[i].Wo + pl.tw[i] - 1) / pl.tw[i]);
+      tiles += a.B * pl.tpi[i];
+    }
+    pl.MT = 3; pl.tiles = tiles;
+    return pl;
+  }
   long npos_all = 0;
   for (int i = 0; i < a.nlev; i++) npos_all += (long)a.B * a.lv[i].Ho * a.lv[i].Wo;
   // tile height: rounds x height on 256 CUs (one layer) / 128 CUs per layer (pair: the grid halves run side by side), times
@@ -754,6 +1029,7 @@ hipError_t launch(const Args& a, hipStream_t st) {
     D.H = a.lv[i].H; D.W = a.lv[i].W; D.Ho = a.lv[i].Ho; D.Wo = a.lv[i].Wo;
     D.planes = a.nconv == 1 ? a.lv[i].planes : nullptr; D.bias = a.lv[i].bias; D.wscale = a.lv[i].wscale;
     D.tile0 = pl.tile0[i]; D.tpi = pl.tpi[i];
+    D.th = pl.halo ? pl.th[i] : 0; D.tw = pl.halo ? pl.tw[i] : 0;
   }
   pad_level_slots(P.lv, a.nlev);
   const int nblk_n = (a.Cout + 255) / 256;
@@ -786,6 +1062,7 @@ hipError_t launch(const Args& a, hipStream_t st) {
       P.amax = a.scratch; P.amax_stride = 1;
     }
     P.wscale[0] = a.wscale[0]; P.wscale[1] = a.nconv == 2 ? a.wscale[1] : a.wscale[0];
+    if (pl.halo) return a.out_nchw ? launch_halo<true>(P, tiles, nblk_n, st) : launch_halo<false>(P, tiles, nblk_n, st);
     return plain ? launch_m<3, true>(MT, P, tiles, nblk_n, a.out_nchw != 0, st)
                  : launch_m<3, false>(MT, P, tiles, nblk_n, a.out_nchw != 0, st);
   }

@@ -45,8 +45,18 @@ struct Args {
 };
 
 // the tile table of a launch (what the kernel and orp_conv_split_gn_finish agree on)
-struct Plan { int MT, tiles; int tile0[kMaxLevels], tpi[kMaxLevels]; };
+struct Plan {
+  int MT, tiles; int tile0[kMaxLevels], tpi[kMaxLevels];
+  int halo;                                // 1: the halo kernel's spatial tiles of th[l] x tw[l] positions (tpi[l] = tiles per image, row-major)
+  int th[kMaxLevels], tw[kMaxLevels];
+};
 Plan plan(const Args& a);
+// The one place that chooses between the two plain-convolution kernels: true when the launch `a` takes the halo kernel (fp16-pieces mode,
+// 3x3, stride 1, dilation 1, padding 1, Cin % 64 == 0, Cin <= 256, no offsets) and `on`, with the tile shape per level.  plan() asks it
+// with `on` = halo_switch(); a caller that sizes a buffer for either choice asks with on = 1.
+bool halo_tiles(const Args& a, int on, int* th, int* tw);
+int halo_switch();                         // ORP_CONV_HALO (default 1) unless set_halo() said otherwise
+void set_halo(int on);                     // 0 / 1; -1: back to the environment's choice
 
 // cin % 64 == 0, cout % 64 == 0, taps <= 9
 bool shape_ok(int c_in, int c_out, int kh, int kw);

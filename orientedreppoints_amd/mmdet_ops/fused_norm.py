@@ -559,6 +559,25 @@ def conv_split_ok(conv, x=None):
     return ok
 
 
+def conv_split_set_halo(on):
+    """The halo kernel of the 3x3 stride-1 fp16-pieces convolutions on (1) / off (0: the linear-tile kernel) / -1: back to the
+    default (ORP_CONV_HALO, 1).  A captured graph keeps the kernel it was captured with."""
+    _lib.check(_lib.lib().orp_conv_split_set_halo(int(on)), "orp_conv_split_set_halo")
+
+
+def conv_split_halo_tile(sizes, batch, cin, cout, kh=3, kw=3, stride=1, pad=1, dil=1, nprod=3):
+    """[(th, tw)] per level of the sizes [(H, W)] when a convolution launch of these arguments runs the halo kernel, else None
+    (`orp_conv_split_halo_tile`)."""
+    n = len(sizes)
+    levels = (_ConvLevel * n)()
+    for i, (h, w) in enumerate(sizes):
+        levels[i] = _ConvLevel(None, None, None, None, int(h), int(w))
+    th, tw = (ctypes.c_int * n)(), (ctypes.c_int * n)()
+    if not _lib.lib().orp_conv_split_halo_tile(levels, n, int(batch), int(cin), int(cout), kh, kw, stride, pad, dil, int(nprod), th, tw):
+        return None
+    return [(th[i], tw[i]) for i in range(n)]
+
+
 def conv_split_weights(xs_a, weights_a, xs_b=None, weight_b=None, biases_a=None, bias_b=None, stride=(1, 1), padding=(1, 1),
                        dilation=(1, 1), relu=False, out_channels_last=True, nprod=None, cache_pack=True, amax=None):
     """The launch behind conv_split_multi, on tensors: weights_a = one [Cout,Cin,kh,kw] weight for all of xs_a, or a list with

@@ -3,7 +3,8 @@
 Defaults are the product; each switch exists for A/B timing of one design decision and has a module attribute that overrides it per
 object.  The library's own switches (C side) are `ORP_DCN_SPLIT` (arithmetic of the fp32 contractions: 3 default, 6, 9, 0 = exact fp32
 MFMA; `orp_dcn_set_split_mode`), `ORP_DCNS_MT` (tile height of the split kernel, dev aid), `ORP_DCN_KSPLIT` (tap-granular split of
-the exact-fp32 DeformConv launch) and `ORP_FILL=memset` (fills as hipMemsetAsync instead of kernels: the A/B aid of DESIGN.md 4.5).
+the exact-fp32 DeformConv launch), `ORP_CONV_HALO` (0: the 3x3 stride-1 fp16-pieces convolutions on the linear-tile kernel instead of
+the halo kernel; `orp_conv_split_set_halo`) and `ORP_FILL=memset` (fills as hipMemsetAsync instead of kernels: the A/B aid of DESIGN.md 4.5).
 The table in DESIGN.md section 0 lists them all with what they default to and why.
 """
 import os
