@@ -241,7 +241,8 @@ int orp_dcn_forward_direct(const float* input, const float* offset, const float*
 /* Deformable convolution (DCNv1) backward as two MFMA implicit GEMMs, no column buffer in HBM
  * (deform_conv_backward_input_cuda + deform_conv_backward_parameters_cuda, deform_conv_cuda.cpp:262-488), all levels of
  * one layer in one call.  Requires orp_dcn_backward_mfma_ok (c_in = c_out = 256, groups = deformable_groups = 1,
- * kh*kw <= 9); every other configuration: the column entries below.  All tensors NCHW fp32:
+ * kh*kw <= 9); every other configuration: the column entries below.  All tensors NCHW fp32 (fp16 / bf16 input,
+ * grad_output and grad_input: only through the _ex entry below):
  *   input [B,256,H,W], offset [B,2*kh*kw,Ho,Wo], grad_output [B,256,Ho,Wo] ->
  *   grad_input [B,256,H,W], grad_offset [B,2*kh*kw,Ho,Wo] (both OVERWRITTEN; written when need_input_grads != 0),
  *   grad_weight [256,256,kh,kw] (OVERWRITTEN; NULL = not wanted) = sum over levels and images, added in a fixed order.
@@ -251,7 +252,15 @@ int orp_dcn_forward_direct(const float* input, const float* offset, const float*
  *   zero almost everywhere (a detection head's regression branch: gradient at the positive points only): the few live
  *   rows are scattered with fp32 atomics instead, which skips the fixed cost of the region pass (same values to 1e-4;
  *   summation order not fixed, as in the reference's deformable_col2im).
- * weight is the layer's [256,256,kh,kw] tensor.  workspace: orp_dcn_backward_workspace_bytes() bytes. */
+ * weight is the layer's [256,256,kh,kw] tensor.  workspace: orp_dcn_backward_workspace_bytes() bytes.
+ * Arithmetic (both entries), fp32 accumulation throughout:
+ *   grad_input / grad_offset (/ grad_mask): the contraction over the output channels runs on the 16-bit matrix pipe, two fp16
+ *     pieces per operand after a power-of-two range scaling, like the forward's mode 3 (csrc/orp_range.hpp); environment
+ *     ORP_DCN_BWD_SPLIT=0: exact fp32 MFMAs.
+ *   grad_weight: the contraction over the positions runs on fp16 pieces as well when the call is DCNv1 (no masks) with
+ *     kh*kw >= 2 (and its operands fit 32-bit byte offsets: every level's input, and the call's grad_output pieces, below
+ *     2^31 bytes in the workspace); on exact fp32 MFMAs for DCNv2 (a modulated column has no known range), a single tap,
+ *     or under ORP_DCN_BWD_W16=0 / ORP_DCN_BWD_SPLIT=0. */
 #define ORP_DCN_BWD_INPUT 1
 #define ORP_DCN_BWD_SPARSE 2
 typedef struct { const void* input; const float* offset; const void* grad_output; void* grad_input; float* grad_offset;
@@ -269,9 +278,8 @@ int orp_dcn_backward_multi(const orp_dcn_bwd_level* levels_host, int nlevels, in
  *     grad_weight's columns, grad_input's scatter and grad_offset; grad_masks_host[i] receives d loss / d mask
  *     (= G . sampled value, summed over the channels in a fixed order);
  *   io_dtype 0 / 1 / 2 = input, grad_output and grad_input are fp32 / fp16 / bf16 (converted inside the layout passes the
- *     call runs anyway); offsets, masks, weight and the remaining gradients stay fp32; fp32 accumulation -- grad_weight on fp32
- *     MFMAs, the grad_input / grad_offset contraction on two fp16 pieces per operand like the forward's mode 3 (environment
- *     ORP_DCN_BWD_SPLIT=0: fp32 MFMAs). */
+ *     call runs anyway); offsets, masks, weight and the remaining gradients stay fp32.  The contractions: as stated above
+ *     (masks put grad_weight on the exact fp32 MFMAs). */
 int orp_dcn_backward_multi_ex(const orp_dcn_bwd_level* levels_host, const float* const* masks_host,
                               float* const* grad_masks_host, int io_dtype, int nlevels, int batch, int c_in, int c_out,
                               const float* weight, float* grad_weight, int need_input_grads, int kh, int kw, int stride_h,

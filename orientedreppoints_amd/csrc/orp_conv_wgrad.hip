@@ -206,11 +206,7 @@ conv_wgrad_split_kernel(const WParams P) {
       const float sc = is_x ? sx : sg;
       h8 hi, lo;
 #pragma unroll
-      for (int e = 0; e < 8; e++) {
-        const float sv = it[u].v[e] * sc;                                 // exact
-        hi[e] = (_Float16)sv;
-        lo[e] = (_Float16)(sv - (float)hi[e]);                            // the residual is exact in fp32
-      }
+      for (int e = 0; e < 8; e++) orp::range_split(it[u].v[e] * sc, hi, lo, e);     // (the scaling is exact)
       _Float16* dst = sT + (size_t)buf * BUF + (size_t)(is_x ? 2 : 0) * PL + (size_t)(r & (CH - 1)) * RS + q * 8;
       *reinterpret_cast<h8*>(dst) = hi;
       *reinterpret_cast<h8*>(dst + PL) = lo;
@@ -341,7 +337,7 @@ wgrad_absmax_kernel(const WAbs A, unsigned* __restrict__ out) {
   __syncthreads();
   if (threadIdx.x == 0) {
     const unsigned v = max(max(red[0], red[1]), max(red[2], red[3]));
-    if (v > __atomic_load_n(out + A.slot[t], __ATOMIC_RELAXED)) atomicMax(out + A.slot[t], v);
+    orp::range_raise(out + A.slot[t], v);
   }
 }
 

@@ -6,7 +6,7 @@
 // The reference (and orp_dcn_bwd.hip's column formulation) writes the [Cin*9, B*Ho*Wo] column buffers to HBM twice
 // (grad columns = W^T . grad_out, and im2col for grad_W) around two library GEMMs; here neither buffer exists:
 //
-//   kernel A  (grad_input, grad_offset)   per tile of MT*32 positions and per kernel tap t:
+//   kernel A  (grad_input, grad_offset)   per chunk of 32 positions and per kernel tap t:
 //       G_t[p, c] = sum_o  go[p, o] * W[o, c, t]                      (v_mfma_f32_32x32x2_f32, K = 256 output channels)
 //     the grad_out tile stays in LDS for all nine taps, wave w owns input channels [32w, 32w+32) and streams its W^T
 //     fragments L2 -> registers; the accumulator of a tap is consumed in place: the two coordinate derivatives
@@ -20,7 +20,7 @@
 //     pixels once, coalesced.  Every pixel is written by exactly one workgroup (no zero fill, no atomics), the summation
 //     order is fixed: bitwise reproducible.  Round 2 scattered with 4 x 9 x 256 fp32 atomics per position: 402 M
 //     lane-atomics per launch left the L2 as 1.555 GB of single transactions (profiles/r02_pmc.json) for 45 MB of
-//     gradient, 1.43 ms; that path is still selectable (ORP_DCN_BWD_ATOMIC=1, dev aid) for comparison.
+//     gradient, 1.43 ms; that path serves the callers that ask for it (ORP_DCN_BWD_SPARSE in need_input_grads).
 //   kernel B  (grad_weight)   workgroup (split s, tap t):
 //       gW_t[o, c] = sum_p  go[p, o] * col_t[p, c],    col_t[p, c] = bilinear(x[:, c], p + t + offset)
 //     K = positions, walked in 32-position chunks: the col tile is gathered exactly like the forward's A tile (coalesced
@@ -66,6 +66,7 @@ constexpr int ASTR = CH + 4;     // kernel A: grad_out tile row stride (conflict
 constexpr int ASTRH = CH + 8;    // kernel A, fp16 pieces: row stride of a plane in halves (132 dwords: conflict-free ds_read_b128 over 16 rows)
 constexpr int RS = CH + 32;      // kernel B: row stride with RS % 64 == 32 (two half-waves read rows k, k+1 conflict-free)
 constexpr int kThreads = 512;
+constexpr int kChunk = 32;       // positions per chunk: kernel A's tile, one K-step of kernel B, the unit of the active list
 
 struct BLevel {
   const float* x;      // NHWC [B, H, W, 256]
@@ -76,8 +77,7 @@ struct BLevel {
   const float* mask;   // DCNv2: NCHW [B, taps, Ho, Wo] modulation, or nullptr (DCNv1)
   float* gmask;        // DCNv2: its gradient
   int H, W, Ho, Wo;
-  int tile0;           // kernel A: first tile of this level
-  int chunk0;          // kernel B: first 32-position chunk of this level
+  int tile0;           // first 32-position chunk of this level (what level_of_tile searches by)
   int reg0, RH, RW;    // kernel A2: first 8 x 8-pixel region of this level, regions per image column / row
 };
 struct BwdParams {
@@ -94,7 +94,7 @@ struct BwdParams {
   float* partial;      // [nsplit][tap][o][c]
   int nsplit, total_chunks;
   const int* active;   // [total_chunks] chunk indices with a non-zero grad_out row, ascending; active[total_chunks] = count
-  float* G;            // kernel A -> A2: G[(position * taps + tap)][256], positions numbered chunk0 * 32 + p (NULL: atomics)
+  float* G;            // kernel A -> A2: G[(position * taps + tap)][256], positions numbered tile0 * 32 + p (NULL: atomics)
   const int* flags;    // [total_chunks] chunk holds a non-zero grad_out row
   int nregions;
   unsigned* keys;      // [4 * total_chunks * 32 * taps] region of slot (sample, k); nregions = unused slot
@@ -111,12 +111,18 @@ struct TransposeSet {
   int in_code, out_code;         // element type of the inputs / outputs: 0 fp32, 1 fp16, 2 bf16 (the other side is fp32)
   int R[2 * MAXL], S[2 * MAXL];
   int t0[2 * MAXL + 1];
-  int chunk0[2 * MAXL];          // >= 0: tensor i is a grad_out [256][HoWo]; flags[chunk0 + (b*S + s) / 32] = 1 where non-zero
+  int flag0[2 * MAXL];           // >= 0: tensor i is a grad_out [256][HoWo]; flags[flag0 + (b*S + s) / 32] = 1 where non-zero
   int n;
   int* flags;
   unsigned* amax;                // (or nullptr) [1] max |v| over the grad_out tensors as float bits, raised with atomicMax (zeroed by the caller)
   unsigned* amax_x;              // (or nullptr) the same over the tensors that are not a grad_out (the inputs x; kernel B on the 16-bit pipe)
 };
+// a wave's maximum of range_bits folded into a range word
+__device__ __forceinline__ void raise_from_wave(unsigned* word, unsigned m) {
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) m = max(m, (unsigned)__shfl_xor((int)m, o, 64));
+  if ((threadIdx.x & 63) == 0) orp::range_raise(word, m);
+}
 __global__ void transpose_set_kernel(const TransposeSet T) {
   __shared__ float tile[32][33];
   int i = 0;
@@ -140,7 +146,7 @@ __global__ void transpose_set_kernel(const TransposeSet T) {
     tile[k][tx] = v;
   }
   __syncthreads();
-  const int c0 = T.chunk0[i];
+  const int c0 = T.flag0[i];
   unsigned vmax = 0u;
   for (int k = ty; k < 32; k += 8) {
     const int s = s0 + k, r = r0 + tx;
@@ -158,16 +164,23 @@ __global__ void transpose_set_kernel(const TransposeSet T) {
       if (mine && tx == 0 && s < S) T.flags[c0 + (int)(((long)blockIdx.y * S + s) >> 5)] = 1;
     }
   }
-  if (c0 >= 0 && T.amax) {                                          // (block-uniform) range of grad_out for the fp16-pieces contraction
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) vmax = max(vmax, (unsigned)__shfl_xor((int)vmax, o, 64));
-    if ((threadIdx.x & 63) == 0 && vmax > __atomic_load_n(T.amax, __ATOMIC_RELAXED)) atomicMax(T.amax, vmax);
-  }
-  if (c0 < 0 && T.amax_x) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) vmax = max(vmax, (unsigned)__shfl_xor((int)vmax, o, 64));
-    if ((threadIdx.x & 63) == 0 && vmax > __atomic_load_n(T.amax_x, __ATOMIC_RELAXED)) atomicMax(T.amax_x, vmax);
-  }
+  unsigned* word = c0 >= 0 ? T.amax : T.amax_x;                      // (block-uniform) range of grad_out / of x for the fp16-pieces contractions
+  if (word) raise_from_wave(word, vmax);
+}
+
+// host: begin, append every tensor (at most 2 * MAXL), finish; the launch is dim3(T.t0[T.n], batch) x 256 threads
+void transpose_set_begin(TransposeSet& T, int in_code, int out_code, int* flags, unsigned* amax, unsigned* amax_x) {
+  T.n = 0; T.t0[0] = 0;
+  T.in_code = in_code; T.out_code = out_code;
+  T.flags = flags; T.amax = amax; T.amax_x = amax_x;
+}
+void transpose_set_append(TransposeSet& T, const void* in, void* out, int R, int S, int flag0) {
+  const int i = T.n++;
+  T.in[i] = in; T.out[i] = out; T.R[i] = R; T.S[i] = S; T.flag0[i] = flag0;
+  T.t0[i + 1] = T.t0[i] + ((R + 31) / 32) * ((S + 31) / 32);
+}
+void transpose_set_finish(TransposeSet& T) {                          // unused slots: valid pointers, never selected
+  for (int i = T.n; i < 2 * MAXL; i++) { T.in[i] = T.in[0]; T.out[i] = T.out[0]; T.R[i] = T.S[i] = 0; T.flag0[i] = -1; T.t0[i + 1] = T.t0[T.n]; }
 }
 
 // flags[n] -> ascending list of the set indices, list[n] = count (one workgroup; n is a few thousand)
@@ -207,9 +220,7 @@ __global__ void pack_wT_kernel(const float* __restrict__ w, int taps, float* __r
 __global__ void __launch_bounds__(256) absmax_w_kernel(const float* __restrict__ w, int n, unsigned* __restrict__ out) {
   unsigned m = 0u;
   for (int i = blockIdx.x * blockDim.x + threadIdx.x; i < n; i += gridDim.x * blockDim.x) m = max(m, orp::range_bits(w[i]));
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) m = max(m, (unsigned)__shfl_xor((int)m, o, 64));
-  if ((threadIdx.x & 63) == 0 && m > __atomic_load_n(out, __ATOMIC_RELAXED)) atomicMax(out, m);
+  raise_from_wave(out, m);
 }
 // the power of two that puts a tensor's largest magnitude (float bits `am`) into [2^14, 2^15): fp16 pieces then neither overflow
 // nor lose their low piece to the subnormal range (csrc/orp_range.hpp)
@@ -228,10 +239,10 @@ __global__ void pack_wT16_kernel(const float* __restrict__ w, int taps, const un
     const int ob = r % (CH / 16), tap = r / (CH / 16);
     const int o = ob * 16 + khh * 8 + e;
     const float v = w[((size_t)o * CH + c) * taps + tap] * sc;
-    const _Float16 hi = (_Float16)v;
-    const _Float16 lo = (_Float16)(v - (float)hi);
-    planes[i] = __builtin_bit_cast(uint16_t, hi);
-    planes[total + i] = __builtin_bit_cast(uint16_t, lo);
+    _Float16 hi[1], lo[1];
+    orp::range_split(v, hi, lo, 0);
+    planes[i] = __builtin_bit_cast(uint16_t, hi[0]);
+    planes[total + i] = __builtin_bit_cast(uint16_t, lo[0]);
   }
 }
 
@@ -277,6 +288,13 @@ __device__ inline float sample_mask(const BLevel& L, long p, int tap, int taps, 
   return L.mask[((size_t)b * taps + tap) * HoWo + hw];
 }
 
+// one of the four bilinear corner weights of a sampling point's fractional parts (lh, lw): K = 0 top-left, 1 top-right, 2 bottom-left,
+// 3 bottom-right.  The caller applies the corner's validity and the modulation / range scale.
+template <int K>
+__device__ __forceinline__ float corner(float lh, float lw) {
+  return ((K & 2) ? lh : 1.f - lh) * ((K & 1) ? lw : 1.f - lw);
+}
+
 template <int CTRL, int ROW_MASK>
 __device__ inline float dpp_add(float v) {
   return v + __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(v), CTRL, ROW_MASK, 0xf, false));
@@ -292,7 +310,8 @@ __device__ inline float half_wave_sum(float v) {
 }
 
 // ---- kernel A: grad_input + grad_offset ---------------------------------------------------------------------------
-// One tile = one 32-position chunk (MT = 1: two to three workgroups per CU hide the epilogue's load / atomic latency; two
+// One tile = one 32-position chunk (kChunk), and the kernel has no tile-height parameter: taller tiles were measured and rejected
+// twice (two to three workgroups per CU hide the epilogue's load / atomic latency; two
 // sub-tiles per workgroup measured 5 % slower in round 2, and again in round 3 for the G-row variant: 64 positions per
 // workgroup halve the L2 -> CU weight stream (3.2 GB per launch) but leave one workgroup per CU (140 KB of LDS); even with
 // the x values of a tap's coordinate derivatives loaded one group of rows ahead of their use: 1 356 vs 1 231 us for
@@ -303,22 +322,22 @@ __device__ inline float half_wave_sum(float v) {
 // Round 5, F16: the contraction on the 16-bit matrix pipe, as the forward's (csrc/orp_dcn_split.hip): grad_out and W each as TWO fp16
 // pieces after an exact power-of-two range scaling (|v - (hi + lo)| <= 2^-22 |v|), products lo*hi, hi*lo into a side accumulator and
 // hi*hi into the main one, fp32 accumulation, scaled back once per tap.  48 MFMAs of 32 cycles per tap and wave instead of 128 of 64.
-template <int MT>
-constexpr size_t input_tile_bytes() {
-  return sizeof(float) * 32 * MT * ASTR > (size_t)2 * 2 * 32 * MT * ASTRH ? sizeof(float) * 32 * MT * ASTR : (size_t)2 * 2 * 32 * MT * ASTRH;
+constexpr size_t input_tile_bytes() {     // the grad_out tile: fp32 rows, or two planes of halves
+  return sizeof(float) * kChunk * ASTR > (size_t)2 * 2 * kChunk * ASTRH ? sizeof(float) * kChunk * ASTR : (size_t)2 * 2 * kChunk * ASTRH;
 }
-template <int MT, bool STORE_G, bool F16>
+constexpr size_t input_smem() {
+  return input_tile_bytes() + (sizeof(int4) + sizeof(float4) + 8 * 3 * sizeof(float)) * kChunk * MAXT + sizeof(int) * kChunk;
+}
+template <bool STORE_G, bool F16>
 __global__ void __launch_bounds__(kThreads)
 dcn_bwd_input_kernel(const BwdParams P) {
-  constexpr int BM2 = 32 * MT;
-  static_assert(MT == 1, "the active-chunk list is in units of 32 positions");
   extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
-  float* sG = reinterpret_cast<float*>(smem);                       // [BM2][ASTR] grad_out rows  (F16: two planes [BM2][ASTRH] of halves)
+  float* sG = reinterpret_cast<float*>(smem);                       // [kChunk][ASTR] grad_out rows  (F16: two planes [kChunk][ASTRH] of halves)
   uint16_t* sGh = reinterpret_cast<uint16_t*>(smem);
-  int4* sCi = reinterpret_cast<int4*>(smem + input_tile_bytes<MT>());   // [BM2 * taps]
-  float4* sCl = reinterpret_cast<float4*>(sCi + BM2 * MAXT);        // [BM2 * taps] (lh, lw, modulation, -)
-  float* sGO = reinterpret_cast<float*>(sCl + BM2 * MAXT);          // [8 waves][BM2][taps][3] grad_offset (+ grad_mask) partials
-  int* sNZ = reinterpret_cast<int*>(sGO + 8 * BM2 * MAXT * 3);      // [BM2] row has a non-zero grad_out value
+  int4* sCi = reinterpret_cast<int4*>(smem + input_tile_bytes());   // [kChunk * taps]
+  float4* sCl = reinterpret_cast<float4*>(sCi + kChunk * MAXT);     // [kChunk * taps] (lh, lw, modulation, -)
+  float* sGO = reinterpret_cast<float*>(sCl + kChunk * MAXT);       // [8 waves][kChunk][taps][3] grad_offset (+ grad_mask) partials
+  int* sNZ = reinterpret_cast<int*>(sGO + 8 * kChunk * MAXT * 3);   // [kChunk] row has a non-zero grad_out value
 
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   const int taps = P.kh * P.kw;
@@ -333,9 +352,9 @@ dcn_bwd_input_kernel(const BwdParams P) {
   const BLevel L = P.lv[level_of_tile(P.lv, P.nlev, tile)];
   const int HoWo = L.Ho * L.Wo;
   const long npos = (long)P.B * HoWo;
-  const long p0 = (long)(tile - L.tile0) * BM2;
+  const long p0 = (long)(tile - L.tile0) * kChunk;
 
-  for (int e = tid; e < BM2 * taps; e += kThreads) {
+  for (int e = tid; e < kChunk * taps; e += kThreads) {
     const int m = e / taps, tap = e - m * taps;
     int4 ix = make_int4(-1, -1, -1, -1);
     float2 fr = make_float2(0.f, 0.f);
@@ -343,22 +362,22 @@ dcn_bwd_input_kernel(const BwdParams P) {
     if (p0 + m < npos) { sample_point(P, L, p0 + m, tap, taps, HoWo, ix, fr); mm = sample_mask(L, p0 + m, tap, taps, HoWo); }
     sCi[e] = ix; sCl[e] = make_float4(fr.x, fr.y, mm, 0.f);
   }
-  for (int e = tid; e < 8 * BM2 * MAXT * 3; e += kThreads) sGO[e] = 0.f;
+  for (int e = tid; e < 8 * kChunk * MAXT * 3; e += kThreads) sGO[e] = 0.f;
   float sx = 1.f;                                                   // F16: grad_out scale 2^k, accumulator scale 2^-(k + kw)
   int kxw = 0;
   if (F16) { const int k = orp::range_exp(P.go_amax[0]); sx = orp::range_scale(k); kxw = k + orp::range_exp_of(P.wscale[0]); }
-  for (int r = wave; r < BM2; r += 8) {
+  for (int r = wave; r < kChunk; r += 8) {
     float4 v = make_float4(0.f, 0.f, 0.f, 0.f);
     if (p0 + r < npos) v = *reinterpret_cast<const float4*>(L.go + (size_t)(p0 + r) * CH + lane * 4);
     if (F16) {
       const float sv[4] = {v.x * sx, v.y * sx, v.z * sx, v.w * sx};   // exact (power of two)
       _Float16 h[4], l[4];
 #pragma unroll
-      for (int i = 0; i < 4; i++) { h[i] = (_Float16)sv[i]; l[i] = (_Float16)(sv[i] - (float)h[i]); }
+      for (int i = 0; i < 4; i++) orp::range_split(sv[i], h, l, i);
       const h2 h01 = {h[0], h[1]}, h23 = {h[2], h[3]}, l01 = {l[0], l[1]}, l23 = {l[2], l[3]};
       uint16_t* dst = sGh + (size_t)r * ASTRH + lane * 4;
       *reinterpret_cast<uint2*>(dst) = make_uint2(__builtin_bit_cast(unsigned, h01), __builtin_bit_cast(unsigned, h23));
-      *reinterpret_cast<uint2*>(dst + BM2 * ASTRH) = make_uint2(__builtin_bit_cast(unsigned, l01), __builtin_bit_cast(unsigned, l23));
+      *reinterpret_cast<uint2*>(dst + kChunk * ASTRH) = make_uint2(__builtin_bit_cast(unsigned, l01), __builtin_bit_cast(unsigned, l23));
     } else {
       *reinterpret_cast<float4*>(sG + (size_t)r * ASTR + lane * 4) = v;
     }
@@ -389,9 +408,7 @@ dcn_bwd_input_kernel(const BwdParams P) {
 
 #pragma unroll 1
   for (int tap = 0; tap < taps; tap++) {
-    floatx16 acc[MT], side[MT];                                     // (side: F16 only -- the small partial products)
-#pragma unroll
-    for (int mt = 0; mt < MT; mt++) { acc[mt] = floatx16{0}; side[mt] = floatx16{0}; }
+    floatx16 acc = floatx16{0}, side = floatx16{0};                 // (side: F16 only -- the small partial products)
 #pragma unroll
     for (int j = 0; j < CH / 16; j++) {
       // (16 chunks per tap and WD + 1 ring slots: the slot of chunk (tap, j) is j % (WD + 1), a compile-time index because
@@ -407,50 +424,39 @@ dcn_bwd_input_kernel(const BwdParams P) {
       if (F16) {
         const uint16_t* ar = sGh + (size_t)mrow * ASTRH + j * 16 + 8 * kh;
         const h8 w_hi = __builtin_bit_cast(h8, bq[0]), w_lo = __builtin_bit_cast(h8, bq[1]);
-#pragma unroll
-        for (int mt = 0; mt < MT; mt++) {
-          const h8 g_hi = *reinterpret_cast<const h8*>(ar + (size_t)mt * 32 * ASTRH);
-          const h8 g_lo = *reinterpret_cast<const h8*>(ar + (size_t)mt * 32 * ASTRH + BM2 * ASTRH);
-          if (STORE_G) {                                               // D[channel][position]: lane = position
-            side[mt] = __builtin_amdgcn_mfma_f32_32x32x16_f16(w_lo, g_hi, side[mt], 0, 0, 0);
-            side[mt] = __builtin_amdgcn_mfma_f32_32x32x16_f16(w_hi, g_lo, side[mt], 0, 0, 0);
-            acc[mt] = __builtin_amdgcn_mfma_f32_32x32x16_f16(w_hi, g_hi, acc[mt], 0, 0, 0);
-          } else {                                                     // D[position][channel]: lane = channel
-            side[mt] = __builtin_amdgcn_mfma_f32_32x32x16_f16(g_hi, w_lo, side[mt], 0, 0, 0);
-            side[mt] = __builtin_amdgcn_mfma_f32_32x32x16_f16(g_lo, w_hi, side[mt], 0, 0, 0);
-            acc[mt] = __builtin_amdgcn_mfma_f32_32x32x16_f16(g_hi, w_hi, acc[mt], 0, 0, 0);
-          }
+        const h8 g_hi = *reinterpret_cast<const h8*>(ar);
+        const h8 g_lo = *reinterpret_cast<const h8*>(ar + kChunk * ASTRH);
+        if (STORE_G) {                                                 // D[channel][position]: lane = position
+          side = __builtin_amdgcn_mfma_f32_32x32x16_f16(w_lo, g_hi, side, 0, 0, 0);
+          side = __builtin_amdgcn_mfma_f32_32x32x16_f16(w_hi, g_lo, side, 0, 0, 0);
+          acc = __builtin_amdgcn_mfma_f32_32x32x16_f16(w_hi, g_hi, acc, 0, 0, 0);
+        } else {                                                       // D[position][channel]: lane = channel
+          side = __builtin_amdgcn_mfma_f32_32x32x16_f16(g_hi, w_lo, side, 0, 0, 0);
+          side = __builtin_amdgcn_mfma_f32_32x32x16_f16(g_lo, w_hi, side, 0, 0, 0);
+          acc = __builtin_amdgcn_mfma_f32_32x32x16_f16(g_hi, w_hi, acc, 0, 0, 0);
         }
         continue;
       }
       const float* arow = sG + (size_t)mrow * ASTR + j * 16 + 4 * kh;
 #pragma unroll
       for (int t = 0; t < 2; t++) {
-        float4 a4[MT];
-#pragma unroll
-        for (int mt = 0; mt < MT; mt++) a4[mt] = *reinterpret_cast<const float4*>(arow + (size_t)mt * 32 * ASTR + 8 * t);
+        const float4 a4 = *reinterpret_cast<const float4*>(arow + 8 * t);
 #pragma unroll
         for (int i = 0; i < 4; i++) {
           const float b0 = (i == 0) ? bq[t].x : (i == 1) ? bq[t].y : (i == 2) ? bq[t].z : bq[t].w;
-#pragma unroll
-          for (int mt = 0; mt < MT; mt++) {
-            const float av = (i == 0) ? a4[mt].x : (i == 1) ? a4[mt].y : (i == 2) ? a4[mt].z : a4[mt].w;
-            if (STORE_G)
-              acc[mt] = __builtin_amdgcn_mfma_f32_32x32x2f32(b0, av, acc[mt], 0, 0, 0);     // D[channel][position]: lane = position
-            else
-              acc[mt] = __builtin_amdgcn_mfma_f32_32x32x2f32(av, b0, acc[mt], 0, 0, 0);     // D[position][channel]: lane = channel
-          }
+          const float av = (i == 0) ? a4.x : (i == 1) ? a4.y : (i == 2) ? a4.z : a4.w;
+          if (STORE_G)
+            acc = __builtin_amdgcn_mfma_f32_32x32x2f32(b0, av, acc, 0, 0, 0);     // D[channel][position]: lane = position
+          else
+            acc = __builtin_amdgcn_mfma_f32_32x32x2f32(av, b0, acc, 0, 0, 0);     // D[position][channel]: lane = channel
         }
       }
     }
     // (even / odd k-steps into two independent accumulator tiles: measured 792 vs 791 us, +16 VGPRs -- not taken)
     if (F16) {
+      acc += side;
 #pragma unroll
-      for (int mt = 0; mt < MT; mt++) {
-        acc[mt] += side[mt];
-#pragma unroll
-        for (int r = 0; r < 16; r++) acc[mt][r] = orp::range_unscale(acc[mt][r], kxw);
-      }
+      for (int r = 0; r < 16; r++) acc[r] = orp::range_unscale(acc[r], kxw);
     }
     // ---- consume G_t: scatter into grad_input, coordinate derivatives into the tile's grad_offset ---------------
     if (STORE_G) {
@@ -470,10 +476,10 @@ dcn_bwd_input_kernel(const BwdParams P) {
       // (a) the row G_t[m, :] for kernel A2: 16 channels per lane as four 16-byte stores (the two half-waves interleave
       //     into whole 32-byte sectors; the row's 1 KB is completed by the 8 waves)
       if (row_ok) {
-        float* grow = P.G + ((size_t)((long)tile * BM2 + m) * taps + tap) * CH + wave * 32 + 4 * kh;
+        float* grow = P.G + ((size_t)((long)tile * kChunk + m) * taps + tap) * CH + wave * 32 + 4 * kh;
 #pragma unroll
         for (int q = 0; q < 4; q++)
-          *reinterpret_cast<float4*>(grow + 8 * q) = make_float4(acc[0][4 * q], acc[0][4 * q + 1], acc[0][4 * q + 2], acc[0][4 * q + 3]);
+          *reinterpret_cast<float4*>(grow + 8 * q) = make_float4(acc[4 * q], acc[4 * q + 1], acc[4 * q + 2], acc[4 * q + 3]);
       }
       // (b) the derivative sums
       const bool live = sNZ[m] != 0;                                   // a zero grad_out row gives G = 0: nothing to add
@@ -494,10 +500,10 @@ dcn_bwd_input_kernel(const BwdParams P) {
           float sk = 0.f;
 #pragma unroll
           for (int q = 0; q < 4; q++) {
-            sk = __builtin_fmaf(acc[0][4 * q], v[k][q].x, sk);
-            sk = __builtin_fmaf(acc[0][4 * q + 1], v[k][q].y, sk);
-            sk = __builtin_fmaf(acc[0][4 * q + 2], v[k][q].z, sk);
-            sk = __builtin_fmaf(acc[0][4 * q + 3], v[k][q].w, sk);
+            sk = __builtin_fmaf(acc[4 * q], v[k][q].x, sk);
+            sk = __builtin_fmaf(acc[4 * q + 1], v[k][q].y, sk);
+            sk = __builtin_fmaf(acc[4 * q + 2], v[k][q].z, sk);
+            sk = __builtin_fmaf(acc[4 * q + 3], v[k][q].w, sk);
           }
           S[k] = (live && ixs[k] >= 0) ? sk : 0.f;
         }
@@ -507,99 +513,103 @@ dcn_bwd_input_kernel(const BwdParams P) {
         if (kh == 0) {
           const float4 fr = sCl[e];
           const float lh = fr.x, lw = fr.y, uh = 1.f - lh, uw = 1.f - lw, mm = fr.z;
-          float* slot = sGO + (size_t)(wave * BM2 * MAXT + e) * 3;
+          float* slot = sGO + (size_t)(wave * kChunk * MAXT + e) * 3;
           slot[0] = mm * (uw * (S[2] - S[0]) + lw * (S[3] - S[1]));
           slot[1] = mm * (uh * (S[1] - S[0]) + lh * (S[3] - S[2]));
-          slot[2] = L.gmask ? (uh * uw * S[0] + uh * lw * S[1] + lh * uw * S[2] + lh * lw * S[3]) : 0.f;
+          slot[2] = L.gmask ? (corner<0>(lh, lw) * S[0] + corner<1>(lh, lw) * S[1] + corner<2>(lh, lw) * S[2] +
+                               corner<3>(lh, lw) * S[3]) : 0.f;
         }
       }
       continue;
     }
     // grad_input by atomics (STORE_G = false): lane = channel
-#pragma unroll
-    for (int mt = 0; mt < MT; mt++) {
 #pragma unroll 4
-      for (int r = 0; r < 16; r++) {
-        const int m = mt * 32 + (r & 3) + 8 * (r >> 2) + 4 * kh;
-        const int e = m * taps + tap;
-        const bool live = sNZ[m] != 0;                                // a zero grad_out row gives G = 0: nothing to add
-        if (__ballot(live) == 0) continue;
-        const int4 ix = live ? sCi[e] : make_int4(-1, -1, -1, -1);
-        const float4 fr = sCl[e];
-        const float g = acc[mt][r];
-        const float lh = fr.x, lw = fr.y, uh = 1.f - lh, uw = 1.f - lw, mm = fr.z;
-        const size_t o1 = (size_t)(ix.x < 0 ? 0 : ix.x) * CH + c, o2 = (size_t)(ix.y < 0 ? 0 : ix.y) * CH + c;
-        const size_t o3 = (size_t)(ix.z < 0 ? 0 : ix.z) * CH + c, o4 = (size_t)(ix.w < 0 ? 0 : ix.w) * CH + c;
-        const float v1 = ix.x >= 0 ? L.x[o1] : 0.f, v2 = ix.y >= 0 ? L.x[o2] : 0.f;
-        const float v3 = ix.z >= 0 ? L.x[o3] : 0.f, v4 = ix.w >= 0 ? L.x[o4] : 0.f;
-        const float gm = g * mm;
-        if (ix.x >= 0) atomicAdd(L.gx + o1, uh * uw * gm);
-        if (ix.y >= 0) atomicAdd(L.gx + o2, uh * lw * gm);
-        if (ix.z >= 0) atomicAdd(L.gx + o3, lh * uw * gm);
-        if (ix.w >= 0) atomicAdd(L.gx + o4, lh * lw * gm);
-        float dh = g * mm * (-uw * v1 - lw * v2 + uw * v3 + lw * v4);
-        float dw = g * mm * (-uh * v1 + uh * v2 - lh * v3 + lh * v4);
-        dh = half_wave_sum(dh);
-        dw = half_wave_sum(dw);
-        float dm = 0.f;
-        if (L.gmask) {                                               // DCNv2: d loss / d modulation = G . sampled value
-          dm = g * (uh * uw * v1 + uh * lw * v2 + lh * uw * v3 + lh * lw * v4);
-          dm = half_wave_sum(dm);
-        }
-        // this wave's 32-channel partial of (position, tap): one writer per slot, summed over the waves in order below
-        if (mrow == 31) {
-          float* slot = sGO + (size_t)(wave * BM2 * MAXT + e) * 3;
-          slot[0] = dh; slot[1] = dw; slot[2] = dm;
-        }
+    for (int r = 0; r < 16; r++) {
+      const int m = (r & 3) + 8 * (r >> 2) + 4 * kh;
+      const int e = m * taps + tap;
+      const bool live = sNZ[m] != 0;                                // a zero grad_out row gives G = 0: nothing to add
+      if (__ballot(live) == 0) continue;
+      const int4 ix = live ? sCi[e] : make_int4(-1, -1, -1, -1);
+      const float4 fr = sCl[e];
+      const float g = acc[r];
+      const float lh = fr.x, lw = fr.y, uh = 1.f - lh, uw = 1.f - lw, mm = fr.z;
+      const size_t o1 = (size_t)(ix.x < 0 ? 0 : ix.x) * CH + c, o2 = (size_t)(ix.y < 0 ? 0 : ix.y) * CH + c;
+      const size_t o3 = (size_t)(ix.z < 0 ? 0 : ix.z) * CH + c, o4 = (size_t)(ix.w < 0 ? 0 : ix.w) * CH + c;
+      const float v1 = ix.x >= 0 ? L.x[o1] : 0.f, v2 = ix.y >= 0 ? L.x[o2] : 0.f;
+      const float v3 = ix.z >= 0 ? L.x[o3] : 0.f, v4 = ix.w >= 0 ? L.x[o4] : 0.f;
+      const float gm = g * mm;
+      if (ix.x >= 0) atomicAdd(L.gx + o1, corner<0>(lh, lw) * gm);
+      if (ix.y >= 0) atomicAdd(L.gx + o2, corner<1>(lh, lw) * gm);
+      if (ix.z >= 0) atomicAdd(L.gx + o3, corner<2>(lh, lw) * gm);
+      if (ix.w >= 0) atomicAdd(L.gx + o4, corner<3>(lh, lw) * gm);
+      float dh = g * mm * (-uw * v1 - lw * v2 + uw * v3 + lw * v4);
+      float dw = g * mm * (-uh * v1 + uh * v2 - lh * v3 + lh * v4);
+      dh = half_wave_sum(dh);
+      dw = half_wave_sum(dw);
+      float dm = 0.f;
+      if (L.gmask) {                                               // DCNv2: d loss / d modulation = G . sampled value
+        dm = g * (corner<0>(lh, lw) * v1 + corner<1>(lh, lw) * v2 + corner<2>(lh, lw) * v3 + corner<3>(lh, lw) * v4);
+        dm = half_wave_sum(dm);
+      }
+      // this wave's 32-channel partial of (position, tap): one writer per slot, summed over the waves in order below
+      if (mrow == 31) {
+        float* slot = sGO + (size_t)(wave * kChunk * MAXT + e) * 3;
+        slot[0] = dh; slot[1] = dw; slot[2] = dm;
       }
     }
   }
   __syncthreads();
   // grad_offset [B, 2*taps, Ho, Wo]: plane-major so that consecutive lanes write consecutive positions
-  for (int e2 = tid; e2 < BM2 * taps * 2; e2 += kThreads) {
-    const int plane = e2 / BM2, m = e2 - plane * BM2;
+  for (int e2 = tid; e2 < kChunk * taps * 2; e2 += kThreads) {
+    const int plane = e2 / kChunk, m = e2 - plane * kChunk;
     const long p = p0 + m;
     if (p < npos) {
       const int b = (int)(p / HoWo), hw = (int)(p - (long)b * HoWo);
       const int tap = plane >> 1, comp = plane & 1;
       float v = 0.f;
 #pragma unroll
-      for (int w = 0; w < 8; w++) v += sGO[(size_t)(w * BM2 * MAXT + m * taps + tap) * 3 + comp];   // fixed order: reproducible
+      for (int w = 0; w < 8; w++) v += sGO[(size_t)(w * kChunk * MAXT + m * taps + tap) * 3 + comp];   // fixed order: reproducible
       L.goff[((size_t)b * 2 * taps + plane) * HoWo + hw] = v;
     }
   }
   if (L.gmask) {
-    for (int e2 = tid; e2 < BM2 * taps; e2 += kThreads) {
-      const int tap = e2 / BM2, m = e2 - tap * BM2;
+    for (int e2 = tid; e2 < kChunk * taps; e2 += kThreads) {
+      const int tap = e2 / kChunk, m = e2 - tap * kChunk;
       const long p = p0 + m;
       if (p < npos) {
         const int b = (int)(p / HoWo), hw = (int)(p - (long)b * HoWo);
         float v = 0.f;
 #pragma unroll
-        for (int w = 0; w < 8; w++) v += sGO[(size_t)(w * BM2 * MAXT + m * taps + tap) * 3 + 2];
+        for (int w = 0; w < 8; w++) v += sGO[(size_t)(w * kChunk * MAXT + m * taps + tap) * 3 + 2];
         L.gmask[((size_t)b * taps + tap) * HoWo + hw] = v;
       }
     }
   }
 }
 
-template <int MT>
-size_t input_smem() {
-  return input_tile_bytes<MT>() + (sizeof(int4) + sizeof(float4) + 8 * 3 * sizeof(float)) * 32 * MT * MAXT + sizeof(int) * 32 * MT;
-}
-
 // ---- kernel A2: grad_input without atomics ------------------------------------------------------------------------------
-// region of the pixel with linear index q = (b * H + h) * W + w of level L
-__device__ inline int region_of_pixel(const BLevel& L, int q) {
+// the pixel with linear index q = (b * H + h) * W + w of level L
+struct Pixel { int b, h, w; };
+__device__ __forceinline__ Pixel pixel_at(const BLevel& L, int q) {
   const int w = q % L.W, bh = q / L.W;
-  const int h = bh % L.H, b = bh / L.H;
-  return L.reg0 + (b * L.RH + (h >> 3)) * L.RW + (w >> 3);
+  return {bh / L.H, bh % L.H, w};
 }
-__device__ inline int level_of_chunk(const BwdParams& P, int chunk) {
+__device__ inline int region_of_pixel(const BLevel& L, int q) {
+  const Pixel px = pixel_at(L, q);
+  return L.reg0 + (px.b * L.RH + (px.h >> 3)) * L.RW + (px.w >> 3);
+}
+// region reg of the launch: its level, and its image and place in the image's grid of 8 x 8-pixel regions
+__device__ __forceinline__ int level_of_region(const BwdParams& P, int reg) {
   int lvl = 0;
 #pragma unroll 1
-  for (int i = 1; i < P.nlev; i++) if (chunk >= P.lv[i].chunk0) lvl = i;
+  for (int i = 1; i < P.nlev; i++) if (reg >= P.lv[i].reg0) lvl = i;
   return lvl;
+}
+struct Region { int b, rh, rw; };
+__device__ __forceinline__ Region region_at(const BLevel& L, int reg) {
+  const int rl = reg - L.reg0;
+  const int rw = rl % L.RW, rbh = rl / L.RW;
+  return {rbh / L.RH, rbh % L.RH, rw};
 }
 
 // one thread per (position, tap) sample e = (chunk * 32 + m) * taps + tap: slots 4e .. 4e+3 receive the distinct regions
@@ -613,9 +623,9 @@ __global__ void bin_samples_kernel(const BwdParams P) {
   const int tap = (int)(e - pg * taps);
   const int chunk = (int)(pg >> 5);
   unsigned k[4] = {(unsigned)P.nregions, (unsigned)P.nregions, (unsigned)P.nregions, (unsigned)P.nregions};
-  const BLevel& L = P.lv[level_of_chunk(P, chunk)];
+  const BLevel& L = P.lv[level_of_tile(P.lv, P.nlev, chunk)];
   const int HoWo = L.Ho * L.Wo;
-  const long p = pg - (long)L.chunk0 * 32;
+  const long p = pg - (long)L.tile0 * 32;
   if (P.flags[chunk] == 0) {
     // kernel A skips this chunk: its grad_offset is zero (written here instead of one memset per level)
     if (p < (long)P.B * HoWo) {
@@ -668,32 +678,26 @@ __global__ void build_desc_kernel(const BwdParams P, const unsigned* __restrict_
   if (i >= (long)P.rcount[P.nregions]) return;                       // slots past the last region's list are unused
   const int reg = (int)keys_sorted[i];
   const unsigned e = P.sorted_vals[i];
-  int lvl = 0;
-#pragma unroll 1
-  for (int k = 1; k < P.nlev; k++) if (reg >= P.lv[k].reg0) lvl = k;
-  const BLevel& L = P.lv[lvl];
-  const int rl = reg - L.reg0;
-  const int rw = rl % L.RW, rbh = rl / L.RW;
-  const int rh = rbh % L.RH, rb = rbh / L.RH;
+  const BLevel& L = P.lv[level_of_region(P, reg)];
+  const Region rg = region_at(L, reg);
   const long pg = (long)(e / (unsigned)taps);
   const int tap = (int)(e - (unsigned)pg * (unsigned)taps);
-  const long p = pg - (long)L.chunk0 * 32;                           // the sample belongs to this region's level
+  const long p = pg - (long)L.tile0 * 32;                            // the sample belongs to this region's level
   int4 ix; float2 fr;
   sample_point(P, L, p, tap, taps, L.Ho * L.Wo, ix, fr);
   const float mm = sample_mask(L, p, tap, taps, L.Ho * L.Wo);        // DCNv2: the sample's modulation scales its scatter
-  const float lh = fr.x, lw = fr.y, uh = 1.f - lh, uw = 1.f - lw;
+  const float lh = fr.x, lw = fr.y;
   auto local = [&](int q) {                                          // pixel -> row of this region, 64 = another region's / outside
     if (q < 0) return 64;
-    const int w = q % L.W, bh = q / L.W;
-    const int h = bh % L.H, b = bh / L.H;
-    return (b == rb && (h >> 3) == rh && (w >> 3) == rw) ? ((h & 7) * 8 + (w & 7)) : 64;
+    const Pixel px = pixel_at(L, q);
+    return (px.b == rg.b && (px.h >> 3) == rg.rh && (px.w >> 3) == rg.rw) ? ((px.h & 7) * 8 + (px.w & 7)) : 64;
   };
   const int i0 = local(ix.x), i1 = local(ix.y), i2 = local(ix.z), i3 = local(ix.w);
   SampleDesc d;
   d.row = e; d.pad0 = d.pad1 = d.pad2 = 0;
   d.q[0] = i0 * CH; d.q[1] = i1 * CH; d.q[2] = i2 * CH; d.q[3] = i3 * CH;
-  d.w[0] = i0 < 64 ? uh * uw * mm : 0.f; d.w[1] = i1 < 64 ? uh * lw * mm : 0.f;
-  d.w[2] = i2 < 64 ? lh * uw * mm : 0.f; d.w[3] = i3 < 64 ? lh * lw * mm : 0.f;
+  d.w[0] = i0 < 64 ? corner<0>(lh, lw) * mm : 0.f; d.w[1] = i1 < 64 ? corner<1>(lh, lw) * mm : 0.f;
+  d.w[2] = i2 < 64 ? corner<2>(lh, lw) * mm : 0.f; d.w[3] = i3 < 64 ? corner<3>(lh, lw) * mm : 0.f;
   desc[i] = d;
 }
 
@@ -709,13 +713,8 @@ dcn_bwd_scatter_kernel(const BwdParams P, const SampleDesc* __restrict__ desc) {
     reg = (blockIdx.x & 7) * per + (blockIdx.x >> 3);
     if ((int)(blockIdx.x >> 3) >= per || reg >= P.nregions) return;
   }
-  int lvl = 0;
-#pragma unroll 1
-  for (int i = 1; i < P.nlev; i++) if (reg >= P.lv[i].reg0) lvl = i;
-  const BLevel L = P.lv[lvl];
-  const int rl = reg - L.reg0;
-  const int rw = rl % L.RW, rbh = rl / L.RW;
-  const int rh = rbh % L.RH, rb = rbh / L.RH;
+  const BLevel L = P.lv[level_of_region(P, reg)];
+  const Region rg = region_at(L, reg);
   // Thread c only ever touches acc[.][c], and every wave keeps its own copy of 64 list entries in registers (lane t <->
   // entry s0 + t, handed to the other lanes by v_readlane): no barrier, no atomics, no shared metadata.
   const int c = tid;
@@ -775,8 +774,8 @@ dcn_bwd_scatter_kernel(const BwdParams P, const SampleDesc* __restrict__ desc) {
   }
   // every pixel of the region is written exactly once (zeros included): no memset, no atomics
   for (int l = 0; l < 64; l++) {
-    const int h = rh * 8 + (l >> 3), w = rw * 8 + (l & 7);
-    if (h < L.H && w < L.W) L.gx[((size_t)(rb * L.H + h) * L.W + w) * CH + c] = mine[l * CH];
+    const int h = rg.rh * 8 + (l >> 3), w = rg.rw * 8 + (l & 7);
+    if (h < L.H && w < L.W) L.gx[((size_t)(rg.b * L.H + h) * L.W + w) * CH + c] = mine[l * CH];
   }
 }
 
@@ -797,17 +796,11 @@ dcn_bwd_weight_kernel(const BwdParams P) {
   const int c_begin = blockIdx.x * per;
   const int c_end = (c_begin + per < n_active) ? c_begin + per : n_active;
 
-  auto level_of = [&](int chunk) {
-    int lvl = 0;
-#pragma unroll 1
-    for (int i = 1; i < P.nlev; i++) if (chunk >= P.lv[i].chunk0) lvl = i;
-    return lvl;
-  };
   auto make_coef = [&](int ci, int buf) {                            // threads 0..31; ci indexes the active list
     const int chunk = P.active[ci];
-    const BLevel& L = P.lv[level_of(chunk)];
+    const BLevel& L = P.lv[level_of_tile(P.lv, P.nlev, chunk)];
     const int HoWo = L.Ho * L.Wo;
-    const long p = (long)(chunk - L.chunk0) * 32 + tid;
+    const long p = (long)(chunk - L.tile0) * 32 + tid;
     float4 w = make_float4(0.f, 0.f, 0.f, 0.f);
     int4 ixc = make_int4(0, 0, 0, 0);
     long row = -1;
@@ -815,16 +808,16 @@ dcn_bwd_weight_kernel(const BwdParams P) {
       int4 ix; float2 fr;
       sample_point(P, L, p, tap, taps, HoWo, ix, fr);
       const float mm = sample_mask(L, p, tap, taps, HoWo);           // DCNv2: the column is the modulated sample
-      const float lh = fr.x, lw = fr.y, uh = 1.f - lh, uw = 1.f - lw;
-      w.x = ix.x >= 0 ? uh * uw * mm : 0.f; w.y = ix.y >= 0 ? uh * lw * mm : 0.f;
-      w.z = ix.z >= 0 ? lh * uw * mm : 0.f; w.w = ix.w >= 0 ? lh * lw * mm : 0.f;
+      const float lh = fr.x, lw = fr.y;
+      w.x = ix.x >= 0 ? corner<0>(lh, lw) * mm : 0.f; w.y = ix.y >= 0 ? corner<1>(lh, lw) * mm : 0.f;
+      w.z = ix.z >= 0 ? corner<2>(lh, lw) * mm : 0.f; w.w = ix.w >= 0 ? corner<3>(lh, lw) * mm : 0.f;
       ixc = make_int4(ix.x < 0 ? 0 : ix.x, ix.y < 0 ? 0 : ix.y, ix.z < 0 ? 0 : ix.z, ix.w < 0 ? 0 : ix.w);
       row = p;
     }
     sCw[buf * 32 + tid] = w; sCi[buf * 32 + tid] = ixc; sRow[buf * 32 + tid] = row;
   };
   auto gather_issue = [&](int ci, int buf, int row, float4 (&g)[4], float4& gr) {
-    const BLevel& L = P.lv[level_of(P.active[ci])];
+    const BLevel& L = P.lv[level_of_tile(P.lv, P.nlev, P.active[ci])];
     const int4 ix = sCi[buf * 32 + row];
     const long prow = sRow[buf * 32 + row];
     const float* base = L.x + lane * 4;
@@ -959,11 +952,9 @@ __global__ void __launch_bounds__(256) sample_table_kernel(const BwdParams P, co
   const int tap = (int)(i / per_tap);
   const long e = i - (long)tap * per_tap;
   const int chunk = (int)(e >> 5), m = (int)(e & 31);
-  int lvl = 0;
-  for (int k = 1; k < P.nlev; k++) if (chunk >= P.lv[k].chunk0) lvl = k;
-  const BLevel& L = P.lv[lvl];
+  const BLevel& L = P.lv[level_of_tile(P.lv, P.nlev, chunk)];
   const int HoWo = L.Ho * L.Wo;
-  const long p = (long)(chunk - L.chunk0) * 32 + m;
+  const long p = (long)(chunk - L.tile0) * 32 + m;
   SampleTab t;
   t.ix[0] = t.ix[1] = t.ix[2] = t.ix[3] = 0;
   t.w[0] = t.w[1] = t.w[2] = t.w[3] = 0.f;
@@ -971,9 +962,9 @@ __global__ void __launch_bounds__(256) sample_table_kernel(const BwdParams P, co
     int4 ix; float2 fr;
     sample_point(P, L, p, tap, taps, HoWo, ix, fr);
     const float sx = range_scale(*amax_x);                            // a power of two: scaling the weights scales the column exactly
-    const float lh = fr.x, lw = fr.y, uh = 1.f - lh, uw = 1.f - lw;
-    t.w[0] = ix.x >= 0 ? uh * uw * sx : 0.f; t.w[1] = ix.y >= 0 ? uh * lw * sx : 0.f;
-    t.w[2] = ix.z >= 0 ? lh * uw * sx : 0.f; t.w[3] = ix.w >= 0 ? lh * lw * sx : 0.f;
+    const float lh = fr.x, lw = fr.y;
+    t.w[0] = ix.x >= 0 ? corner<0>(lh, lw) * sx : 0.f; t.w[1] = ix.y >= 0 ? corner<1>(lh, lw) * sx : 0.f;
+    t.w[2] = ix.z >= 0 ? corner<2>(lh, lw) * sx : 0.f; t.w[3] = ix.w >= 0 ? corner<3>(lh, lw) * sx : 0.f;
     const int rb = CH * (int)sizeof(float);                           // (the host checked that every level's rows fit 2^31 bytes)
     t.ix[0] = ix.x < 0 ? 0 : ix.x * rb; t.ix[1] = ix.y < 0 ? 0 : ix.y * rb; t.ix[2] = ix.z < 0 ? 0 : ix.z * rb; t.ix[3] = ix.w < 0 ? 0 : ix.w * rb;
   }
@@ -993,18 +984,15 @@ constexpr size_t kGo16ChunkHalves = (size_t)2 * 4 * CH * 8;       // grad_out pl
 // Rows past a level's end are zero.
 __global__ void __launch_bounds__(256) pack_go16_kernel(const BwdParams P, _Float16* __restrict__ planes) {
   const int chunk = blockIdx.x >> 2, q = blockIdx.x & 3, c = threadIdx.x;
-  int lvl = 0;
-  for (int k = 1; k < P.nlev; k++) if (chunk >= P.lv[k].chunk0) lvl = k;
-  const BLevel& L = P.lv[lvl];
+  const BLevel& L = P.lv[level_of_tile(P.lv, P.nlev, chunk)];
   const long npos = (long)P.B * L.Ho * L.Wo;
-  const long p0 = (long)(chunk - L.chunk0) * 32 + q * 8;
+  const long p0 = (long)(chunk - L.tile0) * 32 + q * 8;
   const float sg = range_scale(*P.go_amax);
   h8 hi, lo;
 #pragma unroll
   for (int e = 0; e < 8; e++) {
     const float v = (p0 + e < npos ? L.go[(size_t)(p0 + e) * CH + c] : 0.f) * sg;
-    hi[e] = (_Float16)v;
-    lo[e] = (_Float16)(v - (float)hi[e]);
+    orp::range_split(v, hi, lo, e);
   }
   _Float16* dst = planes + (size_t)chunk * kGo16ChunkHalves + ((size_t)q * CH + c) * 8;
   *reinterpret_cast<h8*>(dst) = hi;
@@ -1035,15 +1023,9 @@ dcn_bwd_weight16_kernel(const BwdParams P, const SampleTab* __restrict__ tab, co
   typedef float f2 __attribute__((ext_vector_type(2)));
   struct Raw { f2 x[4][4]; };
   struct GRaw { h8 v[2][2]; };
-  auto level_of = [&](int chunk) {
-    int lvl = 0;
-#pragma unroll 1
-    for (int i = 1; i < P.nlev; i++) if (chunk >= P.lv[i].chunk0) lvl = i;
-    return lvl;
-  };
   auto issue_half = [&](int ci, int half, Raw& r) {                   // 2 positions x 4 corners of this thread's channel pair: positions px + 2 half, + 1
     const int chunk = P.active[ci];
-    const BLevel& L = P.lv[level_of(chunk)];
+    const BLevel& L = P.lv[level_of_tile(P.lv, P.nlev, chunk)];
     const SampleTab* t = tap_tab + (size_t)chunk * 32 + 2 * half;
     const __amdgpu_buffer_rsrc_t rs = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(L.x), 0, P.B * L.H * L.W * CH * (int)sizeof(float), 0x00020000);
 #pragma unroll
@@ -1061,9 +1043,7 @@ dcn_bwd_weight16_kernel(const BwdParams P, const SampleTab* __restrict__ tab, co
 #pragma unroll
       for (int cc = 0; cc < 2; cc++) {
         const float sv = __builtin_fmaf(t[e].w[3], x[3][cc], __builtin_fmaf(t[e].w[2], x[2][cc], __builtin_fmaf(t[e].w[1], x[1][cc], t[e].w[0] * x[0][cc])));
-        const _Float16 hi = (_Float16)sv;
-        out[cc][0][e] = hi;
-        out[cc][1][e] = (_Float16)(sv - (float)hi);                   // the residual is exact in fp32
+        orp::range_split(sv, out[cc][0], out[cc][1], e);
       }
     }
   };
@@ -1255,6 +1235,170 @@ int make_plan(const orp_dcn_bwd_level* lv, int nlevels, int batch, int kh, int k
   return ORP_OK;
 }
 
+// "set the kernel's dynamic-LDS limit once per (instantiation, device), then launch" (the pattern of csrc/orp_dcn_half.hip: the
+// function-local tag is a distinct type per KERNEL)
+template <auto KERNEL, typename... Args>
+hipError_t launch_lds(dim3 grid, dim3 block, size_t smem, hipStream_t st, const Args&... args) {
+  struct Tag {};
+  const hipError_t e = orp::set_max_dynamic_lds_once<Tag>(reinterpret_cast<const void*>(KERNEL), smem);
+  if (e != hipSuccess) return e;
+  hipLaunchKernelGGL(KERNEL, grid, block, smem, st, args...);
+  return hipSuccess;
+}
+// kernel A over the XCD slab grid (a multiple of 8 workgroups): store_g = G rows for kernel A2 / atomics, f16 = the contraction
+hipError_t launch_input_kernel(bool store_g, bool f16, const BwdParams& P, hipStream_t st) {
+  const dim3 grid(((P.total_chunks + 7) >> 3) * 8), block(kThreads);
+  if (store_g) return f16 ? launch_lds<dcn_bwd_input_kernel<true, true>>(grid, block, input_smem(), st, P)
+                          : launch_lds<dcn_bwd_input_kernel<true, false>>(grid, block, input_smem(), st, P);
+  return f16 ? launch_lds<dcn_bwd_input_kernel<false, true>>(grid, block, input_smem(), st, P)
+             : launch_lds<dcn_bwd_input_kernel<false, false>>(grid, block, input_smem(), st, P);
+}
+
+// One call of the entry point: the plan, the kernels' parameter block and what its three steps share.
+struct Call {
+  Plan pl;
+  BwdParams P;
+  TransposeSet TI, TO;             // x, grad_out -> the NHWC workspace; grad_input -> the caller's NCHW
+  const orp_dcn_bwd_level* levels;
+  char* ws;
+  int* flags;
+  unsigned* scale_words;           // [0] max |grad_out|, [1] max |W|, [2] the weights' scale, [3] max |x|
+  int taps;
+  bool f16, w16;                   // kernel A / kernel B on the 16-bit matrix pipe
+  hipStream_t st;
+
+  // the parameter block and the two transposition sets (the plan is made, the workspace is large enough)
+  int set_up(const float* const* masks_host, float* const* grad_masks_host, int io_dtype, int need_input_grads) {
+    P.wT = reinterpret_cast<float*>(ws + pl.wT_off);
+    P.wT16 = reinterpret_cast<const uint16_t*>(ws + pl.wT_off);     // (the fp32 layout and the two fp16 planes have the same size)
+    P.w16_plane = (size_t)CH * CH * taps;
+    P.wscale = reinterpret_cast<const float*>(scale_words + 2);
+    P.go_amax = scale_words;
+    P.partial = reinterpret_cast<float*>(ws + pl.partial_off);
+    P.nsplit = pl.nsplit; P.total_chunks = pl.total_chunks;
+    P.active = reinterpret_cast<int*>(ws + pl.list_off);
+    P.G = nullptr; P.flags = nullptr; P.nregions = 0; P.keys = nullptr; P.vals = nullptr; P.rcount = nullptr; P.sorted_vals = nullptr;
+    // x / grad_out arrive in the I/O type and the workspace is fp32; grad_input leaves in the I/O type
+    transpose_set_begin(TI, io_dtype, 0, flags, (f16 || w16) ? scale_words : nullptr, w16 ? scale_words + 3 : nullptr);
+    transpose_set_begin(TO, 0, io_dtype, flags, nullptr, nullptr);
+    int chunks = 0;
+    for (int i = 0; i < P.nlev; i++) {
+      const orp_dcn_bwd_level& lv = levels[i];
+      if (!lv.input || !lv.offset || !lv.grad_output) return ORP_EINVAL;
+      if (need_input_grads && (!lv.grad_input || !lv.grad_offset)) return ORP_EINVAL;
+      BLevel& D = P.lv[i];
+      D.H = lv.height; D.W = lv.width; D.Ho = pl.Ho[i]; D.Wo = pl.Wo[i];
+      D.x = reinterpret_cast<float*>(ws + pl.x_off[i]);
+      D.go = reinterpret_cast<float*>(ws + pl.go_off[i]);
+      D.gx = reinterpret_cast<float*>(ws + pl.gx_off[i]);
+      D.off = lv.offset; D.goff = lv.grad_offset;
+      D.mask = masks_host ? masks_host[i] : nullptr;
+      D.gmask = (masks_host && grad_masks_host && need_input_grads) ? grad_masks_host[i] : nullptr;
+      if (masks_host && !D.mask) return ORP_EINVAL;
+      if (masks_host && need_input_grads && !D.gmask) return ORP_EINVAL;
+      D.tile0 = chunks;
+      D.reg0 = pl.reg0[i]; D.RH = pl.RH[i]; D.RW = pl.RW[i];
+      chunks += (int)(((long)P.B * D.Ho * D.Wo + kChunk - 1) / kChunk);
+      const int HW = lv.height * lv.width;
+      transpose_set_append(TI, lv.input, const_cast<float*>(D.x), CH, HW, -1);
+      transpose_set_append(TI, lv.grad_output, const_cast<float*>(D.go), CH, D.Ho * D.Wo, D.tile0);
+      transpose_set_append(TO, D.gx, lv.grad_input, HW, CH, -1);
+    }
+    pad_level_slots(P.lv, P.nlev);
+    for (int i = P.nlev; i < MAXL; i++) P.lv[i].reg0 = 0x7fffffff;
+    transpose_set_finish(TI);
+    transpose_set_finish(TO);
+    return ORP_OK;
+  }
+
+  // grad_input, grad_offset (and grad_mask): the weights packed for kernel A, the scatter route's pre-pass (atomics: the fills; regions:
+  // bin, sort, bounds), kernel A, the route's post-pass (regions: descriptors, scatter), grad_input back to NCHW
+  int input_grads(const float* weight, bool use_atomics) {
+    hipError_t e;
+    if (f16) {
+      hipLaunchKernelGGL(absmax_w_kernel, dim3(256), dim3(256), 0, st, weight, CH * CH * taps, scale_words + 1);
+      hipLaunchKernelGGL(pack_wT16_kernel, dim3(1024), dim3(256), 0, st, weight, taps, scale_words + 1, const_cast<uint16_t*>(P.wT16),
+                         reinterpret_cast<float*>(scale_words + 2));
+    } else {
+      hipLaunchKernelGGL(pack_wT_kernel, dim3(1024), dim3(256), 0, st, weight, taps, const_cast<float*>(P.wT));
+    }
+    P.flags = flags;
+    P.nregions = pl.nregions;
+    P.keys = reinterpret_cast<unsigned*>(ws + pl.keys_in_off);
+    P.vals = reinterpret_cast<unsigned*>(ws + pl.vals_in_off);
+    P.rcount = reinterpret_cast<int*>(ws + pl.rcount_off);
+    unsigned* keys_sorted = reinterpret_cast<unsigned*>(ws + pl.keys_out_off);
+    unsigned* vals_sorted = reinterpret_cast<unsigned*>(ws + pl.vals_out_off);
+    P.sorted_vals = vals_sorted;
+    const dim3 slot_grid((unsigned)((pl.nslots + 255) / 256));
+    if (use_atomics) {
+      P.G = nullptr;
+      e = orp::fill_async(ws + pl.gx_begin, 0, pl.gx_bytes, st);
+      if (e != hipSuccess) return (int)e;
+      for (int i = 0; i < P.nlev; i++) {                             // grad_offset of the chunks that are skipped is zero
+        e = orp::fill_async(levels[i].grad_offset, 0, sizeof(float) * (size_t)P.B * 2 * taps * pl.Ho[i] * pl.Wo[i], st);
+        if (e != hipSuccess) return (int)e;
+        if (P.lv[i].gmask) e = orp::fill_async(P.lv[i].gmask, 0, sizeof(float) * (size_t)P.B * taps * pl.Ho[i] * pl.Wo[i], st);
+        if (e != hipSuccess) return (int)e;
+      }
+    } else {
+      P.G = reinterpret_cast<float*>(ws + pl.G_off);
+      // (region, sample) slots -> stable sort by region: every region's list in ascending sample order
+      orp_prof_begin(ORP_PROF_DCN_BWD_SCATTER, st);          // pre-passes + scatter kernel (ends behind the scatter launch)
+      hipLaunchKernelGGL(bin_samples_kernel, dim3((unsigned)((pl.nslots / 4 + 255) / 256)), dim3(256), 0, st, P);
+      size_t cub_bytes = pl.cub_bytes;
+      e = hipcub::DeviceRadixSort::SortPairs(ws + pl.cub_off, cub_bytes, P.keys, keys_sorted, P.vals, vals_sorted, (int)pl.nslots, 0,
+                                             pl.key_bits, st);
+      if (e != hipSuccess) return (int)e;
+      hipLaunchKernelGGL(region_bounds_kernel, slot_grid, dim3(256), 0, st, keys_sorted, pl.nslots, pl.nregions, P.rcount);
+      orp_prof_end(ORP_PROF_DCN_BWD_SCATTER, st);            // (paused around the GEMM kernel, which has its own slot)
+    }
+    {
+      OrpProfScope prof_in(ORP_PROF_DCN_BWD_INPUT, st);
+      e = launch_input_kernel(!use_atomics, f16, P, st);
+      if (e != hipSuccess) return (int)e;
+    }
+    if (!use_atomics) {
+      orp_prof_begin(ORP_PROF_DCN_BWD_SCATTER, st);
+      const SampleDesc* desc = reinterpret_cast<SampleDesc*>(ws + pl.desc_off);
+      hipLaunchKernelGGL(build_desc_kernel, slot_grid, dim3(256), 0, st, P, keys_sorted, const_cast<SampleDesc*>(desc));
+      e = launch_lds<dcn_bwd_scatter_kernel>(dim3(((pl.nregions + 7) >> 3) * 8), dim3(kScatterThreads), scatter_smem(), st, P, desc);
+      if (e != hipSuccess) return (int)e;
+      orp_prof_end(ORP_PROF_DCN_BWD_SCATTER, st);
+    }
+    e = hipGetLastError();
+    if (e != hipSuccess) return (int)e;
+    hipLaunchKernelGGL(transpose_set_kernel, dim3(TO.t0[TO.n], P.B), dim3(256), 0, st, TO);
+    return (int)hipGetLastError();
+  }
+
+  // grad_weight: the splits' partial sums (on the 16-bit pipe behind its two pre-passes, or exact fp32), added in fixed order
+  int weight_grad(float* grad_weight) {
+    hipError_t e;
+    OrpProfScope prof_w(ORP_PROF_DCN_BWD_WEIGHT, st);
+    int ns_w = pl.nsplit;
+    if (w16) {
+      // the sampling table lives where kernel A left the G rows for A2 (both are done with them by now, in stream order)
+      // and the two fp16 pieces of grad_out behind it (taps >= 2: both fit into the G rows' space)
+      SampleTab* tab = reinterpret_cast<SampleTab*>(ws + pl.G_off);
+      const long nsamp = (long)pl.total_chunks * 32 * taps;
+      _Float16* go16 = reinterpret_cast<_Float16*>(ws + pl.G_off + align256(sizeof(SampleTab) * (size_t)nsamp));
+      const unsigned* amax_x = scale_words + 3;
+      ns_w = pl.nsplit >= 2 ? pl.nsplit / 2 : 1;                     // two workgroups (column halves) per (split, tap)
+      hipLaunchKernelGGL(sample_table_kernel, dim3((unsigned)((nsamp + 255) / 256)), dim3(256), 0, st, P, amax_x, tab);
+      hipLaunchKernelGGL(pack_go16_kernel, dim3((unsigned)pl.total_chunks * 4), dim3(256), 0, st, P, go16);
+      e = launch_lds<dcn_bwd_weight16_kernel>(dim3(ns_w, taps, CH / CX16), dim3(kThreads), weight16_smem(), st, P,
+                                              static_cast<const SampleTab*>(tab), static_cast<const _Float16*>(go16), amax_x, ns_w);
+    } else {
+      e = launch_lds<dcn_bwd_weight_kernel>(dim3(pl.nsplit, taps), dim3(kThreads), weight_smem(), st, P);
+    }
+    if (e == hipSuccess) e = hipGetLastError();
+    if (e != hipSuccess) return (int)e;
+    hipLaunchKernelGGL(reduce_partial_kernel, dim3(1024), dim3(256), 0, st, P.partial, ns_w, taps, grad_weight);
+    return (int)hipGetLastError();
+  }
+};
+
 }  // namespace
 
 extern "C" {
@@ -1290,194 +1434,38 @@ int orp_dcn_backward_multi_ex(const orp_dcn_bwd_level* levels_host, const float*
   if (!orp_dcn_backward_mfma_ok(c_in, c_out, kh, kw, 1, 1)) return ORP_EINVAL;
   if (io_dtype < 0 || io_dtype > 2 || (need_input_grads && masks_host && !grad_masks_host)) return ORP_EINVAL;
   if (!grad_weight && !need_input_grads) return ORP_OK;
-  hipStream_t st = (hipStream_t)stream;
-  Plan pl;
+  Call c;
+  Plan& pl = c.pl;
   int rc = make_plan(levels_host, nlevels, batch, kh, kw, stride_h, stride_w, pad_h, pad_w, dil_h, dil_w, device_cus(), pl);
   if (rc != ORP_OK) return rc;
   if (workspace_bytes < pl.total) return ORP_EWORKSPACE;
-  char* ws = reinterpret_cast<char*>(workspace);
-  const int taps = kh * kw;
-
-  constexpr int MT = 1;
-  BwdParams P;
-  P.nlev = nlevels; P.B = batch;
-  P.kh = kh; P.kw = kw; P.sh = stride_h; P.sw = stride_w; P.ph = pad_h; P.pw = pad_w; P.dh = dil_h; P.dw = dil_w;
-  P.wT = reinterpret_cast<float*>(ws + pl.wT_off);
-  P.partial = reinterpret_cast<float*>(ws + pl.partial_off);
-  P.nsplit = pl.nsplit; P.total_chunks = pl.total_chunks;
-  P.G = nullptr; P.flags = nullptr; P.nregions = 0; P.keys = nullptr; P.vals = nullptr; P.rcount = nullptr; P.sorted_vals = nullptr;
-  int* flags = reinterpret_cast<int*>(ws + pl.flags_off);
-  P.active = reinterpret_cast<int*>(ws + pl.list_off);
-  TransposeSet TI, TO;
-  int ti = 0, tiles = 0, chunks = 0, tin = 0, tout = 0;
-  for (int i = 0; i < nlevels; i++) {
-    const orp_dcn_bwd_level& lv = levels_host[i];
-    if (!lv.input || !lv.offset || !lv.grad_output) return ORP_EINVAL;
-    if (need_input_grads && (!lv.grad_input || !lv.grad_offset)) return ORP_EINVAL;
-    BLevel& D = P.lv[i];
-    D.H = lv.height; D.W = lv.width; D.Ho = pl.Ho[i]; D.Wo = pl.Wo[i];
-    D.x = reinterpret_cast<float*>(ws + pl.x_off[i]);
-    D.go = reinterpret_cast<float*>(ws + pl.go_off[i]);
-    D.gx = reinterpret_cast<float*>(ws + pl.gx_off[i]);
-    D.off = lv.offset; D.goff = lv.grad_offset;
-    D.mask = masks_host ? masks_host[i] : nullptr;
-    D.gmask = (masks_host && grad_masks_host && need_input_grads) ? grad_masks_host[i] : nullptr;
-    if (masks_host && !D.mask) return ORP_EINVAL;
-    if (masks_host && need_input_grads && !D.gmask) return ORP_EINVAL;
-    D.tile0 = tiles; D.chunk0 = chunks;
-    D.reg0 = pl.reg0[i]; D.RH = pl.RH[i]; D.RW = pl.RW[i];
-    const long npos = (long)batch * D.Ho * D.Wo;
-    tiles += (int)((npos + 32 * MT - 1) / (32 * MT));
-    chunks += (int)((npos + 31) / 32);
-    const int HW = lv.height * lv.width, HoWo = D.Ho * D.Wo;
-    TI.in[ti] = lv.input; TI.out[ti] = const_cast<float*>(D.x); TI.R[ti] = CH; TI.S[ti] = HW; TI.t0[ti] = tin;
-    TI.chunk0[ti] = -1;
-    tin += ((HW + 31) / 32) * (CH / 32); ti++;
-    TI.in[ti] = lv.grad_output; TI.out[ti] = const_cast<float*>(D.go); TI.R[ti] = CH; TI.S[ti] = HoWo; TI.t0[ti] = tin;
-    TI.chunk0[ti] = D.chunk0;
-    tin += ((HoWo + 31) / 32) * (CH / 32); ti++;
-    TO.in[i] = D.gx; TO.out[i] = lv.grad_input; TO.R[i] = HW; TO.S[i] = CH; TO.t0[i] = tout; TO.chunk0[i] = -1;
-    tout += ((HW + 31) / 32) * (CH / 32);
-  }
-  for (int i = nlevels; i < MAXL; i++) { P.lv[i] = P.lv[0]; P.lv[i].tile0 = 0x7fffffff; P.lv[i].chunk0 = 0x7fffffff; P.lv[i].reg0 = 0x7fffffff; }
-  TI.n = ti; TO.n = nlevels;
-  for (int i = ti; i <= 2 * MAXL; i++) TI.t0[i] = tin;
-  for (int i = nlevels; i <= 2 * MAXL; i++) TO.t0[i] = tout;
-  for (int i = ti; i < 2 * MAXL; i++) { TI.in[i] = TI.in[0]; TI.out[i] = TI.out[0]; TI.R[i] = TI.S[i] = 0; TI.chunk0[i] = -1; }
-  for (int i = nlevels; i < 2 * MAXL; i++) { TO.in[i] = TO.in[0]; TO.out[i] = TO.out[0]; TO.R[i] = TO.S[i] = 0; TO.chunk0[i] = -1; }
-  TI.flags = flags; TO.flags = flags;
+  c.levels = levels_host; c.taps = kh * kw; c.st = (hipStream_t)stream;
+  c.ws = reinterpret_cast<char*>(workspace);
+  c.flags = reinterpret_cast<int*>(c.ws + pl.flags_off);
+  c.scale_words = reinterpret_cast<unsigned*>(c.ws + pl.scale_off);
   // the contraction of kernel A: 1 (default) = fp16 pieces on the 16-bit matrix pipe, 0 = exact fp32 (v_mfma_f32_32x32x2_f32)
   static const int split_mode = getenv("ORP_DCN_BWD_SPLIT") ? atoi(getenv("ORP_DCN_BWD_SPLIT")) : 1;
-  const bool f16 = split_mode != 0 && need_input_grads;
+  c.f16 = split_mode != 0 && need_input_grads;
   // ... of kernel B: 1 (default) = fp16 pieces as well (DCNv1: the sampled columns are bounded by max |x|), 0 / DCNv2 = exact fp32
   static const int w16_env = getenv("ORP_DCN_BWD_W16") ? atoi(getenv("ORP_DCN_BWD_W16")) : 1;        // dev aid (A/B timing)
-  bool w16 = split_mode != 0 && w16_env != 0 && grad_weight && !masks_host && taps >= 2 && (long)pl.total_chunks * 32768 < (1L << 31);
-  for (int i = 0; i < nlevels; i++) w16 = w16 && (long)batch * levels_host[i].height * levels_host[i].width * CH * 4 < (1L << 31);   // 32-bit buffer offsets
-  unsigned* scale_words = reinterpret_cast<unsigned*>(ws + pl.scale_off);    // [0] max |grad_out|, [1] max |W|, [2] the weights' scale, [3] max |x|
-  TI.amax = (f16 || w16) ? scale_words : nullptr; TO.amax = nullptr;
-  TI.amax_x = w16 ? scale_words + 3 : nullptr; TO.amax_x = nullptr;
-  P.wT16 = reinterpret_cast<const uint16_t*>(ws + pl.wT_off);      // (the fp32 layout and the two fp16 planes have the same size)
-  P.w16_plane = (size_t)CH * CH * taps;
-  P.wscale = reinterpret_cast<const float*>(scale_words + 2);
-  P.go_amax = scale_words;
-  TI.in_code = io_dtype; TI.out_code = 0;                   // x / grad_out arrive in the I/O type, the workspace is fp32
-  TO.in_code = 0; TO.out_code = io_dtype;                   // grad_input leaves in the I/O type
+  c.w16 = split_mode != 0 && w16_env != 0 && grad_weight && !masks_host && c.taps >= 2 && (long)pl.total_chunks * 32768 < (1L << 31);
+  for (int i = 0; i < nlevels; i++) c.w16 = c.w16 && (long)batch * levels_host[i].height * levels_host[i].width * CH * 4 < (1L << 31);   // 32-bit buffer offsets
+  BwdParams& P = c.P;
+  P.nlev = nlevels; P.B = batch;
+  P.kh = kh; P.kw = kw; P.sh = stride_h; P.sw = stride_w; P.ph = pad_h; P.pw = pad_w; P.dh = dil_h; P.dw = dil_w;
+  rc = c.set_up(masks_host, grad_masks_host, io_dtype, need_input_grads);
+  if (rc != ORP_OK) return rc;
 
-  OrpProfScope prof(ORP_PROF_DCN_BWD, st);
-  hipError_t e = orp::fill_async(flags, 0, pl.scale_off + 256 - pl.flags_off, st);      // flags + range words
+  OrpProfScope prof(ORP_PROF_DCN_BWD, c.st);
+  hipError_t e = orp::fill_async(c.flags, 0, pl.scale_off + 256 - pl.flags_off, c.st);      // flags + range words
   if (e != hipSuccess) return (int)e;
-  hipLaunchKernelGGL(transpose_set_kernel, dim3(tin, batch), dim3(256), 0, st, TI);
-  hipLaunchKernelGGL(compact_flags_kernel, dim3(1), dim3(1024), 0, st, flags, pl.total_chunks, const_cast<int*>(P.active));
+  hipLaunchKernelGGL(transpose_set_kernel, dim3(c.TI.t0[c.TI.n], batch), dim3(256), 0, c.st, c.TI);
+  hipLaunchKernelGGL(compact_flags_kernel, dim3(1), dim3(1024), 0, c.st, c.flags, pl.total_chunks, const_cast<int*>(P.active));
   e = hipGetLastError();
   if (e != hipSuccess) return (int)e;
-
-  if (need_input_grads) {
-    static const int force = getenv("ORP_DCN_BWD_ATOMIC") ? atoi(getenv("ORP_DCN_BWD_ATOMIC")) : -1;   // dev aid: 1 / 0 force a path
-    const bool use_atomics = force >= 0 ? force != 0 : (need_input_grads & ORP_DCN_BWD_SPARSE) != 0;
-    if (f16) {
-      hipLaunchKernelGGL(absmax_w_kernel, dim3(256), dim3(256), 0, st, weight, CH * CH * taps, scale_words + 1);
-      hipLaunchKernelGGL(pack_wT16_kernel, dim3(1024), dim3(256), 0, st, weight, taps, scale_words + 1, const_cast<uint16_t*>(P.wT16),
-                         reinterpret_cast<float*>(scale_words + 2));
-    } else {
-      hipLaunchKernelGGL(pack_wT_kernel, dim3(1024), dim3(256), 0, st, weight, taps, const_cast<float*>(P.wT));
-    }
-    const int per = (tiles + 7) >> 3;
-    P.flags = flags;
-    P.nregions = pl.nregions;
-    P.keys = reinterpret_cast<unsigned*>(ws + pl.keys_in_off);
-    P.vals = reinterpret_cast<unsigned*>(ws + pl.vals_in_off);
-    P.rcount = reinterpret_cast<int*>(ws + pl.rcount_off);
-    P.sorted_vals = reinterpret_cast<unsigned*>(ws + pl.vals_out_off);
-    if (use_atomics) {
-      P.G = nullptr;
-      e = orp::fill_async(ws + pl.gx_begin, 0, pl.gx_bytes, st);
-      if (e != hipSuccess) return (int)e;
-      for (int i = 0; i < nlevels; i++) {                            // grad_offset of the chunks that are skipped is zero
-        e = orp::fill_async(levels_host[i].grad_offset, 0, sizeof(float) * (size_t)batch * 2 * taps * pl.Ho[i] * pl.Wo[i], st);
-        if (e != hipSuccess) return (int)e;
-        if (P.lv[i].gmask) {
-          e = orp::fill_async(P.lv[i].gmask, 0, sizeof(float) * (size_t)batch * taps * pl.Ho[i] * pl.Wo[i], st);
-          if (e != hipSuccess) return (int)e;
-        }
-      }
-      struct T1 { int unused; };
-      struct T1h { int unused; };
-      e = f16 ? orp::set_max_dynamic_lds_once<T1h>(reinterpret_cast<const void*>(&dcn_bwd_input_kernel<MT, false, true>), input_smem<MT>())
-              : orp::set_max_dynamic_lds_once<T1>(reinterpret_cast<const void*>(&dcn_bwd_input_kernel<MT, false, false>), input_smem<MT>());
-      if (e != hipSuccess) return (int)e;
-      OrpProfScope prof_in(ORP_PROF_DCN_BWD_INPUT, st);
-      if (f16) hipLaunchKernelGGL((dcn_bwd_input_kernel<MT, false, true>), dim3(per * 8), dim3(kThreads), input_smem<MT>(), st, P);
-      else hipLaunchKernelGGL((dcn_bwd_input_kernel<MT, false, false>), dim3(per * 8), dim3(kThreads), input_smem<MT>(), st, P);
-    } else {
-      P.G = reinterpret_cast<float*>(ws + pl.G_off);
-      // (region, sample) slots -> stable sort by region: every region's list in ascending sample order
-      const long E = pl.nslots / 4;
-      orp_prof_begin(ORP_PROF_DCN_BWD_SCATTER, st);          // pre-passes + scatter kernel (ends behind the scatter launch)
-      hipLaunchKernelGGL(bin_samples_kernel, dim3((unsigned)((E + 255) / 256)), dim3(256), 0, st, P);
-      size_t cub_bytes = pl.cub_bytes;
-      e = hipcub::DeviceRadixSort::SortPairs(ws + pl.cub_off, cub_bytes, P.keys, reinterpret_cast<unsigned*>(ws + pl.keys_out_off),
-                                             P.vals, reinterpret_cast<unsigned*>(ws + pl.vals_out_off), (int)pl.nslots, 0,
-                                             pl.key_bits, st);
-      if (e != hipSuccess) return (int)e;
-      hipLaunchKernelGGL(region_bounds_kernel, dim3((unsigned)((pl.nslots + 255) / 256)), dim3(256), 0, st,
-                         reinterpret_cast<const unsigned*>(ws + pl.keys_out_off), pl.nslots, pl.nregions, P.rcount);
-      struct T2 { int unused; };
-      struct T2h { int unused; };
-      e = f16 ? orp::set_max_dynamic_lds_once<T2h>(reinterpret_cast<const void*>(&dcn_bwd_input_kernel<MT, true, true>), input_smem<MT>())
-              : orp::set_max_dynamic_lds_once<T2>(reinterpret_cast<const void*>(&dcn_bwd_input_kernel<MT, true, false>), input_smem<MT>());
-      if (e != hipSuccess) return (int)e;
-      orp_prof_end(ORP_PROF_DCN_BWD_SCATTER, st);            // (paused around the GEMM kernel, which has its own slot)
-      {
-        OrpProfScope prof_in(ORP_PROF_DCN_BWD_INPUT, st);
-        if (f16) hipLaunchKernelGGL((dcn_bwd_input_kernel<MT, true, true>), dim3(per * 8), dim3(kThreads), input_smem<MT>(), st, P);
-        else hipLaunchKernelGGL((dcn_bwd_input_kernel<MT, true, false>), dim3(per * 8), dim3(kThreads), input_smem<MT>(), st, P);
-      }
-      orp_prof_begin(ORP_PROF_DCN_BWD_SCATTER, st);
-      struct T3 { int unused; };
-      e = orp::set_max_dynamic_lds_once<T3>(reinterpret_cast<const void*>(&dcn_bwd_scatter_kernel), scatter_smem());
-      if (e != hipSuccess) return (int)e;
-      const int rper = (pl.nregions + 7) >> 3;
-      SampleDesc* desc = reinterpret_cast<SampleDesc*>(ws + pl.desc_off);
-      hipLaunchKernelGGL(build_desc_kernel, dim3((unsigned)((pl.nslots + 255) / 256)), dim3(256), 0, st, P,
-                         reinterpret_cast<const unsigned*>(ws + pl.keys_out_off), desc);
-      hipLaunchKernelGGL(dcn_bwd_scatter_kernel, dim3(rper * 8), dim3(kScatterThreads), scatter_smem(), st, P, desc);
-      orp_prof_end(ORP_PROF_DCN_BWD_SCATTER, st);
-    }
-    e = hipGetLastError();
-    if (e != hipSuccess) return (int)e;
-    hipLaunchKernelGGL(transpose_set_kernel, dim3(tout, batch), dim3(256), 0, st, TO);
-    e = hipGetLastError();
-    if (e != hipSuccess) return (int)e;
-  }
-  if (grad_weight) {
-    struct TW { int unused; };
-    e = orp::set_max_dynamic_lds_once<TW>(reinterpret_cast<const void*>(&dcn_bwd_weight_kernel), weight_smem());
-    if (e != hipSuccess) return (int)e;
-    OrpProfScope prof_w(ORP_PROF_DCN_BWD_WEIGHT, st);
-    int ns_w = pl.nsplit;
-    if (w16) {
-      struct TW16 { int unused; };
-      e = orp::set_max_dynamic_lds_once<TW16>(reinterpret_cast<const void*>(&dcn_bwd_weight16_kernel), weight16_smem());
-      if (e != hipSuccess) return (int)e;
-      // the sampling table lives where kernel A left the G rows for A2 (both are done with them by now, in stream order)
-      // and the two fp16 pieces of grad_out behind it (taps >= 2: both fit into the G rows' space)
-      SampleTab* tab = reinterpret_cast<SampleTab*>(ws + pl.G_off);
-      const long nsamp = (long)pl.total_chunks * 32 * taps;
-      _Float16* go16 = reinterpret_cast<_Float16*>(ws + pl.G_off + align256(sizeof(SampleTab) * (size_t)nsamp));
-      ns_w = pl.nsplit >= 2 ? pl.nsplit / 2 : 1;                       // two workgroups (column halves) per (split, tap)
-      hipLaunchKernelGGL(sample_table_kernel, dim3((unsigned)((nsamp + 255) / 256)), dim3(256), 0, st, P, scale_words + 3, tab);
-      hipLaunchKernelGGL(pack_go16_kernel, dim3((unsigned)pl.total_chunks * 4), dim3(256), 0, st, P, go16);
-      hipLaunchKernelGGL(dcn_bwd_weight16_kernel, dim3(ns_w, taps, CH / CX16), dim3(kThreads), weight16_smem(), st, P, tab, go16, scale_words + 3, ns_w);
-    } else {
-      hipLaunchKernelGGL(dcn_bwd_weight_kernel, dim3(pl.nsplit, taps), dim3(kThreads), weight_smem(), st, P);
-    }
-    e = hipGetLastError();
-    if (e != hipSuccess) return (int)e;
-    hipLaunchKernelGGL(reduce_partial_kernel, dim3(1024), dim3(256), 0, st, P.partial, ns_w, taps, grad_weight);
-    e = hipGetLastError();
-    if (e != hipSuccess) return (int)e;
-  }
-  return ORP_OK;
+  if (need_input_grads) rc = c.input_grads(weight, (need_input_grads & ORP_DCN_BWD_SPARSE) != 0);
+  if (rc == ORP_OK && grad_weight) rc = c.weight_grad(grad_weight);
+  return rc;
 }
 
 }  // extern "C"

@@ -141,7 +141,7 @@ absmax_kernel(const AbsMaxArgs A, unsigned* __restrict__ out) {
   __syncthreads();
   if (threadIdx.x == 0) {                                  // (the atomic only where it would change the value: one address)
     const unsigned mx = max(max(red[0], red[1]), max(red[2], red[3]));
-    if (mx > __atomic_load_n(out + A.slot[t], __ATOMIC_RELAXED)) atomicMax(out + A.slot[t], mx);
+    orp::range_raise(out + A.slot[t], mx);
   }
 }
 
@@ -160,10 +160,10 @@ __global__ void pack_planes16_kernel(const float* __restrict__ w, int cout, int 
     const int cblk = (int)(r % (cin / 16)), tap = (int)(r / (cin / 16));
     const int c = cblk * 16 + kg * 8 + e;
     const float v = w[((long)o * cin + c) * taps + tap] * sc;
-    const _Float16 hi = (_Float16)v;
-    const _Float16 lo = (_Float16)(v - (float)hi);
-    planes[i] = __builtin_bit_cast(uint16_t, hi);
-    planes[total + i] = __builtin_bit_cast(uint16_t, lo);
+    _Float16 hi[1], lo[1];
+    orp::range_split(v, hi, lo, 0);
+    planes[i] = __builtin_bit_cast(uint16_t, hi[0]);
+    planes[total + i] = __builtin_bit_cast(uint16_t, lo[0]);
   }
 }
 
@@ -492,11 +492,7 @@ dcn_fwd_split_kernel(const FwdS P, int total_tiles) {
     if (F16) {
       _Float16 h[4], l[4];
 #pragma unroll
-      for (int i = 0; i < 4; i++) {
-        const float sv = s[i] * sx;                                             // exact (power of two)
-        h[i] = (_Float16)sv;                                                    // round to nearest
-        l[i] = (_Float16)(sv - (float)h[i]);                                    // the residual is exact in fp32
-      }
+      for (int i = 0; i < 4; i++) orp::range_split(s[i] * sx, h, l, i);         // (the scaling is exact: a power of two)
       const h2 h01 = {h[0], h[1]}, h23 = {h[2], h[3]}, l01 = {l[0], l[1]}, l23 = {l[2], l[3]};
       *reinterpret_cast<uint2*>(dst) = make_uint2(__builtin_bit_cast(unsigned, h01), __builtin_bit_cast(unsigned, h23));
       *reinterpret_cast<uint2*>(dst + PLANE) = make_uint2(__builtin_bit_cast(unsigned, l01), __builtin_bit_cast(unsigned, l23));

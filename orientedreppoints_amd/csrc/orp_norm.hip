@@ -411,7 +411,7 @@ fpn_topdown_nhwc_kernel(const GnParams P, const TdLevels T) {
     __shared__ unsigned redm[4];
     const unsigned mx = block_max(m, redm);
     // one address, thousands of workgroups: the atomic only where it would raise the value (see to_channels_last_kernel)
-    if (threadIdx.x == 0 && mx > __atomic_load_n(T.amax, __ATOMIC_RELAXED)) atomicMax(T.amax, mx);
+    if (threadIdx.x == 0) orp::range_raise(T.amax, mx);
   }
 }
 

@@ -17,6 +17,7 @@
 //   range_unscale     acc x 2^-(kx + kw) as one ldexp: one rounding, exact wherever the result is a normal float, and no
 //                     intermediate 1 / (2^kx 2^kw) that overflows to Inf (-> 0) when kx + kw > 127.  For operands inside the
 //                     old clamp its bits are those of the power-of-two multiply it replaces.
+//   range_split, range_raise   (device only) see below
 #pragma once
 #include <stdint.h>
 #include <string.h>
@@ -66,5 +67,22 @@ ORP_RANGE_FN float range_scale(int k) { return range_bits_float((unsigned)(127 +
 ORP_RANGE_FN int range_exp_of(float scale) { return (int)((range_float_bits(scale) >> 23) & 0xffu) - 127; }
 
 ORP_RANGE_FN float range_unscale(float acc, int k) { return ldexpf(acc, -k); }
+
+#if defined(__HIPCC__)
+// device only (the host test has no fp16 type and no atomics)
+//   range_split       the two pieces of an ALREADY SCALED value into element e of two arrays or vectors of halves: hi = the nearest
+//                     fp16, lo = the residual (exact in fp32), rounded
+//   range_raise       fold `bits` (a max of range_bits) into a range word: the atomic only where it would change the value (thousands
+//                     of workgroups, one address -- a contended atomicMax per workgroup serialises in the L2)
+template <typename H, typename L>
+__device__ __forceinline__ void range_split(float sv, H& hi, L& lo, int e) {
+  const _Float16 h = (_Float16)sv;
+  hi[e] = h;
+  lo[e] = (_Float16)(sv - (float)h);
+}
+__device__ __forceinline__ void range_raise(unsigned* word, unsigned bits) {
+  if (bits > __atomic_load_n(word, __ATOMIC_RELAXED)) atomicMax(word, bits);
+}
+#endif
 
 }  // namespace orp
