@@ -597,6 +597,24 @@ int orp_conv1x1_pack_weight(const float* weight, int c_out, int c_in, float* pac
 int orp_conv1x1_multi(const orp_bias_level* levels_host, int nlevels, int batch, int c_in, int c_out,
                       const float* weight_packed, const float* bias, const float* sub, int relu, void* stream);
 
+/* orp_conv1x1_bn_act: a ResNet bottleneck's 1x1 / stride 1 convolution with what follows it in the epilogue (inference):
+ *   y = relu?( fma(conv1x1(x, w), scale[c], shift[c]) (+ r) ), r = nothing (residual NULL) | residual | fma(residual, scale2[c],
+ *   shift2[c]) rounded to fp32 (scale2 / shift2 not NULL: the downsample branch's raw output, as orp_affine2_act takes it).
+ *   x [B,Cin,hw], residual / y [B,Cout,hw] NCHW fp32, y a tensor of its own; weight_t: the [Cout,Cin] weight stored [Cin][Cout],
+ *   16-byte aligned.  Exact fp32 MFMA, one accumulator per output fed in ascending k (bitwise reproducible, independent of the
+ *   tiling); the epilogue gives the bits of orp_affine_act / orp_affine2_act on the raw convolution output.
+ *   orp_conv1x1_bn_act_ok: 64 <= Cin <= 2048, Cin % 32 == 0, 64 <= Cout <= 4096, Cout % 32 == 0; anything else is ORP_EINVAL.
+ *   orp_conv1x1_bn_act_pays: 1 where this launch was MEASURED faster than library convolution + pass on MI355X (the routing rule
+ *   of mmdet_ops/fused_norm.py:conv1x1_bn_act; docs/notebook/round12.md has the table), else 0. */
+int orp_conv1x1_bn_act_ok(int c_in, int c_out);
+int orp_conv1x1_bn_act_pays(int c_in, int c_out, int hw, int batch, int has_residual);
+/* the workgroup tile (output channels x positions: 128 x 128, 64 x 128 or 64 x 64) a launch of this shape runs with; returns 0 and
+ * writes nothing where the shape is not supported */
+int orp_conv1x1_bn_act_tile(int c_in, int c_out, int hw, int batch, int* tile_channels, int* tile_positions);
+int orp_conv1x1_bn_act(const float* x, const float* weight_t, const float* scale, const float* shift, const float* residual,
+                       const float* scale2, const float* shift2, float* y, int batch, int c_in, int c_out, int hw, int relu,
+                       void* stream);
+
 /* orp_conv3x3_small_multi: 3x3 / stride 1 / pad 1 convolution (no bias) of the SMALL FPN levels -- the 32^2 / 16^2 / 8^2
  *   maps the head's seven 256->256 convolutions (orientedreppoints_head.py:91-132) also visit -- all levels in ONE
  *   launch: exact-fp32 MFMA implicit GEMM reading and writing NCHW [B,C,H,W] fp32 (input != output).  weight_packed: the

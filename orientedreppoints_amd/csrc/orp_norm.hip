@@ -31,6 +31,7 @@
 #include <stdlib.h>
 
 #include "../../include/orp_hip.h"
+#include "orp_affine.hpp"
 #include "orp_launch.hpp"
 #include "orp_range.hpp"
 
@@ -120,21 +121,7 @@ __device__ __forceinline__ float2 gn_coef(float mean, float rstd, float gamma_c,
   const float a = rstd * gamma_c;
   return make_float2(a, beta_c - mean * a);
 }
-__device__ __forceinline__ void relu4(float4& t) { t.x = fmaxf(t.x, 0.f); t.y = fmaxf(t.y, 0.f); t.z = fmaxf(t.z, 0.f); t.w = fmaxf(t.w, 0.f); }
-__device__ __forceinline__ float affine_act(float x, float a, float b, int relu) {
-  float t = x * a + b;
-  if (relu) t = fmaxf(t, 0.f);
-  return t;
-}
-// one coefficient pair (a, b) per component
-__device__ __forceinline__ void affine_act4(float4& t, float2 k0, float2 k1, float2 k2, float2 k3, int relu) {
-  t.x = t.x * k0.x + k0.y; t.y = t.y * k1.x + k1.y; t.z = t.z * k2.x + k2.y; t.w = t.w * k3.x + k3.y;
-  if (relu) relu4(t);
-}
-__device__ __forceinline__ void affine_act4(float4& t, float a, float b, int relu) {
-  const float2 k = make_float2(a, b);
-  affine_act4(t, k, k, k, k, relu);
-}
+// (relu4, affine_act, affine_act4: orp_affine.hpp, shared with the fused 1x1 convolution's epilogue)
 
 // A chunk of n <= 4096 floats held in registers, 16 per thread: as float4s (vec: n % 4 == 0 and src 16-byte aligned) thread t holds
 // elements 4 (t + 256 q) .. + 3, else elements t + 256 q; 0 past the end.  Returns the thread's sum.
@@ -438,10 +425,7 @@ affine_act_kernel(const float* __restrict__ x, const float* __restrict__ res, co
     }
   } else {
     for (int i = blockIdx.x * blockDim.x + threadIdx.x; i < hw; i += gridDim.x * blockDim.x) {
-      float t = x[base + i] * a + b;
-      if (res) t += res[base + i];
-      if (relu) t = fmaxf(t, 0.f);
-      y[base + i] = t;
+      y[base + i] = res ? affine_res_act(x[base + i], a, b, res[base + i], relu) : affine_act(x[base + i], a, b, relu);
     }
   }
 }
@@ -474,11 +458,7 @@ affine2_act_kernel(const float* __restrict__ x, const float* __restrict__ res, c
     }
   } else {
     for (int i = blockIdx.x * blockDim.x + threadIdx.x; i < hw; i += gridDim.x * blockDim.x) {
-      float t = x[base + i] * a + b;
-      float r = res[base + i] * a2 + b2;
-      t += r;
-      if (relu) t = fmaxf(t, 0.f);
-      y[base + i] = t;
+      y[base + i] = affine_res_act(x[base + i], a, b, affine_act(res[base + i], a2, b2, 0), relu);
     }
   }
 }

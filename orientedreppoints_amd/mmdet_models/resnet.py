@@ -63,19 +63,37 @@ class Bottleneck(nn.Module):
         return bool(on) and isinstance(ds, nn.Sequential) and len(ds) == 2 and isinstance(ds[0], nn.Conv2d) and \
             isinstance(ds[1], nn.BatchNorm2d) and not ds[1].training
 
+    def _conv1x1_fusable(self):
+        """conv1 / conv3 may run with their BatchNorm (+ residual) + ReLU in the convolution's epilogue where that was measured
+        faster (`fuse_conv1x1` attribute, or ORP_BN_CONV1X1_FUSE=0 for A/B timing); the shapes are decided by
+        `conv1x1_bn_act` (`orp_conv1x1_bn_act_pays`)"""
+        from .. import switches
+        on = getattr(self, 'fuse_conv1x1', None)
+        if on is None:
+            on = switches.BN_CONV1X1_FUSE
+        return bool(on)
+
     def _forward_fused(self, x):
-        from ..mmdet_ops.fused_norm import bn_act
-        out = bn_act(self.conv1(x).contiguous(), self.bn1, relu=True)
+        from ..mmdet_ops.fused_norm import bn_act, conv1x1_bn_act
+        fuse = self._conv1x1_fusable()
+
+        def conv_bn_act(t, conv, bn, **kw):
+            # conv1 / conv3: where the fused kernel pays, the raw convolution output is never written; everywhere else (and with
+            # the switch off) the library's convolution and the pass.  conv2 and the downsample convolution stay on the library.
+            if fuse:
+                return conv1x1_bn_act(t, conv, bn, **kw)
+            return bn_act(conv(t).contiguous(), bn, **kw)
+        out = conv_bn_act(x, self.conv1, self.bn1, relu=True)
         out = bn_act(self.conv2(out).contiguous(), self.bn2, relu=True)
-        out = self.conv3(out).contiguous()
         if self._downsample_norm_fusable():
             # the downsample BatchNorm rides in the block's last pass: no read-modify-write pass of its own over the identity
-            return bn_act(out, self.bn3, residual=self.downsample[0](x).contiguous(), residual_bn=self.downsample[1], relu=True)
+            return conv_bn_act(out, self.conv3, self.bn3, residual=self.downsample[0](x).contiguous(),
+                               residual_bn=self.downsample[1], relu=True)
         if self.downsample is not None:
             identity = bn_act(self.downsample[0](x).contiguous(), self.downsample[1], relu=False)
         else:
             identity = x.contiguous()
-        return bn_act(out, self.bn3, residual=identity, relu=True)
+        return conv_bn_act(out, self.conv3, self.bn3, residual=identity, relu=True)
 
     def forward(self, x):
         if self._fused_ok(x):

@@ -188,6 +188,65 @@ def bn_act(x, bn, residual=None, relu=True, residual_bn=None):
     return x
 
 
+_packed_1x1_t = _packcache.new_cache("conv1x1_bn_weight")
+
+
+def _transposed_1x1_weight(weight):
+    """[Cout,Cin,1,1] -> the [Cin][Cout] layout orp_conv1x1_bn_act reads, cached on the live parameter (inference only), keyed
+    by the tensor's storage / version state."""
+    w = weight.detach()
+    state = _packcache.tensor_state(w)
+    hit = _packed_1x1_t.get(weight, state)
+    if hit is None:
+        hit = _packed_1x1_t.put(weight, state, w.float().reshape(w.size(0), w.size(1)).t().contiguous())
+    return _lib.keep_for_graph(hit)
+
+
+def conv1x1_bn_act_ok(x, conv, bn):
+    """conv is a bias-free 1x1 / stride 1 / groups 1 nn.Conv2d of a shape `orp_conv1x1_bn_act` takes, bn an eval-mode
+    BatchNorm2d, x an fp32 CUDA [B,Cin,H,W] tensor"""
+    w = conv.weight
+    return bool(isinstance(conv, torch.nn.Conv2d) and isinstance(bn, torch.nn.BatchNorm2d) and not bn.training and
+                x.is_cuda and x.dtype == torch.float32 and x.dim() == 4 and w.dtype == torch.float32 and w.dim() == 4 and
+                w.size(2) == 1 and w.size(3) == 1 and x.size(1) == w.size(1) and conv.bias is None and
+                tuple(conv.stride) == (1, 1) and tuple(conv.padding) == (0, 0) and tuple(conv.dilation) == (1, 1) and
+                conv.groups == 1 and x.size(2) * x.size(3) > 0 and _lib.lib().orp_conv1x1_bn_act_ok(w.size(1), w.size(0)))
+
+
+def conv1x1_bn_act(x, conv, bn, residual=None, residual_bn=None, relu=True, force=False):
+    """relu?(BatchNorm_eval(conv(x)) (+ residual)) for a bottleneck's 1x1 convolution, as a new contiguous tensor.  Where
+    `orp_conv1x1_bn_act_pays` says the fused launch was measured faster (or force=True, at any supported shape) the BatchNorm,
+    the residual (residual_bn: the residual is a RAW convolution output and this eval-mode BatchNorm is applied to it, as in
+    `bn_act`) and the ReLU run in the epilogue of the exact-fp32 MFMA kernel `orp_conv1x1_bn_act`; everywhere else this is
+    `bn_act(conv(x).contiguous(), ...)`: the library's convolution and the pass.  Inference only."""
+    if residual_bn is not None and residual is None:
+        raise ValueError("conv1x1_bn_act: residual_bn without a residual")
+    L = _lib.lib()
+    fused = conv1x1_bn_act_ok(x, conv, bn) and (residual_bn is None or not residual_bn.training)
+    if fused and not force:
+        fused = bool(L.orp_conv1x1_bn_act_pays(x.size(1), conv.weight.size(0), x.size(2) * x.size(3), x.size(0),
+                                                1 if residual is not None else 0))
+    if not fused:
+        return bn_act(conv(x).contiguous(), bn, residual=residual, relu=relu, residual_bn=residual_bn)
+    x = x.detach().contiguous()
+    B, cin, H, W = x.shape
+    cout = conv.weight.size(0)
+    if residual is not None:
+        residual = residual.detach()
+        if not (tuple(residual.shape) == (B, cout, H, W) and residual.is_contiguous() and residual.dtype == torch.float32):
+            raise ValueError("conv1x1_bn_act: residual must be a contiguous fp32 tensor of the output's shape")
+    wt = _transposed_1x1_weight(conv.weight)
+    scale, shift = _bn_affine(bn)
+    scale2, shift2 = _bn_affine(residual_bn) if residual_bn is not None else (None, None)
+    y = torch.empty((B, cout, H, W), dtype=torch.float32, device=x.device)
+    with torch.cuda.device(x.device):
+        rc = L.orp_conv1x1_bn_act(_lib.ptr(x), _lib.ptr(wt), _lib.ptr(scale), _lib.ptr(shift), _lib.ptr(residual),
+                                  _lib.ptr(scale2), _lib.ptr(shift2), _lib.ptr(y), B, cin, cout, H * W, 1 if relu else 0,
+                                  _lib.stream_of(x))
+    _lib.check(rc, "orp_conv1x1_bn_act")
+    return y
+
+
 def bn_relu_maxpool(x, bn):
     """max_pool2d(relu(BatchNorm_eval(x)), kernel 3, stride 2, padding 1) as ONE kernel (`orp_affine_relu_maxpool`, the ResNet
     stem): x [B,C,H,W] fp32 CUDA, contiguous, left as it is; returns a new [B,C,(H-1)//2+1,(W-1)//2+1] tensor."""
