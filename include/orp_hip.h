@@ -460,6 +460,11 @@ int orp_poly_nms_f64_batched(const double* dets, int n_total, const int32_t* seg
  * new == src the output is orp_scene_tiles' bit for bit.  Table indices outside the patch are clamped into it.
  * pad_w % 4 == 0 (float32) or pad_w % 8 == 0 (16-bit types), else ORP_EINVAL; num_tiles <= 65535.
  *
+ * orp_scene_tiles_flip / orp_scene_tiles_resized_flip: the same arguments, rules and error cases, with the test pipeline's
+ * horizontal RandomFlip between the resize and the normalisation (Resize -> RandomFlip -> Normalize -> Pad): out[.., y, x] =
+ * plain[.., y, new_w - 1 - x] for x < new_w (new_w = tile for the native form), zeros beyond new_w / new_h as in the plain
+ * form.  Bit-identical to mirroring the plain kernel's output over those new_w columns.
+ *
  * orp_scene_collect: packed [num_tiles, max_rows + 1, 28] f32 = the per-tile results of the static post-processing (rows of
  * 18 point coordinates, 8 corners, score, label; last row = count, overflow flag) -> dets [capacity_rows,9] DOUBLE:
  * x = ((double)x + left) / rate, y = ((double)y + up) / rate (poly2origpoly, ResultMerge_multi_process.py:175-180, on the
@@ -475,6 +480,14 @@ int orp_scene_tiles_resized(const uint8_t* scene, int height, int width, long lo
                             int num_tiles, int src_w, int src_h, int new_w, int new_h, int pad_w, int pad_h, const int32_t* x_i0,
                             const float* x_w1, const int32_t* y_i0, const float* y_w1, const float* mean_host,
                             const float* std_host, int to_rgb, int out_dtype, void* out, void* stream);
+int orp_scene_tiles_flip(const uint8_t* scene, int height, int width, long long row_stride_bytes, const int32_t* origins,
+                         int num_tiles, int tile, const float* mean_host, const float* std_host, int to_rgb, int out_dtype,
+                         void* out, void* stream);
+int orp_scene_tiles_resized_flip(const uint8_t* scene, int height, int width, long long row_stride_bytes, const int32_t* origins,
+                                 int num_tiles, int src_w, int src_h, int new_w, int new_h, int pad_w, int pad_h,
+                                 const int32_t* x_i0, const float* x_w1, const int32_t* y_i0, const float* y_w1,
+                                 const float* mean_host, const float* std_host, int to_rgb, int out_dtype, void* out,
+                                 void* stream);
 size_t orp_scene_collect_workspace_bytes(int num_tiles, int num_classes);
 int orp_scene_collect(const float* packed, int num_tiles, int max_rows, const int32_t* origins, double rate, int num_classes,
                       int capacity_rows, double* dets, int32_t* seg_offsets, int32_t* src, int32_t* flag, void* workspace,
@@ -749,7 +762,34 @@ int orp_conv_wgrad_split(const orp_wgrad_level* levels_host, int nlevels, int ba
  *   orp_pp_pack   : keep / num_keep from orp_rnms_batched -> packed [max_out + 1, 28] fp32: rows = [reppoints(18) |
  *     corners(8) | score | label] in the reference's output order (ascending index, or the max_out highest scores in
  *     descending order when more survive); last row = (count, overflow, 0...).
+ *   orp_pp_compact_views: orp_pp_compact for the union of up to 8 views of one image (test-time augmentation:
+ *     orientedreppoints_detector.py:49-144, merge_aug_results + one multiclass_rnms).  views_host [num_views] describes
+ *     every view: sig_all [num_classes, n], cand [m0], boxes [m0,8], reppoints [m0,18] (device pointers), m0, n, flip,
+ *     img_width (of the view's img_shape) and scale (its scale_factor).  Every view's corners and rep-points are mapped back
+ *     to the original image -- the flip first, on the x coordinates only, then the rescale -- and written, view-major, to
+ *     boxes_all [sum m0, 8] / reppoints_all [sum m0, 18]: the row order of torch.cat over the views.  The arithmetic is what
+ *     merge_aug_results computes on device tensors with a host-scalar scale_factor (a Python float or numpy.float32), bit
+ *     for bit, every operation rounded on its own:
+ *         flip     x' = (float(img_width) - x) - 1.0f
+ *         rescale  v' = v * float(1.0 / (double)scale)
+ *     PyTorch's GPU division of a tensor by a HOST scalar is a multiplication by the reciprocal, formed in fp64 and rounded
+ *     to fp32 once; it is not the IEEE quotient that dividing by a 0-dim DEVICE tensor gives (the single-view rescale=True
+ *     path), and the two differ in the last bit where the reciprocal is inexact (scale 0.9375, 1333/1024, ...).
+ *     Then every (view, candidate, class) triple with score > score_thr is emitted, view-major, then candidate, then class,
+ *     exactly as orp_pp_compact emits pairs: dets [capacity,9] with max_coordinate taken over the emitted pairs' MAPPED
+ *     boxes of all views, sel_cand = row of the concatenation, sel_label, seg2, total.  orp_rnms_batched and orp_pp_pack
+ *     (with boxes_all / reppoints_all) follow unchanged.  Two launches and a 4-byte fill for all views; stream-ordered, no
+ *     host synchronisation, capturable.  One view with flip = 0 and scale = 1 gives orp_pp_compact's outputs bit for bit.
+ *     num_views in [1, 8] else ORP_EINVAL; scratch: orp_pp_compact_views_scratch_bytes(sum m0) bytes of device memory.
  * ------------------------------------------------------------------------------------------------------- */
+typedef struct {
+  const float* sig_all;
+  const int64_t* cand;
+  const float* boxes;
+  const float* reppoints;
+  int m0, n, flip, img_width;
+  double scale;
+} orp_pp_view;
 size_t orp_pp_select_scratch_bytes(int n, int nms_pre, int nlevels);
 int orp_pp_select(const float* sig_all, int num_classes, int n, const int* level_offsets_host, int nlevels, int nms_pre,
                   int64_t* cand, void* scratch, size_t scratch_bytes, void* stream);
@@ -760,6 +800,10 @@ size_t orp_pp_compact_scratch_bytes(int m0);
 int orp_pp_compact(const float* sig_all, const int64_t* cand, int m0, int n, int num_classes, const float* boxes,
                    float score_thr, int capacity, float* dets, int32_t* sel_cand, int32_t* sel_label, int32_t* seg2,
                    int32_t* total, void* scratch, size_t scratch_bytes, void* stream);
+size_t orp_pp_compact_views_scratch_bytes(int total_m0);
+int orp_pp_compact_views(const orp_pp_view* views_host, int num_views, int num_classes, float score_thr, int capacity,
+                         float* boxes_all, float* reppoints_all, float* dets, int32_t* sel_cand, int32_t* sel_label,
+                         int32_t* seg2, int32_t* total, void* scratch, size_t scratch_bytes, void* stream);
 int orp_pp_pack(const int64_t* keep, const int32_t* num_keep, const float* dets, const int32_t* sel_cand,
                 const int32_t* sel_label, const float* boxes, const float* reppoints, const int32_t* total, int capacity,
                 int max_out, float* packed, void* stream);

@@ -93,6 +93,9 @@ _SIGNATURES = {
     "orp_scene_tiles": (_i, [_vp, _i, _i, ctypes.c_longlong, _vp, _i, _i, _vp, _vp, _i, _i, _vp, _vp]),
     "orp_scene_tiles_resized": (_i, [_vp, _i, _i, ctypes.c_longlong, _vp, _i, _i, _i, _i, _i, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp, _i,
                                      _i, _vp, _vp]),
+    "orp_scene_tiles_flip": (_i, [_vp, _i, _i, ctypes.c_longlong, _vp, _i, _i, _vp, _vp, _i, _i, _vp, _vp]),
+    "orp_scene_tiles_resized_flip": (_i, [_vp, _i, _i, ctypes.c_longlong, _vp, _i, _i, _i, _i, _i, _i, _i, _vp, _vp, _vp, _vp, _vp,
+                                          _vp, _i, _i, _vp, _vp]),
     "orp_scene_collect_workspace_bytes": (_sz, [_i, _i]),
     "orp_scene_collect": (_i, [_vp, _i, _i, _vp, ctypes.c_double, _i, _i, _vp, _vp, _vp, _vp, _vp, _sz, _vp]),
     "orp_soft_rnms_host": (_i, [_vp, _i, _f, _i, _f, _f, _vp, _vp]),
@@ -109,6 +112,8 @@ _SIGNATURES = {
     "orp_pp_gather": (_i, [_vp, _vp, _i, _i, _vp, _vp, _vp, _i, _vp, _vp, _vp, _vp, _vp]),
     "orp_pp_compact_scratch_bytes": (_sz, [_i]),
     "orp_pp_compact": (_i, [_vp, _vp, _i, _i, _i, _vp, _f, _i, _vp, _vp, _vp, _vp, _vp, _vp, _sz, _vp]),
+    "orp_pp_compact_views_scratch_bytes": (_sz, [_i]),
+    "orp_pp_compact_views": (_i, [_vp, _i, _i, _f, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _sz, _vp]),
     "orp_pp_pack": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _vp, _vp]),
     "orp_groupnorm_workspace_bytes": (_sz, [_vp, _i, _i, _i, _i]),
     "orp_groupnorm_act_multi": (_i, [_vp, _i, _i, _i, _i, _vp, _vp, _f, _i, _vp, _sz, _vp]),

@@ -62,6 +62,30 @@ __device__ __forceinline__ float ord2f(unsigned u) { return __uint_as_float((u &
 // max_coordinate -- and with it every class offset -- exactly as in the reference (bbox_nms.py:156-158)
 __device__ __forceinline__ float max_nan(float a, float b) { return (a != a || b != b) ? __uint_as_float(0x7fc00000u) : fmaxf(a, b); }
 
+// every detection row starts as padding (score -inf: sorts last, never evaluated); the compaction kernel behind the flags
+// kernel overwrites the first `count` rows -- filling 8 K rows is parallel work, not something for its single workgroup
+__device__ __forceinline__ void fill_padding(int first, int step, int cap, float* __restrict__ dets,
+                                             int32_t* __restrict__ sel_cand, int32_t* __restrict__ sel_label) {
+  for (int r = first; r < cap; r += step) {
+#pragma unroll
+    for (int k = 0; k < 8; k++) dets[(size_t)r * 9 + k] = 0.f;
+    dets[(size_t)r * 9 + 8] = -INFINITY;
+    sel_cand[r] = 0; sel_label[r] = 0;
+  }
+}
+
+// the 256-thread block's NaN-propagating maximum into *max_ord: one atomicMax per workgroup
+__device__ __forceinline__ void block_max_to(float mx, float* red, unsigned* __restrict__ max_ord) {
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) mx = max_nan(mx, __shfl_xor(mx, o, 64));
+  if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = mx;
+  __syncthreads();
+  if (threadIdx.x == 0) {
+    mx = max_nan(max_nan(red[0], red[1]), max_nan(red[2], red[3]));
+    if (mx > -INFINITY || mx != mx) atomicMax(max_ord, f2ord(mx));      // +NaN maps above +inf in the ordered space
+  }
+}
+
 // ---- detections, step 1 (parallel): per candidate the bit set of classes above the threshold, and the max coordinate of
 // the boxes that own at least one detection (bboxes.max() of the expanded set) through one atomicMax per workgroup
 __global__ void __launch_bounds__(256)
@@ -70,14 +94,7 @@ pp_flags_kernel(const float* __restrict__ sig_all, const int64_t* __restrict__ c
                 int cap, float* __restrict__ dets, int32_t* __restrict__ sel_cand, int32_t* __restrict__ sel_label) {
   __shared__ float red[4];
   const int j = blockIdx.x * blockDim.x + threadIdx.x;
-  // every detection row starts as padding (score -inf: sorts last, never evaluated); the compaction kernel behind this
-  // one overwrites the first `count` rows -- filling 8 K rows is parallel work, not something for its single workgroup
-  for (int r = j; r < cap; r += gridDim.x * blockDim.x) {
-#pragma unroll
-    for (int k = 0; k < 8; k++) dets[(size_t)r * 9 + k] = 0.f;
-    dets[(size_t)r * 9 + 8] = -INFINITY;
-    sel_cand[r] = 0; sel_label[r] = 0;
-  }
+  fill_padding(j, gridDim.x * blockDim.x, cap, dets, sel_cand, sel_label);
   float mx = -INFINITY;
   if (j < m0) {
     const int g = (int)cand[j];
@@ -89,14 +106,7 @@ pp_flags_kernel(const float* __restrict__ sig_all, const int64_t* __restrict__ c
       for (int k = 0; k < 8; k++) mx = max_nan(mx, boxes[(size_t)j * 8 + k]);
     }
   }
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) mx = max_nan(mx, __shfl_xor(mx, o, 64));
-  if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = mx;
-  __syncthreads();
-  if (threadIdx.x == 0) {
-    mx = max_nan(max_nan(red[0], red[1]), max_nan(red[2], red[3]));
-    if (mx > -INFINITY || mx != mx) atomicMax(max_ord, f2ord(mx));      // +NaN maps above +inf in the ordered space
-  }
+  block_max_to(mx, red, max_ord);
 }
 
 // inclusive scan over the workgroup (wave shuffles + one LDS hop): returns the EXCLUSIVE prefix, *total = block sum
@@ -116,12 +126,14 @@ __device__ __forceinline__ int block_excl_scan(int v, int* wsum, int* total) {
 }
 
 // ---- detections, step 2 (one workgroup): ordered compaction, row-major over (candidate, class), with the class-offset
-// coordinates.  dets rows >= count get score -inf (they sort last and are never evaluated).
-__global__ void __launch_bounds__(kScanThreads)
-pp_compact_kernel(const float* __restrict__ sig_all, const int64_t* __restrict__ cand, int m0, int n,
-                  const unsigned* __restrict__ bits, const unsigned* __restrict__ max_ord,
-                  const float* __restrict__ boxes, int cap, float* __restrict__ dets, int32_t* __restrict__ sel_cand,
-                  int32_t* __restrict__ sel_label, int32_t* __restrict__ seg, int32_t* __restrict__ total_out, int fill_here) {
+// coordinates.  dets rows >= count get score -inf (they sort last and are never evaluated).  `score(j, c)` reads the score
+// of candidate row j and class c.
+template <typename Score>
+__device__ __forceinline__ void compact_rows(int m0, const unsigned* __restrict__ bits, const unsigned* __restrict__ max_ord,
+                                             const float* __restrict__ boxes, int cap, float* __restrict__ dets,
+                                             int32_t* __restrict__ sel_cand, int32_t* __restrict__ sel_label,
+                                             int32_t* __restrict__ seg, int32_t* __restrict__ total_out, int fill_here,
+                                             Score score) {
   __shared__ int wsum[kScanThreads / 64];
   const int tid = threadIdx.x;
   const float span = ord2f(*max_ord) + 1.0f;                 // max_coordinate + 1
@@ -133,7 +145,6 @@ pp_compact_kernel(const float* __restrict__ sig_all, const int64_t* __restrict__
     int chunk_total;
     int pos = running + block_excl_scan(cnt, wsum, &chunk_total);
     if (cnt > 0) {
-      const int g = (int)cand[j];
       float b8[8];
 #pragma unroll
       for (int k = 0; k < 8; k++) b8[k] = boxes[(size_t)j * 8 + k];
@@ -145,7 +156,7 @@ pp_compact_kernel(const float* __restrict__ sig_all, const int64_t* __restrict__
           const float offs = (float)c * span;                // labels.to(bboxes) * (max_coordinate + 1)
 #pragma unroll
           for (int k = 0; k < 8; k++) dets[(size_t)pos * 9 + k] = b8[k] + offs;
-          dets[(size_t)pos * 9 + 8] = sig_all[(size_t)c * n + g];
+          dets[(size_t)pos * 9 + 8] = score(j, c);
           sel_cand[pos] = j; sel_label[pos] = c;
         }
         pos++;
@@ -154,13 +165,82 @@ pp_compact_kernel(const float* __restrict__ sig_all, const int64_t* __restrict__
     running += chunk_total;
   }
   const int count = running < cap ? running : cap;
-  if (fill_here) for (int r = count + tid; r < cap; r += kScanThreads) {      // (no candidates: the flags kernel did not run)
-#pragma unroll
-    for (int k = 0; k < 8; k++) dets[(size_t)r * 9 + k] = 0.f;
-    dets[(size_t)r * 9 + 8] = -INFINITY;
-    sel_cand[r] = 0; sel_label[r] = 0;
-  }
+  if (fill_here) fill_padding(count + tid, kScanThreads, cap, dets, sel_cand, sel_label);   // (no candidates: no flags kernel ran)
   if (tid == 0) { seg[0] = 0; seg[1] = count; total_out[0] = running; }
+}
+
+__global__ void __launch_bounds__(kScanThreads)
+pp_compact_kernel(const float* __restrict__ sig_all, const int64_t* __restrict__ cand, int m0, int n,
+                  const unsigned* __restrict__ bits, const unsigned* __restrict__ max_ord,
+                  const float* __restrict__ boxes, int cap, float* __restrict__ dets, int32_t* __restrict__ sel_cand,
+                  int32_t* __restrict__ sel_label, int32_t* __restrict__ seg, int32_t* __restrict__ total_out, int fill_here) {
+  compact_rows(m0, bits, max_ord, boxes, cap, dets, sel_cand, sel_label, seg, total_out, fill_here,
+               [=](int j, int c) { return sig_all[(size_t)c * n + (int)cand[j]]; });
+}
+
+// ---- the multi-view form (test-time augmentation): the candidates of up to kMaxViews views of ONE image, mapped back to the
+// original image and concatenated view-major -- torch.cat over the views -- in front of the same compaction.
+// The mapping is OrientedRepPointsDetector.merge_aug_results' on device tensors with a host-scalar scale_factor, bit for bit:
+//   flip     x -> (float(w) - x) - 1.0f on the x coordinates (`w - t` and `- 1`, two tensor ops, each rounded);
+//   rescale  v -> v * inv with inv = float(1.0 / double(scale)): PyTorch's GPU division of a tensor by a host scalar
+//            multiplies by the reciprocal, which it forms in fp64 and rounds to fp32 once.  That is NOT the IEEE
+//            quotient v / float(scale) the single-view rescale=True path computes (a tensor divided by a 0-dim device
+//            tensor): the two differ in the last bit wherever the reciprocal is inexact (0.9375, 1333/1024, ...).
+constexpr int kMaxViews = 8;
+struct ViewParams {
+  const float* sig[kMaxViews]; const int64_t* cand[kMaxViews]; const float* boxes[kMaxViews]; const float* rep[kMaxViews];
+  int off[kMaxViews + 1];        // first row of each view in the concatenation
+  int n[kMaxViews]; int flip[kMaxViews]; float width[kMaxViews]; float inv[kMaxViews];
+  int nviews;
+};
+
+__device__ __forceinline__ int view_of(const ViewParams& P, int j) {
+  int v = 0;
+#pragma unroll 1
+  for (int i = 1; i < P.nviews; i++) if (j >= P.off[i]) v = i;       // (the LAST view that starts at or before j: empty views own no row)
+  return v;
+}
+
+__device__ __forceinline__ float map_back(float v, bool is_x, int flip, float width, float inv) {
+  if (flip && is_x) v = __fsub_rn(__fsub_rn(width, v), 1.0f);
+  return __fmul_rn(v, inv);
+}
+
+__global__ void __launch_bounds__(256)
+pp_flags_views_kernel(ViewParams P, int m_all, int num_cls, float thr, float* __restrict__ boxes_all,
+                      float* __restrict__ rep_all, unsigned* __restrict__ bits, unsigned* __restrict__ max_ord, int cap,
+                      float* __restrict__ dets, int32_t* __restrict__ sel_cand, int32_t* __restrict__ sel_label) {
+  __shared__ float red[4];
+  const int j = blockIdx.x * blockDim.x + threadIdx.x;
+  fill_padding(j, gridDim.x * blockDim.x, cap, dets, sel_cand, sel_label);
+  float mx = -INFINITY;
+  if (j < m_all) {
+    const int v = view_of(P, j), lj = j - P.off[v], n = P.n[v], flip = P.flip[v];
+    const float width = P.width[v], inv = P.inv[v];
+    const int g = (int)P.cand[v][lj];
+    const float* sig = P.sig[v];
+    unsigned b = 0;
+    for (int c = 0; c < num_cls; c++) b |= (sig[(size_t)c * n + g] > thr) ? (1u << c) : 0u;
+    bits[j] = b;
+#pragma unroll
+    for (int k = 0; k < 8; k++) {
+      const float m = map_back(P.boxes[v][(size_t)lj * 8 + k], (k & 1) == 0, flip, width, inv);
+      boxes_all[(size_t)j * 8 + k] = m;
+      if (b) mx = max_nan(mx, m);
+    }
+#pragma unroll
+    for (int k = 0; k < 18; k++)
+      rep_all[(size_t)j * 18 + k] = map_back(P.rep[v][(size_t)lj * 18 + k], (k & 1) == 0, flip, width, inv);
+  }
+  block_max_to(mx, red, max_ord);
+}
+
+__global__ void __launch_bounds__(kScanThreads)
+pp_compact_views_kernel(ViewParams P, int m_all, const unsigned* __restrict__ bits, const unsigned* __restrict__ max_ord,
+                        const float* __restrict__ boxes_all, int cap, float* __restrict__ dets, int32_t* __restrict__ sel_cand,
+                        int32_t* __restrict__ sel_label, int32_t* __restrict__ seg, int32_t* __restrict__ total_out, int fill_here) {
+  compact_rows(m_all, bits, max_ord, boxes_all, cap, dets, sel_cand, sel_label, seg, total_out, fill_here,
+               [&](int j, int c) { const int v = view_of(P, j); return P.sig[v][(size_t)c * P.n[v] + (int)P.cand[v][j - P.off[v]]]; });
 }
 
 // ---- packing: NMS survivors -> [reppoints | corners | score | label] rows + (count, overflow) tail row -----------------
@@ -514,6 +594,47 @@ int orp_pp_compact(const float* sig_all, const int64_t* cand, int m0, int n, int
                        score_thr, bits, max_ord, capacity, dets, sel_cand, sel_label);
   hipLaunchKernelGGL(pp_compact_kernel, dim3(1), dim3(kScanThreads), 0, st, sig_all, cand, m0, n, bits, max_ord, boxes,
                      capacity, dets, sel_cand, sel_label, seg2, total, m0 > 0 ? 0 : 1);
+  return done();
+}
+
+size_t orp_pp_compact_views_scratch_bytes(int total_m0) { return orp_pp_compact_scratch_bytes(total_m0); }
+
+int orp_pp_compact_views(const orp_pp_view* views_host, int num_views, int num_classes, float score_thr, int capacity,
+                         float* boxes_all, float* reppoints_all, float* dets, int32_t* sel_cand, int32_t* sel_label,
+                         int32_t* seg2, int32_t* total, void* scratch, size_t scratch_bytes, void* stream) {
+  if (!views_host || num_views <= 0 || num_views > kMaxViews || num_classes <= 0 || num_classes > 32 || capacity <= 0 ||
+      !dets || !sel_cand || !sel_label || !seg2 || !total)
+    return ORP_EINVAL;
+  ViewParams P;
+  P.nviews = num_views;
+  long long m_all = 0;
+  for (int v = 0; v < kMaxViews; v++) {
+    const orp_pp_view& w = views_host[v < num_views ? v : num_views - 1];
+    if (v < num_views) {
+      if (w.m0 < 0 || w.n <= 0 || w.img_width < 0 || !(w.scale > 0.0)) return ORP_EINVAL;
+      if (w.m0 > 0 && (!w.sig_all || !w.cand || !w.boxes || !w.reppoints)) return ORP_EINVAL;
+    }
+    P.sig[v] = w.sig_all; P.cand[v] = w.cand; P.boxes[v] = w.boxes; P.rep[v] = w.reppoints;
+    P.off[v] = (int)m_all;
+    P.n[v] = w.n; P.flip[v] = w.flip != 0; P.width[v] = (float)w.img_width;
+    P.inv[v] = (float)(1.0 / w.scale);
+    if (v < num_views) m_all += w.m0;
+    if (m_all > 0x7fffffffLL / 32) return ORP_ETOOBIG;
+  }
+  P.off[kMaxViews] = (int)m_all;
+  const int m = (int)m_all;
+  if (m > 0 && (!boxes_all || !reppoints_all)) return ORP_EINVAL;
+  if (!scratch || scratch_bytes < orp_pp_compact_views_scratch_bytes(m)) return ORP_EWORKSPACE;
+  hipStream_t st = (hipStream_t)stream;
+  unsigned* max_ord = reinterpret_cast<unsigned*>(scratch);
+  unsigned* bits = max_ord + 64;
+  hipError_t e = orp::fill_async(max_ord, 0, sizeof(unsigned), st);     // as orp_pp_compact: "no box yet"
+  if (e != hipSuccess) return (int)e;
+  if (m > 0)
+    hipLaunchKernelGGL(pp_flags_views_kernel, dim3((m + 255) / 256), dim3(256), 0, st, P, m, num_classes, score_thr, boxes_all,
+                       reppoints_all, bits, max_ord, capacity, dets, sel_cand, sel_label);
+  hipLaunchKernelGGL(pp_compact_views_kernel, dim3(1), dim3(kScanThreads), 0, st, P, m, bits, max_ord, boxes_all, capacity,
+                     dets, sel_cand, sel_label, seg2, total, m > 0 ? 0 : 1);
   return done();
 }
 

@@ -53,7 +53,9 @@ constexpr int kTileIters = 2;          // item chunks per block: the table costs
 
 struct Norm3 { float mean[3]; float std[3]; };
 
-template <typename T>
+// kFlip (the test pipeline's RandomFlip, horizontal, between the crop and Normalize): output column x holds the tile's column
+// S - 1 - x.  A lane still loads one aligned group of kPix source pixels -- the mirrored group -- and stores them in reverse.
+template <typename T, bool kFlip>
 __global__ void __launch_bounds__(kTileThreads)
 scene_tiles_kernel(const unsigned char* __restrict__ scene, int H, int W, long long row_stride,
                    const int32_t* __restrict__ origins, int S, Norm3 nrm, int to_rgb, T* __restrict__ out) {
@@ -76,7 +78,7 @@ scene_tiles_kernel(const unsigned char* __restrict__ scene, int H, int W, long l
     if (item >= items) break;
     const int y = (int)(item / groups);
     const int x0 = (int)(item % groups) * kPix;
-    const long long ys = (long long)up + y, xs = (long long)left + x0;
+    const long long ys = (long long)up + y, xs = (long long)left + (kFlip ? S - kPix - x0 : x0);
     unsigned w[kWords];
 #pragma unroll
     for (int j = 0; j < kWords; j++) w[j] = 0u;
@@ -116,7 +118,7 @@ scene_tiles_kernel(const unsigned char* __restrict__ scene, int H, int W, long l
       for (int c = 0; c < 3; c++) {
         const int k = 3 * p + c;                                       // byte k of the stream: pixel p, source channel c
         const unsigned byte = (w[k >> 2] >> (8 * (k & 3))) & 255u;
-        o[c].v[p] = in ? lut[to_rgb ? 2 - c : c][byte] : zero;
+        o[c].v[kFlip ? kPix - 1 - p : p] = in ? lut[to_rgb ? 2 - c : c][byte] : zero;
       }
     }
     const size_t plane = (size_t)S * S;
@@ -126,7 +128,7 @@ scene_tiles_kernel(const unsigned char* __restrict__ scene, int H, int W, long l
   }
 }
 
-template <typename T>
+template <typename T, bool kFlip>
 int launch_tiles(const uint8_t* scene, int H, int W, long long stride, const int32_t* origins, int T_, int S, const Norm3& nrm,
                  int to_rgb, void* out, hipStream_t st) {
   constexpr int kPix = 16 / (int)sizeof(T);
@@ -135,7 +137,7 @@ int launch_tiles(const uint8_t* scene, int H, int W, long long stride, const int
   const long long per_block = (long long)kTileThreads * kTileIters;
   const long long blocks = (items + per_block - 1) / per_block;
   if (blocks > 0x7fffffffLL || T_ > 65535) return ORP_ETOOBIG;
-  hipLaunchKernelGGL(scene_tiles_kernel<T>, dim3((unsigned)blocks, (unsigned)T_), dim3(kTileThreads), 0, st, scene, H, W, stride,
+  hipLaunchKernelGGL((scene_tiles_kernel<T, kFlip>), dim3((unsigned)blocks, (unsigned)T_), dim3(kTileThreads), 0, st, scene, H, W, stride,
                      origins, S, nrm, to_rgb, reinterpret_cast<T*>(out));
   return done();
 }
@@ -150,7 +152,9 @@ int launch_tiles(const uint8_t* scene, int H, int W, long long stride, const int
 
 constexpr int kResRows = 4 * kTileIters;             // output rows per block
 
-template <typename T>
+// kFlip mirrors inside the resized patch's own width (Resize -> RandomFlip -> Normalize -> Pad): output column x < new_w takes the
+// axis-table entry of column new_w - 1 - x, so the arithmetic per pixel -- and with it every value -- is the unflipped kernel's.
+template <typename T, bool kFlip>
 __global__ void __launch_bounds__(kTileThreads)
 scene_tiles_resized_kernel(const unsigned char* __restrict__ scene, int H, int W, long long row_stride,
                            const int32_t* __restrict__ origins, int src_w, int src_h, int new_w, int new_h, int pad_w, int pad_h,
@@ -171,8 +175,9 @@ scene_tiles_resized_kernel(const unsigned char* __restrict__ scene, int H, int W
   for (int i = threadIdx.x; i < kResCols; i += kTileThreads) {
     const int x = col0 + i;
     const bool in = x < new_w;
-    col_i0[i] = in ? min(max(x_i0[x], 0), src_w - 1) : 0;   // (clamped: a wrong table cannot leave the patch)
-    col_w1[i] = in ? x_w1[x] : 0.f;
+    const int xt = kFlip ? new_w - 1 - x : x;               // (in [0, new_w) whenever x is)
+    col_i0[i] = in ? min(max(x_i0[xt], 0), src_w - 1) : 0;  // (clamped: a wrong table cannot leave the patch)
+    col_w1[i] = in ? x_w1[xt] : 0.f;
   }
   if (threadIdx.x < kResRows) {
     const int y = rowb + (int)threadIdx.x;
@@ -230,7 +235,7 @@ scene_tiles_resized_kernel(const unsigned char* __restrict__ scene, int H, int W
 
 struct Axes { const int32_t* x_i0; const float* x_w1; const int32_t* y_i0; const float* y_w1; };
 
-template <typename T>
+template <typename T, bool kFlip>
 int launch_tiles_resized(const uint8_t* scene, int H, int W, long long stride, const int32_t* origins, int T_, int src_w,
                          int src_h, int new_w, int new_h, int pad_w, int pad_h, const Axes& ax, const Norm3& nrm, int to_rgb,
                          void* out, hipStream_t st) {
@@ -238,7 +243,7 @@ int launch_tiles_resized(const uint8_t* scene, int H, int W, long long stride, c
   if (pad_w % kPix != 0) return ORP_EINVAL;
   const int bx = (pad_w + 64 * kPix - 1) / (64 * kPix), by = (pad_h + kResRows - 1) / kResRows;
   if (by > 65535 || T_ > 65535) return ORP_ETOOBIG;
-  hipLaunchKernelGGL(scene_tiles_resized_kernel<T>, dim3((unsigned)bx, (unsigned)by, (unsigned)T_), dim3(kTileThreads), 0, st,
+  hipLaunchKernelGGL((scene_tiles_resized_kernel<T, kFlip>), dim3((unsigned)bx, (unsigned)by, (unsigned)T_), dim3(kTileThreads), 0, st,
                      scene, H, W, stride, origins, src_w, src_h, new_w, new_h, pad_w, pad_h, ax.x_i0, ax.x_w1, ax.y_i0, ax.y_w1,
                      nrm, to_rgb, reinterpret_cast<T*>(out));
   return done();
@@ -364,11 +369,9 @@ collect_scatter_kernel(const float* __restrict__ packed, int m, int C, const int
   }
 }
 
-}  // namespace
-
-extern "C" {
-
-int orp_scene_tiles(const uint8_t* scene, int height, int width, long long row_stride_bytes, const int32_t* origins,
+// ---- the entry points' bodies: plain and mirrored differ in one template argument
+template <bool kFlip>
+int scene_tiles_entry(const uint8_t* scene, int height, int width, long long row_stride_bytes, const int32_t* origins,
                     int num_tiles, int tile, const float* mean_host, const float* std_host, int to_rgb, int out_dtype,
                     void* out, void* stream) {
   if (!scene || !origins || !mean_host || !std_host || !out || height <= 0 || width <= 0 || num_tiles < 0 || tile <= 0 ||
@@ -379,14 +382,15 @@ int orp_scene_tiles(const uint8_t* scene, int height, int width, long long row_s
   for (int c = 0; c < 3; c++) { nrm.mean[c] = mean_host[c]; nrm.std[c] = std_host[c]; }
   hipStream_t st = (hipStream_t)stream;
   switch (out_dtype) {
-    case 0: return launch_tiles<float>(scene, height, width, row_stride_bytes, origins, num_tiles, tile, nrm, to_rgb != 0, out, st);
-    case 1: return launch_tiles<_Float16>(scene, height, width, row_stride_bytes, origins, num_tiles, tile, nrm, to_rgb != 0, out, st);
-    case 2: return launch_tiles<bf16_bits>(scene, height, width, row_stride_bytes, origins, num_tiles, tile, nrm, to_rgb != 0, out, st);
+    case 0: return launch_tiles<float, kFlip>(scene, height, width, row_stride_bytes, origins, num_tiles, tile, nrm, to_rgb != 0, out, st);
+    case 1: return launch_tiles<_Float16, kFlip>(scene, height, width, row_stride_bytes, origins, num_tiles, tile, nrm, to_rgb != 0, out, st);
+    case 2: return launch_tiles<bf16_bits, kFlip>(scene, height, width, row_stride_bytes, origins, num_tiles, tile, nrm, to_rgb != 0, out, st);
     default: return ORP_EINVAL;
   }
 }
 
-int orp_scene_tiles_resized(const uint8_t* scene, int height, int width, long long row_stride_bytes, const int32_t* origins,
+template <bool kFlip>
+int scene_tiles_resized_entry(const uint8_t* scene, int height, int width, long long row_stride_bytes, const int32_t* origins,
                             int num_tiles, int src_w, int src_h, int new_w, int new_h, int pad_w, int pad_h, const int32_t* x_i0,
                             const float* x_w1, const int32_t* y_i0, const float* y_w1, const float* mean_host,
                             const float* std_host, int to_rgb, int out_dtype, void* out, void* stream) {
@@ -400,14 +404,49 @@ int orp_scene_tiles_resized(const uint8_t* scene, int height, int width, long lo
   const Axes ax = {x_i0, x_w1, y_i0, y_w1};
   hipStream_t st = (hipStream_t)stream;
   switch (out_dtype) {
-    case 0: return launch_tiles_resized<float>(scene, height, width, row_stride_bytes, origins, num_tiles, src_w, src_h, new_w, new_h,
+    case 0: return launch_tiles_resized<float, kFlip>(scene, height, width, row_stride_bytes, origins, num_tiles, src_w, src_h, new_w, new_h,
                                                pad_w, pad_h, ax, nrm, to_rgb != 0, out, st);
-    case 1: return launch_tiles_resized<_Float16>(scene, height, width, row_stride_bytes, origins, num_tiles, src_w, src_h, new_w,
+    case 1: return launch_tiles_resized<_Float16, kFlip>(scene, height, width, row_stride_bytes, origins, num_tiles, src_w, src_h, new_w,
                                                   new_h, pad_w, pad_h, ax, nrm, to_rgb != 0, out, st);
-    case 2: return launch_tiles_resized<bf16_bits>(scene, height, width, row_stride_bytes, origins, num_tiles, src_w, src_h, new_w,
+    case 2: return launch_tiles_resized<bf16_bits, kFlip>(scene, height, width, row_stride_bytes, origins, num_tiles, src_w, src_h, new_w,
                                                    new_h, pad_w, pad_h, ax, nrm, to_rgb != 0, out, st);
     default: return ORP_EINVAL;
   }
+}
+
+}  // namespace
+
+extern "C" {
+
+int orp_scene_tiles(const uint8_t* scene, int height, int width, long long row_stride_bytes, const int32_t* origins,
+                    int num_tiles, int tile, const float* mean_host, const float* std_host, int to_rgb, int out_dtype,
+                    void* out, void* stream) {
+  return scene_tiles_entry<false>(scene, height, width, row_stride_bytes, origins, num_tiles, tile, mean_host, std_host, to_rgb,
+                                  out_dtype, out, stream);
+}
+
+int orp_scene_tiles_flip(const uint8_t* scene, int height, int width, long long row_stride_bytes, const int32_t* origins,
+                         int num_tiles, int tile, const float* mean_host, const float* std_host, int to_rgb, int out_dtype,
+                         void* out, void* stream) {
+  return scene_tiles_entry<true>(scene, height, width, row_stride_bytes, origins, num_tiles, tile, mean_host, std_host, to_rgb,
+                                 out_dtype, out, stream);
+}
+
+int orp_scene_tiles_resized(const uint8_t* scene, int height, int width, long long row_stride_bytes, const int32_t* origins,
+                            int num_tiles, int src_w, int src_h, int new_w, int new_h, int pad_w, int pad_h, const int32_t* x_i0,
+                            const float* x_w1, const int32_t* y_i0, const float* y_w1, const float* mean_host,
+                            const float* std_host, int to_rgb, int out_dtype, void* out, void* stream) {
+  return scene_tiles_resized_entry<false>(scene, height, width, row_stride_bytes, origins, num_tiles, src_w, src_h, new_w, new_h,
+                                          pad_w, pad_h, x_i0, x_w1, y_i0, y_w1, mean_host, std_host, to_rgb, out_dtype, out, stream);
+}
+
+int orp_scene_tiles_resized_flip(const uint8_t* scene, int height, int width, long long row_stride_bytes, const int32_t* origins,
+                                 int num_tiles, int src_w, int src_h, int new_w, int new_h, int pad_w, int pad_h,
+                                 const int32_t* x_i0, const float* x_w1, const int32_t* y_i0, const float* y_w1,
+                                 const float* mean_host, const float* std_host, int to_rgb, int out_dtype, void* out,
+                                 void* stream) {
+  return scene_tiles_resized_entry<true>(scene, height, width, row_stride_bytes, origins, num_tiles, src_w, src_h, new_w, new_h,
+                                         pad_w, pad_h, x_i0, x_w1, y_i0, y_w1, mean_host, std_host, to_rgb, out_dtype, out, stream);
 }
 
 size_t orp_scene_collect_workspace_bytes(int num_tiles, int num_classes) {

@@ -5,6 +5,7 @@
   multiclass_rnms                    mmdet/core/post_processing/bbox_nms.py:93-182
   rbbox2result                       mmdet/core/bbox/transforms.py:356-375
 """
+import ctypes
 from functools import partial
 
 import numpy as np
@@ -194,15 +195,9 @@ def multiclass_rnms_static(multi_bboxes, multi_scores, score_thr, nms_cfg, max_n
     return torch.cat([body, tail], 0)
 
 
-def fused_postprocess(cls_scores, points_preds, strides, cfg, num_points=9, scale_factor=None):
-    """get_bboxes_single + multiclass_rnms + packing for ONE image on the fused HIP kernels (csrc/orp_postproc.hip):
-    cls_scores[l] [C,H,W] logits, points_preds[l] [2*num_points,H,W] refine offsets ((y,x)-interleaved, grid units).
-    scale_factor (a scalar; `rescale=True` of get_bboxes_single): the decoded boxes and rep-points are divided by it in fp32
-    before the selection and the NMS, with the dynamic path's own division (a tensor by a 0-dim device tensor).
-    Same detections in the same order as the tensor-op path (`multiclass_rnms_static`); torch keeps the numerically
-    sensitive pieces (sigmoid, class max, top-k), everything else is three kernels around min-area-rect and the NMS.
-    Returns the packed [max_per_img + 1, 28] tensor of `rbbox2result_packed`."""
-    import ctypes
+def _decode_candidates(cls_scores, points_preds, strides, cfg, num_points=9):
+    """The front of the fused post-processing for one image: sigmoid, candidate selection, `orp_pp_gather`, min-area-rect decode.
+    Returns (sig [C, N], cand [m0] int64, boxes [m0, 8], reppoints [m0, 18]), fp32, boxes and rep-points in the image's own scale."""
     from ..mmdet_ops.minarea_rect import minaerarect_decode
     assert num_points == 9
     L = _lib.lib()
@@ -240,15 +235,18 @@ def fused_postprocess(cls_scores, points_preds, strides, cfg, num_points=9, scal
     lo = (ctypes.c_int * len(sizes))(*[int(o) for o in offs[:-1]])
     lw = (ctypes.c_int * len(sizes))(*widths)
     ls = (ctypes.c_float * len(sizes))(*[float(s) for s in strides])
-    st = _lib.stream_of(sig)
     with torch.cuda.device(dev):
         _lib.check(L.orp_pp_gather(_lib.ptr(pts_all), _lib.ptr(cand), m0, N, lo, lw, ls, len(sizes), _lib.ptr(pts_xy),
-                                   _lib.ptr(centers), _lib.ptr(strd), _lib.ptr(rep), st), "orp_pp_gather")
-    boxes = minaerarect_decode(pts_xy, centers, strd)                                # [m0, 8]
-    if scale_factor is not None:
-        scale = scale_scalar(scale_factor, dev)
-        boxes /= scale
-        rep /= scale
+                                   _lib.ptr(centers), _lib.ptr(strd), _lib.ptr(rep), _lib.stream_of(sig)), "orp_pp_gather")
+    return sig, cand, minaerarect_decode(pts_xy, centers, strd), rep
+
+
+def _nms_and_pack(compact, sig, m0, C, cfg, boxes, rep):
+    """The back of the fused post-processing: `compact(cap, dets, sel_cand, sel_label, seg, total)` fills the detections of
+    m0 candidate rows, then one `rnms_batched_device` and one `orp_pp_pack` over `boxes` / `rep`.  Returns packed [m + 1, 28]."""
+    L = _lib.lib()
+    dev = sig.device
+    f32 = dict(dtype=torch.float32, device=dev)
     cap = int(min(cfg.get('static_capacity', 8192), m0 * C))
     max_num = int(cfg.max_per_img)
     m = int(min(max_num, cap)) if max_num > 0 else cap
@@ -259,17 +257,91 @@ def fused_postprocess(cls_scores, points_preds, strides, cfg, num_points=9, scal
     total = torch.empty((1,), dtype=torch.int32, device=dev)
     nms_cfg_ = dict(cfg.nms)
     assert nms_cfg_.pop('type', 'rnms') == 'rnms'
-    with torch.cuda.device(dev):
-        scratch = torch.empty((L.orp_pp_compact_scratch_bytes(m0),), dtype=torch.uint8, device=dev)
-        _lib.check(L.orp_pp_compact(_lib.ptr(sig), _lib.ptr(cand), m0, N, C, _lib.ptr(boxes), float(cfg.score_thr), cap,
-                                    _lib.ptr(dets), _lib.ptr(sel_cand), _lib.ptr(sel_label), _lib.ptr(seg),
-                                    _lib.ptr(total), _lib.ptr(scratch), scratch.numel(), st), "orp_pp_compact")
+    compact(cap, dets, sel_cand, sel_label, seg, total)
     keep, num = nms_wrapper.rnms_batched_device(dets, seg, cap, nms_cfg_.get('iou_thr', 0.4))
     packed = torch.empty((m + 1, 28), **f32)
     with torch.cuda.device(dev):
         _lib.check(L.orp_pp_pack(_lib.ptr(keep), _lib.ptr(num), _lib.ptr(dets), _lib.ptr(sel_cand), _lib.ptr(sel_label),
-                                 _lib.ptr(boxes), _lib.ptr(rep), _lib.ptr(total), cap, m, _lib.ptr(packed), st),
-                   "orp_pp_pack")
+                                 _lib.ptr(boxes), _lib.ptr(rep), _lib.ptr(total), cap, m, _lib.ptr(packed),
+                                 _lib.stream_of(sig)), "orp_pp_pack")
+    return packed
+
+
+def fused_postprocess(cls_scores, points_preds, strides, cfg, num_points=9, scale_factor=None):
+    """get_bboxes_single + multiclass_rnms + packing for ONE image on the fused HIP kernels (csrc/orp_postproc.hip):
+    cls_scores[l] [C,H,W] logits, points_preds[l] [2*num_points,H,W] refine offsets ((y,x)-interleaved, grid units).
+    scale_factor (a scalar; `rescale=True` of get_bboxes_single): the decoded boxes and rep-points are divided by it in fp32
+    before the selection and the NMS, with the dynamic path's own division (a tensor by a 0-dim device tensor).
+    Same detections in the same order as the tensor-op path (`multiclass_rnms_static`); torch keeps the numerically
+    sensitive pieces (sigmoid, class max, top-k), everything else is three kernels around min-area-rect and the NMS.
+    Returns the packed [max_per_img + 1, 28] tensor of `rbbox2result_packed`."""
+    L = _lib.lib()
+    sig, cand, boxes, rep = _decode_candidates(cls_scores, points_preds, strides, cfg, num_points)
+    dev, C, N, m0 = sig.device, int(sig.size(0)), int(sig.size(1)), cand.numel()
+    if scale_factor is not None:
+        scale = scale_scalar(scale_factor, dev)
+        boxes /= scale
+        rep /= scale
+
+    def compact(cap, dets, sel_cand, sel_label, seg, total):
+        with torch.cuda.device(dev):
+            scratch = torch.empty((L.orp_pp_compact_scratch_bytes(m0),), dtype=torch.uint8, device=dev)
+            _lib.check(L.orp_pp_compact(_lib.ptr(sig), _lib.ptr(cand), m0, N, C, _lib.ptr(boxes), float(cfg.score_thr), cap,
+                                        _lib.ptr(dets), _lib.ptr(sel_cand), _lib.ptr(sel_label), _lib.ptr(seg),
+                                        _lib.ptr(total), _lib.ptr(scratch), scratch.numel(), _lib.stream_of(sig)),
+                       "orp_pp_compact")
+    return _nms_and_pack(compact, sig, m0, C, cfg, boxes, rep)
+
+
+class PpView(ctypes.Structure):
+    """`orp_pp_view` of include/orp_hip.h."""
+    _fields_ = [(k, ctypes.c_void_p) for k in ('sig_all', 'cand', 'boxes', 'reppoints')] + \
+               [(k, ctypes.c_int) for k in ('m0', 'n', 'flip', 'img_width')] + [('scale', ctypes.c_double)]
+
+
+def compact_views(views, num_classes, score_thr, capacity, boxes_all, rep_all, dets, sel_cand, sel_label, seg, total):
+    """`orp_pp_compact_views`: views = per view (sig [C, n], cand [m0] int64, boxes [m0, 8], reppoints [m0, 18], flip,
+    img_width, scale), CUDA fp32 contiguous.  Fills the mapped-back, concatenated boxes_all [sum m0, 8] / rep_all [sum m0, 18]
+    and dets [capacity, 9] / sel_cand / sel_label / seg [2] / total [1]."""
+    L = _lib.lib()
+    dev = dets.device
+    arr = (PpView * max(1, len(views)))()
+    for a, (sig, cand, boxes, rep, flip, width, scale) in zip(arr, views):
+        a.sig_all, a.cand, a.boxes, a.reppoints = [t.data_ptr() or None for t in (sig, cand, boxes, rep)]
+        a.m0, a.n, a.flip, a.img_width, a.scale = cand.numel(), sig.size(1), int(bool(flip)), int(width), float(scale)
+    m_all = sum(v[1].numel() for v in views)
+    if tuple(boxes_all.shape) != (m_all, 8) or tuple(rep_all.shape) != (m_all, 18):
+        raise ValueError("compact_views: boxes_all / rep_all must hold the %d rows of all views" % m_all)
+    with torch.cuda.device(dev):
+        scratch = torch.empty((L.orp_pp_compact_views_scratch_bytes(m_all),), dtype=torch.uint8, device=dev)
+        _lib.check(L.orp_pp_compact_views(arr, len(views), int(num_classes), float(score_thr), int(capacity), _lib.ptr(boxes_all),
+                                          _lib.ptr(rep_all), _lib.ptr(dets), _lib.ptr(sel_cand), _lib.ptr(sel_label),
+                                          _lib.ptr(seg), _lib.ptr(total), _lib.ptr(scratch), scratch.numel(),
+                                          _lib.stream_of(dets)), "orp_pp_compact_views")
+
+
+def fused_postprocess_views(outs_per_view, strides, cfg, metas, rescale=False, num_points=9):
+    """The test-time-augmentation form of `fused_postprocess` for ONE image seen through several views (`aug_test`: every view's
+    decode without NMS, `merge_aug_results`, one `multiclass_rnms` over the union): outs_per_view[v] = (cls_scores[l] [C,H,W],
+    points_preds[l] [18,H,W]) of view v, metas[v] its meta dict (`img_shape`, scalar `scale_factor`, `flip`).  Per view the
+    selection, gather and min-area-rect decode of the single-view path; then ONE `orp_pp_compact_views` (maps every view back
+    to the original image with `merge_aug_results`' arithmetic and emits the union view-major), one rotated NMS, one packing.
+    With `rescale=False` corners and rep-points are multiplied by the first view's factor afterwards, on the device, as
+    `aug_test` does.  No host synchronisation; capturable.  Returns the packed [max_per_img + 1, 28] tensor."""
+    views = []
+    for (cls_scores, points_preds), meta in zip(outs_per_view, metas):
+        sig, cand, boxes, rep = _decode_candidates(cls_scores, points_preds, strides, cfg, num_points)
+        views.append((sig, cand, boxes, rep, meta['flip'], meta['img_shape'][1], meta['scale_factor']))
+    sig0 = views[0][0]
+    C, m_all = int(sig0.size(0)), sum(v[1].numel() for v in views)
+    boxes_all = torch.empty((m_all, 8), dtype=torch.float32, device=sig0.device)
+    rep_all = torch.empty((m_all, 18), dtype=torch.float32, device=sig0.device)
+
+    def compact(cap, dets, sel_cand, sel_label, seg, total):
+        compact_views(views, C, cfg.score_thr, cap, boxes_all, rep_all, dets, sel_cand, sel_label, seg, total)
+    packed = _nms_and_pack(compact, sig0, m_all, C, cfg, boxes_all, rep_all)
+    if not rescale:
+        packed[:-1, :26] *= metas[0]['scale_factor']           # (a host scalar: a kernel argument, nothing to upload)
     return packed
 
 
@@ -277,7 +349,6 @@ def select_candidates(sig, offs, nms_pre):
     """`scores.max(dim=1)` + per-level `topk(nms_pre)` of get_bboxes_single (head :730-737) as one radix select + counting
     rank (`orp_pp_select`): sig [C, N] sigmoid scores of all levels, offs = first point of each level (+ N).  Returns the
     int64 candidate indices, level-major, descending class-maximum score inside a selected level."""
-    import ctypes
     L = _lib.lib()
     C, N = int(sig.size(0)), int(sig.size(1))
     nlev = len(offs) - 1

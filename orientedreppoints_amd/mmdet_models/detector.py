@@ -3,7 +3,7 @@ base.py:97-149): backbone + neck on stock PyTorch-ROCm, dense head on the HIP op
 import torch
 import torch.nn as nn
 
-from .core import multiclass_rnms, rbbox2result, rbbox2result_packed
+from .core import fused_postprocess_views, is_scalar_scale, multiclass_rnms, rbbox2result, rbbox2result_packed
 from .registry import DETECTORS, build_backbone, build_head, build_neck
 
 
@@ -95,13 +95,39 @@ class OrientedRepPointsDetector(nn.Module):
             return bboxes
         return bboxes, torch.cat(aug_scores, dim=0)
 
+    def aug_static_ok(self, img, img_metas):
+        """Whether `aug_test` takes the fused static route for these views: the condition of `simple_test_batch`, plus what the
+        fused kernels need (sigmoid scores, one scale factor per view)."""
+        cfg = self.test_cfg
+        return (img.is_cuda and cfg.get('static_postprocess', True) and cfg.nms.get('type', 'rnms') == 'rnms'
+                and not torch.is_grad_enabled() and cfg.get('fused_postprocess', True) and self.bbox_head.use_sigmoid_cls
+                and all(is_scalar_scale(m[0]['scale_factor']) for m in img_metas))
+
+    def aug_postprocess_static(self, outs_per_view, img_metas, rescale, img_id=0):
+        """Image `img_id` of every view's head outputs -> the packed result of `fused_postprocess_views` (on the device)."""
+        head = self.bbox_head
+        per_view = [([c[img_id].detach() for c in outs[0]], [p[img_id].detach() for p in outs[2]]) for outs in outs_per_view]
+        return fused_postprocess_views(per_view, head.point_strides, self.test_cfg, [m[img_id] for m in img_metas], rescale,
+                                       head.num_points)
+
+    def aug_result_packed(self, packed):
+        """One D2H copy of an augmented packed result -> `aug_test`'s per-class [k, 9] lists; None when the capacity overflowed."""
+        result = rbbox2result_packed(packed, self.bbox_head.num_classes)
+        return None if result is None else [r[:, -9:] for r in result]
+
     def aug_test(self, imgs, img_metas, rescale=False):
         """Every view through backbone / neck / head and the decode WITHOUT NMS (fused HIP decode: hull -> min-area rect ->
         image space), candidates of all views mapped back and ONE multiclass rotated NMS over their union.  As in the
-        reference, boxes are in the original image's scale when `rescale`, else multiplied by the first view's factor."""
+        reference, boxes are in the original image's scale when `rescale`, else multiplied by the first view's factor.
+        Under `simple_test_batch`'s condition the part behind the head is `fused_postprocess_views` -- no host synchronisation,
+        one D2H --; if its capacity overflows, the tensor-op route below runs on the same head outputs."""
+        outs_per_view = [self.bbox_head(self.extract_feat(img)) for img in imgs]
+        if self.aug_static_ok(imgs[0], img_metas):
+            result = self.aug_result_packed(self.aug_postprocess_static(outs_per_view, img_metas, rescale))
+            if result is not None:
+                return result
         aug_bboxes, aug_scores = [], []
-        for img, img_meta in zip(imgs, img_metas):
-            outs = self.bbox_head(self.extract_feat(img))
+        for outs, img_meta in zip(outs_per_view, img_metas):
             det_bboxes, det_scores = self.bbox_head.get_bboxes(*(tuple(outs) + (img_meta, self.test_cfg, False, False)))[0]
             aug_bboxes.append(det_bboxes)
             aug_scores.append(det_scores)

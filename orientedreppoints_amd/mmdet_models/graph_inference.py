@@ -54,8 +54,29 @@ class GraphedInference(object):
         outs = head(model.extract_feat(self.static_img))
         return head.get_bboxes(*(tuple(outs) + (self.metas, model.test_cfg, self.rescale)), static=True)
 
+    @property
+    def inputs(self):
+        """What a device-side producer fills before a replay (`PipelinedInference.submit_device`)."""
+        return self.static_img
+
+    @property
+    def device(self):
+        return self.static_img.device
+
+    def load(self, img):
+        self.static_img.copy_(img, non_blocking=True)
+
+    def decode(self, packed):
+        """The packed results (device or pinned host) -> per-image result lists; an entry is None where the capacity overflowed."""
+        return [rbbox2result_packed(p, self.num_classes) for p in packed]
+
+    def fallback(self, img):
+        """The reference-shaped route for a call whose static capacity overflowed."""
+        with torch.no_grad():
+            return self.model.simple_test_batch(img, self.metas, self.rescale)
+
     def _capture(self):
-        dev = self.static_img.device
+        dev = self.device
         self.graph = None                                     # release the previous graph (and its pool) first
         self.packed = None
         self._refs = []
@@ -85,18 +106,69 @@ class GraphedInference(object):
 
     def __call__(self, img):
         """The per-image result lists of `simple_test_batch(img, img_metas, rescale)`."""
-        self.static_img.copy_(img, non_blocking=True)
+        self.load(img)
         self.graph.replay()
         # checked while the replay runs (keeps ~50 us of host work off the critical path): if the weights changed, the
         # packs / folded affines baked into the graph are stale -> capture again and redo this call
         if _param_fingerprint(self._tensors) != self._fingerprint:
             self._capture()
             self.graph.replay()
-        results = [rbbox2result_packed(p, self.num_classes) for p in self.packed]
+        results = self.decode(self.packed)
         if any(r is None for r in results):               # more pairs above score_thr than the static capacity holds
-            with torch.no_grad():
-                return self.model.simple_test_batch(img, self.metas, self.rescale)
+            return self.fallback(img)
         return results
+
+
+class GraphedAugInference(GraphedInference):
+    """`GraphedInference` for test-time augmentation: `model.aug_test(imgs, img_metas, rescale)` as one graph.  imgs: one
+    [B, 3, H_v, W_v] tensor per view (every view has its own static input buffer; B tiles of a view share it), img_metas: per
+    view the B meta dicts.  All views' forwards and, per image, one merged post-processing (`fused_postprocess_views`) are
+    captured together.  `__call__(imgs)` returns, per image, `aug_test`'s per-class [k, 9] lists.  Ownership, keep-alive,
+    fingerprint / recapture are `GraphedInference`'s; on overflow the call goes to `model.aug_test`."""
+
+    def __init__(self, model, imgs, img_metas, warmup=3, rescale=True):
+        self.model, self.metas, self.rescale = model, [list(m) for m in img_metas], bool(rescale)
+        imgs = list(imgs)
+        if len(imgs) == 0 or len(imgs) != len(self.metas) or any(len(m) != img.size(0) for img, m in zip(imgs, self.metas)):
+            raise ValueError("GraphedAugInference: one image tensor and one list of metas per view, one meta per image")
+        if len(set(int(img.size(0)) for img in imgs)) != 1:
+            raise ValueError("GraphedAugInference: every view holds the same number of images")
+        if model.training or not all(img.is_cuda for img in imgs):
+            raise ValueError("GraphedAugInference needs an eval-mode model and CUDA images")
+        with torch.no_grad():
+            if not model.aug_static_ok(imgs[0], self.metas):
+                raise ValueError("GraphedAugInference needs the fused static rnms post-processing and one scale factor per view "
+                                 "(keep_ratio=True)")
+        self.num_classes = model.bbox_head.num_classes
+        self.static_imgs = [img.clone() for img in imgs]
+        self.warmup = max(1, warmup)
+        self.captures = 0
+        self._capture()
+
+    @property
+    def inputs(self):
+        return self.static_imgs
+
+    @property
+    def device(self):
+        return self.static_imgs[0].device
+
+    def load(self, imgs):
+        for buf, img in zip(self.static_imgs, imgs):
+            buf.copy_(img, non_blocking=True)
+
+    def _device_part(self):
+        model = self.model
+        outs = [model.bbox_head(model.extract_feat(buf)) for buf in self.static_imgs]
+        return [model.aug_postprocess_static(outs, self.metas, self.rescale, b) for b in range(self.static_imgs[0].size(0))]
+
+    def decode(self, packed):
+        return [self.model.aug_result_packed(p) for p in packed]
+
+    def fallback(self, imgs):
+        with torch.no_grad():
+            return [self.model.aug_test([img[b:b + 1] for img in imgs], [[m[b]] for m in self.metas], self.rescale)
+                    for b in range(imgs[0].size(0))]
 
 
 class PipelinedInference(object):
@@ -109,7 +181,7 @@ class PipelinedInference(object):
     `rescale` is passed on to it."""
 
     def __init__(self, model, img, img_metas, depth=2, warmup=3, _allow_half=False, rescale=False):
-        dev = img.device
+        dev = img[0].device if isinstance(img, (list, tuple)) else img.device
         if (depth > 2 and not _allow_half and torch.backends.cudnn.deterministic
                 and any(p.dtype != torch.float32 for p in model.parameters())):
             # measured (round 6, tests/checks/half_pipeline_probe.py): with the library restricted to its reproducible solvers
@@ -126,7 +198,7 @@ class PipelinedInference(object):
         prev = getattr(head, 'tower_streams', None)
         head.tower_streams = False
         try:
-            self.slots = [GraphedInference(model, img, img_metas, warmup, rescale) for _ in range(depth)]
+            self.slots = [self._make_slot(model, img, img_metas, warmup, rescale) for _ in range(depth)]
         finally:
             head.tower_streams = prev
         self.streams = [torch.cuda.Stream(device=dev) for _ in range(depth)]
@@ -135,14 +207,15 @@ class PipelinedInference(object):
         self.pending = [None] * depth
         self.count = 0
 
+    _make_slot = staticmethod(GraphedInference)
+
     def _collect(self, k):
         img = self.pending[k]
         self.pending[k] = None
         self.events[k].synchronize()
-        results = [rbbox2result_packed(h, self.num_classes) for h in self.host[k]]
+        results = self.slots[k].decode(self.host[k])
         if any(r is None for r in results):               # static capacity overflow: the reference-shaped path, synchronously
-            with torch.no_grad():
-                return self.model.simple_test_batch(img, self.metas, self.rescale)
+            return self.slots[k].fallback(img)
         return results
 
     def _fresh_slot(self, k):
@@ -160,7 +233,7 @@ class PipelinedInference(object):
 
     def submit_device(self, fill, sink):
         """`submit` for a producer and a consumer that live on the device (`SceneInference`): `fill(static_img)` writes the
-        next slot's input and `sink(packed)` reads its packed results, both on the slot's stream around the replay.  No
+        next slot's input (`fill(list of view buffers)` for `PipelinedAugInference`) and `sink(packed)` reads its packed results, both on the slot's stream around the replay.  No
         host copy and nothing pending: stream order alone keeps a slot's replays apart, the host never waits, and the
         caller makes its own stream wait on `streams` before it uses what `sink` wrote.  Not to be mixed with `submit`
         while results of that are in flight."""
@@ -168,9 +241,9 @@ class PipelinedInference(object):
         if self.pending[k] is not None:
             raise RuntimeError("PipelinedInference.submit_device: results of submit() are still in flight; flush() first")
         slot, s = self._fresh_slot(k), self.streams[k]
-        s.wait_stream(torch.cuda.current_stream(slot.static_img.device))
+        s.wait_stream(torch.cuda.current_stream(slot.device))
         with torch.cuda.stream(s):
-            fill(slot.static_img)
+            fill(slot.inputs)
             slot.graph.replay()
             sink(slot.packed)
         self.count += 1
@@ -179,9 +252,9 @@ class PipelinedInference(object):
         k = self.count % self.depth
         out = self._collect(k) if self.pending[k] is not None else None
         slot, s = self._fresh_slot(k), self.streams[k]
-        s.wait_stream(torch.cuda.current_stream(img.device))     # the image may have been produced on the caller's stream
+        s.wait_stream(torch.cuda.current_stream(slot.device))    # the image may have been produced on the caller's stream
         with torch.cuda.stream(s):
-            slot.static_img.copy_(img, non_blocking=True)
+            slot.load(img)
             slot.graph.replay()
             for h, p in zip(self.host[k], slot.packed):
                 h.copy_(p, non_blocking=True)
@@ -197,3 +270,14 @@ class PipelinedInference(object):
             if self.pending[k] is not None:
                 outs.append(self._collect(k))
         return outs
+
+
+class PipelinedAugInference(PipelinedInference):
+    """`PipelinedInference` over `GraphedAugInference` slots: `img` is the list of view tensors, `img_metas` the per-view meta
+    lists, `submit(imgs)` / `flush()` return `aug_test`'s results per image, and `submit_device(fill, sink)` hands `fill` the
+    slot's list of view buffers.  `rescale` defaults to what a scene's patches need (rows in original-image coordinates)."""
+
+    def __init__(self, model, imgs, img_metas, depth=2, warmup=3, _allow_half=False, rescale=True):
+        super(PipelinedAugInference, self).__init__(model, list(imgs), img_metas, depth, warmup, _allow_half, rescale)
+
+    _make_slot = staticmethod(GraphedAugInference)

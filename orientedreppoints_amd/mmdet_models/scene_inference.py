@@ -8,6 +8,9 @@ host, results to a pickle) -> `tools/parse_pkl/parse_pkl_mege_results_for_dota_e
     tile plan (`dota_devkit.img_split`)  ->  `orp_scene_tiles` / `orp_scene_tiles_resized` straight into a captured graph's
     input buffer  ->  graph replay (`PipelinedInference`)  ->  packed results stay on the device  ->  `orp_scene_collect`
     ->  one `orp_poly_nms_f64_batched`  ->  one gather, one D2H.
+
+With `views` (test-time flip / multi-scale augmentation) every tile batch fills all of its views -- `orp_scene_tiles_flip` /
+`orp_scene_tiles_resized_flip` for the mirrored ones -- and replays one augmented graph (`PipelinedAugInference`).
 """
 import os
 
@@ -18,8 +21,9 @@ import torch.nn.functional as F
 from ..dota_devkit.img_split import scaled_size, split_origins
 from ..mmdet_ops.nms_wrapper import poly_nms_f64_batched_device
 from ..mmdet_datasets.imops import rescale_size
-from ..mmdet_ops.scene_ops import resize_tables, scene_collect, scene_tiles, scene_tiles_resized
-from .graph_inference import PipelinedInference
+from ..mmdet_ops.scene_ops import (resize_tables, scene_collect, scene_tiles, scene_tiles_flip, scene_tiles_resized,
+                                   scene_tiles_resized_flip)
+from .graph_inference import PipelinedAugInference, PipelinedInference
 
 DOTA_CLASSES = ('plane', 'baseball-diamond', 'bridge', 'ground-track-field', 'small-vehicle', 'large-vehicle', 'ship',
                 'tennis-court', 'basketball-court', 'storage-tank', 'soccer-ball-field', 'roundabout', 'harbor',
@@ -38,11 +42,11 @@ class _Plan(object):
 class _Shape(object):
     """What the patches of one shape go through under `img_scale`: src = (w, h) of a patch, new = (w, h) after the resize,
     pad = (w, h) of the detector's input, the scale factor, the metas the host pipeline would set, and (once captured) the
-    graphs of that input shape."""
+    graphs of that input shape.  `img_scale=None` (a native-size view of `_AugShape`): no resize, scale factor 1."""
 
     def __init__(self, src, img_scale, divisor, batch):
         self.src = (int(src[0]), int(src[1]))
-        new_w, new_h, self.scale_factor = rescale_size(self.src, img_scale)
+        new_w, new_h, self.scale_factor = (self.src + (1.0,)) if img_scale is None else rescale_size(self.src, img_scale)
         self.new = (new_w, new_h)
         self.pad = (-(-new_w // divisor) * divisor, -(-new_h // divisor) * divisor)
         # an identity resize of a square patch the divisor leaves alone: `orp_scene_tiles`' case
@@ -50,6 +54,16 @@ class _Shape(object):
         self.metas = [dict(img_shape=(new_h, new_w, 3), pad_shape=(self.pad[1], self.pad[0], 3),
                            scale_factor=self.scale_factor, flip=False) for _ in range(batch)]
         self.pipe = self.tables = None
+
+
+class _AugShape(object):
+    """The views of the patches of one shape (`views=`): per view its `_Shape` and flip flag, the metas `aug_test` takes (per
+    view, one per tile of a batch) and, once captured, the augmented graphs of these input shapes."""
+
+    def __init__(self, shapes, flips):
+        self.views = list(zip(shapes, flips))
+        self.metas = [[dict(m, flip=bool(f)) for m in sh.metas] for sh, f in self.views]
+        self.pipe = None
 
 
 class SceneInference(object):
@@ -76,7 +90,13 @@ class SceneInference(object):
       graphs divide boxes and rep-points by the scale factor before the NMS (`rescale=True`), so their rows are in patch
       coordinates as the file route's are.  Graphs are kept per patch shape (four shapes, oldest dropped).  A patch
       whose resize is the identity goes through `orp_scene_tiles`.
-    * Flip and multi-scale test augmentation (`MultiScaleFlipAug` with `flip=True` or several scales) are not built.
+    * `views=[(img_scale or None, flip), ...]` (at most 8): flip and multi-scale test augmentation, `MultiScaleFlipAug`'s views of
+      every patch in its own order -- `from_config(model, cfg, aug=True)` reads them from the config.  Every tile batch fills all of
+      its views on the device (a view's scale as `img_scale` above, None = native size; a flipped view is mirrored after its resize,
+      inside the resized patch's own width, as `RandomFlip` between `RotateResize` and `Normalize` does) and replays ONE augmented
+      graph: all views' forwards, the candidates mapped back to the patch, one rotated NMS over their union -- `aug_test`, bit
+      for bit.  Its rows are in patch coordinates and go through the same collect and merge.  Rates and views compose: every rate
+      runs all views.  Not to be combined with `img_scale`.  An overflowed tile is re-run through `model.aug_test`.
     * rates != 1: the scene is resampled once on the device with torch's bicubic `interpolate` (`align_corners=False`),
       rounded and clamped to uint8, to `img_split.scaled_size`.  This follows OpenCV's conventions but is NOT checked against
       cv2's `INTER_CUBIC` pixels.  The rate used in coordinates is `float(str(rate))`, as the patch-name grammar implies.
@@ -93,7 +113,8 @@ class SceneInference(object):
     `RotateResize(keep_ratio)`: set `img_scale`).  Segments above `ORP_NMS_MAX_BOXES` raise `OrpHipError` in the merge."""
 
     def __init__(self, model, subsize=1024, gap=200, rates=(1.0,), batch=1, depth=4, nms_thresh=0.1,
-                 mean=(123.675, 116.28, 103.53), std=(58.395, 57.12, 57.375), to_rgb=True, img_scale=None, size_divisor=32):
+                 mean=(123.675, 116.28, 103.53), std=(58.395, 57.12, 57.375), to_rgb=True, img_scale=None, size_divisor=32,
+                 views=None):
         subsize, gap, batch, depth = int(subsize), int(gap), int(batch), int(depth)
         if subsize <= 0 or subsize % 32 != 0:
             raise ValueError("SceneInference: subsize (%d) must be a positive multiple of 32, the test pipeline's Pad divisor" % subsize)
@@ -102,6 +123,9 @@ class SceneInference(object):
             if len(img_scale) != 2 or min(img_scale) <= 0:
                 raise ValueError("SceneInference: img_scale must be None or two positive edge bounds, e.g. (1333, 960)")
         self.img_scale, self.size_divisor = img_scale, int(size_divisor)
+        self.views = None if views is None else self._check_views(views)
+        if self.views is not None and img_scale is not None:
+            raise ValueError("SceneInference: give the scales in views, not in img_scale as well")
         if self.size_divisor <= 0 or self.size_divisor % 8 != 0:
             raise ValueError("SceneInference: size_divisor must be a positive multiple of 8 (16 bytes of an output row per lane)")
         if not 0 <= gap < subsize:
@@ -124,25 +148,50 @@ class SceneInference(object):
                       for _ in range(batch)]
         self.pipe = None                           # the native-size graphs (img_scale=None)
         self._shapes = {}                          # (width, height) of a patch -> _Shape (img_scale set; at most 4)
+        self._aug_shapes = {}                      # (width, height) of a patch -> _AugShape (views set; at most 4)
         self._origins = {}                         # (width, height) of a scaled scene -> (host list, padded device tensor)
         self.fallback_tiles = 0                    # tiles re-run because their packed result overflowed (all calls)
 
+    @staticmethod
+    def _check_views(views):
+        """views -> [(img_scale tuple or None, flip bool)]; ValueError for anything else."""
+        out = []
+        if not isinstance(views, (list, tuple)) or not 1 <= len(views) <= 8:
+            raise ValueError("SceneInference: views must be a list of 1 to 8 (img_scale or None, flip) pairs")
+        for v in views:
+            if not isinstance(v, (list, tuple)) or len(v) != 2 or not isinstance(v[1], (bool, np.bool_)):
+                raise ValueError("SceneInference: a view is (img_scale or None, flip), got %r" % (v,))
+            scale = v[0]
+            if scale is not None:
+                if not isinstance(scale, (list, tuple)) or len(scale) != 2 or \
+                        not all(isinstance(e, (int, np.integer)) and e > 0 for e in scale):
+                    raise ValueError("SceneInference: a view's img_scale must be None or two positive edge bounds, got %r" % (scale,))
+                scale = (int(scale[0]), int(scale[1]))
+            out.append((scale, bool(v[1])))
+        return out
+
     @classmethod
-    def from_config(cls, model, cfg, **kw):
+    def from_config(cls, model, cfg, aug=False, **kw):
         """`SceneInference(model, ...)` with `img_scale`, `mean`, `std`, `to_rgb` and `size_divisor` read from
-        `cfg.data.test.pipeline` (`MultiScaleFlipAug` around `RotateResize` / `Normalize` / `Pad`); keywords override.  Raises
-        ValueError for a pipeline this class does not reproduce: `flip=True`, more than one scale, `keep_ratio=False`, an
-        interpolation other than bilinear, a fixed-size `Pad`."""
+        `cfg.data.test.pipeline` (`MultiScaleFlipAug` around `RotateResize` / `Normalize` / `Pad`); keywords override.  With
+        `aug=True` the pipeline's `flip` and scale list become `views`, in `MultiScaleFlipAug`'s order: for each scale the plain
+        view, then the flipped one if `flip`.  Raises ValueError for a pipeline this class does not reproduce: without `aug=True`,
+        `flip=True` or more than one scale; always `keep_ratio=False`, an interpolation other than bilinear, a fixed-size `Pad`."""
+        want_aug = bool(aug)
         aug = [t for t in cfg.data.test.pipeline if t['type'] == 'MultiScaleFlipAug']
         if len(aug) != 1:
             raise ValueError("SceneInference.from_config: the test pipeline must hold one MultiScaleFlipAug")
         aug = aug[0]
         scales = aug['img_scale'] if isinstance(aug['img_scale'], list) else [aug['img_scale']]
-        if aug.get('flip', False):
-            raise ValueError("SceneInference.from_config: flip=True (test-time flip augmentation) is not reproduced")
-        if len(scales) != 1:
-            raise ValueError("SceneInference.from_config: %d test scales (multi-scale augmentation) are not reproduced" % len(scales))
-        got = dict(img_scale=tuple(scales[0]))
+        flip = bool(aug.get('flip', False))
+        if want_aug:
+            got = dict(views=[(tuple(sc), f) for sc in scales for f in ((False, True) if flip else (False,))])
+        else:
+            if flip:
+                raise ValueError("SceneInference.from_config: flip=True (test-time flip augmentation) is not reproduced")
+            if len(scales) != 1:
+                raise ValueError("SceneInference.from_config: %d test scales (multi-scale augmentation) are not reproduced" % len(scales))
+            got = dict(img_scale=tuple(scales[0]))
         for t in aug['transforms']:
             if t['type'] in ('RotateResize', 'Resize', 'PolyResize'):
                 if not t.get('keep_ratio', True):
@@ -165,6 +214,9 @@ class SceneInference(object):
         out = []
         for r, v in self.rates:
             w, h = (W, H) if v == 1.0 else scaled_size(W, H, v)
+            if self.views is not None:
+                out.append(((w, h), self._aug_shape(r, w, h)))
+                continue
             if self.img_scale is None:
                 if min(w, h) < self.subsize:
                     raise ValueError("SceneInference: the scene at rate %s is %d x %d, smaller than a %d tile (the reference "
@@ -180,6 +232,24 @@ class SceneInference(object):
                 self._shapes[src] = _Shape(src, self.img_scale, self.size_divisor, self.batch)
             out.append(((w, h), self._shapes[src]))
         return out
+
+    def _aug_shape(self, r, w, h):
+        """The `_AugShape` of the patches of a w x h scaled scene (views of one scale share a `_Shape`)."""
+        if min(w, h) < 1:
+            raise ValueError("SceneInference: the scene at rate %s is empty" % r)
+        if min(w, h) < self.subsize and any(sc is None for sc, _ in self.views):
+            raise ValueError("SceneInference: the scene at rate %s is %d x %d, smaller than a %d tile (the reference would "
+                             "upscale such a patch: give the native-size views an img_scale)" % (r, w, h, self.subsize))
+        src = (min(w, self.subsize), min(h, self.subsize))
+        if src not in self._aug_shapes:
+            if len(self._aug_shapes) >= 4:
+                self._aug_shapes.pop(next(iter(self._aug_shapes)))
+            per_scale = {}
+            for sc, _ in self.views:
+                if sc not in per_scale:
+                    per_scale[sc] = _Shape(src, sc, self.size_divisor, self.batch)
+            self._aug_shapes[src] = _AugShape([per_scale[sc] for sc, _ in self.views], [f for _, f in self.views])
+        return self._aug_shapes[src]
 
     def prepare(self, scene):
         """Upload (if needed), resample per rate, plan the tiles, capture the graphs on first use.  Returns the plan."""
@@ -212,6 +282,14 @@ class SceneInference(object):
             plan.origins_dev.append(on_dev)
         for _, shape in planned:
             plan.shapes.append(shape)
+            if isinstance(shape, _AugShape):
+                if shape.pipe is None:
+                    imgs = [torch.zeros((self.batch, 3, sh.pad[1], sh.pad[0]), dtype=p.dtype, device=dev) for sh, _ in shape.views]
+                    shape.pipe = PipelinedAugInference(self.model, imgs, shape.metas, depth=self.depth, rescale=True)
+                for sh, _ in shape.views:                      # the axis tables' upload happens here, not in the tile loop
+                    if not sh.native:
+                        sh.tables = [resize_tables(a, b, dev) for a, b in zip(sh.src, sh.new)]
+                continue
             if shape is None and self.pipe is None:
                 img = torch.zeros((self.batch, 3, self.subsize, self.subsize), dtype=p.dtype, device=dev)
                 self.pipe = PipelinedInference(self.model, img, self.metas, depth=self.depth)
@@ -222,11 +300,16 @@ class SceneInference(object):
                 shape.tables = [resize_tables(a, b, dev) for a, b in zip(shape.src, shape.new)]
         return plan
 
-    def _fill(self, shape, scene, origins, static_img):
-        """The tiles at `origins` of `scene` into a detector input buffer."""
+    def _fill(self, shape, scene, origins, static_img, flip=False):
+        """The tiles at `origins` of `scene` into a detector input buffer (`_AugShape`: every view into its own buffer)."""
+        if isinstance(shape, _AugShape):
+            for (sh, f), buf in zip(shape.views, static_img):
+                self._fill(sh, scene, origins, buf, f)
+            return static_img
         if shape is None or shape.native:
-            return scene_tiles(scene, origins, static_img, self.mean, self.std, self.to_rgb)
-        return scene_tiles_resized(scene, origins, shape.src, shape.new, static_img, self.mean, self.std, self.to_rgb)
+            return (scene_tiles_flip if flip else scene_tiles)(scene, origins, static_img, self.mean, self.std, self.to_rgb)
+        return (scene_tiles_resized_flip if flip else scene_tiles_resized)(scene, origins, shape.src, shape.new, static_img,
+                                                                           self.mean, self.std, self.to_rgb)
 
     @staticmethod
     def _resample(scene, w, h):
@@ -302,17 +385,22 @@ class SceneInference(object):
 
     def _rerun_overflowed(self, plan, i):
         """Rate i has tiles whose packed result overflowed the static capacity: run their batches through
-        `model.simple_test_batch` (which takes the dynamic path for them) and write the rows into the tiles' packed slots."""
+        `model.simple_test_batch` -- `model.aug_test` per tile with `views` -- (which take the dynamic path for them) and write
+        the rows into the tiles' packed slots."""
         packed, on_dev, B = plan.packed[i], plan.origins_dev[i], self.batch
         T, m = len(plan.origins[i]), packed.size(1) - 1
         over = np.nonzero(packed[:T, m, 1].cpu().numpy())[0]
         redo = {}
         shape = plan.shapes[i] if plan.shapes else None
-        img = torch.empty_like((self.pipe if shape is None else shape.pipe).slots[0].static_img)
+        inputs = (self.pipe if shape is None else shape.pipe).slots[0].inputs
+        img = [torch.empty_like(v) for v in inputs] if isinstance(shape, _AugShape) else torch.empty_like(inputs)
         for b in sorted(set(int(t) // B for t in over)):
             self._fill(shape, plan.scenes[i], on_dev[b * B:(b + 1) * B], img)
             with torch.no_grad():
-                if shape is None:
+                if isinstance(shape, _AugShape):               # per class [k, 9]: no rep-points on this route, zeros in their place
+                    results = [[np.concatenate([np.zeros((len(r), 18), np.float32), r], 1) for r in per_class]
+                               for per_class in shape.pipe.slots[0].fallback(img)]
+                elif shape is None:
                     results = self.model.simple_test_batch(img, self.metas)
                 else:
                     results = self.model.simple_test_batch(img, shape.metas, rescale=True)

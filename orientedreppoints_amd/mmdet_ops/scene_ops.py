@@ -1,6 +1,7 @@
 """Thin wrappers of the whole-scene kernels (csrc/orp_scene.hip): `scene_tiles` crops, channel-swaps, normalises and converts
 T tiles of a uint8 scene on the device; `scene_tiles_resized` resamples every patch first (the test pipeline's `RotateResize`)
-and pads behind it; `scene_collect` turns the packed per-tile detections into the per-class fp64
+and pads behind it; `scene_tiles_flip` / `scene_tiles_resized_flip` mirror the patch as the pipeline's `RandomFlip` does (the
+flipped views of test-time augmentation); `scene_collect` turns the packed per-tile detections into the per-class fp64
 segments `poly_nms_f64_batched_device` takes.  All only enqueue work on PyTorch's current stream."""
 import ctypes
 
@@ -12,7 +13,7 @@ from .. import _lib
 _DTYPES = {torch.float32: 0, torch.float16: 1, torch.bfloat16: 2}
 
 
-def scene_tiles(scene, origins, out, mean, std, to_rgb=True):
+def scene_tiles(scene, origins, out, mean, std, to_rgb=True, _entry="orp_scene_tiles"):
     """scene uint8 [H, W, 3] CUDA (any row stride; pixels contiguous), origins int32 [T, 2] CUDA (left, up),
     out [T, 3, S, S] contiguous CUDA float32 / float16 / bfloat16: out[t] = `imnormalize(scene[up:up+S, left:left+S], mean,
     std, to_rgb)` as CHW, rounded once to out's type; pixels outside the scene are 0.  Returns out."""
@@ -30,11 +31,17 @@ def scene_tiles(scene, origins, out, mean, std, to_rgb=True):
     m = (ctypes.c_float * 3)(*[float(v) for v in np.asarray(mean, np.float32).reshape(3)])
     s = (ctypes.c_float * 3)(*[float(v) for v in np.asarray(std, np.float32).reshape(3)])
     with torch.cuda.device(out.device):
-        rc = _lib.lib().orp_scene_tiles(ctypes.c_void_p(scene.data_ptr()), scene.size(0), scene.size(1), scene.stride(0),
-                                        _lib.ptr(origins), origins.size(0), out.size(2), m, s, int(bool(to_rgb)),
-                                        _DTYPES[out.dtype], _lib.ptr(out), _lib.stream_of(out))
-    _lib.check(rc, "orp_scene_tiles")
+        rc = getattr(_lib.lib(), _entry)(ctypes.c_void_p(scene.data_ptr()), scene.size(0), scene.size(1), scene.stride(0),
+                                         _lib.ptr(origins), origins.size(0), out.size(2), m, s, int(bool(to_rgb)),
+                                         _DTYPES[out.dtype], _lib.ptr(out), _lib.stream_of(out))
+    _lib.check(rc, _entry)
     return out
+
+
+def scene_tiles_flip(scene, origins, out, mean, std, to_rgb=True):
+    """`scene_tiles` with the test pipeline's horizontal `RandomFlip` in front of the normalisation: out[t, :, y, x] =
+    scene_tiles(...)[t, :, y, S - 1 - x], bit for bit."""
+    return scene_tiles(scene, origins, out, mean, std, to_rgb, _entry="orp_scene_tiles_flip")
 
 
 def resize_axis(n_in, n_out):
@@ -65,7 +72,7 @@ def resize_tables(n_in, n_out, device):
     return t
 
 
-def scene_tiles_resized(scene, origins, src_size, new_size, out, mean, std, to_rgb=True):
+def scene_tiles_resized(scene, origins, src_size, new_size, out, mean, std, to_rgb=True, _entry="orp_scene_tiles_resized"):
     """scene and origins as for `scene_tiles`; src_size = (src_w, src_h) of every patch, new_size = (new_w, new_h) it is resized
     to; out [T, 3, pad_h, pad_w] contiguous CUDA float32 / float16 / bfloat16 with pad >= new.  out[t, :, :new_h, :new_w] =
     `imnormalize(resize(scene[up:up+src_h, left:left+src_w]), mean, std, to_rgb)` as CHW, the rest 0 -- the test pipeline's
@@ -94,12 +101,19 @@ def scene_tiles_resized(scene, origins, src_size, new_size, out, mean, std, to_r
     m = (ctypes.c_float * 3)(*[float(v) for v in np.asarray(mean, np.float32).reshape(3)])
     s = (ctypes.c_float * 3)(*[float(v) for v in np.asarray(std, np.float32).reshape(3)])
     with torch.cuda.device(out.device):
-        rc = _lib.lib().orp_scene_tiles_resized(ctypes.c_void_p(scene.data_ptr()), scene.size(0), scene.size(1), scene.stride(0),
-                                                _lib.ptr(origins), origins.size(0), src_w, src_h, new_w, new_h, out.size(3),
-                                                out.size(2), _lib.ptr(x_i0), _lib.ptr(x_w1), _lib.ptr(y_i0), _lib.ptr(y_w1), m, s,
-                                                int(bool(to_rgb)), _DTYPES[out.dtype], _lib.ptr(out), _lib.stream_of(out))
-    _lib.check(rc, "orp_scene_tiles_resized")
+        rc = getattr(_lib.lib(), _entry)(ctypes.c_void_p(scene.data_ptr()), scene.size(0), scene.size(1), scene.stride(0),
+                                         _lib.ptr(origins), origins.size(0), src_w, src_h, new_w, new_h, out.size(3),
+                                         out.size(2), _lib.ptr(x_i0), _lib.ptr(x_w1), _lib.ptr(y_i0), _lib.ptr(y_w1), m, s,
+                                         int(bool(to_rgb)), _DTYPES[out.dtype], _lib.ptr(out), _lib.stream_of(out))
+    _lib.check(rc, _entry)
     return out
+
+
+def scene_tiles_resized_flip(scene, origins, src_size, new_size, out, mean, std, to_rgb=True):
+    """`scene_tiles_resized` with the horizontal `RandomFlip` between the resize and the normalisation (Resize -> RandomFlip ->
+    Normalize -> Pad): the mirror is inside the resized patch's own width, out[t, :, y, x] = scene_tiles_resized(...)[t, :, y,
+    new_w - 1 - x] for x < new_w, zeros beyond new_w / new_h as there.  Bit for bit that mirror."""
+    return scene_tiles_resized(scene, origins, src_size, new_size, out, mean, std, to_rgb, _entry="orp_scene_tiles_resized_flip")
 
 
 def scene_collect(packed, origins, rate, num_classes):
