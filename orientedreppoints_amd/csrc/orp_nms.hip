@@ -52,13 +52,8 @@ using orp::Pt;
 typedef unsigned long long u64;
 using orp_tile::TileLds;
 using orp_tile::TermLds;
-using orp_tile::pack_signs;
 
 constexpr int kMaskThreads = 256;   // 4 waves per workgroup
-
-// Development aid (-DORP_NMS_PHASE_PROF, tests/checks/nms_phase_prof.py; macros in orp_tile.hpp): shader-clock cycles
-// thread 0 of every workgroup spends in each phase of a tile, summed over all tiles: [0] staging, [1] phase A,
-// [2] drain (B1..B3: slots 8..12), [3] mask words out, [4] tiles, [5] whole kernel per workgroup, [6] workgroups.
 constexpr int kSweepThreads = 1024;
 constexpr int kSortMax = 8192;      // boxes per segment the one-launch rank + prepare handles (keys staged in 32 KB of LDS)
 constexpr int kNzCap = 8192;        // sparse sweep: non-zero mask words kept in LDS per segment; more -> dense sweep
@@ -80,15 +75,19 @@ __device__ __forceinline__ void prepare_box(const float* __restrict__ s, orp::Qu
   prep[i] = p;
 }
 
+// the segment that holds row i (binary search): seg_off[s] <= i < seg_off[s + 1], given seg_off[0] <= i < seg_off[nseg]
+__device__ __forceinline__ int find_segment(const int32_t* __restrict__ seg_off, int nseg, int i) {
+  int lo = 0, hi = nseg;   // seg_off[lo] <= i < seg_off[hi]
+  while (hi - lo > 1) { const int mid = (lo + hi) >> 1; if (seg_off[mid] <= i) lo = mid; else hi = mid; }
+  return lo;
+}
+
 // ---- stage 1, large segments: keys[i] = (segment << 32) | flipped score ; vals[i] = i, device-wide radix sort ----
 __global__ void make_keys_kernel(const float* __restrict__ dets, int n, const int32_t* __restrict__ seg_off, int nseg,
                                  u64* __restrict__ keys, int32_t* __restrict__ vals) {
   int i = blockIdx.x * blockDim.x + threadIdx.x;
   if (i >= n) return;
-  // binary search the segment of row i
-  int lo = 0, hi = nseg;   // seg_off[lo] <= i < seg_off[hi]
-  while (hi - lo > 1) { int mid = (lo + hi) >> 1; if (seg_off[mid] <= i) lo = mid; else hi = mid; }
-  keys[i] = ((u64)(unsigned)lo << 32) | (u64)float_flip_desc(dets[(size_t)i * 9 + 8]);
+  keys[i] = ((u64)(unsigned)find_segment(seg_off, nseg, i) << 32) | (u64)float_flip_desc(dets[(size_t)i * 9 + 8]);
   vals[i] = i;
 }
 
@@ -168,8 +167,8 @@ nms_rankprep_kernel(const float* __restrict__ dets, int32_t* __restrict__ seg_of
 }
 
 // ---- mask kernel -------------------------------------------------------------------------------------------
-// grid = (max_cb, row_groups, nseg); block = 256.  Block (c, g, s) owns the tile rows [g*RB, +RB) x columns
-// [64c, 64c+64) of segment s (RB = 4 * rows_per_wave <= 64), in two phases:
+// grid = (bounded tile count, 1, nseg); block = 256.  A workgroup loops over upper-triangular tiles of its segment (TileMap
+// below); a tile is the rows [g*RB, +RB) x columns [64c, 64c+64) (RB = 4 * rows_per_wave <= 64), done in two phases:
 //   A  lane = column, the wave's row is uniform (scalar loads of its QuadPrep): orp::pair_is_far decides -- without a
 //      division -- that every fan term of the pair is exactly 0 (84 % of the pairs of a dense DOTA scene).  Resolved
 //      pairs set their bit by one wavefront ballot; the others go to a workgroup queue in LDS;
@@ -178,138 +177,36 @@ nms_rankprep_kernel(const float* __restrict__ dets, int32_t* __restrict__ seg_of
 //      lane per TERM -- the register decision tree of orp_quadfast.hpp (generic polygon loop only for the ~1e-4 of
 //      terms the tree does not cover); B3 one lane per pair -- ordered sum, threshold, atomicOr into the row's word.
 //      Heavy work is thus packed densely into wavefronts instead of idling next to resolved pairs.
-// one (rpb rows x 64 columns) tile: phase A, queue, phase B, mask words out
-// Compile-time switches of the round-3 changes (tools/build_variant.py builds A/B variants with -D...=0 / 1; measured on the
-// 2 000-box, 15-class scene of the bench, profiles/r03_nms_variants_*.log, r03_nms_decomp_a.log):
-//   ORP_NMS_ROWLDS    (off) phase A reads its wave-uniform row (vertices, max |coordinate|, |area|, flags) from the tile's LDS
-//                     copy with the NEXT row's reads issued before the current row's arithmetic, instead of ~11 scalar
-//                     global loads per row in front of it; the unresolved columns of a row are parked as one mask word
-//                     and filed after the row loop with ONE LDS reservation per wave.  Measured slower: the row operands
-//                     move from SGPRs to VGPRs and the VALU count, which is what bounds the kernel, goes up
-//   ORP_NMS_DIAGLAST  (on) tiles on the diagonal (half of their pairs are below it: half the work) are enumerated last, so
-//                     the final partial round of workgroups is made of the cheap tiles
-//   ORP_NMS_XCD       (on, where it applies) XCD-aware tile map for single segments whose column-block count is a multiple
-//                     of 16 (2 048-box capacity launches): workgroup b (XCD b % 8 on gfx950) only visits the column blocks of
-//                     its XCD's set, so a column record is fetched into ONE L2 (FETCH 2.7 -> 2.2 MB per launch)
-//   ORP_NMS_AGGAPPEND (on) the non-zero words of a tile are appended to the segment's side list with one reservation per tile
-//                     (WRITE 2.4 -> 1.4 MB per launch)
-// Together with the padded edge tables (SQ_LDS_BANK_CONFLICT / SQ_LDS_IDX_ACTIVE 0.46 -> 0.33): 83 -> 75 us.  What bounds the
-// kernel is fp32 VALU issue: per-workgroup timeline (ORP_NMS_PHASE_PROF) shows 4 resident workgroups per CU for the first
-// 45 us of the launch, phase A 22 k + drain 28 k of the 57 k cycles of a tile, and the timing-only variants (ORP_NMS_DBG) put
-// the classifier alone at 34 us, the term evaluation at another 47 us.
-#ifndef ORP_NMS_ROWLDS
-#define ORP_NMS_ROWLDS 0
-#endif
-#ifndef ORP_NMS_DIAGLAST
-#define ORP_NMS_DIAGLAST 1
-#endif
-#ifndef ORP_NMS_XCD
-#define ORP_NMS_XCD 1
-#endif
-#ifndef ORP_NMS_AGGAPPEND
-#define ORP_NMS_AGGAPPEND 1
-#endif
-
+// Rejected alternatives, one line each (2 000-box, 15-class scene of the bench; docs/notebook/kernels_rounds1-5.md):
+//   phase A reading its row from the tile's LDS copy instead of ~11 scalar loads: slower, the row operands move from SGPRs to VGPRs and VALU issue bounds the kernel (profiles/r03_nms_variants_a.log)
+//   one side-list reservation per non-zero word instead of one per tile: WRITE 2.4 instead of 1.4 MB per launch, same time (profiles/r03_nms_variants_a.log, variant noagg)
+// mask_tile: one (rpb rows x 64 columns) tile -- staging, phase A, queue, phase B, mask words out
 template <bool GUARD>
 __device__ __forceinline__ void mask_tile(TileLds& T, TermLds& X, const orp::QuadPrep* __restrict__ prep, int s0, int n, int c,
                                           int row_base, int rpb, int rows_per_wave, int mask_stride, float thr,
-                                          u64* __restrict__ mask, int dbg, int* __restrict__ nz_count,
-                                          unsigned* __restrict__ nz_rc) {
+                                          u64* __restrict__ mask, int* __restrict__ nz_count, unsigned* __restrict__ nz_rc) {
   const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63;
-  ORP_PHASE_T(pt0);
 
   // ---- stage the tile's row / column records in LDS (phase B reads them with per-lane indices) ----------------
   const int col = c * 64 + lane;
   orp::FarCol fc;
   {
-    orp::QuadPrep cp;
-    if (col < n) {
-      cp = prep[s0 + col];
-    } else {
-#pragma unroll
-      for (int k = 0; k < 4; k++) { cp.ax[k] = cp.ay[k] = cp.bx[k] = cp.by[k] = cp.vx[k] = cp.vy[k] = 0.f; cp.s[k] = 0; }
-      cp.area_abs = 0.f; cp.force_slow = 0; cp.mabs = 0.f;
-    }
+    const orp::QuadPrep cp = (col < n) ? prep[s0 + col] : orp::quad_prep_empty<float>();
     fc = orp::far_col(cp);
-    if (wave == 0) {
-#pragma unroll
-      for (int k = 0; k < 4; k++) T.colE[k][lane] = make_float4(cp.ax[k], cp.ay[k], cp.bx[k], cp.by[k]);
-      T.colS[lane] = pack_signs(cp);
-      T.colArea[lane] = cp.area_abs;
-      X.colM[lane] = cp.mabs;
-    }
+    if (wave == 0) orp_tile::stage_col(T, X, lane, cp);
     if (tid < rpb) {
-      const int r = row_base + tid;
-      if (r < n) {
-        const orp::QuadPrep rp = prep[s0 + r];
-#pragma unroll
-        for (int k = 0; k < 4; k++) T.rowE[k][tid] = make_float4(rp.ax[k], rp.ay[k], rp.bx[k], rp.by[k]);
-        T.rowS[tid] = pack_signs(rp);
-        T.rowArea[tid] = rp.area_abs;
-        X.rowM[tid] = rp.mabs;
-#if ORP_NMS_ROWLDS
-        T.rowV[0][tid] = make_float4(rp.vx[0], rp.vx[1], rp.vx[2], rp.vx[3]);
-        T.rowV[1][tid] = make_float4(rp.vy[0], rp.vy[1], rp.vy[2], rp.vy[3]);
-#endif
-      }
+      if (row_base + tid < n) orp_tile::stage_row(T, X, tid, prep[s0 + row_base + tid]);
       T.words[tid] = 0ull;
     }
     if (tid == 0) T.qcount = 0;
     orp_tile::term_lds_reset(X, tid);
   }
   __syncthreads();
-  ORP_PHASE_T(pt1);
   const bool cslow = (T.colS[lane] >> 8) != 0;
   const float carea = T.colArea[lane];
 
   // ---- phase A ---------------------------------------------------------------------------------------------------
   const int rl_first = __builtin_amdgcn_readfirstlane(wave * rows_per_wave);
-#if ORP_NMS_ROWLDS
-  {
-    // rows of this wave that exist (uniform); the row record comes from LDS (same address in every lane: broadcast)
-    int nrows = n - (row_base + rl_first);
-    nrows = nrows < 0 ? 0 : (nrows > rows_per_wave ? rows_per_wave : nrows);
-    float4 vx4 = make_float4(0.f, 0.f, 0.f, 0.f), vy4 = vx4;
-    float rm = 0.f, rarea = 0.f;
-    int rflags = 0;
-    if (nrows > 0) {
-      vx4 = T.rowV[0][rl_first]; vy4 = T.rowV[1][rl_first];
-      rm = X.rowM[rl_first]; rarea = T.rowArea[rl_first]; rflags = T.rowS[rl_first];
-    }
-    int wave_total = 0;
-    for (int rr = 0; rr < nrows; rr++) {
-      const int rl = rl_first + rr;                      // wave-uniform
-      const int r = row_base + rl;
-      const float rvx[4] = {vx4.x, vx4.y, vx4.z, vx4.w}, rvy[4] = {vy4.x, vy4.y, vy4.z, vy4.w};
-      const float crm = rm, crarea = rarea;
-      const bool rslow = (rflags >> 8) != 0;
-      if (rr + 1 < nrows) {                              // next row's reads fly during this row's arithmetic
-        vx4 = T.rowV[0][rl + 1]; vy4 = T.rowV[1][rl + 1];
-        rm = X.rowM[rl + 1]; rarea = T.rowArea[rl + 1]; rflags = T.rowS[rl + 1];
-      }
-      const bool valid = (col < n) & (col > r);
-      bool resolved = false;
-      if (valid && !(cslow | rslow)) resolved = (dbg & 2) ? true : orp::pair_is_far(rvx, rvy, crm, fc);
-      const bool hit0 = resolved && (orp::iou_of_zero_inter<GUARD>(crarea, carea) > thr);
-      const u64 bits = __ballot(hit0);
-      const u64 pmask = __ballot(valid && !resolved);
-      wave_total += __popcll(pmask);
-      if (lane == 0) { T.pend[rl] = pmask; if (bits) T.words[rl] = bits; }   // this wave owns row rl in phase A
-    }
-    // file the wave's unresolved pairs: one reservation, rows in order, columns ascending within a row
-    if (wave_total > 0) {
-      int base = 0;
-      if (lane == 0) base = atomicAdd(&T.qcount, wave_total);
-      base = __builtin_amdgcn_readfirstlane(base);
-      for (int rr = 0; rr < nrows; rr++) {
-        const int rl = rl_first + rr;
-        const u64 pm = T.pend[rl];                       // written by this wave's lane 0 above (same wave: in order)
-        if ((pm >> lane) & 1ull) T.queue[base + __popcll(pm & ((1ull << lane) - 1ull))] = (unsigned short)((rl << 6) | lane);
-        base += __popcll(pm);
-      }
-    }
-  }
-#else
   for (int rr = 0; rr < rows_per_wave; rr++) {
     const int rl = rl_first + rr;                        // wave-uniform
     const int r = row_base + rl;
@@ -321,35 +218,20 @@ __device__ __forceinline__ void mask_tile(TileLds& T, TermLds& X, const orp::Qua
       float rvx[4], rvy[4];
 #pragma unroll
       for (int k = 0; k < 4; k++) { rvx[k] = rp->vx[k]; rvy[k] = rp->vy[k]; }
-      resolved = (dbg & 2) ? true : orp::pair_is_far(rvx, rvy, rp->mabs, fc);
+      resolved = orp::pair_is_far(rvx, rvy, rp->mabs, fc);
     }
     const bool hit0 = resolved && (orp::iou_of_zero_inter<GUARD>(rp->area_abs, carea) > thr);
     const u64 bits = __ballot(hit0);
-    const bool pend = valid && !resolved;
-    const u64 pmask = __ballot(pend);
-    if (pmask) {
-      int base = 0;
-      if (lane == 0) base = atomicAdd(&T.qcount, __popcll(pmask));
-      base = __builtin_amdgcn_readfirstlane(base);
-      if (pend) {
-        const int pos = base + __popcll(pmask & ((1ull << lane) - 1ull));
-        T.queue[pos] = (unsigned short)((rl << 6) | lane);
-      }
-    }
+    orp_tile::queue_pending(T, rl, lane, valid && !resolved);
     if (lane == 0 && bits) T.words[rl] = bits;          // this wave owns row rl in phase A
   }
-#endif
   __syncthreads();
-  ORP_PHASE_T(pt2);
 
   // ---- phase B: per-term screen, one surviving fan term per lane, ordered sum per pair (orp_tile.hpp) ----------
-  const int nq = (dbg & 1) ? 0 : T.qcount;
-  orp_tile::tile_drain_terms<GUARD>(T, X, nq, [&](int rl, int cl, float iou) {
+  orp_tile::tile_drain_terms<GUARD>(T, X, T.qcount, [&](int rl, int cl, float iou) {
     if (iou > thr) atomicOr(&T.words[rl], 1ull << cl);
-  }, dbg);
+  });
   __syncthreads();
-  ORP_PHASE_T(pt3);
-#if ORP_NMS_AGGAPPEND
   if (wave == 0) {                                       // rpb <= 64: the tile's rows are the lanes of wave 0
     const bool have = (lane < rpb) && (row_base + lane < n);
     const u64 w = have ? T.words[lane] : 0ull;
@@ -363,21 +245,6 @@ __device__ __forceinline__ void mask_tile(TileLds& T, TermLds& X, const orp::Qua
       if (w != 0ull && pos < kNzCap) nz_rc[pos] = ((unsigned)(row_base + lane) << 11) | (unsigned)c;
     }
   }
-#else
-  if (tid < rpb && row_base + tid < n) {
-    const u64 w = T.words[tid];
-    mask[(size_t)(c) * mask_stride + (s0 + row_base + tid)] = w;
-    if (w) {                                             // sparse side list of this segment for the LDS-resident sweep
-      const int pos = atomicAdd(nz_count, 1);
-      if (pos < kNzCap) nz_rc[pos] = ((unsigned)(row_base + tid) << 11) | (unsigned)c;
-    }
-  }
-#endif
-#ifdef ORP_NMS_PHASE_PROF
-  { ORP_PHASE_T(pt4);
-    ORP_PHASE_ADD(0, pt0, pt1); ORP_PHASE_ADD(1, pt1, pt2); ORP_PHASE_ADD(2, pt2, pt3); ORP_PHASE_ADD(3, pt3, pt4);
-    ORP_PHASE_ADD(4, 0ull, 1ull); }
-#endif
 }
 
 // ---- tile enumeration ---------------------------------------------------------------------------------------------------
@@ -395,7 +262,9 @@ struct TileMap {
     n_full = full_before(last);                                       // the last batch has no full tile
     n_diag = ngroups;                                                 // one diagonal tile per row group
   }
-  // t in [0, n_full + n_diag): full tiles first (batch by batch, row group by row group), then the diagonal tiles
+  // t in [0, n_full + n_diag): full tiles first (batch by batch, row group by row group), then the diagonal tiles, so that
+  // the last partial round of workgroups is made of the cheap tiles (the diagonal tile first in every row group measured
+  // the same within noise, 81.3 vs 84.3 us: profiles/r03_nms_variants_a.log, variant nodiag)
   __device__ __forceinline__ void decode_diag_last(long t, int& g, int& c) const {
     if (t >= n_full) { g = (int)(t - n_full); c = g / q; return; }
     const double b = 2.0 * cbn - 1.0;
@@ -405,19 +274,6 @@ struct TileMap {
     while (j + 1 < last && full_before(j + 1) <= t) j++;
     const int r = (int)(t - full_before(j)), w = cbn - 1 - j;
     g = j * q + r / w; c = j + 1 + r % w;
-  }
-  // round-2 order: batch by batch, the diagonal tile first in every row group
-  __device__ __forceinline__ long any_before(int j) const { return (long)q * ((long)j * cbn - (long)j * (j - 1) / 2); }
-  __device__ __forceinline__ void decode_row_major(long t, int& g, int& c) const {
-    const long t_last = any_before(last);
-    if (t >= t_last) { g = last * q + (int)(t - t_last); c = last; return; }
-    const double b = 2.0 * cbn + 1.0;
-    int j = (int)((b - sqrt(b * b - 8.0 * (double)t / (double)q)) * 0.5);
-    j = j < 0 ? 0 : (j > last - 1 ? last - 1 : j);
-    while (j > 0 && any_before(j) > t) j--;
-    while (j + 1 < last && any_before(j + 1) <= t) j++;
-    const int r = (int)(t - any_before(j)), w = cbn - j;
-    g = j * q + r / w; c = j + r % w;
   }
   // XCD-aware lists: XCD x owns the column blocks c_m = 8m + (m even ? x : 7 - x) (boustrophedon: the tile counts of
   // the eight lists differ by at most one column's worth).  List x: the full tiles of its columns (column c has q*c of
@@ -446,20 +302,14 @@ struct TileMap {
 // an 8 K capacity holding 2 K boxes must not pay for 60 K empty workgroups).  A bounded grid of workgroups loops over the
 // UPPER-TRIANGULAR tiles of the actual count (enumerated in closed form; lower-triangular tiles are never read by the
 // sweep), which also balances the load: 117 -> 83 us at 2000 boxes against one workgroup per tile of the full grid.
-#ifndef ORP_MASK_WGS
-#define ORP_MASK_WGS 4
-#endif
+constexpr int kMaskWgs = 4;         // resident workgroups per CU asked for; 6 and 8 measured slower (profiles/r06_nms_occupancy.log)
 template <bool GUARD>
-__global__ void __launch_bounds__(kMaskThreads, ORP_MASK_WGS)
+__global__ void __launch_bounds__(kMaskThreads, kMaskWgs)
 nms_mask_loop_kernel(const orp::QuadPrep* __restrict__ prep, const int32_t* __restrict__ seg_off, int rows_per_wave,
-                     int mask_stride, float thr, u64* __restrict__ mask, int dbg, int* __restrict__ nz_count,
-                     unsigned* __restrict__ nz_rc, int xcd_map) {
+                     int mask_stride, float thr, u64* __restrict__ mask, int* __restrict__ nz_count,
+                     unsigned* __restrict__ nz_rc, bool single_segment) {
   __shared__ TileLds T;
   __shared__ TermLds X;
-  ORP_PHASE_T(pk0);
-#ifdef ORP_NMS_PHASE_PROF
-  if (threadIdx.x == 0) orp_tile::g_phase_cycles[(blockIdx.x % orp_tile::kPhaseRows) * 16 + 13] = wall_clock64();   // 100 MHz, chip-wide
-#endif
   const int seg = blockIdx.z;
   const int s0 = seg_off[seg], n = seg_off[seg + 1] - s0;
   const int rpb = rows_per_wave * (kMaskThreads / 64);
@@ -469,7 +319,7 @@ nms_mask_loop_kernel(const orp::QuadPrep* __restrict__ prep, const int32_t* __re
   const long total_tiles = M.n_full + M.n_diag;
   // gfx950 places workgroup b on XCD b % 8 (observed, used for speed only: any placement gives the same mask)
   // (only when the eight lists are equally long: a multiple of 16 column blocks)
-  const bool xcd = ORP_NMS_XCD && (xcd_map & 1) && M.cbn >= 16 && (M.cbn & 15) == 0 && (gridDim.x & 7) == 0;
+  const bool xcd = single_segment && M.cbn >= 16 && (M.cbn & 15) == 0 && (gridDim.x & 7) == 0;
   const int x = blockIdx.x & 7;
   const long step = xcd ? (long)(gridDim.x >> 3) : (long)gridDim.x;
   for (long k = xcd ? (long)(blockIdx.x >> 3) : (long)blockIdx.x;; k += step) {
@@ -479,17 +329,13 @@ nms_mask_loop_kernel(const orp::QuadPrep* __restrict__ prep, const int32_t* __re
       row_base = g * rpb;
     } else {
       if (k >= total_tiles) break;
-      if (ORP_NMS_DIAGLAST) M.decode_diag_last(k, g, c); else M.decode_row_major(k, g, c);
+      M.decode_diag_last(k, g, c);
       row_base = g * rpb;
     }
-    mask_tile<GUARD>(T, X, prep, s0, n, c, row_base, rpb, rows_per_wave, mask_stride, thr, mask, dbg, nz_count + seg,
+    mask_tile<GUARD>(T, X, prep, s0, n, c, row_base, rpb, rows_per_wave, mask_stride, thr, mask, nz_count + seg,
                      nz_rc + (size_t)seg * kNzCap);
     __syncthreads();                                     // the LDS tile is reused by the next tile
   }
-#ifdef ORP_NMS_PHASE_PROF
-  { ORP_PHASE_T(pk1); ORP_PHASE_ADD(5, pk0, pk1); ORP_PHASE_ADD(6, 0ull, 1ull);
-    if (threadIdx.x == 0) orp_tile::g_phase_cycles[(blockIdx.x % orp_tile::kPhaseRows) * 16 + 14] = wall_clock64(); }
-#endif
 }
 
 // ---- fp64 mask kernel: the merge NMS of DOTA_devkit/ResultMerge.py (polyiou.cpp arithmetic) -------------------------
@@ -519,14 +365,7 @@ nms_mask_f64_kernel(const orp::QuadPrepT<double>* __restrict__ prep, int n, int 
   if (row_base >= n || c * 64 >= n) return;
   if ((row_base >> 6) > c) return;
   const int col = c * 64 + lane;
-  orp::QuadPrepT<double> cp;
-  if (col < n) {
-    cp = prep[col];
-  } else {
-#pragma unroll
-    for (int k = 0; k < 4; k++) { cp.ax[k] = cp.ay[k] = cp.bx[k] = cp.by[k] = cp.vx[k] = cp.vy[k] = 0.0; cp.s[k] = 0; }
-    cp.area_abs = 0.0; cp.force_slow = 0; cp.mabs = 0.0; cp.pad0 = 0.0;
-  }
+  const orp::QuadPrepT<double> cp = (col < n) ? prep[col] : orp::quad_prep_empty<double>();
   const int r_first = __builtin_amdgcn_readfirstlane(row_base + wave * rows_per_wave);
   for (int rr = 0; rr < rows_per_wave; rr++) {
     const int r = r_first + rr;
@@ -591,9 +430,7 @@ __global__ void seg_keys_kernel(const int32_t* __restrict__ vals, int n, const i
   const int i = vals[k];
   if (i < seg_off[0]) { keys[k] = 0ull; return; }
   if (i >= seg_off[nseg]) { keys[k] = (u64)nseg + 1ull; return; }
-  int lo = 0, hi = nseg;   // seg_off[lo] <= i < seg_off[hi]
-  while (hi - lo > 1) { const int mid = (lo + hi) >> 1; if (seg_off[mid] <= i) lo = mid; else hi = mid; }
-  keys[k] = (u64)lo + 1ull;
+  keys[k] = (u64)find_segment(seg_off, nseg, i) + 1ull;
 }
 
 __global__ void prep_boxes_f64_seg_kernel(const double* __restrict__ dets, const int32_t* __restrict__ order, int n,
@@ -678,14 +515,7 @@ nms_mask_f64_seg_kernel(const orp::QuadPrepT<double>* __restrict__ prep, const H
       if (lane < r_last - r_first) mask[(size_t)(c) * mask_stride + (s0 + r_first + lane)] = 0ull;
       continue;
     }
-    orp::QuadPrepT<double> cp;
-    if (col_ok) {
-      cp = prep[s0 + col];
-    } else {
-#pragma unroll
-      for (int q = 0; q < 4; q++) { cp.ax[q] = cp.ay[q] = cp.bx[q] = cp.by[q] = cp.vx[q] = cp.vy[q] = 0.0; cp.s[q] = 0; }
-      cp.area_abs = 0.0; cp.force_slow = 0; cp.mabs = 0.0; cp.pad0 = 0.0;
-    }
+    const orp::QuadPrepT<double> cp = col_ok ? prep[s0 + col] : orp::quad_prep_empty<double>();
     for (int r = r_first; r < r_last; r++) {
       bool hit = false;
       if (col_ok && col > r) {
@@ -720,28 +550,61 @@ nms_mask_f64_seg_kernel(const orp::QuadPrepT<double>* __restrict__ prep, const H
 //   [0,8) kept word | [16, 16+4096) scan scratch | removed[cb] u64 | keepbits[cb] u64 | origbits[cb] u64
 constexpr size_t kSweepHdr = 16 + sizeof(int) * kSweepThreads;
 
-// exclusive prefix (over the whole block, chunk by chunk) of popcounts of words[0..nw); calls emit(i, word, offset)
-template <typename Emit>
-__device__ __forceinline__ int popc_scan_emit(const u64* words, int nw, int* tmp, Emit emit) {
+// Chunked exclusive scan over the whole block through tmp[kSweepThreads]: emit(i, value(0) + .. + value(i - 1)) for every
+// i in [0, nw); returns the total.  Every thread calls it (barriers); what emit writes to LDS is visible on return.
+template <typename Value, typename Emit>
+__device__ __forceinline__ int block_scan_emit(int nw, int* tmp, Value value, Emit emit) {
   const int tid = threadIdx.x;
   int running = 0;
   for (int base = 0; base < nw; base += kSweepThreads) {
     const int i = base + tid;
-    const int cnt = (i < nw) ? __popcll(words[i]) : 0;
-    tmp[tid] = cnt;
+    const int v = (i < nw) ? value(i) : 0;
+    tmp[tid] = v;
     __syncthreads();
     for (int off = 1; off < kSweepThreads; off <<= 1) {
-      int v = (tid >= off) ? tmp[tid - off] : 0;
+      const int u = (tid >= off) ? tmp[tid - off] : 0;
       __syncthreads();
-      tmp[tid] += v;
+      tmp[tid] += u;
       __syncthreads();
     }
-    if (i < nw) emit(i, words[i], running + tmp[tid] - cnt);
+    if (i < nw) emit(i, running + tmp[tid] - v);
     const int chunk_total = tmp[kSweepThreads - 1];
     __syncthreads();
     running += chunk_total;
   }
   return running;
+}
+
+// The greedy pass inside one 64-row block, by one whole wave: lane = row, d = the row's diagonal mask word (the columns
+// of its own block), removed0 = the block's rows that earlier blocks suppressed (any lane's copy), valid = rows the
+// block has.  Only rows with a non-zero word can suppress; they are visited in ascending order, their word fetched
+// with readlane.  Returns the rows that are kept (wave-uniform).
+__device__ __forceinline__ u64 diag_pass(u64 d, u64 removed0, int valid) {
+  const unsigned clo = (unsigned)__builtin_amdgcn_readfirstlane((int)(unsigned)removed0);
+  const unsigned chi = (unsigned)__builtin_amdgcn_readfirstlane((int)(unsigned)(removed0 >> 32));
+  u64 cur = ((u64)chi << 32) | clo;
+  valid = __builtin_amdgcn_readfirstlane(valid);
+  const u64 vmask = (valid >= 64) ? ~0ull : ((1ull << valid) - 1ull);
+  const int dlo = (int)(unsigned)d, dhi = (int)(unsigned)(d >> 32);
+  u64 todo = __ballot(d != 0ull) & vmask;
+  while (todo) {                                         // wave-uniform
+    const int kk = __ffsll((long long)todo) - 1;
+    todo &= todo - 1;
+    if (!((cur >> kk) & 1ull))
+      cur |= ((u64)(unsigned)__builtin_amdgcn_readlane(dhi, kk) << 32) | (u64)(unsigned)__builtin_amdgcn_readlane(dlo, kk);
+  }
+  return ~cur & vmask;
+}
+
+// keep flags by visiting position -> keep flags by ORIGINAL index (segment-local); orig must be zero, barrier afterwards
+__device__ __forceinline__ void scatter_keep_to_original(const u64* keepbits, u64* orig, const int32_t* __restrict__ order,
+                                                         int s0, int n) {
+  for (int i = threadIdx.x; i < n; i += kSweepThreads) {
+    if ((keepbits[i >> 6] >> (i & 63)) & 1ull) {
+      const int o = order[s0 + i] - s0;
+      atomicOr(&orig[o >> 6], 1ull << (o & 63));
+    }
+  }
 }
 
 // ---- sweep of a small segment (<= 4096 boxes, sparse list fits): the serial part by ONE wave ---------------------------
@@ -801,22 +664,8 @@ __device__ __forceinline__ void sweep_small(unsigned char* smem, const u64* __re
   __syncthreads();
   if (wave == 0) {
     for (int blk = 0; blk < cb; blk++) {
-      const u64 d = diagw[blk * 64 + lane];
-      const u64 cur0 = removed[blk];                       // same address for the whole wave: broadcast
-      unsigned clo = (unsigned)__builtin_amdgcn_readfirstlane((int)(unsigned)cur0);
-      unsigned chi = (unsigned)__builtin_amdgcn_readfirstlane((int)(unsigned)(cur0 >> 32));
-      u64 cur = ((u64)chi << 32) | clo;
-      const int valid = min(64, n - blk * 64);
-      const u64 vmask = (valid >= 64) ? ~0ull : ((1ull << valid) - 1ull);
-      const int dlo = (int)(unsigned)d, dhi = (int)(unsigned)(d >> 32);
-      u64 todo = __ballot(d != 0ull) & vmask;              // rows that can suppress inside this block
-      while (todo) {                                       // wave-uniform, ascending row order
-        const int kk = __ffsll((long long)todo) - 1;
-        todo &= todo - 1;
-        if (!((cur >> kk) & 1ull))
-          cur |= ((u64)(unsigned)__builtin_amdgcn_readlane(dhi, kk) << 32) | (u64)(unsigned)__builtin_amdgcn_readlane(dlo, kk);
-      }
-      const u64 kept = ~cur & vmask;
+      // removed[blk]: the same address for the whole wave, a broadcast read
+      const u64 kept = diag_pass(diagw[blk * 64 + lane], removed[blk], min(64, n - blk * 64));
       if (lane == 0) keepbits[blk] = kept;
       const int b0 = blk ? bend[blk - 1] : 0, b1 = bend[blk];
       for (int i = b0 + lane; i < b1; i += 64) {
@@ -831,12 +680,7 @@ __device__ __forceinline__ void sweep_small(unsigned char* smem, const u64* __re
   // ---- compaction ----------------------------------------------------------------------------------------------------------
   const u64* bits = keepbits;                               // visiting order: positions are the answer's order
   if (order_out != 1) {                                    // ascending original index: scatter the flags first
-    for (int i = tid; i < n; i += kSweepThreads) {
-      if ((keepbits[i >> 6] >> (i & 63)) & 1ull) {
-        const int o = order[s0 + i] - s0;
-        atomicOr(&origbits[o >> 6], 1ull << (o & 63));
-      }
-    }
+    scatter_keep_to_original(keepbits, origbits, order, s0, n);
     __syncthreads();
     bits = origbits;
   }
@@ -903,26 +747,8 @@ nms_sweep_kernel(const u64* __restrict__ mask, const int32_t* __restrict__ order
     __syncthreads();
     for (int i = tid; i < nnz; i += kSweepThreads) atomicAdd(&bend[my_rc[i] >> 17], 1);
     __syncthreads();
-    // exclusive scan of the bucket sizes (cb <= 2048), chunk by chunk through tmp
-    {
-      int running = 0;
-      for (int base = 0; base < cb; base += kSweepThreads) {
-        const int i = base + tid;
-        const int v = (i < cb) ? bend[i] : 0;
-        tmp[tid] = v;
-        __syncthreads();
-        for (int off = 1; off < kSweepThreads; off <<= 1) {
-          const int u = (tid >= off) ? tmp[tid - off] : 0;
-          __syncthreads();
-          tmp[tid] += u;
-          __syncthreads();
-        }
-        if (i < cb) bend[i] = running + tmp[tid] - v;               // start of bucket i (becomes its end below)
-        const int chunk_total = tmp[kSweepThreads - 1];
-        __syncthreads();
-        running += chunk_total;
-      }
-    }
+    // bucket sizes (cb <= 2048) -> start of every bucket (becomes its end below)
+    block_scan_emit(cb, tmp, [&](int i) { return bend[i]; }, [&](int i, int start) { bend[i] = start; });
     for (int i = tid; i < nnz; i += kSweepThreads) {
       const unsigned rc = my_rc[i];
       const int pos = atomicAdd(&bend[rc >> 17], 1);
@@ -938,21 +764,7 @@ nms_sweep_kernel(const u64* __restrict__ mask, const int32_t* __restrict__ order
       if (wave == 0) {
         const u64 d = diag[(blk & 1) * 64 + lane];
         diag[(blk & 1) * 64 + lane] = 0ull;                       // this buffer is refilled for block blk + 2
-        const u64 cur0 = removed[blk];
-        unsigned clo = (unsigned)__builtin_amdgcn_readfirstlane((int)(unsigned)cur0);
-        unsigned chi = (unsigned)__builtin_amdgcn_readfirstlane((int)(unsigned)(cur0 >> 32));
-        u64 cur = ((u64)chi << 32) | clo;
-        const int valid = __builtin_amdgcn_readfirstlane(min(64, n - blk * 64));
-        const u64 vmask = (valid >= 64) ? ~0ull : ((1ull << valid) - 1ull);
-        const int dlo = (int)(unsigned)d, dhi = (int)(unsigned)(d >> 32);
-        u64 todo = __ballot(d != 0ull) & vmask;
-        while (todo) {
-          const int kk = __ffsll((long long)todo) - 1;
-          todo &= todo - 1;
-          if (!((cur >> kk) & 1ull))
-            cur |= ((u64)(unsigned)__builtin_amdgcn_readlane(dhi, kk) << 32) | (u64)(unsigned)__builtin_amdgcn_readlane(dlo, kk);
-        }
-        const u64 kept = ~cur & vmask;
+        const u64 kept = diag_pass(d, removed[blk], min(64, n - blk * 64));
         if (lane == 0) { *s_kept = kept; keepbits[blk] = kept; }
       }
       __syncthreads();
@@ -1001,21 +813,7 @@ nms_sweep_kernel(const u64* __restrict__ mask, const int32_t* __restrict__ order
       const u64 d = d_next;
       const int nrow = (blk + 1) * 64 + lane;
       d_next = (blk + 1 < cb && nrow < n) ? mask[(size_t)(blk + 1) * mask_stride + (s0 + nrow)] : 0ull;
-      const u64 cur0 = removed[blk];
-      unsigned clo = (unsigned)__builtin_amdgcn_readfirstlane((int)(unsigned)cur0);
-      unsigned chi = (unsigned)__builtin_amdgcn_readfirstlane((int)(unsigned)(cur0 >> 32));
-      u64 cur = ((u64)chi << 32) | clo;
-      const int valid = __builtin_amdgcn_readfirstlane(min(64, n - blk * 64));
-      const u64 vmask = (valid >= 64) ? ~0ull : ((1ull << valid) - 1ull);
-      const int dlo = (int)(unsigned)d, dhi = (int)(unsigned)(d >> 32);
-      u64 todo = __ballot(d != 0ull) & vmask;          // rows that can suppress inside this block
-      while (todo) {                                     // wave-uniform, ascending row order
-        const int kk = __ffsll((long long)todo) - 1;
-        todo &= todo - 1;
-        if (!((cur >> kk) & 1ull))
-          cur |= ((u64)(unsigned)__builtin_amdgcn_readlane(dhi, kk) << 32) | (u64)(unsigned)__builtin_amdgcn_readlane(dlo, kk);
-      }
-      const u64 kept = ~cur & vmask;
+      const u64 kept = diag_pass(d, removed[blk], min(64, n - blk * 64));
       if (lane == 0) { *s_kept = kept; keepbits[blk] = kept; }
     }
     __syncthreads();
@@ -1041,25 +839,19 @@ nms_sweep_kernel(const u64* __restrict__ mask, const int32_t* __restrict__ order
     __syncthreads();
   }
 
-  int total;
-  if (order_out == 1) {
-    // visiting (score) order: positions -> original indices through `order`
-    total = popc_scan_emit(keepbits, cb, tmp, [&](int i, u64 w, int o) {
-      while (w) { int k = __ffsll((long long)w) - 1; w &= w - 1; keep_out[s0 + o++] = (int64_t)order[s0 + i * 64 + k]; }
-    });
-  } else {
-    // ascending original index: scatter the flags into original-index space, then compact
-    for (int i = tid; i < n; i += kSweepThreads) {
-      if ((keepbits[i >> 6] >> (i & 63)) & 1ull) {
-        const int o = order[s0 + i] - s0;
-        atomicOr(&origbits[o >> 6], 1ull << (o & 63));
-      }
-    }
+  // ---- compaction: the kept boxes in visiting order (order_out == 1) or by ascending original index ---------------------
+  const u64* bits = keepbits;
+  if (order_out != 1) {
+    scatter_keep_to_original(keepbits, origbits, order, s0, n);
     __syncthreads();
-    total = popc_scan_emit(origbits, cb, tmp, [&](int i, u64 w, int o) {
-      while (w) { int k = __ffsll((long long)w) - 1; w &= w - 1; keep_out[s0 + o++] = (int64_t)(s0 + i * 64 + k); }
-    });
+    bits = origbits;
   }
+  const int total = block_scan_emit(cb, tmp, [&](int i) { return __popcll(bits[i]); }, [&](int i, int o) {
+    int64_t* out = keep_out + (s0 + o);
+    const int p0 = s0 + i * 64;
+    if (order_out == 1) for (u64 w = bits[i]; w; w &= w - 1) *out++ = (int64_t)order[p0 + __ffsll((long long)w) - 1];
+    else for (u64 w = bits[i]; w; w &= w - 1) *out++ = (int64_t)(p0 + __ffsll((long long)w) - 1);
+  });
   if (tid == 0) num_keep[seg] = total;
 }
 
@@ -1109,8 +901,6 @@ inline hipError_t sweep_attr() {     // > 64 KB of dynamic LDS needs the attribu
 }
 
 int pick_rows_per_wave(int max_seg, int nseg) {
-  static const int forced = getenv("ORP_NMS_ROWS") ? atoi(getenv("ORP_NMS_ROWS")) : 0;   // dev aid
-  if (forced == 1 || forced == 2 || forced == 4 || forced == 8 || forced == 16) return forced;
   const long cb = (max_seg + 63) / 64;
   const long tiles = cb * (cb + 1) / 2 * (nseg > 0 ? nseg : 1);
   // one workgroup per (4R rows x 64 cols) tile; aim at >= 2048 workgroups (8 per CU) when the problem is big enough
@@ -1118,6 +908,30 @@ int pick_rows_per_wave(int max_seg, int nseg) {
   int R = 1;
   while (R * 2 <= r && R < 16) R *= 2;
   return R;
+}
+
+// grid.x of the mask kernels: about the upper-triangular (rpb rows x 64 columns) tiles of a segment of max_seg boxes, bounded
+// so that all segments together stay near 4096 workgroups; the workgroups loop over the tiles of the actual count
+long mask_grid_x(int max_seg, int rpb, int nseg) {
+  const int max_cb = (max_seg + 63) / 64;
+  const long ntile = ((long)max_cb * ((max_seg + rpb - 1) / rpb)) / 2 + max_cb;
+  const long cap_wg = 4096 / (nseg < 8 ? nseg : 8);
+  return ntile > cap_wg ? cap_wg : ntile;
+}
+
+// stage 3 of every NMS flavour: one sweep workgroup per segment.  profiled: the launch alone (not the attribute call in
+// front of it) is timed into the ORP_PROF_NMS_SWEEP slot
+int launch_sweep(const u64* mask, const int32_t* order, const int32_t* seg, int nseg, int max_seg, int mask_stride,
+                 int order_out, int64_t* keep_out, int32_t* num_keep, const int* nz_count, const unsigned* nz_rc,
+                 hipStream_t st, bool profiled) {
+  const hipError_t ea = sweep_attr();
+  if (ea != hipSuccess) return (int)ea;
+  if (profiled) orp_prof_begin(ORP_PROF_NMS_SWEEP, st);
+  hipLaunchKernelGGL(nms_sweep_kernel, dim3(nseg), dim3(kSweepThreads), sweep_smem_bytes((max_seg + 63) / 64), st, mask, order,
+                     seg, mask_stride, order_out, keep_out, num_keep, nz_count, nz_rc);
+  if (profiled) orp_prof_end(ORP_PROF_NMS_SWEEP, st);
+  const hipError_t e = hipGetLastError();
+  return e == hipSuccess ? ORP_OK : (int)e;
 }
 
 int launch_nms(const float* dets, int n_total, const int32_t* seg_off_dev, int nseg, int max_seg, float thr, int flavor,
@@ -1180,40 +994,26 @@ int launch_nms(const float* dets, int n_total, const int32_t* seg_off_dev, int n
   }
 
   // ---- stage 2: the suppression mask ---------------------------------------------------------------------------------------
-  const int max_cb = (max_seg + 63) / 64;
   // exact_n: max_seg IS the box count (orp_rnms); otherwise it is only a capacity (batched / sync-free callers: the
   // count lives in device memory): 16-row tiles and a bounded grid whose workgroups loop over the tiles of the actual
   // count -- an 8 K capacity holding 2 K boxes must not pay for 60 K empty workgroups
   const bool exact_n = single_segment;
   // capacity callers: 16-row tiles (a 4-row tile spends its time staging: 201 -> measured below for 240 segments of <= 168)
   const int R = exact_n ? pick_rows_per_wave(max_seg, nseg) : (max_seg <= 8192 ? 4 : 16);
-  const int rpb = R * (kMaskThreads / 64);
-  long ntile = ((long)max_cb * ((max_seg + rpb - 1) / rpb)) / 2 + max_cb;       // ~ the upper-triangular tiles at max_seg
-  const long cap_wg = 4096 / (nseg < 8 ? nseg : 8);
-  if (ntile > cap_wg) ntile = cap_wg;
+  long ntile = mask_grid_x(max_seg, R * (kMaskThreads / 64), nseg);
   // XCD-aware tile lists for one segment (TileMap::decode_xcd; the kernel checks the actual count).  Measured round 3:
   // the launch time does not change (82.9 vs 83.9 us), the column records are fetched into one L2 instead of eight
-  static const int forced_map = getenv("ORP_NMS_MAP") ? atoi(getenv("ORP_NMS_MAP")) : -1;   // dev aid
-  const int xcd_map = forced_map >= 0 ? forced_map : (nseg == 1 ? 1 : 0);
-  if (xcd_map & 1) ntile = (ntile + 7) & ~7L;              // grid.x a multiple of 8
+  const bool one_seg = nseg == 1;
+  if (one_seg) ntile = (ntile + 7) & ~7L;                  // grid.x a multiple of 8
   const dim3 grid((unsigned)ntile, 1, nseg);
-  static const int dbg = getenv("ORP_NMS_DBG") ? atoi(getenv("ORP_NMS_DBG")) : 0;   // dev aid (timing): 1 = skip phase B, 2 = skip classifier, 4/8/16 = see tile_drain_terms
   {
     OrpProfScope prof(ORP_PROF_NMS_MASK, st);
-    if (flavor == 0) hipLaunchKernelGGL(nms_mask_loop_kernel<false>, grid, dim3(kMaskThreads), 0, st, boxes, seg, R, n_total, thr, mask, dbg, nz_count, nz_rc, xcd_map);
-    else hipLaunchKernelGGL(nms_mask_loop_kernel<true>, grid, dim3(kMaskThreads), 0, st, boxes, seg, R, n_total, thr, mask, dbg, nz_count, nz_rc, xcd_map);
+    if (flavor == 0) hipLaunchKernelGGL(nms_mask_loop_kernel<false>, grid, dim3(kMaskThreads), 0, st, boxes, seg, R, n_total, thr, mask, nz_count, nz_rc, one_seg);
+    else hipLaunchKernelGGL(nms_mask_loop_kernel<true>, grid, dim3(kMaskThreads), 0, st, boxes, seg, R, n_total, thr, mask, nz_count, nz_rc, one_seg);
   }
 
   // ---- stage 3: greedy sweep + compaction ------------------------------------------------------------------------------------
-  const size_t smem = sweep_smem_bytes(max_cb);
-  if (sweep_attr() != hipSuccess) return (int)sweep_attr();
-  {
-    OrpProfScope prof(ORP_PROF_NMS_SWEEP, st);
-    hipLaunchKernelGGL(nms_sweep_kernel, dim3(nseg), dim3(kSweepThreads), smem, st, mask, order, seg, n_total, order_out,
-                       keep_out, num_keep, nz_count, nz_rc);
-  }
-  hipError_t e = hipGetLastError();
-  return e == hipSuccess ? ORP_OK : (int)e;
+  return launch_sweep(mask, order, seg, nseg, max_seg, n_total, order_out, keep_out, num_keep, nz_count, nz_rc, st, true);
 }
 
 // ---- segmented fp64 merge NMS: workspace layout and launch sequence ---------------------------------------------------
@@ -1304,42 +1104,17 @@ int launch_nms_f64(const double* dets, int n_total, const int32_t* seg_off_dev, 
   }
   hipLaunchKernelGGL(prep_boxes_f64_seg_kernel, dim3(nb), dim3(tb), 0, st, dets, order, n_total, prep, hbb, nz_count, nseg);
   // ---- stage 2: the suppression mask (16-row tiles, bounded grid over the actual counts, as launch_nms' capacity case) -
-  const int max_cb = (max_seg + 63) / 64;
   const int R = 4;
-  const int rpb = R * (kMaskThreads / 64);
-  long ntile = ((long)max_cb * ((max_seg + rpb - 1) / rpb)) / 2 + max_cb;
-  const long cap_wg = 4096 / (nseg < 8 ? nseg : 8);
-  if (ntile > cap_wg) ntile = cap_wg;
+  const long ntile = mask_grid_x(max_seg, R * (kMaskThreads / 64), nseg);
   hipLaunchKernelGGL(nms_mask_f64_seg_kernel, dim3((unsigned)ntile, 1, nseg), dim3(kMaskThreads), 0, st, prep, hbb, seg, R,
                      n_total, thr, hbb_prefilter, mask, nz_count, nz_rc);
   // ---- stage 3: greedy sweep + compaction, kept original indices in visiting order ---------------------------------------
-  if (sweep_attr() != hipSuccess) return (int)sweep_attr();
-  hipLaunchKernelGGL(nms_sweep_kernel, dim3(nseg), dim3(kSweepThreads), sweep_smem_bytes(max_cb), st, mask, order, seg,
-                     n_total, 1, keep_out, num_keep, nz_count, nz_rc);
-  hipError_t e = hipGetLastError();
-  return e == hipSuccess ? ORP_OK : (int)e;
+  return launch_sweep(mask, order, seg, nseg, max_seg, n_total, 1, keep_out, num_keep, nz_count, nz_rc, st, false);
 }
 
 }  // namespace
 
 extern "C" {
-
-#ifdef ORP_NMS_PHASE_PROF
-int orp_nms_phase_prof_raw(unsigned long long* out /* [4096 * 16] */) {
-  return hipMemcpyFromSymbol(out, HIP_SYMBOL(orp_tile::g_phase_cycles), sizeof(unsigned long long) * 16 * orp_tile::kPhaseRows) == hipSuccess ? 0 : -1;
-}
-int orp_nms_phase_prof_read(unsigned long long* out16, int reset) {
-  const size_t nb = sizeof(unsigned long long) * 16 * orp_tile::kPhaseRows;
-  unsigned long long* h = (unsigned long long*)malloc(nb);
-  if (!h) return -1;
-  if (hipMemcpyFromSymbol(h, HIP_SYMBOL(orp_tile::g_phase_cycles), nb) != hipSuccess) { free(h); return -1; }
-  for (int k = 0; k < 16; k++) out16[k] = 0;
-  for (int r = 0; r < orp_tile::kPhaseRows; r++) for (int k = 0; k < 16; k++) out16[k] += h[r * 16 + k];
-  if (reset) { memset(h, 0, nb); if (hipMemcpyToSymbol(HIP_SYMBOL(orp_tile::g_phase_cycles), h, nb) != hipSuccess) { free(h); return -1; } }
-  free(h);
-  return 0;
-}
-#endif
 
 size_t orp_rnms_workspace_bytes(int n) { return nms_layout(n, 1, n).total; }
 
@@ -1429,12 +1204,7 @@ int orp_poly_nms_f64(const double* dets_sorted, int n, double iou_thr, int64_t* 
   const int rpb = R * (kMaskThreads / 64);
   hipLaunchKernelGGL(nms_mask_f64_kernel, dim3(max_cb, (n + rpb - 1) / rpb), dim3(kMaskThreads), 0, st, prep, n, R,
                      n, iou_thr, mask);
-  const size_t smem = sweep_smem_bytes(max_cb);
-  if (sweep_attr() != hipSuccess) return (int)sweep_attr();
-  hipLaunchKernelGGL(nms_sweep_kernel, dim3(1), dim3(kSweepThreads), smem, st, mask, order, seg, n, 1, keep_out,
-                     num_keep, (const int*)nullptr, (const unsigned*)nullptr);
-  hipError_t e = hipGetLastError();
-  return e == hipSuccess ? ORP_OK : (int)e;
+  return launch_sweep(mask, order, seg, 1, n, n, 1, keep_out, num_keep, nullptr, nullptr, st, false);
 }
 
 // Segmented fp64 merge NMS (include/orp_hip.h): every (class, scene) segment in one launch sequence.

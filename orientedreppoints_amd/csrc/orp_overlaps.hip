@@ -76,13 +76,7 @@ iou_matrix_kernel(const float* __restrict__ a, int n, const float* __restrict__ 
     orp::QuadPrep cp;
     orp::quad_prepare(q8, cp);
     fc = orp::far_col(cp);
-    if (wave == 0) {
-#pragma unroll
-      for (int e = 0; e < 4; e++) T.colE[e][lane] = make_float4(cp.ax[e], cp.ay[e], cp.bx[e], cp.by[e]);
-      T.colS[lane] = orp_tile::pack_signs(cp);
-      T.colArea[lane] = cp.area_abs;
-      X.colM[lane] = cp.mabs;
-    }
+    if (wave == 0) orp_tile::stage_col(T, X, lane, cp);
   }
   if (tid < kRows) {
     const int r = row_base + tid;
@@ -101,15 +95,10 @@ iou_matrix_kernel(const float* __restrict__ a, int n, const float* __restrict__ 
     }
     orp::QuadPrep rp;
     orp::quad_prepare(p8, rp);
+    orp_tile::stage_row(T, X, tid, rp);
 #pragma unroll
-    for (int e = 0; e < 4; e++) {
-      T.rowE[e][tid] = make_float4(rp.ax[e], rp.ay[e], rp.bx[e], rp.by[e]);
-      rowF[tid].vx[e] = rp.vx[e]; rowF[tid].vy[e] = rp.vy[e];
-    }
+    for (int e = 0; e < 4; e++) { rowF[tid].vx[e] = rp.vx[e]; rowF[tid].vy[e] = rp.vy[e]; }
     rowF[tid].mabs = rp.mabs; rowF[tid].slow = rp.force_slow;
-    T.rowS[tid] = orp_tile::pack_signs(rp);
-    T.rowArea[tid] = rp.area_abs;
-    X.rowM[tid] = rp.mabs;
   }
   if (tid == 0) T.qcount = 0;
   orp_tile::term_lds_reset(X, tid);
@@ -132,14 +121,7 @@ iou_matrix_kernel(const float* __restrict__ a, int n, const float* __restrict__ 
       resolved = orp::pair_is_far(rvx, rvy, rowF[rl].mabs, fc);
     }
     if (resolved) out[(size_t)r * k + col] = orp::iou_of_zero_inter<GUARD>(T.rowArea[rl], carea);
-    const bool pend = valid && !resolved;
-    const unsigned long long pmask = __ballot(pend);
-    if (pmask) {
-      int base = 0;
-      if (lane == 0) base = atomicAdd(&T.qcount, __popcll(pmask));
-      base = __builtin_amdgcn_readfirstlane(base);
-      if (pend) T.queue[base + __popcll(pmask & ((1ull << lane) - 1ull))] = (unsigned short)((rl << 6) | lane);
-    }
+    orp_tile::queue_pending(T, rl, lane, valid && !resolved);
   }
   __syncthreads();
 
@@ -195,8 +177,6 @@ done:
 #undef ORP_CHK
 }
 
-#ifndef ORP_BUILD_ID
-#define ORP_BUILD_ID "dev"
-#endif
+// ORP_BUILD_ID: the hash of every kernel source, always given on the command line (build.py; "dev" from tools/build_variant.py)
 const char* orp_version(void) { return "orp_hip gfx950 abi1 " ORP_BUILD_ID; }
 }

@@ -47,6 +47,15 @@ template <typename T> struct QuadPrepT {   // float: 32 words = 128 B per box
 };
 typedef QuadPrepT<float> QuadPrep;
 
+// the all-zero record that stands for a box past the end of its segment: every fan term degenerate, |area| 0
+template <typename T>
+ORP_HD QuadPrepT<T> quad_prep_empty() {
+  QuadPrepT<T> p;
+  for (int k = 0; k < 4; k++) { p.ax[k] = p.ay[k] = p.bx[k] = p.by[k] = p.vx[k] = p.vy[k] = (T)0; p.s[k] = 0; }
+  p.area_abs = (T)0; p.force_slow = 0; p.mabs = (T)0; p.pad0 = (T)0;
+  return p;
+}
+
 // quad8 = x1,y1,..,x4,y4 as stored in dets rows.  Mirrors the head of quad_iou(): polygon-level reversal when the
 // signed area is negative, areas recomputed after the reversal, then the per-term orientation of tri_term().
 template <typename T>

@@ -1,7 +1,7 @@
 // orp_tile.hpp -- the (rows x 64 columns) pair tile shared by the rotated-NMS mask kernel and the IoU-matrix kernels
-// (gfx950, device only): LDS records of the tile's prepared boxes, the unresolved-pair queue, and the phase-B drain
-// of that queue as a TERM queue (tile_drain_terms: per-term exact-zero screen, one surviving fan term per lane,
-// ordered sum per pair).  See orp_quadfast.hpp for the arithmetic contract.
+// (gfx950, device only): LDS records of the tile's prepared boxes and their staging (stage_col, stage_row), the
+// unresolved-pair queue (queue_pending), and the phase-B drain of that queue as a TERM queue (tile_drain_terms: per-term
+// exact-zero screen, one surviving fan term per lane, ordered sum per pair).  See orp_quadfast.hpp for the arithmetic contract.
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -11,24 +11,7 @@ namespace orp_tile {
 using orp::Pt;
 typedef unsigned long long u64;
 
-// Development aid (-DORP_NMS_PHASE_PROF): shader-clock cycles of thread 0 per phase, summed over all tiles of a launch.
-// Slots 0..6 belong to the including kernel file, 8 = B1, 9 = B2, 10 = B3, 11 = chunks, 12 = B2 iterations.
-#ifdef ORP_NMS_PHASE_PROF
-// One row of 16 counters per workgroup (plain read-modify-write by thread 0: no atomics, the measurement must not queue
-// behind itself); the host sums the rows.
-constexpr int kPhaseRows = 4096;
-static __device__ unsigned long long g_phase_cycles[kPhaseRows * 16];
-#define ORP_PHASE_T(var) const unsigned long long var = __builtin_readcyclecounter()
-#define ORP_PHASE_ADD(slot, t0, t1) do { if (threadIdx.x == 0) orp_tile::g_phase_cycles[(blockIdx.x % orp_tile::kPhaseRows) * 16 + (slot)] += (unsigned long long)((t1) - (t0)); } while (0)
-#else
-#define ORP_PHASE_T(var)
-#define ORP_PHASE_ADD(slot, t0, t1)
-#endif
-
-#ifndef ORP_TILE_ROWS
-#define ORP_TILE_ROWS 64
-#endif
-constexpr int kMaxTileRows = ORP_TILE_ROWS;   // rows a tile may have (dev aid: 16 shrinks the LDS footprint for occupancy experiments)
+constexpr int kMaxTileRows = 64;   // rows a tile may have; 16 (smaller LDS footprint, more resident workgroups) measured slower (profiles/r06_nms_occupancy.log)
 
 struct TileLds {
   // oriented fan edges (ax, ay, bx, by) per edge, per tile row / column.  One float4 of padding per edge plane: phase
@@ -43,10 +26,6 @@ struct TileLds {
   u64 words[kMaxTileRows];
   unsigned short queue[kMaxTileRows * 64];
   int qcount;
-  // phase A of the NMS mask kernel reads its (wave-uniform) row from here instead of scalar global loads: the quad's
-  // vertices in polygon order (x0..x3 | y0..y3), and the row's mask of unresolved columns until the wave files them
-  float4 rowV[2][kMaxTileRows];
-  u64 pend[kMaxTileRows];
 };
 
 __device__ __forceinline__ int pack_signs(const orp::QuadPrep& p) {
@@ -72,10 +51,7 @@ __device__ __forceinline__ int unpack_sign(int packed, int k) {
 //   B3  one lane per pair: the values are summed in the reference's order (row edge outer, column edge inner -- the
 //       run is in ascending term order), then `sink`.
 // Chunks of kChunkPairs pairs; kChunkPairs * 16 term slots.
-#ifndef ORP_CHUNK_PAIRS
-#define ORP_CHUNK_PAIRS 256
-#endif
-constexpr int kChunkPairs = ORP_CHUNK_PAIRS;   // (a power of two <= kDrainThreads; 128 halves the term queue's 16 KB of LDS)
+constexpr int kChunkPairs = 256;   // a power of two <= kDrainThreads; 128 (half the term queue's 16 KB of LDS) measured slower (profiles/r06_nms_occupancy.log)
 constexpr int kTermCap = kChunkPairs * 16;
 constexpr int kDrainThreads = 256;          // workgroup size of the callers
 constexpr int kTermGeneric = 1 << 30;       // queue entry flag: skip the tree
@@ -92,11 +68,38 @@ __device__ __forceinline__ void term_lds_reset(TermLds& X, int tid) {
   if (tid == 0) X.tcount = 0;
 }
 
+// ---- staging: what phase B reads of a prepared box, filed at tile column `lane` / tile row `rl` ------------------------
+__device__ __forceinline__ void stage_col(TileLds& T, TermLds& X, int lane, const orp::QuadPrep& p) {
+#pragma unroll
+  for (int k = 0; k < 4; k++) T.colE[k][lane] = make_float4(p.ax[k], p.ay[k], p.bx[k], p.by[k]);
+  T.colS[lane] = pack_signs(p);
+  T.colArea[lane] = p.area_abs;
+  X.colM[lane] = p.mabs;
+}
+__device__ __forceinline__ void stage_row(TileLds& T, TermLds& X, int rl, const orp::QuadPrep& p) {
+#pragma unroll
+  for (int k = 0; k < 4; k++) T.rowE[k][rl] = make_float4(p.ax[k], p.ay[k], p.bx[k], p.by[k]);
+  T.rowS[rl] = pack_signs(p);
+  T.rowArea[rl] = p.area_abs;
+  X.rowM[rl] = p.mabs;
+}
+
+// Phase A, whole wave, row rl wave-uniform: the lanes with `pend` file their pair (rl, lane) in T.queue, columns
+// ascending, behind one LDS reservation per wave.
+__device__ __forceinline__ void queue_pending(TileLds& T, int rl, int lane, bool pend) {
+  const u64 pmask = __ballot(pend);
+  if (pmask) {
+    int base = 0;
+    if (lane == 0) base = atomicAdd(&T.qcount, __popcll(pmask));
+    base = __builtin_amdgcn_readfirstlane(base);
+    if (pend) T.queue[base + __popcll(pmask & ((1ull << lane) - 1ull))] = (unsigned short)((rl << 6) | lane);
+  }
+}
+
 // Drains T.queue[0, nq) with a 256-thread workgroup (every thread must call it; contains barriers).  X must have been
 // reset (term_lds_reset + barrier).  sink(rl, cl, iou) is called once per queued pair by one lane.
-// dbg (development aid, timing only): 4 = skip B2, 8 = no per-term screen, 16 = skip B3.
 template <bool GUARD, typename Sink>
-__device__ __forceinline__ void tile_drain_terms(const TileLds& T, TermLds& X, int nq, Sink sink, int dbg = 0) {
+__device__ __forceinline__ void tile_drain_terms(const TileLds& T, TermLds& X, int nq, Sink sink) {
   const int tid = threadIdx.x, lane = tid & 63;
   for (int q0 = 0; q0 < nq; q0 += kChunkPairs) {
     if (q0 > 0) {                                        // the previous chunk's B3 still reads tq
@@ -105,7 +108,6 @@ __device__ __forceinline__ void tile_drain_terms(const TileLds& T, TermLds& X, i
       __syncthreads();
     }
     // ---- B1 ----------------------------------------------------------------------------------------------------
-    ORP_PHASE_T(tb0);
     const bool live = (tid < kChunkPairs) && (q0 + tid) < nq;
     const int item = live ? T.queue[q0 + tid] : 0;
     const int rl = item >> 6, cl = item & 63;
@@ -123,7 +125,7 @@ __device__ __forceinline__ void tile_drain_terms(const TileLds& T, TermLds& X, i
         s1[e] = unpack_sign(rs, e); s2[e] = unpack_sign(cs, e);
       }
       forced = ((rs | cs) >> 8) != 0;                    // non-finite / huge coordinates: generic loop, every term
-      if (forced || (dbg & 8)) {
+      if (forced) {
 #pragma unroll
         for (int t = 0; t < 16; t++) alive |= (s1[t >> 2] != 0 && s2[t & 3] != 0) ? (1u << t) : 0u;
       } else {
@@ -159,9 +161,8 @@ __device__ __forceinline__ void tile_drain_terms(const TileLds& T, TermLds& X, i
       }
     }
     __syncthreads();
-    ORP_PHASE_T(tb1);
     // ---- B2 ----------------------------------------------------------------------------------------------------
-    const int total = (dbg & 4) ? 0 : X.tcount;
+    const int total = X.tcount;
     for (int e = tid; e < total; e += kDrainThreads) {
       const int ent = X.tq[e];
       const int p = (ent >> 4) & (kChunkPairs - 1), i = (ent >> 2) & 3, j = ent & 3;
@@ -185,9 +186,8 @@ __device__ __forceinline__ void tile_drain_terms(const TileLds& T, TermLds& X, i
       X.tq[e] = __float_as_int(v);
     }
     __syncthreads();
-    ORP_PHASE_T(tb2);
     // ---- B3 ----------------------------------------------------------------------------------------------------
-    if (live && alive != 0u && !(dbg & 16)) {
+    if (live && alive != 0u) {
       float inter = 0.f;
       for (int t = 0; t < cnt; t++) inter += __int_as_float(X.tq[base + t]);
       const float uni = T.rowArea[rl] + T.colArea[cl] - inter;
@@ -196,11 +196,6 @@ __device__ __forceinline__ void tile_drain_terms(const TileLds& T, TermLds& X, i
       else iou = inter / uni;
       sink(rl, cl, iou);
     }
-#ifdef ORP_NMS_PHASE_PROF
-    { ORP_PHASE_T(tb3);
-      ORP_PHASE_ADD(8, tb0, tb1); ORP_PHASE_ADD(9, tb1, tb2); ORP_PHASE_ADD(10, tb2, tb3); ORP_PHASE_ADD(11, 0ull, 1ull);
-      ORP_PHASE_ADD(12, 0ull, (unsigned long long)((total + kDrainThreads - 1) / kDrainThreads)); }
-#endif
   }
 }
 

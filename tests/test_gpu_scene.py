@@ -90,13 +90,17 @@ def test_batched_merge_nms_presorted_is_numpy_order(dev):
 
 @pytest.mark.gpu
 def test_batched_full_merge_matches_orp_poly_nms_f64(dev):
-    """hbb_prefilter = 0 makes the same decisions as the existing single-segment orp_poly_nms_f64 (py_gpu_nms_poly)."""
+    """hbb_prefilter = 0 makes the same decisions as the single-segment orp_poly_nms_f64 (py_gpu_nms_poly), which is one
+    presorted segment of the same launch sequence: both are held to the CPU oracle's py_cpu_nms_poly."""
+    from oracle import orp_oracle as O
     from orientedreppoints_amd.dota_devkit.result_merge import py_gpu_nms_poly
     segs = [_segment(n, 50 + i) for i, n in enumerate([1, 65, 3000])]
     orders = [d[:, 8].argsort()[::-1] for d in segs]
     got = _run([d[o] for d, o in zip(segs, orders)], 0.3, False, True, dev)
     for d, o, g in zip(segs, orders, got):
-        assert [int(o[i]) for i in g] == py_gpu_nms_poly(d, 0.3)
+        single = py_gpu_nms_poly(d, 0.3)
+        assert [int(i) for i in O.py_cpu_nms_poly(d, 0.3)] == single
+        assert [int(o[i]) for i in g] == single
 
 
 @pytest.mark.gpu

@@ -25,6 +25,8 @@ def main():
         base = os.path.splitext(src)[0]
         if src in srcs:
             obj = os.path.join(out_dir, "%s_%s.o" % (base, name))
+            if src == B.VERSION_SOURCE:
+                extra = extra + ['-DORP_BUILD_ID="dev"']      # orp_version() of a variant does not claim the in-tree build's id
             r = subprocess.run([B.HIPCC] + B.COMMON + extra + flags + ["-c", os.path.join(B.CSRC, src), "-o", obj], cwd=B.CSRC,
                                stderr=subprocess.PIPE, universal_newlines=True)
             sys.stderr.write("\n".join(l for l in r.stderr.splitlines() if "'-packed-fp32-ops' is not a recognized feature" not in l))
