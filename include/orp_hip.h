@@ -628,6 +628,37 @@ int orp_conv1x1_bn_act(const float* x, const float* weight_t, const float* scale
                        const float* scale2, const float* shift2, float* y, int batch, int c_in, int c_out, int hw, int relu,
                        void* stream);
 
+/* ... with range_out != NULL (no residual then): one word of device memory left holding max range_bits(y) (csrc/orp_range.hpp) as
+ * float bits, zeroed by a kernel launch in front -- what orp_conv3x3_bn_act reads as range_in without a pass over y */
+int orp_conv1x1_bn_act_range(const float* x, const float* weight_t, const float* scale, const float* shift, const float* residual,
+                             const float* scale2, const float* shift2, float* y, int batch, int c_in, int c_out, int hw, int relu,
+                             uint32_t* range_out, void* stream);
+/* the same optional output for the BatchNorm pass (blocks whose conv1 stays on the library) */
+int orp_affine_act_range(const float* x, const float* residual, const float* scale, const float* shift, float* y, int batch,
+                         int channels, int hw, int relu, uint32_t* range_out, void* stream);
+
+/* orp_conv3x3_bn_act: a ResNet bottleneck's conv2 -- bias-free 3x3 / stride 1 / padding 1 / dilation 1 / groups 1 -- with its eval-mode
+ *   BatchNorm and the ReLU in the epilogue (inference): y = relu?(fma(conv3x3(x, w), scale[c], shift[c])), x and y NCHW fp32.
+ *   Arithmetic: fp16-pieces (two fp16 pieces per operand after a power-of-two range scale, three products, fp32 accumulation:
+ *   csrc/orp_range.hpp), NOT bit-identical to the library's convolution; deterministic.  weight_packed: orp_conv3x3_bn_packed_bytes
+ *   bytes (16-byte aligned) from orp_conv3x3_bn_pack_weight for the [Cout,Cin,3,3] weight: its two fp16 planes and their scale
+ *   (4 bytes per weight).  range_in: one device word, float bits of (a bound of) max |x| over finite x
+ *   (orp_conv1x1_bn_act_range / orp_affine_act_range leave it).
+ *   orp_conv3x3_bn_act_ok: Cin == Cout in {64, 128, 256}; anything else is ORP_EINVAL.
+ *   orp_conv3x3_bn_act_pays: 1 where the launch was MEASURED faster than library convolution + pass on MI355X (closed table,
+ *   docs/notebook/round15.md), else 0.
+ *   orp_conv3x3_bn_act_tile: the spatial tile (tile_h x tile_w outputs) and the wave layout (waves_pos x waves_ch = 8) of a launch of
+ *   this shape; 0 where the shape is not supported. */
+int orp_conv3x3_bn_act_ok(int c_in, int c_out);
+int orp_conv3x3_bn_act_pays(int c_in, int c_out, int height, int width, int batch);
+int orp_conv3x3_bn_act_tile(int c_in, int c_out, int height, int width, int batch, int* tile_h, int* tile_w, int* waves_pos,
+                            int* waves_ch);
+size_t orp_conv3x3_bn_packed_bytes(int c_in, int c_out);
+int orp_conv3x3_bn_pack_weight(const float* weight, int c_in, int c_out, void* packed, void* stream);
+int orp_conv3x3_bn_act(const float* x, const void* weight_packed, const float* scale, const float* shift, const uint32_t* range_in,
+                       float* y, int batch, int c_in, int c_out, int height, int width, int relu, void* stream);
+
+
 /* orp_conv3x3_small_multi: 3x3 / stride 1 / pad 1 convolution (no bias) of the SMALL FPN levels -- the 32^2 / 16^2 / 8^2
  *   maps the head's seven 256->256 convolutions (orientedreppoints_head.py:91-132) also visit -- all levels in ONE
  *   launch: exact-fp32 MFMA implicit GEMM reading and writing NCHW [B,C,H,W] fp32 (input != output).  weight_packed: the

@@ -25,6 +25,8 @@
 
 #include "../../include/orp_hip.h"
 #include "orp_affine.hpp"
+#include "orp_range.hpp"
+#include "orp_launch.hpp"
 
 namespace {
 
@@ -42,12 +44,15 @@ struct Args {
   float* y;              // [B][Cout][hw]
   int cin, cout, hw, relu;
   int ntm, ntn;          // tiles per image: channels, positions
+  unsigned* range;       // RANGE: one word, raised to max range_bits(y) (orp_range.hpp) for the fp16-pieces kernel that reads y
 };
 
 // VEC: hw % 4 == 0 and x 16-byte aligned -> the input rows are fetched as float4.  MODE: the residual term (0 nothing, 1 res,
 // 2 res with its own affine) -- a template parameter so that the epilogue is straight-line code: with a run-time mode the requested
 // residual values meet an undefined value at a join and the compiler waits for every one of them in front of the last MFMAs.
-template <int WM, int WN, bool VEC, int MODE>
+// RANGE: the stored values' range word leaves with them (a wave maximum, the four waves' through LDS, one conditional atomic per
+// workgroup); a template parameter so that the other instantiations keep their instruction stream.
+template <int WM, int WN, bool VEC, int MODE, bool RANGE = false>
 __global__ void __launch_bounds__(kThreads, 2)
 conv1x1_bn_act_kernel(const Args P) {
   constexpr int BM = 64 * WM, BN = 64 * WN;
@@ -179,6 +184,7 @@ conv1x1_bn_act_kernel(const Args P) {
   __builtin_amdgcn_sched_barrier(0);
   mma();
 
+  unsigned rmax = 0u;
 #pragma unroll
   for (int mi = 0; mi < WM; mi++) {
 #pragma unroll
@@ -206,10 +212,22 @@ conv1x1_bn_act_kernel(const Args P) {
           if (MODE == 0) t = affine_act(v, av[q], bv[q], P.relu);
           else if (MODE == 1) t = affine_res_act(v, av[q], bv[q], rv[mi][ni][r], P.relu);
           else t = affine_res_act(v, av[q], bv[q], affine_act(rv[mi][ni][r], a2v[q], b2v[q], 0), P.relu);
-          if (chg < cout && p < hw) P.y[(plane0 + chg + q) * hw + p] = t;
+          if (chg < cout && p < hw) {
+            P.y[(plane0 + chg + q) * hw + p] = t;
+            if (RANGE) rmax = max(rmax, orp::range_bits(t));
+          }
         }
       }
     }
+  }
+  if (RANGE) {
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) rmax = max(rmax, (unsigned)__shfl_xor((int)rmax, o, 64));
+    unsigned* red = reinterpret_cast<unsigned*>(Ws);          // (free once every wave is behind its last MFMAs)
+    __syncthreads();
+    if (lane == 0) red[wave] = rmax;
+    __syncthreads();
+    if (tid == 0) orp::range_raise(P.range, max(max(red[0], red[1]), max(red[2], red[3])));
   }
 }
 
@@ -235,7 +253,11 @@ void launch_mode(const Args& A, int batch, bool vec, hipStream_t st) {
 }
 template <int WM, int WN>
 void launch(const Args& A, int batch, bool vec, hipStream_t st) {
-  if (!A.res) launch_mode<WM, WN, 0>(A, batch, vec, st);
+  if (A.range) {                                             // (conv1: no residual)
+    const dim3 grid((unsigned)((long)A.ntm * A.ntn * batch));
+    if (vec) hipLaunchKernelGGL((conv1x1_bn_act_kernel<WM, WN, true, 0, true>), grid, dim3(kThreads), 0, st, A);
+    else hipLaunchKernelGGL((conv1x1_bn_act_kernel<WM, WN, false, 0, true>), grid, dim3(kThreads), 0, st, A);
+  } else if (!A.res) launch_mode<WM, WN, 0>(A, batch, vec, st);
   else if (!A.scale2) launch_mode<WM, WN, 1>(A, batch, vec, st);
   else launch_mode<WM, WN, 2>(A, batch, vec, st);
 }
@@ -285,9 +307,13 @@ int orp_conv1x1_bn_act_pays(int c_in, int c_out, int hw, int batch, int has_resi
   return 0;
 }
 
-int orp_conv1x1_bn_act(const float* x, const float* weight_t, const float* scale, const float* shift, const float* residual,
-                       const float* scale2, const float* shift2, float* y, int batch, int c_in, int c_out, int hw, int relu,
-                       void* stream) {
+// range_out (or NULL): one word of device memory that is left holding max range_bits(y) as float bits -- zeroed here by a
+// kernel launch (orp_launch.hpp fill_async: a captured graph replays it), raised by one conditional atomicMax per workgroup.
+// No residual with it (conv1 is what feeds a range-reading convolution).
+int orp_conv1x1_bn_act_range(const float* x, const float* weight_t, const float* scale, const float* shift, const float* residual,
+                             const float* scale2, const float* shift2, float* y, int batch, int c_in, int c_out, int hw, int relu,
+                             uint32_t* range_out, void* stream) {
+  if (range_out && residual) return ORP_EINVAL;
   if (!x || !weight_t || !scale || !shift || !y || batch <= 0 || hw <= 0 || !orp_conv1x1_bn_act_ok(c_in, c_out)) return ORP_EINVAL;
   if ((scale2 != nullptr) != (shift2 != nullptr) || (scale2 && !residual) || (const float*)y == x || (const float*)y == residual)
     return ORP_EINVAL;
@@ -297,14 +323,25 @@ int orp_conv1x1_bn_act(const float* x, const float* weight_t, const float* scale
   A.x = x; A.wt = weight_t; A.scale = scale; A.shift = shift; A.res = residual; A.scale2 = scale2; A.shift2 = shift2; A.y = y;
   A.cin = c_in; A.cout = c_out; A.hw = hw; A.relu = relu ? 1 : 0;
   A.ntm = (c_out + t.bm - 1) / t.bm; A.ntn = (hw + t.bn - 1) / t.bn;
+  A.range = range_out;
   if ((long)A.ntm * A.ntn * batch >= (1L << 31)) return ORP_ETOOBIG;
   const bool vec = (hw & 3) == 0 && ((uintptr_t)x & 15) == 0;
   hipStream_t st = (hipStream_t)stream;
+  if (range_out) {
+    hipError_t fe = orp::fill_async(range_out, 0, sizeof(uint32_t), st);
+    if (fe != hipSuccess) return (int)fe;
+  }
   if (t.bm == 128) launch<2, 2>(A, batch, vec, st);
   else if (t.bn == 128) launch<1, 2>(A, batch, vec, st);
   else launch<1, 1>(A, batch, vec, st);
   hipError_t e = hipGetLastError();
   return e == hipSuccess ? ORP_OK : (int)e;
+}
+
+int orp_conv1x1_bn_act(const float* x, const float* weight_t, const float* scale, const float* shift, const float* residual,
+                       const float* scale2, const float* shift2, float* y, int batch, int c_in, int c_out, int hw, int relu,
+                       void* stream) {
+  return orp_conv1x1_bn_act_range(x, weight_t, scale, shift, residual, scale2, shift2, y, batch, c_in, c_out, hw, relu, nullptr, stream);
 }
 
 }  // extern "C"

@@ -902,12 +902,10 @@ const float* wscale_of(const float* packed, int c_out, int c_in, int taps) {
   return reinterpret_cast<const float*>(reinterpret_cast<const uint16_t*>(packed + 2 * n) + 5 * n);
 }
 
-hipError_t pack_planes(const float* weight, int c_out, int c_in, int taps, uint16_t* planes, hipStream_t st) {
+// the fp16 planes alone: max |w| -> scale -> two planes [2][tap][c/16][2][o][8] at planes16; tail[0] = the scale, tail[1] = max |w| bits
+hipError_t pack_planes16(const float* weight, int c_out, int c_in, int taps, uint16_t* planes16, float* tail, hipStream_t st) {
   const long total = (long)c_out * c_in * taps;
   int blocks = (int)((total + 255) / 256); if (blocks > 4096) blocks = 4096;
-  hipLaunchKernelGGL(pack_planes_kernel, dim3(blocks), dim3(256), 0, st, weight, c_out, c_in, taps, planes);
-  // the fp16 planes: max |w| -> scale -> two planes
-  float* tail = reinterpret_cast<float*>(planes + 5 * total);              // [0] scale, [1] max |w| bits
   unsigned* amax = reinterpret_cast<unsigned*>(tail + 1);
   hipError_t e = orp::fill_async(amax, 0, sizeof(unsigned), st);
   if (e != hipSuccess) return e;
@@ -916,8 +914,15 @@ hipError_t pack_planes(const float* weight, int c_out, int c_in, int taps, uint1
   for (int i = 0; i < kAbsMaxT; i++) { M.x[i] = weight; M.n[i] = i == 0 ? (size_t)total : 0; M.slot[i] = 0; M.bx0[i] = i == 0 ? 0 : (int)nb; }
   M.bx0[kAbsMaxT] = (int)nb; M.count = 1;
   hipLaunchKernelGGL(absmax_kernel, dim3((int)nb), dim3(256), 0, st, M, amax);
-  hipLaunchKernelGGL(pack_planes16_kernel, dim3(blocks), dim3(256), 0, st, weight, c_out, c_in, taps, amax, planes + 3 * total, tail);
+  hipLaunchKernelGGL(pack_planes16_kernel, dim3(blocks), dim3(256), 0, st, weight, c_out, c_in, taps, amax, planes16, tail);
   return hipGetLastError();
+}
+
+hipError_t pack_planes(const float* weight, int c_out, int c_in, int taps, uint16_t* planes, hipStream_t st) {
+  const long total = (long)c_out * c_in * taps;
+  int blocks = (int)((total + 255) / 256); if (blocks > 4096) blocks = 4096;
+  hipLaunchKernelGGL(pack_planes_kernel, dim3(blocks), dim3(256), 0, st, weight, c_out, c_in, taps, planes);
+  return pack_planes16(weight, c_out, c_in, taps, planes + 3 * total, reinterpret_cast<float*>(planes + 5 * total), st);
 }
 
 // The halo kernel's switch: ORP_CONV_HALO (default 1), orp_conv_split_set_halo() overrides it (-1: back to the environment's choice)

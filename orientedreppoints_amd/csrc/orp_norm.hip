@@ -404,9 +404,13 @@ fpn_topdown_nhwc_kernel(const GnParams P, const TdLevels T) {
 
 // y = act(x * scale[c] + shift[c] (+ residual)), NCHW.  grid.y = (image, channel) plane, so the per-channel constants are
 // block-uniform scalars and no integer division sits in the element loop; float4 traffic when HW % 4 == 0.
+// RANGE: the word `range` is raised to max range_bits(y) (one conditional atomic per workgroup); a template parameter so that the
+// plain instantiation keeps its instruction stream.
+template <bool RANGE>
 __global__ void __launch_bounds__(kThreads)
 affine_act_kernel(const float* __restrict__ x, const float* __restrict__ res, const float* __restrict__ scale,
-                  const float* __restrict__ shift, float* __restrict__ y, int C, int hw, int relu) {
+                  const float* __restrict__ shift, float* __restrict__ y, int C, int hw, int relu, unsigned* __restrict__ range) {
+  unsigned rmax = 0u;
   const int plane = blockIdx.y;                       // b * C + c
   const int c = plane % C;
   const float a = scale[c], b = shift[c];
@@ -422,11 +426,19 @@ affine_act_kernel(const float* __restrict__ x, const float* __restrict__ res, co
       if (r4) { const float4 r = r4[i]; t.x += r.x; t.y += r.y; t.z += r.z; t.w += r.w; }
       if (relu) relu4(t);
       y4[i] = t;
+      if (RANGE) rmax = max(max(rmax, orp::range_bits(t.x)), max(orp::range_bits(t.y), max(orp::range_bits(t.z), orp::range_bits(t.w))));
     }
   } else {
     for (int i = blockIdx.x * blockDim.x + threadIdx.x; i < hw; i += gridDim.x * blockDim.x) {
-      y[base + i] = res ? affine_res_act(x[base + i], a, b, res[base + i], relu) : affine_act(x[base + i], a, b, relu);
+      const float t = res ? affine_res_act(x[base + i], a, b, res[base + i], relu) : affine_act(x[base + i], a, b, relu);
+      y[base + i] = t;
+      if (RANGE) rmax = max(rmax, orp::range_bits(t));
     }
+  }
+  if (RANGE) {
+    __shared__ unsigned redm[4];
+    const unsigned mx = block_max(rmax, redm);
+    if (threadIdx.x == 0) orp::range_raise(range, mx);
   }
 }
 
@@ -1124,13 +1136,27 @@ int orp_groupnorm_act_multi(const orp_norm_level* levels, int nlevels, int batch
                                     stream);
 }
 
-int orp_affine_act(const float* x, const float* residual, const float* scale, const float* shift, float* y, int batch,
-                   int channels, int hw, int relu, void* stream) {
+// range_out (or NULL): one word left holding max range_bits(y) as float bits, zeroed here by a kernel launch (fill_async)
+int orp_affine_act_range(const float* x, const float* residual, const float* scale, const float* shift, float* y, int batch,
+                         int channels, int hw, int relu, uint32_t* range_out, void* stream) {
   if (!x || !scale || !shift || !y || batch <= 0 || channels <= 0 || hw <= 0) return ORP_EINVAL;
   if ((long)batch * channels > 65535L * 1024) return ORP_ETOOBIG;
-  hipLaunchKernelGGL(affine_act_kernel, dim3(plane_blocks(hw), batch * channels), dim3(kThreads), 0, (hipStream_t)stream, x, residual,
-                     scale, shift, y, channels, hw, relu);
+  const dim3 grid(plane_blocks(hw), batch * channels);
+  if (range_out) {
+    hipError_t e = orp::fill_async(range_out, 0, sizeof(uint32_t), (hipStream_t)stream);
+    if (e != hipSuccess) return (int)e;
+    hipLaunchKernelGGL(affine_act_kernel<true>, grid, dim3(kThreads), 0, (hipStream_t)stream, x, residual, scale, shift, y, channels,
+                       hw, relu, range_out);
+  } else {
+    hipLaunchKernelGGL(affine_act_kernel<false>, grid, dim3(kThreads), 0, (hipStream_t)stream, x, residual, scale, shift, y, channels,
+                       hw, relu, (unsigned*)nullptr);
+  }
   return launch_status();
+}
+
+int orp_affine_act(const float* x, const float* residual, const float* scale, const float* shift, float* y, int batch,
+                   int channels, int hw, int relu, void* stream) {
+  return orp_affine_act_range(x, residual, scale, shift, y, batch, channels, hw, relu, nullptr, stream);
 }
 
 int orp_affine2_act(const float* x, const float* residual, const float* scale, const float* shift, const float* scale2,

@@ -73,8 +73,18 @@ class Bottleneck(nn.Module):
             on = switches.BN_CONV1X1_FUSE
         return bool(on)
 
+    def _conv3x3_fusable(self):
+        """conv2 may run on the fp16-pieces kernel with bn2 + ReLU in its epilogue where that was measured faster (`fuse_conv3x3`
+        attribute, or ORP_BN_CONV3X3_FUSE=0 for A/B timing); the shapes are decided by `conv3x3_bn_act`
+        (`orp_conv3x3_bn_act_ok` / `_pays`); `force_conv3x3` (attribute, tests) routes every supported shape"""
+        from .. import switches
+        on = getattr(self, 'fuse_conv3x3', None)
+        if on is None:
+            on = switches.BN_CONV3X3_FUSE
+        return bool(on) and not self.conv2_is_dcn and isinstance(self.bn2, nn.BatchNorm2d) and not self.bn2.training
+
     def _forward_fused(self, x):
-        from ..mmdet_ops.fused_norm import bn_act, conv1x1_bn_act
+        from ..mmdet_ops.fused_norm import bn_act, conv1x1_bn_act, conv3x3_bn_act, conv3x3_bn_act_routed
         fuse = self._conv1x1_fusable()
 
         def conv_bn_act(t, conv, bn, **kw):
@@ -83,8 +93,18 @@ class Bottleneck(nn.Module):
             if fuse:
                 return conv1x1_bn_act(t, conv, bn, **kw)
             return bn_act(conv(t).contiguous(), bn, **kw)
-        out = conv_bn_act(x, self.conv1, self.bn1, relu=True)
-        out = bn_act(self.conv2(out).contiguous(), self.bn2, relu=True)
+        force3 = bool(getattr(self, 'force_conv3x3', False))
+        fuse3 = False
+        if self._conv3x3_fusable() and tuple(self.conv1.stride) == (1, 1):
+            # decided in front of conv1 (whose output has x's positions), so that conv1's kernel leaves the range word conv2 reads
+            fuse3 = conv3x3_bn_act_routed(x, self.conv2, self.bn2, force3,
+                                          shape=(x.size(0), self.conv1.out_channels, x.size(2), x.size(3)))
+        if fuse3:
+            out, bits = conv_bn_act(x, self.conv1, self.bn1, relu=True, want_range=True)
+            out = conv3x3_bn_act(out, self.conv2, self.bn2, relu=True, force=force3, range_bits=bits)
+        else:
+            out = conv_bn_act(x, self.conv1, self.bn1, relu=True)
+            out = bn_act(self.conv2(out).contiguous(), self.bn2, relu=True)
         if self._downsample_norm_fusable():
             # the downsample BatchNorm rides in the block's last pass: no read-modify-write pass of its own over the identity
             return conv_bn_act(out, self.conv3, self.bn3, residual=self.downsample[0](x).contiguous(),

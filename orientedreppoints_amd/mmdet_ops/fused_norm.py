@@ -160,8 +160,10 @@ def _bn_affine(bn):
     return _lib.keep_for_graph(hit[0]), _lib.keep_for_graph(hit[1])
 
 
-def bn_act(x, bn, residual=None, relu=True, residual_bn=None):
+def bn_act(x, bn, residual=None, relu=True, residual_bn=None, want_range=False):
     """relu?(BatchNorm_eval(x) (+ residual)) in ONE pass, in place on x ([B,C,H,W] fp32 CUDA, contiguous).
+    want_range (no residual_bn): returns (x, bits) -- bits a one-element int32 tensor the pass leaves holding max range_bits(y)
+    as float bits (`orp_affine_act_range`), what `conv3x3_bn_act` takes as `range_bits`.
     residual_bn: the residual is a RAW convolution output and this eval-mode BatchNorm is applied to it while it is read
     (`orp_affine2_act`: the downsample branch of a stage's first bottleneck) -- the values of bn_act(residual, residual_bn,
     relu=False) followed by this call, without that pass over memory."""
@@ -172,8 +174,17 @@ def bn_act(x, bn, residual=None, relu=True, residual_bn=None):
         raise ValueError("bn_act: residual must match x")
     if residual_bn is not None and residual is None:
         raise ValueError("bn_act: residual_bn without a residual")
+    if want_range and residual_bn is not None:
+        raise ValueError("bn_act: want_range with residual_bn")
     scale, shift = _bn_affine(bn)
     B, C, H, W = x.shape
+    if want_range:
+        bits = torch.empty(1, dtype=torch.int32, device=x.device)
+        with torch.cuda.device(x.device):
+            rc = _lib.lib().orp_affine_act_range(_lib.ptr(x), _lib.ptr(residual), _lib.ptr(scale), _lib.ptr(shift), _lib.ptr(x),
+                                                 B, C, H * W, 1 if relu else 0, _lib.ptr(bits), _lib.stream_of(x))
+        _lib.check(rc, "orp_affine_act_range")
+        return x, bits
     if residual_bn is not None:
         scale2, shift2 = _bn_affine(residual_bn)
         with torch.cuda.device(x.device):
@@ -213,21 +224,25 @@ def conv1x1_bn_act_ok(x, conv, bn):
                 conv.groups == 1 and x.size(2) * x.size(3) > 0 and _lib.lib().orp_conv1x1_bn_act_ok(w.size(1), w.size(0)))
 
 
-def conv1x1_bn_act(x, conv, bn, residual=None, residual_bn=None, relu=True, force=False):
+def conv1x1_bn_act(x, conv, bn, residual=None, residual_bn=None, relu=True, force=False, want_range=False):
     """relu?(BatchNorm_eval(conv(x)) (+ residual)) for a bottleneck's 1x1 convolution, as a new contiguous tensor.  Where
     `orp_conv1x1_bn_act_pays` says the fused launch was measured faster (or force=True, at any supported shape) the BatchNorm,
     the residual (residual_bn: the residual is a RAW convolution output and this eval-mode BatchNorm is applied to it, as in
     `bn_act`) and the ReLU run in the epilogue of the exact-fp32 MFMA kernel `orp_conv1x1_bn_act`; everywhere else this is
-    `bn_act(conv(x).contiguous(), ...)`: the library's convolution and the pass.  Inference only."""
+    `bn_act(conv(x).contiguous(), ...)`: the library's convolution and the pass.  Inference only.
+    want_range (no residual): returns (y, bits), bits = a one-element int32 tensor with max range_bits(y) as float bits, left by
+    whichever kernel wrote y (`orp_conv1x1_bn_act_range` / `orp_affine_act_range`) -- `conv3x3_bn_act`'s `range_bits`."""
     if residual_bn is not None and residual is None:
         raise ValueError("conv1x1_bn_act: residual_bn without a residual")
+    if want_range and residual is not None:
+        raise ValueError("conv1x1_bn_act: want_range with a residual")
     L = _lib.lib()
     fused = conv1x1_bn_act_ok(x, conv, bn) and (residual_bn is None or not residual_bn.training)
     if fused and not force:
         fused = bool(L.orp_conv1x1_bn_act_pays(x.size(1), conv.weight.size(0), x.size(2) * x.size(3), x.size(0),
                                                 1 if residual is not None else 0))
     if not fused:
-        return bn_act(conv(x).contiguous(), bn, residual=residual, relu=relu, residual_bn=residual_bn)
+        return bn_act(conv(x).contiguous(), bn, residual=residual, relu=relu, residual_bn=residual_bn, want_range=want_range)
     x = x.detach().contiguous()
     B, cin, H, W = x.shape
     cout = conv.weight.size(0)
@@ -239,11 +254,92 @@ def conv1x1_bn_act(x, conv, bn, residual=None, residual_bn=None, relu=True, forc
     scale, shift = _bn_affine(bn)
     scale2, shift2 = _bn_affine(residual_bn) if residual_bn is not None else (None, None)
     y = torch.empty((B, cout, H, W), dtype=torch.float32, device=x.device)
+    if want_range:
+        bits = torch.empty(1, dtype=torch.int32, device=x.device)
+        with torch.cuda.device(x.device):
+            rc = L.orp_conv1x1_bn_act_range(_lib.ptr(x), _lib.ptr(wt), _lib.ptr(scale), _lib.ptr(shift), None, None, None,
+                                            _lib.ptr(y), B, cin, cout, H * W, 1 if relu else 0, _lib.ptr(bits), _lib.stream_of(x))
+        _lib.check(rc, "orp_conv1x1_bn_act_range")
+        return y, bits
     with torch.cuda.device(x.device):
         rc = L.orp_conv1x1_bn_act(_lib.ptr(x), _lib.ptr(wt), _lib.ptr(scale), _lib.ptr(shift), _lib.ptr(residual),
                                   _lib.ptr(scale2), _lib.ptr(shift2), _lib.ptr(y), B, cin, cout, H * W, 1 if relu else 0,
                                   _lib.stream_of(x))
     _lib.check(rc, "orp_conv1x1_bn_act")
+    return y
+
+
+def conv3x3_bn_act_ok(x, conv, bn, shape=None):
+    """conv is a bias-free 3x3 / stride 1 / padding 1 / dilation 1 / groups 1 nn.Conv2d of a shape `orp_conv3x3_bn_act` takes
+    (Cin == Cout in {64, 128, 256}), bn an eval-mode BatchNorm2d, x an fp32 CUDA [B,Cin,H,W] tensor (shape: the input's shape where x
+    is only a tensor of its device and dtype)"""
+    w = getattr(conv, 'weight', None)
+    shape = tuple(x.shape) if shape is None else tuple(shape)
+    return bool(type(conv) is torch.nn.Conv2d and isinstance(bn, torch.nn.BatchNorm2d) and not bn.training and
+                x.is_cuda and x.dtype == torch.float32 and len(shape) == 4 and w.dtype == torch.float32 and w.dim() == 4 and
+                w.size(2) == 3 and w.size(3) == 3 and shape[1] == w.size(1) and conv.bias is None and
+                tuple(conv.stride) == (1, 1) and tuple(conv.padding) == (1, 1) and tuple(conv.dilation) == (1, 1) and
+                conv.groups == 1 and shape[0] * shape[2] * shape[3] > 0 and _lib.lib().orp_conv3x3_bn_act_ok(w.size(1), w.size(0)))
+
+
+def conv3x3_bn_act_routed(x, conv, bn, force=False, shape=None):
+    """`conv3x3_bn_act` would run the fused launch for this input, given its range: supported (`conv3x3_bn_act_ok`) and either
+    forced or measured faster (`orp_conv3x3_bn_act_pays`).  A caller asks BEFORE it produces the input (shape = its shape, x any
+    tensor of its device and dtype), so that the producer leaves the range word."""
+    if not conv3x3_bn_act_ok(x, conv, bn, shape):
+        return False
+    B, _c, H, W = tuple(x.shape) if shape is None else tuple(shape)
+    return bool(force or _lib.lib().orp_conv3x3_bn_act_pays(conv.weight.size(1), conv.weight.size(0), H, W, B))
+
+
+def conv3x3_bn_act_tile(cin, cout, H, W, B):
+    """(tile_h, tile_w, waves over positions, waves over channels) of an `orp_conv3x3_bn_act` launch of this shape, or None"""
+    v = [ctypes.c_int() for _ in range(4)]
+    if not _lib.lib().orp_conv3x3_bn_act_tile(int(cin), int(cout), int(H), int(W), int(B), *[ctypes.byref(t) for t in v]):
+        return None
+    return tuple(t.value for t in v)
+
+
+_packed_3x3 = _packcache.new_cache("conv3x3_bn_weight")
+
+
+def _packed_3x3_planes(weight):
+    """[C,C,3,3] -> the two fp16 planes + scale `orp_conv3x3_bn_act` reads (`orp_conv3x3_bn_pack_weight`: 4 bytes per weight), cached
+    on the live parameter (inference only), keyed by the tensor's storage / version state."""
+    w = weight.detach()
+    state = _packcache.tensor_state(w)
+    hit = _packed_3x3.get(weight, state)
+    if hit is not None:
+        return _lib.keep_for_graph(hit)
+    L = _lib.lib()
+    cout, cin = w.size(0), w.size(1)
+    w32 = w.float().contiguous()
+    packed = torch.empty((L.orp_conv3x3_bn_packed_bytes(cin, cout),), dtype=torch.uint8, device=w.device)
+    with torch.cuda.device(w.device):
+        _lib.check(L.orp_conv3x3_bn_pack_weight(_lib.ptr(w32), cin, cout, _lib.ptr(packed), _lib.stream_of(w32)),
+                   "orp_conv3x3_bn_pack_weight")
+    return _lib.keep_for_graph(_packed_3x3.put(weight, state, packed))
+
+
+def conv3x3_bn_act(x, conv, bn, relu=True, force=False, range_bits=None):
+    """relu?(BatchNorm_eval(conv(x))) for a bottleneck's conv2 as a new contiguous tensor.  Where `conv3x3_bn_act_routed` says so and
+    the input's range is known -- range_bits: the one-element int32 tensor its producer left (`conv1x1_bn_act(want_range=True)`,
+    `bn_act(want_range=True)`) -- this is ONE launch of `orp_conv3x3_bn_act`: the fp16-pieces arithmetic of the towers' convolutions
+    with the BatchNorm and the ReLU in the epilogue, NCHW in and out.  Everywhere else it is `bn_act(conv(x).contiguous(), bn)`:
+    the library's convolution and the pass.  The weight planes are packed once per weight (`_packed_3x3_planes`: cached on the live
+    parameter by storage / version state); nothing else is cached.  Inference only."""
+    if range_bits is None or not conv3x3_bn_act_routed(x, conv, bn, force):
+        return bn_act(conv(x).contiguous(), bn, relu=relu)
+    x = x.detach().contiguous()
+    B, cin, H, W = x.shape
+    cout = conv.weight.size(0)
+    packed = _packed_3x3_planes(conv.weight)
+    scale, shift = _bn_affine(bn)
+    y = torch.empty((B, cout, H, W), dtype=torch.float32, device=x.device)
+    with torch.cuda.device(x.device):
+        rc = _lib.lib().orp_conv3x3_bn_act(_lib.ptr(x), _lib.ptr(packed), _lib.ptr(scale), _lib.ptr(shift), _lib.ptr(range_bits),
+                                           _lib.ptr(y), B, cin, cout, H, W, 1 if relu else 0, _lib.stream_of(x))
+    _lib.check(rc, "orp_conv3x3_bn_act")
     return y
 
 
