@@ -633,6 +633,27 @@ int orp_conv1x1_bn_act(const float* x, const float* weight_t, const float* scale
 int orp_conv1x1_bn_act_range(const float* x, const float* weight_t, const float* scale, const float* shift, const float* residual,
                              const float* scale2, const float* shift2, float* y, int batch, int c_in, int c_out, int hw, int relu,
                              uint32_t* range_out, void* stream);
+/* orp_conv1x1_bn_act_pieces: the same operator and argument set (range_out NULL or as orp_conv1x1_bn_act_range's) on the bf16 matrix
+ *   pipe: every fp32 operand split exactly into three bf16 pieces by truncation (csrc/orp_dcn_split.hip), six products per pair on
+ *   v_mfma_f32_32x32x16_bf16, fp32 accumulation in ONE accumulator per output in a fixed order (no split-K, no atomics, independent of
+ *   the tiling; deterministic).  NOT bit-identical to orp_conv1x1_bn_act on general data (another grouping of the sum; held to
+ *   float64 inside the same bound by tests/test_gpu_conv1x1_bn_pieces.py), bit-identical on exact data.  No range word is read:
+ *   bf16 carries fp32's exponent.  A non-finite x makes the outputs of its own position non-finite -- possibly NaN where the fp32
+ *   kernel gives inf -- and touches no other position.  weight_packed: orp_conv1x1_bn_pieces_packed_bytes bytes (16-byte aligned)
+ *   from orp_conv1x1_bn_pieces_pack_weight for the [Cout,Cin] weight: three bf16 planes [3][Cin/16][2][Cout][8].
+ *   orp_conv1x1_bn_act_pieces_ok: as orp_conv1x1_bn_act_ok with Cin % 64 == 0.  orp_conv1x1_bn_act_pieces_pays: 1 where this launch was MEASURED
+ *   faster than both library convolution + pass and orp_conv1x1_bn_act on MI355X (closed table, docs/notebook/round16.md), else 0;
+ *   mmdet_ops/fused_norm.py:conv1x1_bn_act asks it first.  orp_conv1x1_bn_act_pieces_tile: the workgroup tile (output channels x
+ *   positions: 128 x 128, 128 x 64, 128 x 32, or 64 x 128 for Cout = 64) of a launch of this shape; 0 where not supported. */
+int orp_conv1x1_bn_act_pieces_ok(int c_in, int c_out);
+int orp_conv1x1_bn_act_pieces_pays(int c_in, int c_out, int hw, int batch, int has_residual);
+int orp_conv1x1_bn_act_pieces_tile(int c_in, int c_out, int hw, int batch, int* tile_channels, int* tile_positions);
+size_t orp_conv1x1_bn_pieces_packed_bytes(int c_in, int c_out);
+int orp_conv1x1_bn_pieces_pack_weight(const float* weight, int c_in, int c_out, void* packed, void* stream);
+int orp_conv1x1_bn_act_pieces(const float* x, const void* weight_packed, const float* scale, const float* shift,
+                              const float* residual, const float* scale2, const float* shift2, float* y, int batch, int c_in,
+                              int c_out, int hw, int relu, uint32_t* range_out, void* stream);
+
 /* the same optional output for the BatchNorm pass (blocks whose conv1 stays on the library) */
 int orp_affine_act_range(const float* x, const float* residual, const float* scale, const float* shift, float* y, int batch,
                          int channels, int hw, int relu, uint32_t* range_out, void* stream);

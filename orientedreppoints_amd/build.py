@@ -45,6 +45,7 @@ SOURCES = [
     ("orp_conv_small.hip", []),
     ("orp_conv1x1.hip", []),
     ("orp_conv1x1_bn.hip", []),
+    ("orp_conv1x1_bn_pieces.hip", []),
     ("orp_conv3x3_bn.hip", []),
     ("orp_dcn.hip", []),
     ("orp_dcn_split.hip", ["-ffp-contract=off"]),    # the bilinear combine is the reference's unfused float expression

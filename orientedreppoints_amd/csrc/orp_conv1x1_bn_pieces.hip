@@ -1,0 +1,471 @@
+// orp_conv1x1_bn_pieces.hip -- orp_conv1x1_bn.hip's operator on the 16-bit matrix pipe (gfx950, inference):
+//
+//   y = relu?( fma(conv1x1(x, w), a[c], b[c]) (+ r) ),  r = nothing | res | fma(res, a2[c], b2[c]) rounded to fp32
+//
+// NCHW fp32 in and out, stride 1, the same argument set (the optional range word included) and the same epilogue expressions
+// (orp_affine.hpp).  What changes is the instruction of the contraction.  v_mfma_f32_32x32x2_f32 runs at the vector rate; here every
+// fp32 operand is split EXACTLY into three bf16 pieces by truncation, as in orp_dcn_split.hip,
+//
+//      v = v0 + v1 + v2,   v0 = v & 0xffff0000,   v1 = (v - v0) & 0xffff0000,   v2 = (v - v0) - v1        (8 + 8 + 8 bits)
+//
+// and x w becomes the six products x2 w0, x0 w2, x1 w1, x1 w0, x0 w1, x0 w0 (smallest first; x1 w2, x2 w1 and x2 w2, each at most
+// 2^-24 |x w|, are dropped) on v_mfma_f32_32x32x16_bf16.  Each product of pieces is exact in the fp32 accumulator; bf16 carries
+// fp32's exponent, so no range word is read and no operand is scaled.  Every output has ONE accumulator fed in a fixed order --
+// ascending 16-channel chunks, the six products of a chunk in the order above: no split-K, no atomics, and the value of an output
+// does not depend on the tile it falls in.  Not bit-identical to the fp32 kernel (other grouping of the sum); exact data (every
+// partial sum an integer multiple of one unit below 2^24 of them) gives the same bits.
+//
+// Non-finite x: the split of +-inf leaves inf - inf, so an infinite x gives NaN where the fp32 kernel gives +-inf (and a zero piece
+// of a weight times an infinite piece is NaN as well).  The outputs of that POSITION are non-finite, of possibly another class
+// than fp32's; no other position is touched: the columns of the product are independent and no cross-lane operation sits in
+// the K loop.
+//
+// Per image Y[Cout][HW] = W[Cout][Cin] X[Cin][HW], output channels as MFMA rows and positions as columns (a store instruction
+// writes 32 consecutive positions of two channels).
+//   * weights: packed once per weight tensor (orp_conv1x1_bn_pieces_pack_weight) into three bf16 planes [plane][Cin/16][2][Cout][8]:
+//     one 16-byte load is the 8 k-values of an MFMA lane.  They go from L2 straight into a register ring of one K step, refilled in
+//     place right behind their use.
+//   * activations: K runs in steps of 32 (128-position tiles) or 64 channels.  A thread fetches rows k and k + 1 of four consecutive positions (two 16-byte loads along
+//     positions), splits the eight values in registers and writes the three planes to LDS as [position][K step + 8] bf16, one packed
+//     dword (k, k + 1) per position and plane.  The row stride of 20 or 36 dwords = 4 x odd puts the 16 rows of every ds_read_b128 lane
+//     group on 16 different 16-byte slots of the 64 banks.  For the stores (banks modulo 32) a thread's four positions lie 20 or 4
+//     banks apart and the threads of a row 16 apart: a thread writes its positions in an order rotated by (position quad / 2) % 4, which
+//     leaves a half wave two lanes per bank -- what a 32-bit store does not pay for.  LDS is double buffered: step t + 1 is written
+//     while step t is contracted, one barrier per step; the loads of step t + 2 are in flight meanwhile (the narrow tiles run one or
+//     two workgroups per CU: a K step's MFMAs alone do not cover a trip to memory).
+//   * one workgroup = 4 waves.  Wide layout: each wave owns 32 channels and all positions of the tile (128 channels x 128, 64 or 32
+//     positions): no weight is fetched twice by a workgroup.  Cout = 64: 2 x 2 waves on 64 channels x 128 positions.  A tile
+//     never crosses an image; the last tile of a plane is ragged (loads clamped and zeroed, stores masked), channels past Cout read
+//     the last channel's weights and are not stored.
+//   * the residual of a wave's outputs is requested before the last K step's MFMAs.
+// LDS 27 - 60 KB + the BatchNorm constants.
+#include <hip/hip_runtime.h>
+#include <stdint.h>
+
+#include "../../include/orp_hip.h"
+#include "orp_affine.hpp"
+#include "orp_range.hpp"
+#include "orp_launch.hpp"
+
+namespace {
+
+constexpr int kThreads = 256;
+
+typedef float f32x16 __attribute__((ext_vector_type(16)));
+typedef __bf16 bf8 __attribute__((ext_vector_type(8)));
+
+struct Args {
+  const float* x;                  // [B][Cin][hw]
+  const uint16_t* planes;          // three bf16 planes [pl][Cin/16][2][Cout][8]
+  size_t plane_stride;             // elements between two planes
+  const float* scale; const float* shift;       // [Cout]
+  const float* res;                // [B][Cout][hw] or NULL
+  const float* scale2; const float* shift2;     // [Cout] or NULL: the residual's own affine
+  float* y;                        // [B][Cout][hw]
+  int cin, cout, hw, relu;
+  int ntm, ntn;                    // tiles per image: channels, positions
+  unsigned* range;                 // RANGE: one word, raised to max range_bits(y)
+};
+
+// w [Cout][Cin] fp32 -> three bf16 planes [pl][c/16][kg][o][8]  (kg = (c % 16) / 8, e = c % 8): pack_planes_kernel's split and order
+__global__ void pack_pieces_kernel(const float* __restrict__ w, int cout, int cin, uint16_t* __restrict__ planes) {
+  const long total = (long)cout * cin;
+  for (long i = (long)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += (long)gridDim.x * blockDim.x) {
+    const int e = (int)(i & 7);
+    long r = i >> 3;
+    const int o = (int)(r % cout); r /= cout;
+    const int kg = (int)(r & 1);
+    const int cblk = (int)(r >> 1);
+    const int c = cblk * 16 + kg * 8 + e;
+    const float v = w[(long)o * cin + c];
+    const float v0 = __uint_as_float(__float_as_uint(v) & 0xffff0000u);
+    const float r1 = v - v0;
+    const float v1 = __uint_as_float(__float_as_uint(r1) & 0xffff0000u);
+    const float v2 = r1 - v1;
+    planes[i] = (uint16_t)(__float_as_uint(v0) >> 16);
+    planes[total + i] = (uint16_t)(__float_as_uint(v1) >> 16);
+    planes[2 * total + i] = (uint16_t)(__float_as_uint(v2) >> 16);
+  }
+}
+
+// two fp32 values whose low 16 bits are zero -> one dword of two bf16: (a >> 16) | (b & 0xffff0000)
+__device__ __forceinline__ unsigned pack_hi16(float a, float b) {
+  return __builtin_amdgcn_perm(__float_as_uint(b), __float_as_uint(a), 0x07060302u);
+}
+
+// rows k (a) and k + 1 (b) of one position -> the packed dword of each plane
+__device__ __forceinline__ void split_pair(float a, float b, unsigned (&d)[3]) {
+  const float a0 = __uint_as_float(__float_as_uint(a) & 0xffff0000u), b0 = __uint_as_float(__float_as_uint(b) & 0xffff0000u);
+  const float ar = a - a0, br = b - b0;
+  const float a1 = __uint_as_float(__float_as_uint(ar) & 0xffff0000u), b1 = __uint_as_float(__float_as_uint(br) & 0xffff0000u);
+  d[0] = pack_hi16(a0, b0);
+  d[1] = pack_hi16(a1, b1);
+  d[2] = pack_hi16(ar - a1, br - b1);
+}
+
+// WCH waves over channels (32 each) x 4 / WCH waves over positions (32 WN each).  VEC: hw % 4 == 0 and x 16-byte aligned.  MODE: the
+// residual term (0 nothing, 1 res, 2 res with its own affine); RANGE: the stored values' range word leaves with them -- template
+// parameters for the reasons orp_conv1x1_bn.hip gives.
+template <int WCH, int WN, int BK, bool VEC, int MODE, bool RANGE = false>
+__global__ void __launch_bounds__(kThreads, 2)
+conv1x1_bn_pieces_kernel(const Args P) {
+  constexpr int ASTR = BK + 8;       // bf16 elements per position row in LDS: 20 or 36 dwords = 4 x odd
+  constexpr int NCH = BK / 16;       // MFMA chunks of 16 channels per K step
+  constexpr int WPOS = 4 / WCH;
+  constexpr int BM = 32 * WCH, BN = 32 * WN * WPOS;
+  constexpr int PLANE = BN * ASTR, BUF = 3 * PLANE;            // bf16 elements
+  constexpr int ITEMS = (BK / 2) * (BN / 4);                   // (row pair, position quad) items of a K step
+  constexpr int XV = (ITEMS + kThreads - 1) / kThreads;
+  __shared__ __align__(16) uint16_t lds[2 * BUF + 8 * BM];     // (one array, as in orp_conv1x1_bn.hip)
+  float* Cs = reinterpret_cast<float*>(lds + 2 * BUF);         // [4][BM]: scale, shift, scale2, shift2 of the tile's channels
+
+  const int tid = threadIdx.x;
+  const int bid = blockIdx.x;
+  const int mt = bid % P.ntm, rest = bid / P.ntm;
+  const int nt = rest % P.ntn, b = rest / P.ntn;
+  const int m0 = mt * BM, p0 = nt * BN;
+  const int hw = P.hw, cout = P.cout;
+  const float* xb = P.x + (size_t)b * P.cin * hw;
+  if (tid < BM) {                  // (visible behind the first barrier, never rewritten)
+    const int ch = min(m0 + tid, cout - 1);
+    Cs[tid] = P.scale[ch]; Cs[BM + tid] = P.shift[ch];
+    if (MODE == 2) { Cs[2 * BM + tid] = P.scale2[ch]; Cs[3 * BM + tid] = P.shift2[ch]; }
+  }
+
+  const int lane = tid & 63, wave = tid >> 6;
+  const int kg = lane >> 5, l31 = lane & 31;
+  const int wm0 = (wave / WPOS) * 32, wn0 = (wave % WPOS) * 32 * WN;      // the wave's corner inside the workgroup tile
+
+  // ---- weights: lane (channel, k-group) reads the 8 k-values of a chunk per plane; a register ring of one K step ----
+  const uint16_t* wp = P.planes + ((size_t)kg * cout + min(m0 + wm0 + l31, cout - 1)) * 8;
+  const size_t wblk = (size_t)2 * cout * 8;
+  bf8 wq[NCH][3];
+  auto load_w = [&](int t, int c) {
+    const uint16_t* a = wp + (size_t)(t * NCH + c) * wblk;
+#pragma unroll
+    for (int pl = 0; pl < 3; pl++) wq[c][pl] = *reinterpret_cast<const bf8*>(a + (size_t)pl * P.plane_stride);
+  };
+#pragma unroll
+  for (int c = 0; c < NCH; c++) load_w(0, c);
+
+  // ---- activations: item idx of a K step = rows 2 kp, 2 kp + 1 of positions 4 pq .. 4 pq + 3.  16 consecutive lanes take 16
+  // consecutive quads of one row pair (256 contiguous bytes per row); a half wave holds two row pairs (BN = 32: 8 quads x 4 pairs)
+  float4 xr[2][XV][2];             // two K steps in flight: step t + 2 is requested while step t is contracted
+  int xpq[XV], xkp[XV];
+#pragma unroll
+  for (int i = 0; i < XV; i++) {
+    const int idx = tid + i * kThreads;
+    if (BN >= 64) {
+      const int r = idx >> 5;
+      xpq[i] = (idx & 15) + 16 * (r % (BN / 64));
+      xkp[i] = ((idx >> 4) & 1) + 2 * (r / (BN / 64));
+    } else {
+      xpq[i] = idx & (BN / 4 - 1);
+      xkp[i] = idx / (BN / 4);
+    }
+    xkp[i] &= BK / 2 - 1;          // (threads past ITEMS repeat an item's loads and store nothing)
+  }
+  auto fetch = [&](int k0, float4 (&xr)[XV][2]) {
+#pragma unroll
+    for (int i = 0; i < XV; i++) {
+      const int col = p0 + 4 * xpq[i];
+#pragma unroll
+      for (int h = 0; h < 2; h++) {
+        const float* src = xb + (size_t)(k0 + 2 * xkp[i] + h) * hw;
+        if (VEC) {
+          xr[i][h] = *reinterpret_cast<const float4*>(src + min(col, hw - 4));
+        } else {
+          xr[i][h].x = src[min(col, hw - 1)]; xr[i][h].y = src[min(col + 1, hw - 1)];
+          xr[i][h].z = src[min(col + 2, hw - 1)]; xr[i][h].w = src[min(col + 3, hw - 1)];
+        }
+      }
+    }
+  };
+  auto stage = [&](int buf, const float4 (&xr)[XV][2]) {
+#pragma unroll
+    for (int i = 0; i < XV; i++) {
+      if (ITEMS % kThreads != 0 && tid + i * kThreads >= ITEMS) continue;
+      const int col = p0 + 4 * xpq[i];
+      float v[2][4];
+#pragma unroll
+      for (int h = 0; h < 2; h++) {
+        v[h][0] = col < hw ? xr[i][h].x : 0.f; v[h][1] = col + 1 < hw ? xr[i][h].y : 0.f;
+        v[h][2] = col + 2 < hw ? xr[i][h].z : 0.f; v[h][3] = col + 3 < hw ? xr[i][h].w : 0.f;
+      }
+      // rotate the four positions by rot = (pq / 2) % 4: store j then writes position (j + rot) % 4
+      const int rot = (xpq[i] >> 1) & 3;
+#pragma unroll
+      for (int h = 0; h < 2; h++) {
+        if (rot & 1) { const float t0 = v[h][0]; v[h][0] = v[h][1]; v[h][1] = v[h][2]; v[h][2] = v[h][3]; v[h][3] = t0; }
+        if (rot & 2) { const float t0 = v[h][0], t1 = v[h][1]; v[h][0] = v[h][2]; v[h][1] = v[h][3]; v[h][2] = t0; v[h][3] = t1; }
+      }
+      unsigned* base = reinterpret_cast<unsigned*>(lds + buf * BUF) + xkp[i];
+#pragma unroll
+      for (int j = 0; j < 4; j++) {
+        unsigned d[3];
+        split_pair(v[0][j], v[1][j], d);
+        unsigned* dst = base + (4 * xpq[i] + ((j + rot) & 3)) * (ASTR / 2);
+#pragma unroll
+        for (int pl = 0; pl < 3; pl++) dst[pl * (PLANE / 2)] = d[pl];
+      }
+    }
+  };
+
+  f32x16 acc[WN];
+#pragma unroll
+  for (int ni = 0; ni < WN; ni++)
+#pragma unroll
+    for (int r = 0; r < 16; r++) acc[ni][r] = 0.f;
+
+  // one K step out of buffer `buf`; the weights of chunk c are refilled for step t_next right behind their use
+  auto mma = [&](int buf, int t_next) {
+    const uint16_t* xa = lds + buf * BUF + (wn0 + l31) * ASTR + 8 * kg;
+    auto load_x = [&](int c, bf8 (&q)[WN][3]) {
+#pragma unroll
+      for (int ni = 0; ni < WN; ni++)
+#pragma unroll
+        for (int pl = 0; pl < 3; pl++) q[ni][pl] = *reinterpret_cast<const bf8*>(xa + pl * PLANE + ni * 32 * ASTR + c * 16);
+    };
+    // the narrow tiles read a chunk's fragments one chunk ahead: six or twelve MFMAs do not hide an LDS read behind themselves
+    // with one or two waves per SIMD; at 128 positions per wave the registers go to the accumulators instead
+    constexpr bool AHEAD = WN <= 2;
+    bf8 xqs[AHEAD ? 2 : 1][WN][3];
+    load_x(0, xqs[0]);
+#pragma unroll
+    for (int c = 0; c < NCH; c++) {
+      bf8 (&xq)[WN][3] = xqs[AHEAD ? (c & 1) : 0];
+      if (AHEAD) { if (c + 1 < NCH) load_x(c + 1, xqs[(c + 1) & 1]); }
+      else if (c > 0) load_x(c, xqs[0]);
+      __builtin_amdgcn_sched_barrier(0);
+      // D[channel][position]; smallest products first
+#pragma unroll
+      for (int ni = 0; ni < WN; ni++) acc[ni] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(wq[c][0], xq[ni][2], acc[ni], 0, 0, 0);
+#pragma unroll
+      for (int ni = 0; ni < WN; ni++) acc[ni] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(wq[c][2], xq[ni][0], acc[ni], 0, 0, 0);
+#pragma unroll
+      for (int ni = 0; ni < WN; ni++) acc[ni] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(wq[c][1], xq[ni][1], acc[ni], 0, 0, 0);
+#pragma unroll
+      for (int ni = 0; ni < WN; ni++) acc[ni] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(wq[c][0], xq[ni][1], acc[ni], 0, 0, 0);
+#pragma unroll
+      for (int ni = 0; ni < WN; ni++) acc[ni] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(wq[c][1], xq[ni][0], acc[ni], 0, 0, 0);
+#pragma unroll
+      for (int ni = 0; ni < WN; ni++) acc[ni] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(wq[c][0], xq[ni][0], acc[ni], 0, 0, 0);
+      __builtin_amdgcn_sched_barrier(0);
+      load_w(t_next, c);
+      __builtin_amdgcn_sched_barrier(0);
+    }
+  };
+
+  // Step t (not the last): request step t + 2 into the register set step t's data left, contract step t out of buffer t & 1, write
+  // step t + 1 (requested a step ago) into the other buffer -- its last readers are behind the previous barrier -- one barrier.
+  // Every load is unconditional (past the end the last step is requested again), so the compiler's vmcnt counts are exact.
+  const int nk = P.cin / BK;
+  auto step = [&](int t, float4 (&cur)[XV][2], float4 (&nxt)[XV][2], int buf) {
+    fetch(min(t + 2, nk - 1) * BK, cur);
+    __builtin_amdgcn_sched_barrier(0);      // the requests go out in front of the MFMAs
+    mma(buf, t + 1);
+    stage(buf ^ 1, nxt);
+    __syncthreads();
+  };
+  fetch(0, xr[0]);
+  stage(0, xr[0]);
+  fetch(min(1, nk - 1) * BK, xr[1]);
+  __syncthreads();
+  int t = 0;
+  for (; t + 2 < nk; t += 2) {
+    step(t, xr[0], xr[1], 0);
+    step(t + 1, xr[1], xr[0], 1);
+  }
+  if (t + 1 < nk) step(t, xr[0], xr[1], 0);
+
+  // Epilogue addressing.  Register r of tile ni is channel m0 + wm0 + 8 (r >> 2) + 4 kg + (r & 3) at position
+  // p0 + wn0 + 32 ni + l31: a store instruction writes 32 consecutive positions of two channels.
+  const size_t plane0 = (size_t)b * cout;
+  float rv[WN][16];
+  if (MODE) {               // requested before the last K step's MFMAs (clamped addresses: no branch per load)
+#pragma unroll
+    for (int ni = 0; ni < WN; ni++) {
+      const int p = min(p0 + wn0 + 32 * ni + l31, hw - 1);
+#pragma unroll
+      for (int r = 0; r < 16; r++) {
+        const int ch = min(m0 + wm0 + 8 * (r >> 2) + 4 * kg + (r & 3), cout - 1);
+        rv[ni][r] = P.res[(plane0 + ch) * hw + p];
+      }
+    }
+  }
+  __builtin_amdgcn_sched_barrier(0);
+  mma((nk - 1) & 1, nk - 1);
+
+  unsigned rmax = 0u;
+#pragma unroll
+  for (int g = 0; g < 4; g++) {
+    const int chg = m0 + wm0 + 8 * g + 4 * kg;          // four consecutive channels (Cout % 4 == 0: all in or out)
+    const float* cs = Cs + wm0 + 8 * g + 4 * kg;
+    const float4 a4 = *reinterpret_cast<const float4*>(cs);
+    const float4 b4 = *reinterpret_cast<const float4*>(cs + BM);
+    const float av[4] = {a4.x, a4.y, a4.z, a4.w}, bv[4] = {b4.x, b4.y, b4.z, b4.w};
+    float a2v[4] = {0.f, 0.f, 0.f, 0.f}, b2v[4] = {0.f, 0.f, 0.f, 0.f};
+    if (MODE == 2) {
+      const float4 c4 = *reinterpret_cast<const float4*>(cs + 2 * BM);
+      const float4 d4 = *reinterpret_cast<const float4*>(cs + 3 * BM);
+      a2v[0] = c4.x; a2v[1] = c4.y; a2v[2] = c4.z; a2v[3] = c4.w;
+      b2v[0] = d4.x; b2v[1] = d4.y; b2v[2] = d4.z; b2v[3] = d4.w;
+    }
+#pragma unroll
+    for (int ni = 0; ni < WN; ni++) {
+      const int p = p0 + wn0 + 32 * ni + l31;
+#pragma unroll
+      for (int q = 0; q < 4; q++) {
+        const int r = 4 * g + q;
+        const float v = acc[ni][r];
+        float t;
+        if (MODE == 0) t = affine_act(v, av[q], bv[q], P.relu);
+        else if (MODE == 1) t = affine_res_act(v, av[q], bv[q], rv[ni][r], P.relu);
+        else t = affine_res_act(v, av[q], bv[q], affine_act(rv[ni][r], a2v[q], b2v[q], 0), P.relu);
+        if (chg < cout && p < hw) {
+          P.y[(plane0 + chg + q) * hw + p] = t;
+          if (RANGE) rmax = max(rmax, orp::range_bits(t));
+        }
+      }
+    }
+  }
+  if (RANGE) {
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) rmax = max(rmax, (unsigned)__shfl_xor((int)rmax, o, 64));
+    unsigned* red = reinterpret_cast<unsigned*>(lds);          // (free once every wave is behind its last MFMAs)
+    __syncthreads();
+    if (lane == 0) red[wave] = rmax;
+    __syncthreads();
+    if (tid == 0) orp::range_raise(P.range, max(max(red[0], red[1]), max(red[2], red[3])));
+  }
+}
+
+struct Tile { int bm, bn; };
+
+// the workgroup tile of a launch.  Cout <= 64: the 2 x 2 layout.  Otherwise the widest position tile of the 128-channel layout that
+// still gives the 256 CUs two workgroups each, else the narrowest.
+Tile pick_tile(int cout, int hw, int batch) {
+  if (cout <= 64) return Tile{64, 128};
+  const Tile cand[3] = {{128, 128}, {128, 64}, {128, 32}};
+  for (int i = 0; i < 3; i++) {
+    const Tile t = cand[i];
+    const long wgs = (long)((cout + t.bm - 1) / t.bm) * ((hw + t.bn - 1) / t.bn) * batch;
+    if (wgs >= 512) return t;
+  }
+  return cand[2];
+}
+
+template <int WCH, int WN, int BK, int MODE>
+void launch_mode(const Args& A, int batch, bool vec, hipStream_t st) {
+  const dim3 grid((unsigned)((long)A.ntm * A.ntn * batch));
+  if (vec) hipLaunchKernelGGL((conv1x1_bn_pieces_kernel<WCH, WN, BK, true, MODE>), grid, dim3(kThreads), 0, st, A);
+  else hipLaunchKernelGGL((conv1x1_bn_pieces_kernel<WCH, WN, BK, false, MODE>), grid, dim3(kThreads), 0, st, A);
+}
+template <int WCH, int WN, int BK>
+void launch(const Args& A, int batch, bool vec, hipStream_t st) {
+  if (A.range) {                                             // (conv1: no residual)
+    const dim3 grid((unsigned)((long)A.ntm * A.ntn * batch));
+    if (vec) hipLaunchKernelGGL((conv1x1_bn_pieces_kernel<WCH, WN, BK, true, 0, true>), grid, dim3(kThreads), 0, st, A);
+    else hipLaunchKernelGGL((conv1x1_bn_pieces_kernel<WCH, WN, BK, false, 0, true>), grid, dim3(kThreads), 0, st, A);
+  } else if (!A.res) launch_mode<WCH, WN, BK, 0>(A, batch, vec, st);
+  else if (!A.scale2) launch_mode<WCH, WN, BK, 1>(A, batch, vec, st);
+  else launch_mode<WCH, WN, BK, 2>(A, batch, vec, st);
+}
+
+}  // namespace
+
+extern "C" {
+
+int orp_conv1x1_bn_act_pieces_ok(int c_in, int c_out) {
+  return (c_in >= 64 && c_in <= 2048 && c_in % 64 == 0 && c_out >= 64 && c_out <= 4096 && c_out % 32 == 0) ? 1 : 0;
+}
+
+// the workgroup tile (channels x positions) a launch of this shape runs with; 0 where the shape is not supported
+int orp_conv1x1_bn_act_pieces_tile(int c_in, int c_out, int hw, int batch, int* tile_channels, int* tile_positions) {
+  if (!orp_conv1x1_bn_act_pieces_ok(c_in, c_out) || hw <= 0 || batch <= 0) return 0;
+  const Tile t = pick_tile(c_out, hw, batch);
+  if (tile_channels) *tile_channels = t.bm;
+  if (tile_positions) *tile_positions = t.bn;
+  return 1;
+}
+
+// THE routing rule of the pieces kernel: where its launch was measured faster than BOTH other sides on MI355X -- library convolution
+// + pass and the fp32 fused launch -- slowest pieces run against the fastest run of either (tests/checks/time_bottleneck_1x1_pieces.py;
+// docs/notebook/round16.md has the tables).  A closed table as orp_conv1x1_bn_act_pays: three corners were timed per (Cin, Cout)
+// pair of R-50, the map of a 1024^2 image with one image and with two, and the map of a 1536^2 image with one image; a row routes
+// one image from the 1024^2 map to the 1536^2 map where both ends paid, two images at the 1024^2 map only.  Nothing beyond a timed
+// corner is routed.  Both residual forms paid wherever one did, so has_residual does not enter.  45 of the 48 timed points paid.
+// The three that lost and the rows they leave out: 64 -> 64 with two images and at the 1536^2 map (bandwidth-bound, level with the
+// fp32 kernel: only its 1024^2 corner is routed) and 2048 -> 512 at one image's 1024 positions (64 workgroups' worth of work,
+// the library's GEMM wins: only its other two corners are routed).
+int orp_conv1x1_bn_act_pieces_pays(int c_in, int c_out, int hw, int batch, int has_residual) {
+  if (!orp_conv1x1_bn_act_pieces_ok(c_in, c_out) || hw <= 0 || batch <= 0) return 0;
+  (void)has_residual;
+  static const struct { int cin, cout, hw_min, hw_max, batch; } paid[] = {
+      {64, 64, 65536, 65536, 1},                                        // stage 1: conv1 of block 0
+      {256, 64, 65536, 147456, 1},  {256, 64, 65536, 65536, 2},         //          conv1 of the others
+      {64, 256, 65536, 147456, 1},  {64, 256, 65536, 65536, 2},         //          conv3
+      {256, 128, 65536, 147456, 1}, {256, 128, 65536, 65536, 2},        // stage 2: conv1 of block 0
+      {512, 128, 16384, 36864, 1},  {512, 128, 16384, 16384, 2},        //          conv1 of the others
+      {128, 512, 16384, 36864, 1},  {128, 512, 16384, 16384, 2},        //          conv3
+      {512, 256, 16384, 36864, 1},  {512, 256, 16384, 16384, 2},        // stage 3: conv1 of block 0
+      {1024, 256, 4096, 9216, 1},   {1024, 256, 4096, 4096, 2},         //          conv1 of the others
+      {256, 1024, 4096, 9216, 1},   {256, 1024, 4096, 4096, 2},         //          conv3
+      {1024, 512, 4096, 9216, 1},   {1024, 512, 4096, 4096, 2},         // stage 4: conv1 of block 0
+      {2048, 512, 2304, 2304, 1},   {2048, 512, 1024, 1024, 2},         //          conv1 of the others
+      {512, 2048, 1024, 2304, 1},   {512, 2048, 1024, 1024, 2},         //          conv3
+  };
+  for (const auto& s : paid)
+    if (s.cin == c_in && s.cout == c_out && s.batch == batch && hw >= s.hw_min && hw <= s.hw_max) return 1;
+  return 0;
+}
+
+// the packed weight: three bf16 planes [3][Cin/16][2][Cout][8] (6 bytes per weight)
+size_t orp_conv1x1_bn_pieces_packed_bytes(int c_in, int c_out) {
+  return orp_conv1x1_bn_act_pieces_ok(c_in, c_out) ? (size_t)6 * c_in * c_out : 0;
+}
+
+int orp_conv1x1_bn_pieces_pack_weight(const float* weight, int c_in, int c_out, void* packed, void* stream) {
+  if (!weight || !packed || ((uintptr_t)packed & 15) || !orp_conv1x1_bn_act_pieces_ok(c_in, c_out)) return ORP_EINVAL;
+  const long total = (long)c_in * c_out;
+  const int blocks = (int)((total + 255) / 256 < 4096 ? (total + 255) / 256 : 4096);
+  hipLaunchKernelGGL(pack_pieces_kernel, dim3(blocks), dim3(256), 0, (hipStream_t)stream, weight, c_out, c_in,
+                     reinterpret_cast<uint16_t*>(packed));
+  hipError_t e = hipGetLastError();
+  return e == hipSuccess ? ORP_OK : (int)e;
+}
+
+// range_out (or NULL): as orp_conv1x1_bn_act_range -- zeroed here by a kernel launch, raised by one conditional atomicMax per
+// workgroup; no residual with it.
+int orp_conv1x1_bn_act_pieces(const float* x, const void* weight_packed, const float* scale, const float* shift, const float* residual,
+                              const float* scale2, const float* shift2, float* y, int batch, int c_in, int c_out, int hw, int relu,
+                              uint32_t* range_out, void* stream) {
+  if (range_out && residual) return ORP_EINVAL;
+  if (!x || !weight_packed || !scale || !shift || !y || batch <= 0 || hw <= 0 || !orp_conv1x1_bn_act_pieces_ok(c_in, c_out))
+    return ORP_EINVAL;
+  if ((scale2 != nullptr) != (shift2 != nullptr) || (scale2 && !residual) || (const float*)y == x || (const float*)y == residual)
+    return ORP_EINVAL;
+  if ((uintptr_t)weight_packed & 15) return ORP_EINVAL;
+  const Tile t = pick_tile(c_out, hw, batch);
+  Args A;
+  A.x = x; A.planes = reinterpret_cast<const uint16_t*>(weight_packed); A.plane_stride = (size_t)c_in * c_out;
+  A.scale = scale; A.shift = shift; A.res = residual; A.scale2 = scale2; A.shift2 = shift2; A.y = y;
+  A.cin = c_in; A.cout = c_out; A.hw = hw; A.relu = relu ? 1 : 0;
+  A.ntm = (c_out + t.bm - 1) / t.bm; A.ntn = (hw + t.bn - 1) / t.bn;
+  A.range = range_out;
+  if ((long)A.ntm * A.ntn * batch >= (1L << 31)) return ORP_ETOOBIG;
+  const bool vec = (hw & 3) == 0 && ((uintptr_t)x & 15) == 0;
+  hipStream_t st = (hipStream_t)stream;
+  if (range_out) {
+    hipError_t fe = orp::fill_async(range_out, 0, sizeof(uint32_t), st);
+    if (fe != hipSuccess) return (int)fe;
+  }
+  if (t.bm == 64) launch<2, 2, 32>(A, batch, vec, st);        // (K steps of 64 at 128 positions would leave one workgroup per CU)
+  else if (t.bn == 128) launch<4, 4, 32>(A, batch, vec, st);
+  else if (t.bn == 64) launch<4, 2, 64>(A, batch, vec, st);
+  else launch<4, 1, 64>(A, batch, vec, st);
+  hipError_t e = hipGetLastError();
+  return e == hipSuccess ? ORP_OK : (int)e;
+}
+
+}  // extern "C"

@@ -73,6 +73,15 @@ class Bottleneck(nn.Module):
             on = switches.BN_CONV1X1_FUSE
         return bool(on)
 
+    def _conv1x1_pieces_on(self):
+        """where conv1 / conv3 run fused, the bf16-pieces kernel may take them at the shapes `orp_conv1x1_bn_act_pieces_pays` lists
+        (`fuse_conv1x1_pieces` attribute, or ORP_BN_CONV1X1_PIECES=0 for A/B timing: off gives the launches of before)"""
+        from .. import switches
+        on = getattr(self, 'fuse_conv1x1_pieces', None)
+        if on is None:
+            on = switches.BN_CONV1X1_PIECES
+        return bool(on)
+
     def _conv3x3_fusable(self):
         """conv2 may run on the fp16-pieces kernel with bn2 + ReLU in its epilogue where that was measured faster (`fuse_conv3x3`
         attribute, or ORP_BN_CONV3X3_FUSE=0 for A/B timing); the shapes are decided by `conv3x3_bn_act`
@@ -86,12 +95,13 @@ class Bottleneck(nn.Module):
     def _forward_fused(self, x):
         from ..mmdet_ops.fused_norm import bn_act, conv1x1_bn_act, conv3x3_bn_act, conv3x3_bn_act_routed
         fuse = self._conv1x1_fusable()
+        pieces = None if self._conv1x1_pieces_on() else False       # (None: conv1x1_bn_act asks its table)
 
         def conv_bn_act(t, conv, bn, **kw):
             # conv1 / conv3: where the fused kernel pays, the raw convolution output is never written; everywhere else (and with
             # the switch off) the library's convolution and the pass.  conv2 and the downsample convolution stay on the library.
             if fuse:
-                return conv1x1_bn_act(t, conv, bn, **kw)
+                return conv1x1_bn_act(t, conv, bn, pieces=pieces, **kw)
             return bn_act(conv(t).contiguous(), bn, **kw)
         force3 = bool(getattr(self, 'force_conv3x3', False))
         fuse3 = False

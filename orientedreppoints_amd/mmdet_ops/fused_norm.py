@@ -224,23 +224,80 @@ def conv1x1_bn_act_ok(x, conv, bn):
                 conv.groups == 1 and x.size(2) * x.size(3) > 0 and _lib.lib().orp_conv1x1_bn_act_ok(w.size(1), w.size(0)))
 
 
-def conv1x1_bn_act(x, conv, bn, residual=None, residual_bn=None, relu=True, force=False, want_range=False):
-    """relu?(BatchNorm_eval(conv(x)) (+ residual)) for a bottleneck's 1x1 convolution, as a new contiguous tensor.  Where
-    `orp_conv1x1_bn_act_pays` says the fused launch was measured faster (or force=True, at any supported shape) the BatchNorm,
-    the residual (residual_bn: the residual is a RAW convolution output and this eval-mode BatchNorm is applied to it, as in
-    `bn_act`) and the ReLU run in the epilogue of the exact-fp32 MFMA kernel `orp_conv1x1_bn_act`; everywhere else this is
-    `bn_act(conv(x).contiguous(), ...)`: the library's convolution and the pass.  Inference only.
+_packed_1x1_pieces = _packcache.new_cache("conv1x1_bn_pieces_weight")
+
+
+def _packed_1x1_planes(weight):
+    """[Cout,Cin,1,1] -> the three bf16 planes `orp_conv1x1_bn_act_pieces` reads (`orp_conv1x1_bn_pieces_pack_weight`: 6 bytes per
+    weight), cached on the live parameter (inference only), keyed by the tensor's storage / version state."""
+    w = weight.detach()
+    state = _packcache.tensor_state(w)
+    hit = _packed_1x1_pieces.get(weight, state)
+    if hit is not None:
+        return _lib.keep_for_graph(hit)
+    L = _lib.lib()
+    cout, cin = w.size(0), w.size(1)
+    w32 = w.float().reshape(cout, cin).contiguous()
+    packed = torch.empty((L.orp_conv1x1_bn_pieces_packed_bytes(cin, cout),), dtype=torch.uint8, device=w.device)
+    with torch.cuda.device(w.device):
+        _lib.check(L.orp_conv1x1_bn_pieces_pack_weight(_lib.ptr(w32), cin, cout, _lib.ptr(packed), _lib.stream_of(w32)),
+                   "orp_conv1x1_bn_pieces_pack_weight")
+    return _lib.keep_for_graph(_packed_1x1_pieces.put(weight, state, packed))
+
+
+def conv1x1_bn_act_pieces_tile(cin, cout, hw, B):
+    """(tile channels, tile positions) of an `orp_conv1x1_bn_act_pieces` launch of this shape, or None"""
+    v = [ctypes.c_int() for _ in range(2)]
+    if not _lib.lib().orp_conv1x1_bn_act_pieces_tile(int(cin), int(cout), int(hw), int(B), *[ctypes.byref(t) for t in v]):
+        return None
+    return tuple(t.value for t in v)
+
+
+def conv1x1_bn_act(x, conv, bn, residual=None, residual_bn=None, relu=True, force=False, want_range=False, pieces=None):
+    """relu?(BatchNorm_eval(conv(x)) (+ residual)) for a bottleneck's 1x1 convolution, as a new contiguous tensor.  Two fused
+    kernels carry the BatchNorm, the residual (residual_bn: the residual is a RAW convolution output and this eval-mode BatchNorm is
+    applied to it, as in `bn_act`) and the ReLU in their epilogue.  Asked first: `orp_conv1x1_bn_act_pieces_pays` -- the six-product
+    bf16-pieces kernel `orp_conv1x1_bn_act_pieces` where it was measured fastest (pieces=True: at any supported shape; pieces=False:
+    never; None: where the table says so and ORP_BN_CONV1X1_PIECES is on).  Then, unchanged, `orp_conv1x1_bn_act_pays` -- the
+    exact-fp32 MFMA kernel `orp_conv1x1_bn_act` (force=True: at any supported shape, and the pieces table is not asked).  Everywhere
+    else this is `bn_act(conv(x).contiguous(), ...)`: the library's convolution and the pass.  Inference only.
     want_range (no residual): returns (y, bits), bits = a one-element int32 tensor with max range_bits(y) as float bits, left by
-    whichever kernel wrote y (`orp_conv1x1_bn_act_range` / `orp_affine_act_range`) -- `conv3x3_bn_act`'s `range_bits`."""
+    whichever kernel wrote y (`orp_conv1x1_bn_act_pieces` / `orp_conv1x1_bn_act_range` / `orp_affine_act_range`) --
+    `conv3x3_bn_act`'s `range_bits`."""
     if residual_bn is not None and residual is None:
         raise ValueError("conv1x1_bn_act: residual_bn without a residual")
     if want_range and residual is not None:
         raise ValueError("conv1x1_bn_act: want_range with a residual")
     L = _lib.lib()
     fused = conv1x1_bn_act_ok(x, conv, bn) and (residual_bn is None or not residual_bn.training)
+    shape = (x.size(1), conv.weight.size(0), x.size(2) * x.size(3), x.size(0), 1 if residual is not None else 0) if fused else None
+    use_pieces = False
+    if fused and not (force and pieces is None) and pieces is not False:
+        if pieces is None:
+            from .. import switches
+            pieces = bool(switches.BN_CONV1X1_PIECES) and bool(L.orp_conv1x1_bn_act_pieces_pays(*shape))
+        use_pieces = bool(pieces) and bool(L.orp_conv1x1_bn_act_pieces_ok(shape[0], shape[1]))
+    if use_pieces:
+        x = x.detach().contiguous()
+        B, cin, H, W = x.shape
+        cout = conv.weight.size(0)
+        if residual is not None:
+            residual = residual.detach()
+            if not (tuple(residual.shape) == (B, cout, H, W) and residual.is_contiguous() and residual.dtype == torch.float32):
+                raise ValueError("conv1x1_bn_act: residual must be a contiguous fp32 tensor of the output's shape")
+        packed = _packed_1x1_planes(conv.weight)
+        scale, shift = _bn_affine(bn)
+        scale2, shift2 = _bn_affine(residual_bn) if residual_bn is not None else (None, None)
+        y = torch.empty((B, cout, H, W), dtype=torch.float32, device=x.device)
+        bits = torch.empty(1, dtype=torch.int32, device=x.device) if want_range else None
+        with torch.cuda.device(x.device):
+            rc = L.orp_conv1x1_bn_act_pieces(_lib.ptr(x), _lib.ptr(packed), _lib.ptr(scale), _lib.ptr(shift), _lib.ptr(residual),
+                                             _lib.ptr(scale2), _lib.ptr(shift2), _lib.ptr(y), B, cin, cout, H * W,
+                                             1 if relu else 0, _lib.ptr(bits), _lib.stream_of(x))
+        _lib.check(rc, "orp_conv1x1_bn_act_pieces")
+        return (y, bits) if want_range else y
     if fused and not force:
-        fused = bool(L.orp_conv1x1_bn_act_pays(x.size(1), conv.weight.size(0), x.size(2) * x.size(3), x.size(0),
-                                                1 if residual is not None else 0))
+        fused = bool(L.orp_conv1x1_bn_act_pays(*shape))
     if not fused:
         return bn_act(conv(x).contiguous(), bn, residual=residual, relu=relu, residual_bn=residual_bn, want_range=want_range)
     x = x.detach().contiguous()
