@@ -654,6 +654,28 @@ int orp_conv1x1_bn_act_pieces(const float* x, const void* weight_packed, const f
                               const float* residual, const float* scale2, const float* shift2, float* y, int batch, int c_in,
                               int c_out, int hw, int relu, uint32_t* range_out, void* stream);
 
+/* orp_conv1x1_bn_act_pieces_dual: a bottleneck's conv3 with the downsample convolution of its block contracted in the same launch,
+ *   y = relu?( fma(conv1x1(x, w), scale[c], shift[c]) + r ),  r = fma(conv1x1(x2 sampled at (stride2 oy, stride2 ox), w2),
+ *   scale2[c], shift2[c]) rounded to fp32 -- the downsample output is never in memory.  x [B,Cin,ho,wo], x2 [B,Cin2,h2,w2], y
+ *   [B,Cout,ho,wo] NCHW fp32, y a tensor of its own; stride2 1 or 2 with ho = (h2 - 1) / stride2 + 1, wo = (w2 - 1) / stride2 + 1 (an
+ *   odd input side leaves its last row / column unread); both weights packed by orp_conv1x1_bn_pieces_pack_weight.  Anything else is
+ *   ORP_EINVAL.  Each contraction follows orp_conv1x1_bn_act_pieces' rule (one accumulator, ascending 16-channel chunks, the six
+ *   products smallest first, independent of the tile): the branch first, r = fma(acc, scale2, shift2) kept in registers, then the
+ *   main contraction and the residual epilogue.  For finite data the bits are EXACTLY those of the two launches
+ *   orp_conv1x1_bn_act_pieces(x2 sampled and made contiguous, w2, scale2, shift2, no residual, no ReLU) and
+ *   orp_conv1x1_bn_act_pieces(x, w, scale, shift, residual = that, relu) (tests/test_gpu_conv1x1_bn_dual.py).  No range word, no
+ *   atomics, no communication between workgroups.  Elements of x2 the stride skips are never read.
+ *   orp_conv1x1_bn_act_pieces_dual_ok: orp_conv1x1_bn_act_pieces_ok for both (Cin, Cout) and (Cin2, Cout).  _dual_tile: the workgroup
+ *   tile (128 x 64 where that leaves 512 workgroups, else 128 x 32); 0 where not supported.  _dual_pays: 1 where this launch was
+ *   MEASURED faster than library downsample convolution + the pieces conv3 launch on MI355X (closed table of its own,
+ *   docs/notebook/round17.md; hw = ho * wo), else 0: the routing rule of mmdet_ops/fused_norm.py:conv1x1_bn_act_dual's caller. */
+int orp_conv1x1_bn_act_pieces_dual_ok(int c_in, int c_in2, int c_out);
+int orp_conv1x1_bn_act_pieces_dual_pays(int c_in, int c_in2, int c_out, int hw, int stride2, int batch);
+int orp_conv1x1_bn_act_pieces_dual_tile(int c_in, int c_in2, int c_out, int hw, int batch, int* tile_channels, int* tile_positions);
+int orp_conv1x1_bn_act_pieces_dual(const float* x, const void* w_packed, const float* scale, const float* shift, const float* x2,
+                                   const void* w2_packed, const float* scale2, const float* shift2, int c_in2, int h2, int w2,
+                                   int stride2, float* y, int batch, int c_in, int c_out, int ho, int wo, int relu, void* stream);
+
 /* the same optional output for the BatchNorm pass (blocks whose conv1 stays on the library) */
 int orp_affine_act_range(const float* x, const float* residual, const float* scale, const float* shift, float* y, int batch,
                          int channels, int hw, int relu, uint32_t* range_out, void* stream);

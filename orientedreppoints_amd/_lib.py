@@ -115,6 +115,10 @@ _SIGNATURES = {
     "orp_conv1x1_bn_pieces_packed_bytes": (_sz, [_i, _i]),
     "orp_conv1x1_bn_pieces_pack_weight": (_i, [_vp, _i, _i, _vp, _vp]),
     "orp_conv1x1_bn_act_pieces": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _vp, _vp]),
+    "orp_conv1x1_bn_act_pieces_dual_ok": (_i, [_i, _i, _i]),
+    "orp_conv1x1_bn_act_pieces_dual_pays": (_i, [_i, _i, _i, _i, _i, _i]),
+    "orp_conv1x1_bn_act_pieces_dual_tile": (_i, [_i, _i, _i, _i, _i, _vp, _vp]),
+    "orp_conv1x1_bn_act_pieces_dual": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _vp, _i, _i, _i, _i, _i, _i, _vp]),
     "orp_conv3x3_bn_act_ok": (_i, [_i, _i]),
     "orp_conv3x3_bn_act_pays": (_i, [_i, _i, _i, _i, _i]),
     "orp_conv3x3_bn_act_tile": (_i, [_i, _i, _i, _i, _i, _vp, _vp, _vp, _vp]),

@@ -38,9 +38,17 @@
 //     never crosses an image; the last tile of a plane is ragged (loads clamped and zeroed, stores masked), channels past Cout read
 //     the last channel's weights and are not stored.
 //   * the residual of a wave's outputs is requested before the last K step's MFMAs.
+//   * MODE 3 (orp_conv1x1_bn_act_pieces_dual): r is contracted HERE, out of a second input x2 sampled with stride 1 or 2 and a second
+//     packed weight -- a stage's first block, conv3 with the downsample convolution.  The workgroup runs the branch's K loop on the
+//     same accumulator (its fetch reads x2 at offsets computed once per thread; the elements a stride of 2 skips are never loaded),
+//     turns it into r = fma(acc, a2, b2) in registers, clears it and runs the main K loop; the epilogue is MODE 1's on r.  Each
+//     contraction keeps the rule above, so for finite data the bits are those of this kernel launched on the sampled x2 (MODE 0, no
+//     ReLU) and launched again on x with that as its residual (MODE 1).  The 4 x 1 wave layout at 64 or 32 positions only: r costs 16
+//     registers per 32 positions of a wave through the whole main loop.
 // LDS 27 - 60 KB + the BatchNorm constants.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
+#include <type_traits>
 
 #include "../../include/orp_hip.h"
 #include "orp_affine.hpp"
@@ -65,6 +73,14 @@ struct Args {
   int cin, cout, hw, relu;
   int ntm, ntn;                    // tiles per image: channels, positions
   unsigned* range;                 // RANGE: one word, raised to max range_bits(y)
+};
+// MODE 3 (the residual is contracted here): r = fma(conv1x1(x2 sampled with stride s2, planes2), scale2, shift2).  Arguments of
+// their own, so that the other launches' kernel arguments stay as they are.
+struct DualArgs : Args {
+  const float* x2;                 // [B][Cin2][hw2]
+  const uint16_t* planes2;         // three bf16 planes [pl][Cin2/16][2][Cout][8]
+  size_t plane_stride2;
+  int cin2, hw2, w2, wo, s2;       // input plane and row length, output row length, stride (1 | 2)
 };
 
 // w [Cout][Cin] fp32 -> three bf16 planes [pl][c/16][kg][o][8]  (kg = (c % 16) / 8, e = c % 8): pack_planes_kernel's split and order
@@ -104,11 +120,13 @@ __device__ __forceinline__ void split_pair(float a, float b, unsigned (&d)[3]) {
 }
 
 // WCH waves over channels (32 each) x 4 / WCH waves over positions (32 WN each).  VEC: hw % 4 == 0 and x 16-byte aligned.  MODE: the
-// residual term (0 nothing, 1 res, 2 res with its own affine); RANGE: the stored values' range word leaves with them -- template
-// parameters for the reasons orp_conv1x1_bn.hip gives.
-template <int WCH, int WN, int BK, bool VEC, int MODE, bool RANGE = false>
+// residual term (0 nothing, 1 res, 2 res with its own affine, 3 contracted here out of x2 in front of the main contraction, with
+// its own affine); RANGE: the stored values' range word leaves with them -- template parameters for the reasons
+// orp_conv1x1_bn.hip gives.  SAMP (MODE 3 with VEC): x2 is sampled with stride 2 and the output rows are whole position quads
+// (four 4-byte loads 8 bytes apart per row); VEC without it: stride 1, x2 is fetched as x is; without VEC: one offset per position.
+template <int WCH, int WN, int BK, bool VEC, int MODE, bool RANGE = false, bool SAMP = false>
 __global__ void __launch_bounds__(kThreads, 2)
-conv1x1_bn_pieces_kernel(const Args P) {
+conv1x1_bn_pieces_kernel(const typename std::conditional<MODE == 3, DualArgs, Args>::type P) {
   constexpr int ASTR = BK + 8;       // bf16 elements per position row in LDS: 20 or 36 dwords = 4 x odd
   constexpr int NCH = BK / 16;       // MFMA chunks of 16 channels per K step
   constexpr int WPOS = 4 / WCH;
@@ -129,7 +147,7 @@ conv1x1_bn_pieces_kernel(const Args P) {
   if (tid < BM) {                  // (visible behind the first barrier, never rewritten)
     const int ch = min(m0 + tid, cout - 1);
     Cs[tid] = P.scale[ch]; Cs[BM + tid] = P.shift[ch];
-    if (MODE == 2) { Cs[2 * BM + tid] = P.scale2[ch]; Cs[3 * BM + tid] = P.shift2[ch]; }
+    if (MODE >= 2) { Cs[2 * BM + tid] = P.scale2[ch]; Cs[3 * BM + tid] = P.shift2[ch]; }
   }
 
   const int lane = tid & 63, wave = tid >> 6;
@@ -138,15 +156,20 @@ conv1x1_bn_pieces_kernel(const Args P) {
 
   // ---- weights: lane (channel, k-group) reads the 8 k-values of a chunk per plane; a register ring of one K step ----
   const uint16_t* wp = P.planes + ((size_t)kg * cout + min(m0 + wm0 + l31, cout - 1)) * 8;
+  const uint16_t* wp2 = nullptr;
+  size_t ps2 = 0;
+  if constexpr (MODE == 3) ps2 = P.plane_stride2;
+  if constexpr (MODE == 3) wp2 = P.planes2 + ((size_t)kg * cout + min(m0 + wm0 + l31, cout - 1)) * 8;      // (Cout rows too)
   const size_t wblk = (size_t)2 * cout * 8;
   bf8 wq[NCH][3];
-  auto load_w = [&](int t, int c) {
-    const uint16_t* a = wp + (size_t)(t * NCH + c) * wblk;
+  auto load_w = [&](bool br, int t, int c) {        // br: the branch's weights (MODE 3; a constant at every call)
+    const uint16_t* a = (br ? wp2 : wp) + (size_t)(t * NCH + c) * wblk;
+    const size_t ps = br ? ps2 : P.plane_stride;
 #pragma unroll
-    for (int pl = 0; pl < 3; pl++) wq[c][pl] = *reinterpret_cast<const bf8*>(a + (size_t)pl * P.plane_stride);
+    for (int pl = 0; pl < 3; pl++) wq[c][pl] = *reinterpret_cast<const bf8*>(a + (size_t)pl * ps);
   };
 #pragma unroll
-  for (int c = 0; c < NCH; c++) load_w(0, c);
+  for (int c = 0; c < NCH; c++) load_w(MODE == 3, 0, c);
 
   // ---- activations: item idx of a K step = rows 2 kp, 2 kp + 1 of positions 4 pq .. 4 pq + 3.  16 consecutive lanes take 16
   // consecutive quads of one row pair (256 contiguous bytes per row); a half wave holds two row pairs (BN = 32: 8 quads x 4 pairs)
@@ -165,6 +188,43 @@ conv1x1_bn_pieces_kernel(const Args P) {
     }
     xkp[i] &= BK / 2 - 1;          // (threads past ITEMS repeat an item's loads and store nothing)
   }
+  // MODE 3: where an item's positions lie in a plane of x2 -- position p is input (s2 (p / wo), s2 (p % wo)) -- the same in every K
+  // step; clamped as the main fetch clamps.  VEC: one offset per item (the four positions share an input row, s2 elements apart)
+  constexpr int NXO = MODE == 3 ? (VEC ? 1 : 4) : 0;
+  int xo[XV][NXO > 0 ? NXO : 1];
+  const float* x2b = nullptr;
+  if constexpr (MODE == 3) {
+    x2b = P.x2 + (size_t)b * P.cin2 * P.hw2;
+#pragma unroll
+    for (int i = 0; i < XV; i++) {
+      const int col = p0 + 4 * xpq[i];
+#pragma unroll
+      for (int j = 0; j < NXO; j++) {
+        const int p = VEC ? min(col, hw - 4) : min(col + j, hw - 1);
+        const int oy = p / P.wo;
+        xo[i][j] = P.s2 * (oy * P.w2 + (p - oy * P.wo));
+      }
+    }
+  }
+  auto fetch2 = [&](int k0, float4 (&xr)[XV][2]) {
+    if constexpr (MODE == 3)
+#pragma unroll
+    for (int i = 0; i < XV; i++) {
+#pragma unroll
+      for (int h = 0; h < 2; h++) {
+        const float* src = x2b + (size_t)(k0 + 2 * xkp[i] + h) * P.hw2;
+        if (VEC && !SAMP) {
+          xr[i][h] = *reinterpret_cast<const float4*>(src + xo[i][0]);
+        } else if (VEC) {
+          const float* q = src + xo[i][0];
+          xr[i][h].x = q[0]; xr[i][h].y = q[2]; xr[i][h].z = q[4]; xr[i][h].w = q[6];
+        } else {
+          xr[i][h].x = src[xo[i][0]]; xr[i][h].y = src[xo[i][NXO > 1 ? 1 : 0]];
+          xr[i][h].z = src[xo[i][NXO > 1 ? 2 : 0]]; xr[i][h].w = src[xo[i][NXO > 1 ? 3 : 0]];
+        }
+      }
+    }
+  };
   auto fetch = [&](int k0, float4 (&xr)[XV][2]) {
 #pragma unroll
     for (int i = 0; i < XV; i++) {
@@ -174,6 +234,13 @@ conv1x1_bn_pieces_kernel(const Args P) {
         const float* src = xb + (size_t)(k0 + 2 * xkp[i] + h) * hw;
         if (VEC) {
           xr[i][h] = *reinterpret_cast<const float4*>(src + min(col, hw - 4));
+        } else if (MODE == 3) {
+          // (each offset through a copy the compiler cannot fold into a running address of its own: sixteen of those, held
+          // through the main loop next to r, do not fit)
+          int o[4];
+#pragma unroll
+          for (int j = 0; j < 4; j++) { o[j] = min(col + j, hw - 1); asm volatile("" : "+v"(o[j])); }
+          xr[i][h].x = src[o[0]]; xr[i][h].y = src[o[1]]; xr[i][h].z = src[o[2]]; xr[i][h].w = src[o[3]];
         } else {
           xr[i][h].x = src[min(col, hw - 1)]; xr[i][h].y = src[min(col + 1, hw - 1)];
           xr[i][h].z = src[min(col + 2, hw - 1)]; xr[i][h].w = src[min(col + 3, hw - 1)];
@@ -218,7 +285,7 @@ conv1x1_bn_pieces_kernel(const Args P) {
     for (int r = 0; r < 16; r++) acc[ni][r] = 0.f;
 
   // one K step out of buffer `buf`; the weights of chunk c are refilled for step t_next right behind their use
-  auto mma = [&](int buf, int t_next) {
+  auto mma = [&](bool wnext, int buf, int t_next) {
     const uint16_t* xa = lds + buf * BUF + (wn0 + l31) * ASTR + 8 * kg;
     auto load_x = [&](int c, bf8 (&q)[WN][3]) {
 #pragma unroll
@@ -228,7 +295,7 @@ conv1x1_bn_pieces_kernel(const Args P) {
     };
     // the narrow tiles read a chunk's fragments one chunk ahead: six or twelve MFMAs do not hide an LDS read behind themselves
     // with one or two waves per SIMD; at 128 positions per wave the registers go to the accumulators instead
-    constexpr bool AHEAD = WN <= 2;
+    constexpr bool AHEAD = WN <= 2 && !(MODE == 3 && WN == 2);     // (MODE 3 at 64 positions per wave: the registers go to r)
     bf8 xqs[AHEAD ? 2 : 1][WN][3];
     load_x(0, xqs[0]);
 #pragma unroll
@@ -251,7 +318,7 @@ conv1x1_bn_pieces_kernel(const Args P) {
 #pragma unroll
       for (int ni = 0; ni < WN; ni++) acc[ni] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(wq[c][0], xq[ni][0], acc[ni], 0, 0, 0);
       __builtin_amdgcn_sched_barrier(0);
-      load_w(t_next, c);
+      load_w(wnext, t_next, c);
       __builtin_amdgcn_sched_barrier(0);
     }
   };
@@ -260,29 +327,66 @@ conv1x1_bn_pieces_kernel(const Args P) {
   // step t + 1 (requested a step ago) into the other buffer -- its last readers are behind the previous barrier -- one barrier.
   // Every load is unconditional (past the end the last step is requested again), so the compiler's vmcnt counts are exact.
   const int nk = P.cin / BK;
-  auto step = [&](int t, float4 (&cur)[XV][2], float4 (&nxt)[XV][2], int buf) {
-    fetch(min(t + 2, nk - 1) * BK, cur);
+  auto step = [&](bool br, int nk, int t, float4 (&cur)[XV][2], float4 (&nxt)[XV][2], int buf) {
+    if (MODE == 3 && br) fetch2(min(t + 2, nk - 1) * BK, cur);
+    else fetch(min(t + 2, nk - 1) * BK, cur);
     __builtin_amdgcn_sched_barrier(0);      // the requests go out in front of the MFMAs
-    mma(buf, t + 1);
+    mma(br, buf, t + 1);
     stage(buf ^ 1, nxt);
     __syncthreads();
   };
-  fetch(0, xr[0]);
-  stage(0, xr[0]);
-  fetch(min(1, nk - 1) * BK, xr[1]);
+  float rv[WN][16];
+  if constexpr (MODE == 3) {
+    // The branch first, on the same accumulator.  Its last MFMAs run with the main contraction's steps 0 and 1 requested and its
+    // step-0 weights refilled behind them; then r leaves the accumulator, rounded to fp32 as the two-launch form stores it.
+    const int nk2 = P.cin2 / BK;
+    fetch2(0, xr[0]);
+    stage(0, xr[0]);
+    fetch2(min(1, nk2 - 1) * BK, xr[1]);
+    __syncthreads();
+    int t = 0;
+    for (; t + 2 < nk2; t += 2) {
+      step(true, nk2, t, xr[0], xr[1], 0);
+      step(true, nk2, t + 1, xr[1], xr[0], 1);
+    }
+    if (t + 1 < nk2) step(true, nk2, t, xr[0], xr[1], 0);
+    fetch(0, xr[0]);
+    fetch(min(1, nk - 1) * BK, xr[1]);
+    __builtin_amdgcn_sched_barrier(0);
+    mma(false, (nk2 - 1) & 1, 0);
+#pragma unroll
+    for (int g = 0; g < 4; g++) {
+      const float* cs = Cs + wm0 + 8 * g + 4 * kg;
+      const float4 c4 = *reinterpret_cast<const float4*>(cs + 2 * BM);
+      const float4 d4 = *reinterpret_cast<const float4*>(cs + 3 * BM);
+      const float a2v[4] = {c4.x, c4.y, c4.z, c4.w}, b2v[4] = {d4.x, d4.y, d4.z, d4.w};
+#pragma unroll
+      for (int ni = 0; ni < WN; ni++)
+#pragma unroll
+        for (int q = 0; q < 4; q++) {
+          rv[ni][4 * g + q] = affine_act(acc[ni][4 * g + q], a2v[q], b2v[q], 0);
+          acc[ni][4 * g + q] = 0.f;
+        }
+    }
+    __syncthreads();          // every wave is behind the branch's last LDS reads
+    stage(0, xr[0]);
+  } else {
+    fetch(0, xr[0]);
+    stage(0, xr[0]);
+    fetch(min(1, nk - 1) * BK, xr[1]);
+  }
   __syncthreads();
   int t = 0;
   for (; t + 2 < nk; t += 2) {
-    step(t, xr[0], xr[1], 0);
-    step(t + 1, xr[1], xr[0], 1);
+    step(false, nk, t, xr[0], xr[1], 0);
+    step(false, nk, t + 1, xr[1], xr[0], 1);
   }
-  if (t + 1 < nk) step(t, xr[0], xr[1], 0);
+  if (t + 1 < nk) step(false, nk, t, xr[0], xr[1], 0);
 
   // Epilogue addressing.  Register r of tile ni is channel m0 + wm0 + 8 (r >> 2) + 4 kg + (r & 3) at position
   // p0 + wn0 + 32 ni + l31: a store instruction writes 32 consecutive positions of two channels.
   const size_t plane0 = (size_t)b * cout;
-  float rv[WN][16];
-  if (MODE) {               // requested before the last K step's MFMAs (clamped addresses: no branch per load)
+  if (MODE == 1 || MODE == 2) {   // requested before the last K step's MFMAs (clamped addresses: no branch per load)
 #pragma unroll
     for (int ni = 0; ni < WN; ni++) {
       const int p = min(p0 + wn0 + 32 * ni + l31, hw - 1);
@@ -294,7 +398,7 @@ conv1x1_bn_pieces_kernel(const Args P) {
     }
   }
   __builtin_amdgcn_sched_barrier(0);
-  mma((nk - 1) & 1, nk - 1);
+  mma(false, (nk - 1) & 1, nk - 1);
 
   unsigned rmax = 0u;
 #pragma unroll
@@ -320,7 +424,7 @@ conv1x1_bn_pieces_kernel(const Args P) {
         const float v = acc[ni][r];
         float t;
         if (MODE == 0) t = affine_act(v, av[q], bv[q], P.relu);
-        else if (MODE == 1) t = affine_res_act(v, av[q], bv[q], rv[ni][r], P.relu);
+        else if (MODE == 1 || MODE == 3) t = affine_res_act(v, av[q], bv[q], rv[ni][r], P.relu);
         else t = affine_res_act(v, av[q], bv[q], affine_act(rv[ni][r], a2v[q], b2v[q], 0), P.relu);
         if (chg < cout && p < hw) {
           P.y[(plane0 + chg + q) * hw + p] = t;
@@ -372,6 +476,21 @@ void launch(const Args& A, int batch, bool vec, hipStream_t st) {
   else launch_mode<WCH, WN, BK, 2>(A, batch, vec, st);
 }
 
+// MODE 3 runs on the 4 x 1 wave layout without its widest tile (r costs 16 registers per 32 positions of a wave through the whole
+// main contraction): pick_tile's rule without its first candidate
+Tile pick_tile_dual(int cout, int hw, int batch) {
+  const long wgs = (long)((cout + 127) / 128) * ((hw + 63) / 64) * batch;
+  return wgs >= 512 ? Tile{128, 64} : Tile{128, 32};
+}
+
+template <int WN>
+void launch_dual(const DualArgs& A, int batch, bool vec, hipStream_t st) {
+  const dim3 grid((unsigned)((long)A.ntm * A.ntn * batch));
+  if (vec && A.s2 == 1) hipLaunchKernelGGL((conv1x1_bn_pieces_kernel<4, WN, 64, true, 3, false, false>), grid, dim3(kThreads), 0, st, A);
+  else if (vec) hipLaunchKernelGGL((conv1x1_bn_pieces_kernel<4, WN, 64, true, 3, false, true>), grid, dim3(kThreads), 0, st, A);
+  else hipLaunchKernelGGL((conv1x1_bn_pieces_kernel<4, WN, 64, false, 3, false, true>), grid, dim3(kThreads), 0, st, A);
+}
+
 }  // namespace
 
 extern "C" {
@@ -420,6 +539,41 @@ int orp_conv1x1_bn_act_pieces_pays(int c_in, int c_out, int hw, int batch, int h
   return 0;
 }
 
+int orp_conv1x1_bn_act_pieces_dual_ok(int c_in, int c_in2, int c_out) {
+  return (orp_conv1x1_bn_act_pieces_ok(c_in, c_out) && orp_conv1x1_bn_act_pieces_ok(c_in2, c_out)) ? 1 : 0;
+}
+
+int orp_conv1x1_bn_act_pieces_dual_tile(int c_in, int c_in2, int c_out, int hw, int batch, int* tile_channels, int* tile_positions) {
+  if (!orp_conv1x1_bn_act_pieces_dual_ok(c_in, c_in2, c_out) || hw <= 0 || batch <= 0) return 0;
+  const Tile t = pick_tile_dual(c_out, hw, batch);
+  if (tile_channels) *tile_channels = t.bm;
+  if (tile_positions) *tile_positions = t.bn;
+  return 1;
+}
+
+// THE routing rule of the dual launch (conv3 with the downsample convolution contracted in front of it): where its slowest run
+// beat the fastest run of what it replaces -- library downsample convolution + the pieces conv3 launch that applies the
+// downsample BatchNorm to it -- on MI355X (tests/checks/time_bottleneck_dual.py; docs/notebook/round17.md has the tables).  A
+// closed table of its own as orp_conv1x1_bn_act_pieces_pays, the same three corners per R-50 stage; hw = output positions.  9 of the
+// 12 timed points are routed: stages 1 - 3 at every corner (16 to 57 us less per launch).  Stage 4 has no row: it lost at the 1024^2
+// map with one image and with two (level with the pair: the 128 x 32 tile's weight stream), and its 0.8 us of 150 at the 1536^2 map
+// is inside either side's own spread of 3 - 4 us.  The pair that was timed runs conv3 on the pieces kernel, so a row also requires
+// that conv3 alone is routed there (orp_conv1x1_bn_act_pieces_pays with a residual; true of every row today).
+int orp_conv1x1_bn_act_pieces_dual_pays(int c_in, int c_in2, int c_out, int hw, int stride2, int batch) {
+  if (!orp_conv1x1_bn_act_pieces_dual_ok(c_in, c_in2, c_out) || hw <= 0 || batch <= 0) return 0;
+  if (!orp_conv1x1_bn_act_pieces_pays(c_in, c_out, hw, batch, 1)) return 0;
+  static const struct { int cin, cin2, cout, stride, hw_min, hw_max, batch; } paid[] = {
+      {64, 64, 256, 1, 65536, 147456, 1},    {64, 64, 256, 1, 65536, 65536, 2},        // stage 1
+      {128, 256, 512, 2, 16384, 36864, 1},   {128, 256, 512, 2, 16384, 16384, 2},      // stage 2
+      {256, 512, 1024, 2, 4096, 9216, 1},    {256, 512, 1024, 2, 4096, 4096, 2},       // stage 3
+  };
+  for (const auto& s : paid)
+    if (s.cin == c_in && s.cin2 == c_in2 && s.cout == c_out && s.stride == stride2 && s.batch == batch && hw >= s.hw_min &&
+        hw <= s.hw_max)
+      return 1;
+  return 0;
+}
+
 // the packed weight: three bf16 planes [3][Cin/16][2][Cout][8] (6 bytes per weight)
 size_t orp_conv1x1_bn_pieces_packed_bytes(int c_in, int c_out) {
   return orp_conv1x1_bn_act_pieces_ok(c_in, c_out) ? (size_t)6 * c_in * c_out : 0;
@@ -464,6 +618,41 @@ int orp_conv1x1_bn_act_pieces(const float* x, const void* weight_packed, const f
   else if (t.bn == 128) launch<4, 4, 32>(A, batch, vec, st);
   else if (t.bn == 64) launch<4, 2, 64>(A, batch, vec, st);
   else launch<4, 1, 64>(A, batch, vec, st);
+  hipError_t e = hipGetLastError();
+  return e == hipSuccess ? ORP_OK : (int)e;
+}
+
+// y = relu?( fma(conv1x1(x, w), a, b) + r ),  r = fma(conv1x1(x2 sampled at (stride2 oy, stride2 ox), w2), a2, b2) rounded to fp32: a
+// bottleneck's conv3 with the downsample convolution of its block contracted in the same launch (MODE 3), the downsample output
+// never in memory.  Each contraction follows the kernel's rule (one accumulator, ascending 16-channel chunks, six products smallest
+// first, no dependence on the tile); for finite data the bits are those of orp_conv1x1_bn_act_pieces on the sampled x2 (no residual,
+// no ReLU) followed by orp_conv1x1_bn_act_pieces on x with that as its residual.  No range word, no atomics.
+int orp_conv1x1_bn_act_pieces_dual(const float* x, const void* w_packed, const float* scale, const float* shift, const float* x2,
+                                   const void* w2_packed, const float* scale2, const float* shift2, int c_in2, int h2, int w2,
+                                   int stride2, float* y, int batch, int c_in, int c_out, int ho, int wo, int relu, void* stream) {
+  if (!x || !w_packed || !scale || !shift || !x2 || !w2_packed || !scale2 || !shift2 || !y || batch <= 0 || ho <= 0 || wo <= 0 ||
+      h2 <= 0 || w2 <= 0 || !orp_conv1x1_bn_act_pieces_dual_ok(c_in, c_in2, c_out))
+    return ORP_EINVAL;
+  if (stride2 != 1 && stride2 != 2) return ORP_EINVAL;
+  if (ho != (h2 - 1) / stride2 + 1 || wo != (w2 - 1) / stride2 + 1) return ORP_EINVAL;
+  if ((const float*)y == x || (const float*)y == x2) return ORP_EINVAL;
+  if (((uintptr_t)w_packed & 15) || ((uintptr_t)w2_packed & 15)) return ORP_EINVAL;
+  if ((long)ho * wo >= (1L << 31) / 4 || (long)h2 * w2 >= (1L << 31) / 4) return ORP_ETOOBIG;
+  const int hw = ho * wo;
+  const Tile t = pick_tile_dual(c_out, hw, batch);
+  DualArgs A{};
+  A.x = x; A.planes = reinterpret_cast<const uint16_t*>(w_packed); A.plane_stride = (size_t)c_in * c_out;
+  A.scale = scale; A.shift = shift; A.res = nullptr; A.scale2 = scale2; A.shift2 = shift2; A.y = y;
+  A.cin = c_in; A.cout = c_out; A.hw = hw; A.relu = relu ? 1 : 0;
+  A.ntm = (c_out + t.bm - 1) / t.bm; A.ntn = (hw + t.bn - 1) / t.bn;
+  A.range = nullptr;
+  A.x2 = x2; A.planes2 = reinterpret_cast<const uint16_t*>(w2_packed); A.plane_stride2 = (size_t)c_in2 * c_out;
+  A.cin2 = c_in2; A.hw2 = h2 * w2; A.w2 = w2; A.wo = wo; A.s2 = stride2;
+  if ((long)A.ntm * A.ntn * batch >= (1L << 31)) return ORP_ETOOBIG;
+  const bool vec = (hw & 3) == 0 && ((uintptr_t)x & 15) == 0 && ((uintptr_t)x2 & 15) == 0 && (stride2 == 1 || (wo & 3) == 0);
+  hipStream_t st = (hipStream_t)stream;
+  if (t.bn == 64) launch_dual<2>(A, batch, vec, st);
+  else launch_dual<1>(A, batch, vec, st);
   hipError_t e = hipGetLastError();
   return e == hipSuccess ? ORP_OK : (int)e;
 }

@@ -59,8 +59,11 @@ class Bottleneck(nn.Module):
         on = getattr(self, 'fuse_downsample_norm', None)
         if on is None:
             on = switches.BN_DOWNSAMPLE_FUSE
+        return bool(on) and self._downsample_is_conv_norm()
+
+    def _downsample_is_conv_norm(self):
         ds = self.downsample
-        return bool(on) and isinstance(ds, nn.Sequential) and len(ds) == 2 and isinstance(ds[0], nn.Conv2d) and \
+        return isinstance(ds, nn.Sequential) and len(ds) == 2 and isinstance(ds[0], nn.Conv2d) and \
             isinstance(ds[1], nn.BatchNorm2d) and not ds[1].training
 
     def _conv1x1_fusable(self):
@@ -82,6 +85,17 @@ class Bottleneck(nn.Module):
             on = switches.BN_CONV1X1_PIECES
         return bool(on)
 
+    def _downsample_conv_fusable(self):
+        """where conv3 runs on the bf16-pieces kernel, the downsample convolution (and with it its BatchNorm, whatever
+        `_downsample_norm_fusable` says: the launch has no form without it) may be contracted inside that launch at the shapes
+        `orp_conv1x1_bn_act_pieces_dual_pays` lists (`fuse_downsample_conv` attribute, or ORP_BN_DOWNSAMPLE_CONV_FUSE=0 for A/B
+        timing: off gives the launches and bits of before)"""
+        from .. import switches
+        on = getattr(self, 'fuse_downsample_conv', None)
+        if on is None:
+            on = switches.BN_DOWNSAMPLE_CONV_FUSE
+        return bool(on)
+
     def _conv3x3_fusable(self):
         """conv2 may run on the fp16-pieces kernel with bn2 + ReLU in its epilogue where that was measured faster (`fuse_conv3x3`
         attribute, or ORP_BN_CONV3X3_FUSE=0 for A/B timing); the shapes are decided by `conv3x3_bn_act`
@@ -93,13 +107,14 @@ class Bottleneck(nn.Module):
         return bool(on) and not self.conv2_is_dcn and isinstance(self.bn2, nn.BatchNorm2d) and not self.bn2.training
 
     def _forward_fused(self, x):
-        from ..mmdet_ops.fused_norm import bn_act, conv1x1_bn_act, conv3x3_bn_act, conv3x3_bn_act_routed
+        from ..mmdet_ops.fused_norm import bn_act, conv1x1_bn_act, conv3x3_bn_act, conv3x3_bn_act_routed, \
+            conv1x1_bn_act_dual, conv1x1_bn_act_dual_ok, conv1x1_bn_act_dual_pays
         fuse = self._conv1x1_fusable()
         pieces = None if self._conv1x1_pieces_on() else False       # (None: conv1x1_bn_act asks its table)
 
         def conv_bn_act(t, conv, bn, **kw):
             # conv1 / conv3: where the fused kernel pays, the raw convolution output is never written; everywhere else (and with
-            # the switch off) the library's convolution and the pass.  conv2 and the downsample convolution stay on the library.
+            # the switch off) the library's convolution and the pass.  conv2 stays on the library where its own kernel does not pay.
             if fuse:
                 return conv1x1_bn_act(t, conv, bn, pieces=pieces, **kw)
             return bn_act(conv(t).contiguous(), bn, **kw)
@@ -115,6 +130,14 @@ class Bottleneck(nn.Module):
         else:
             out = conv_bn_act(x, self.conv1, self.bn1, relu=True)
             out = bn_act(self.conv2(out).contiguous(), self.bn2, relu=True)
+        ds = self.downsample
+        if fuse and pieces is None and self._downsample_conv_fusable() and self._downsample_is_conv_norm() and \
+                conv1x1_bn_act_dual_ok(out, self.conv3, self.bn3, x, ds[0], ds[1]) and \
+                conv1x1_bn_act_dual_pays(out, self.conv3, x, ds[0]):
+            # where it was measured faster the whole identity branch rides in conv3's launch: the downsample convolution is
+            # contracted in front of conv3 by the same workgroups, its output never written.  Not under ORP_BN_DOWNSAMPLE_FUSE: with
+            # that switch on or off the block has the same bits, as it had before this launch existed
+            return conv1x1_bn_act_dual(out, self.conv3, self.bn3, x, ds[0], ds[1], relu=True)
         if self._downsample_norm_fusable():
             # the downsample BatchNorm rides in the block's last pass: no read-modify-write pass of its own over the identity
             return conv_bn_act(out, self.conv3, self.bn3, residual=self.downsample[0](x).contiguous(),

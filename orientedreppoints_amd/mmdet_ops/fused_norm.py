@@ -326,6 +326,63 @@ def conv1x1_bn_act(x, conv, bn, residual=None, residual_bn=None, relu=True, forc
     return y
 
 
+def conv1x1_bn_act_dual_ok(x, conv, bn, x2, conv2, bn2):
+    """`conv1x1_bn_act_dual` takes these: conv / bn as `conv1x1_bn_act_ok` wants them for x; conv2 a bias-free 1x1 / groups 1 / padding
+    0 nn.Conv2d of stride (1, 1) or (2, 2) with conv's output channels, bn2 an eval-mode BatchNorm2d, x2 an fp32 CUDA [B,Cin2,h2,w2]
+    tensor whose sampled map is x's map; both channel pairs supported (`orp_conv1x1_bn_act_pieces_dual_ok`)"""
+    if not conv1x1_bn_act_ok(x, conv, bn):
+        return False
+    w2 = getattr(conv2, 'weight', None)
+    if not (isinstance(conv2, torch.nn.Conv2d) and isinstance(bn2, torch.nn.BatchNorm2d) and not bn2.training and
+            x2.is_cuda and x2.dtype == torch.float32 and x2.dim() == 4 and x2.device == x.device and w2.dtype == torch.float32 and
+            w2.dim() == 4 and w2.size(2) == 1 and w2.size(3) == 1 and x2.size(1) == w2.size(1) and conv2.bias is None and
+            tuple(conv2.stride) in ((1, 1), (2, 2)) and tuple(conv2.padding) == (0, 0) and tuple(conv2.dilation) == (1, 1) and
+            conv2.groups == 1 and w2.size(0) == conv.weight.size(0) and x2.size(0) == x.size(0)):
+        return False
+    s = conv2.stride[0]
+    return bool(x2.size(2) > 0 and x2.size(3) > 0 and (x2.size(2) - 1) // s + 1 == x.size(2) and (x2.size(3) - 1) // s + 1 == x.size(3)
+                and _lib.lib().orp_conv1x1_bn_act_pieces_dual_ok(conv.weight.size(1), w2.size(1), w2.size(0)))
+
+
+def conv1x1_bn_act_dual_pays(x, conv, x2, conv2):
+    """the closed table of the dual launch (`orp_conv1x1_bn_act_pieces_dual_pays`) for these shapes"""
+    return bool(_lib.lib().orp_conv1x1_bn_act_pieces_dual_pays(conv.weight.size(1), conv2.weight.size(1), conv.weight.size(0),
+                                                               x.size(2) * x.size(3), conv2.stride[0], x.size(0)))
+
+
+def conv1x1_bn_act_dual_tile(cin, cin2, cout, hw, B):
+    """(tile channels, tile positions) of an `orp_conv1x1_bn_act_pieces_dual` launch of this shape, or None"""
+    v = [ctypes.c_int() for _ in range(2)]
+    if not _lib.lib().orp_conv1x1_bn_act_pieces_dual_tile(int(cin), int(cin2), int(cout), int(hw), int(B), *[ctypes.byref(t) for t in v]):
+        return None
+    return tuple(t.value for t in v)
+
+
+def conv1x1_bn_act_dual(x, conv, bn, x2, conv2, bn2, relu=True):
+    """relu?(BatchNorm_eval(conv(x)) + BatchNorm2_eval(conv2(x2))) as a new contiguous tensor in ONE launch of the bf16-pieces kernel
+    (`orp_conv1x1_bn_act_pieces_dual`): a bottleneck's conv3 / bn3 on x with the block's downsample convolution conv2 (bias-free 1x1,
+    stride (1, 1) or (2, 2), padding 0) and its eval-mode BatchNorm bn2 on the block input x2 contracted in front of it; the
+    downsample output is never written.  The bits of `conv1x1_bn_act(x2[:, :, ::s, ::s].contiguous(), conv2, bn2, relu=False,
+    pieces=True)` followed by `conv1x1_bn_act(x, conv, bn, residual=that, relu=relu, pieces=True)`.  Inference only; unsupported
+    arguments are a ValueError (the caller asks `conv1x1_bn_act_dual_ok` and the routing table first)."""
+    if not conv1x1_bn_act_dual_ok(x, conv, bn, x2, conv2, bn2):
+        raise ValueError("conv1x1_bn_act_dual: unsupported modules or shapes (conv1x1_bn_act_dual_ok)")
+    L = _lib.lib()
+    x, x2 = x.detach().contiguous(), x2.detach().contiguous()
+    B, cin, H, W = x.shape
+    cout, cin2 = conv.weight.size(0), conv2.weight.size(1)
+    packed, packed2 = _packed_1x1_planes(conv.weight), _packed_1x1_planes(conv2.weight)
+    scale, shift = _bn_affine(bn)
+    scale2, shift2 = _bn_affine(bn2)
+    y = torch.empty((B, cout, H, W), dtype=torch.float32, device=x.device)
+    with torch.cuda.device(x.device):
+        rc = L.orp_conv1x1_bn_act_pieces_dual(_lib.ptr(x), _lib.ptr(packed), _lib.ptr(scale), _lib.ptr(shift), _lib.ptr(x2),
+                                              _lib.ptr(packed2), _lib.ptr(scale2), _lib.ptr(shift2), cin2, x2.size(2), x2.size(3),
+                                              conv2.stride[0], _lib.ptr(y), B, cin, cout, H, W, 1 if relu else 0, _lib.stream_of(x))
+    _lib.check(rc, "orp_conv1x1_bn_act_pieces_dual")
+    return y
+
+
 def conv3x3_bn_act_ok(x, conv, bn, shape=None):
     """conv is a bias-free 3x3 / stride 1 / padding 1 / dilation 1 / groups 1 nn.Conv2d of a shape `orp_conv3x3_bn_act` takes
     (Cin == Cout in {64, 128, 256}), bn an eval-mode BatchNorm2d, x an fp32 CUDA [B,Cin,H,W] tensor (shape: the input's shape where x

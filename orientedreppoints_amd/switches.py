@@ -20,6 +20,7 @@ TOWER_GN_FUSE = _on('ORP_TOWER_GN_FUSE')      # GroupNorm fused around the tower
 BN_DOWNSAMPLE_FUSE = _on('ORP_BN_DOWNSAMPLE_FUSE')  # downsample BatchNorm inside the block-final pass (block.fuse_downsample_norm overrides)
 BN_CONV1X1_FUSE = _on('ORP_BN_CONV1X1_FUSE')  # bottleneck conv1 / conv3 with BatchNorm (+ residual) + ReLU in the epilogue where measured faster (block.fuse_conv1x1 overrides)
 BN_CONV1X1_PIECES = _on('ORP_BN_CONV1X1_PIECES')  # bottleneck conv1 / conv3 on the bf16-pieces kernel where measured faster than both the library and the fp32 kernel (block.fuse_conv1x1_pieces overrides)
+BN_DOWNSAMPLE_CONV_FUSE = _on('ORP_BN_DOWNSAMPLE_CONV_FUSE')  # the downsample convolution contracted inside conv3's bf16-pieces launch where measured faster than library convolution + that launch (block.fuse_downsample_conv overrides)
 BN_CONV3X3_FUSE = _on('ORP_BN_CONV3X3_FUSE')  # bottleneck conv2 (3x3, stride 1) on the fp16-pieces kernel with BatchNorm + ReLU in the epilogue where measured faster (block.fuse_conv3x3 overrides)
 STEM_POOL_FUSE = _on('ORP_STEM_POOL_FUSE')    # stem BatchNorm + ReLU + max-pool as one kernel (backbone.fuse_stem_pool overrides)
 FPN_TOPDOWN_FUSE = _on('ORP_FPN_TOPDOWN_FUSE')  # FPN lateral GroupNorm + top-down sum + transposition as one pass (neck.fuse_topdown overrides)
