@@ -1390,7 +1390,9 @@ def test_head_training_forward_all_levels_as_one_dcn_node(dev):
 def test_dcn_pair_with_fused_1x1_heads_vs_separate_launches(dev):
     """orp_dcn_forward_pair_heads: both DeformConvs + ReLU + the 1x1 output convolution behind each (+ `pts_out_init`
     residual) in ONE launch, against the separate route (pair launch with ReLU, then F.conv2d): <= 1e-5 of the output
-    scale -- tiles that straddle images, levels smaller than a tile, offsets outside the map, MT = 2 and 3 tilings."""
+    scale -- tiles that straddle images, levels smaller than a tile, offsets outside the map.  Both configurations (958 and
+    5376 positions) run the 64-row tile: the tile-height rule answers 32 rows for them, which this launch raises to 64.  The
+    96-row tile (what a 1024 x 1024 image runs) is held bit for bit to float64 in tests/test_gpu_head_convs_exact.py."""
     import torch.nn as nn
     import torch.nn.functional as F
     from orientedreppoints_amd.mmdet_ops import DeformConv, deform_conv_forward_pair
@@ -1557,10 +1559,17 @@ def test_bias_act_multi_bit_exact_vs_torch(dev):
 @pytest.mark.parametrize("B,cin,cout,sizes", [(1, 256, 256, [(128, 128), (32, 32), (16, 16), (8, 8)]),
                                               (2, 128, 128, [(7, 5), (13, 9), (1, 1), (31, 33)]),
                                               (3, 384, 64, [(4, 4), (2, 9)]), (1, 64, 64, [(8, 8)])])
-def test_small_level_conv3x3_vs_torch(dev, B, cin, cout, sizes):
+def test_small_level_conv3x3_vs_torch(dev, monkeypatch, B, cin, cout, sizes):
     """The small-level 3x3 convolution (one exact-fp32 MFMA launch for all small levels) against F.conv2d: same zero
-    padding, every level / image / border position; big levels take the library path unchanged."""
-    from orientedreppoints_amd.mmdet_ops.fused_norm import conv3x3_multi
+    padding, every level / image / border position; big levels take the library path unchanged.  The launch is spied: the
+    three parameter sets the kernel supports run orp_conv3x3_small_multi_strided once, over their levels of at most 1024
+    positions; (1, 64, 64, ...) does NOT -- orp_conv3x3_small_ok refuses Cin = 64, that set goes to the library and only
+    pins the routing.  Bit-for-bit checks of the kernel: tests/test_gpu_head_convs_exact.py."""
+    from orientedreppoints_amd import _lib
+    from orientedreppoints_amd.mmdet_ops.fused_norm import SMALL_LEVEL_POSITIONS, conv3x3_multi
+    launches = []
+    orig = _lib.lib().orp_conv3x3_small_multi_strided
+    monkeypatch.setattr(_lib.lib(), "orp_conv3x3_small_multi_strided", lambda *a: launches.append(a[3]) or orig(*a))
     torch.manual_seed(3)
     conv = torch.nn.Conv2d(cin, cout, 3, padding=1, bias=True).to(dev)
     with torch.no_grad():
@@ -1569,6 +1578,8 @@ def test_small_level_conv3x3_vs_torch(dev, B, cin, cout, sizes):
     with torch.no_grad():
         got = conv3x3_multi(xs, conv)
         want = [torch.nn.functional.conv2d(x.double(), conv.weight.double(), None, padding=1) for x in xs]
+    assert launches == ([] if cin == 64 else [sum(h * w <= SMALL_LEVEL_POSITIONS for h, w in sizes)])
+    assert (cin == 64) == (not _lib.lib().orp_conv3x3_small_ok(cin, cout))
     for g_, w_ in zip(got, want):
         assert g_.shape == w_.shape
         assert float((g_.double() - w_).abs().max()) <= 1e-4 * max(1.0, float(w_.abs().max()))
