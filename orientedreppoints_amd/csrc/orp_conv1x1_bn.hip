@@ -27,6 +27,7 @@
 #include "orp_affine.hpp"
 #include "orp_range.hpp"
 #include "orp_launch.hpp"
+#include "orp_conv1x1_bn_host.hpp"
 
 namespace {
 
@@ -231,7 +232,7 @@ conv1x1_bn_act_kernel(const Args P) {
   }
 }
 
-struct Tile { int bm, bn; };
+using orp_c1x1::Tile;
 
 // the workgroup tile of a launch: the largest one that still gives the 256 CUs two workgroups each, else the smallest
 Tile pick_tile(int cout, int hw, int batch) {
@@ -245,21 +246,12 @@ Tile pick_tile(int cout, int hw, int batch) {
   return cand[2];
 }
 
-template <int WM, int WN, int MODE>
-void launch_mode(const Args& A, int batch, bool vec, hipStream_t st) {
-  const dim3 grid((unsigned)((long)A.ntm * A.ntn * batch));
-  if (vec) hipLaunchKernelGGL((conv1x1_bn_act_kernel<WM, WN, true, MODE>), grid, dim3(kThreads), 0, st, A);
-  else hipLaunchKernelGGL((conv1x1_bn_act_kernel<WM, WN, false, MODE>), grid, dim3(kThreads), 0, st, A);
-}
 template <int WM, int WN>
 void launch(const Args& A, int batch, bool vec, hipStream_t st) {
-  if (A.range) {                                             // (conv1: no residual)
-    const dim3 grid((unsigned)((long)A.ntm * A.ntn * batch));
-    if (vec) hipLaunchKernelGGL((conv1x1_bn_act_kernel<WM, WN, true, 0, true>), grid, dim3(kThreads), 0, st, A);
-    else hipLaunchKernelGGL((conv1x1_bn_act_kernel<WM, WN, false, 0, true>), grid, dim3(kThreads), 0, st, A);
-  } else if (!A.res) launch_mode<WM, WN, 0>(A, batch, vec, st);
-  else if (!A.scale2) launch_mode<WM, WN, 1>(A, batch, vec, st);
-  else launch_mode<WM, WN, 2>(A, batch, vec, st);
+  orp_c1x1::dispatch(A, vec, [&](auto mode, auto range, auto v) {
+    hipLaunchKernelGGL((conv1x1_bn_act_kernel<WM, WN, decltype(v)::value, decltype(mode)::value, decltype(range)::value>),
+                       orp_c1x1::grid_of(A, batch), dim3(kThreads), 0, st, A);
+  });
 }
 
 }  // namespace
@@ -291,7 +283,7 @@ int orp_conv1x1_bn_act_tile(int c_in, int c_out, int hw, int batch, int* tile_ch
 int orp_conv1x1_bn_act_pays(int c_in, int c_out, int hw, int batch, int has_residual) {
   if (!orp_conv1x1_bn_act_ok(c_in, c_out) || hw <= 0 || batch <= 0) return 0;
   (void)has_residual;
-  static const struct { int cin, cout, hw_min, hw_max, batch; } paid[] = {
+  static const orp_c1x1::PaidRow paid[] = {
       {64, 64, 65536, 147456, 1},   {64, 64, 65536, 65536, 2},        // stage 1: conv1 of block 0
       {256, 64, 65536, 147456, 1},  {256, 64, 65536, 65536, 2},       //          conv1 of the others
       {64, 256, 65536, 147456, 1},  {64, 256, 65536, 65536, 2},       //          conv3
@@ -302,40 +294,20 @@ int orp_conv1x1_bn_act_pays(int c_in, int c_out, int hw, int batch, int has_resi
       {256, 1024, 4096, 9216, 1},   {256, 1024, 4096, 4096, 2},       //          conv3
       {512, 2048, 1024, 1024, 1},                                     // stage 4: conv3
   };
-  for (const auto& s : paid)
-    if (s.cin == c_in && s.cout == c_out && s.batch == batch && hw >= s.hw_min && hw <= s.hw_max) return 1;
-  return 0;
+  return orp_c1x1::paid(paid, c_in, c_out, hw, batch);
 }
 
-// range_out (or NULL): one word of device memory that is left holding max range_bits(y) as float bits -- zeroed here by a
-// kernel launch (orp_launch.hpp fill_async: a captured graph replays it), raised by one conditional atomicMax per workgroup.
-// No residual with it (conv1 is what feeds a range-reading convolution).
+// range_out (or NULL): the range word, as orp_c1x1::run describes it
 int orp_conv1x1_bn_act_range(const float* x, const float* weight_t, const float* scale, const float* shift, const float* residual,
                              const float* scale2, const float* shift2, float* y, int batch, int c_in, int c_out, int hw, int relu,
                              uint32_t* range_out, void* stream) {
-  if (range_out && residual) return ORP_EINVAL;
-  if (!x || !weight_t || !scale || !shift || !y || batch <= 0 || hw <= 0 || !orp_conv1x1_bn_act_ok(c_in, c_out)) return ORP_EINVAL;
-  if ((scale2 != nullptr) != (shift2 != nullptr) || (scale2 && !residual) || (const float*)y == x || (const float*)y == residual)
-    return ORP_EINVAL;
-  if ((uintptr_t)weight_t & 15) return ORP_EINVAL;
-  const Tile t = pick_tile(c_out, hw, batch);
-  Args A;
-  A.x = x; A.wt = weight_t; A.scale = scale; A.shift = shift; A.res = residual; A.scale2 = scale2; A.shift2 = shift2; A.y = y;
-  A.cin = c_in; A.cout = c_out; A.hw = hw; A.relu = relu ? 1 : 0;
-  A.ntm = (c_out + t.bm - 1) / t.bm; A.ntn = (hw + t.bn - 1) / t.bn;
-  A.range = range_out;
-  if ((long)A.ntm * A.ntn * batch >= (1L << 31)) return ORP_ETOOBIG;
-  const bool vec = (hw & 3) == 0 && ((uintptr_t)x & 15) == 0;
-  hipStream_t st = (hipStream_t)stream;
-  if (range_out) {
-    hipError_t fe = orp::fill_async(range_out, 0, sizeof(uint32_t), st);
-    if (fe != hipSuccess) return (int)fe;
-  }
-  if (t.bm == 128) launch<2, 2>(A, batch, vec, st);
-  else if (t.bn == 128) launch<1, 2>(A, batch, vec, st);
-  else launch<1, 1>(A, batch, vec, st);
-  hipError_t e = hipGetLastError();
-  return e == hipSuccess ? ORP_OK : (int)e;
+  return orp_c1x1::run<Args>(x, weight_t, scale, shift, residual, scale2, shift2, y, batch, c_in, c_out, hw, relu, range_out, stream,
+                             orp_conv1x1_bn_act_ok(c_in, c_out) != 0, pick_tile, [&](Args& A, Tile t, bool vec, hipStream_t st) {
+    A.wt = weight_t;
+    if (t.bm == 128) launch<2, 2>(A, batch, vec, st);
+    else if (t.bn == 128) launch<1, 2>(A, batch, vec, st);
+    else launch<1, 1>(A, batch, vec, st);
+  });
 }
 
 int orp_conv1x1_bn_act(const float* x, const float* weight_t, const float* scale, const float* shift, const float* residual,

@@ -54,6 +54,8 @@
 #include "orp_affine.hpp"
 #include "orp_range.hpp"
 #include "orp_launch.hpp"
+#include "orp_conv1x1_bn_host.hpp"
+#include "orp_dcn_split.hpp"
 
 namespace {
 
@@ -82,27 +84,6 @@ struct DualArgs : Args {
   size_t plane_stride2;
   int cin2, hw2, w2, wo, s2;       // input plane and row length, output row length, stride (1 | 2)
 };
-
-// w [Cout][Cin] fp32 -> three bf16 planes [pl][c/16][kg][o][8]  (kg = (c % 16) / 8, e = c % 8): pack_planes_kernel's split and order
-__global__ void pack_pieces_kernel(const float* __restrict__ w, int cout, int cin, uint16_t* __restrict__ planes) {
-  const long total = (long)cout * cin;
-  for (long i = (long)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += (long)gridDim.x * blockDim.x) {
-    const int e = (int)(i & 7);
-    long r = i >> 3;
-    const int o = (int)(r % cout); r /= cout;
-    const int kg = (int)(r & 1);
-    const int cblk = (int)(r >> 1);
-    const int c = cblk * 16 + kg * 8 + e;
-    const float v = w[(long)o * cin + c];
-    const float v0 = __uint_as_float(__float_as_uint(v) & 0xffff0000u);
-    const float r1 = v - v0;
-    const float v1 = __uint_as_float(__float_as_uint(r1) & 0xffff0000u);
-    const float v2 = r1 - v1;
-    planes[i] = (uint16_t)(__float_as_uint(v0) >> 16);
-    planes[total + i] = (uint16_t)(__float_as_uint(v1) >> 16);
-    planes[2 * total + i] = (uint16_t)(__float_as_uint(v2) >> 16);
-  }
-}
 
 // two fp32 values whose low 16 bits are zero -> one dword of two bf16: (a >> 16) | (b & 0xffff0000)
 __device__ __forceinline__ unsigned pack_hi16(float a, float b) {
@@ -444,7 +425,7 @@ conv1x1_bn_pieces_kernel(const typename std::conditional<MODE == 3, DualArgs, Ar
   }
 }
 
-struct Tile { int bm, bn; };
+using orp_c1x1::Tile;
 
 // the workgroup tile of a launch.  Cout <= 64: the 2 x 2 layout.  Otherwise the widest position tile of the 128-channel layout that
 // still gives the 256 CUs two workgroups each, else the narrowest.
@@ -459,21 +440,12 @@ Tile pick_tile(int cout, int hw, int batch) {
   return cand[2];
 }
 
-template <int WCH, int WN, int BK, int MODE>
-void launch_mode(const Args& A, int batch, bool vec, hipStream_t st) {
-  const dim3 grid((unsigned)((long)A.ntm * A.ntn * batch));
-  if (vec) hipLaunchKernelGGL((conv1x1_bn_pieces_kernel<WCH, WN, BK, true, MODE>), grid, dim3(kThreads), 0, st, A);
-  else hipLaunchKernelGGL((conv1x1_bn_pieces_kernel<WCH, WN, BK, false, MODE>), grid, dim3(kThreads), 0, st, A);
-}
 template <int WCH, int WN, int BK>
 void launch(const Args& A, int batch, bool vec, hipStream_t st) {
-  if (A.range) {                                             // (conv1: no residual)
-    const dim3 grid((unsigned)((long)A.ntm * A.ntn * batch));
-    if (vec) hipLaunchKernelGGL((conv1x1_bn_pieces_kernel<WCH, WN, BK, true, 0, true>), grid, dim3(kThreads), 0, st, A);
-    else hipLaunchKernelGGL((conv1x1_bn_pieces_kernel<WCH, WN, BK, false, 0, true>), grid, dim3(kThreads), 0, st, A);
-  } else if (!A.res) launch_mode<WCH, WN, BK, 0>(A, batch, vec, st);
-  else if (!A.scale2) launch_mode<WCH, WN, BK, 1>(A, batch, vec, st);
-  else launch_mode<WCH, WN, BK, 2>(A, batch, vec, st);
+  orp_c1x1::dispatch(A, vec, [&](auto mode, auto range, auto v) {
+    hipLaunchKernelGGL((conv1x1_bn_pieces_kernel<WCH, WN, BK, decltype(v)::value, decltype(mode)::value, decltype(range)::value>),
+                       orp_c1x1::grid_of(A, batch), dim3(kThreads), 0, st, A);
+  });
 }
 
 // MODE 3 runs on the 4 x 1 wave layout without its widest tile (r costs 16 registers per 32 positions of a wave through the whole
@@ -520,7 +492,7 @@ int orp_conv1x1_bn_act_pieces_tile(int c_in, int c_out, int hw, int batch, int* 
 int orp_conv1x1_bn_act_pieces_pays(int c_in, int c_out, int hw, int batch, int has_residual) {
   if (!orp_conv1x1_bn_act_pieces_ok(c_in, c_out) || hw <= 0 || batch <= 0) return 0;
   (void)has_residual;
-  static const struct { int cin, cout, hw_min, hw_max, batch; } paid[] = {
+  static const orp_c1x1::PaidRow paid[] = {
       {64, 64, 65536, 65536, 1},                                        // stage 1: conv1 of block 0
       {256, 64, 65536, 147456, 1},  {256, 64, 65536, 65536, 2},         //          conv1 of the others
       {64, 256, 65536, 147456, 1},  {64, 256, 65536, 65536, 2},         //          conv3
@@ -534,9 +506,7 @@ int orp_conv1x1_bn_act_pieces_pays(int c_in, int c_out, int hw, int batch, int h
       {2048, 512, 2304, 2304, 1},   {2048, 512, 1024, 1024, 2},         //          conv1 of the others
       {512, 2048, 1024, 2304, 1},   {512, 2048, 1024, 1024, 2},         //          conv3
   };
-  for (const auto& s : paid)
-    if (s.cin == c_in && s.cout == c_out && s.batch == batch && hw >= s.hw_min && hw <= s.hw_max) return 1;
-  return 0;
+  return orp_c1x1::paid(paid, c_in, c_out, hw, batch);
 }
 
 int orp_conv1x1_bn_act_pieces_dual_ok(int c_in, int c_in2, int c_out) {
@@ -579,47 +549,26 @@ size_t orp_conv1x1_bn_pieces_packed_bytes(int c_in, int c_out) {
   return orp_conv1x1_bn_act_pieces_ok(c_in, c_out) ? (size_t)6 * c_in * c_out : 0;
 }
 
+// orp_dcn_split.hip's bf16 packer at one tap: the same split, element order and layout.  The argument rule is this file's own
+// (Cout % 32 == 0, which orp_split::shape_ok does not take): the packer's index arithmetic holds for any Cout and Cin % 16 == 0.
 int orp_conv1x1_bn_pieces_pack_weight(const float* weight, int c_in, int c_out, void* packed, void* stream) {
   if (!weight || !packed || ((uintptr_t)packed & 15) || !orp_conv1x1_bn_act_pieces_ok(c_in, c_out)) return ORP_EINVAL;
-  const long total = (long)c_in * c_out;
-  const int blocks = (int)((total + 255) / 256 < 4096 ? (total + 255) / 256 : 4096);
-  hipLaunchKernelGGL(pack_pieces_kernel, dim3(blocks), dim3(256), 0, (hipStream_t)stream, weight, c_out, c_in,
-                     reinterpret_cast<uint16_t*>(packed));
-  hipError_t e = hipGetLastError();
+  hipError_t e = orp_split::pack_planes_bf16(weight, c_out, c_in, 1, reinterpret_cast<uint16_t*>(packed), (hipStream_t)stream);
   return e == hipSuccess ? ORP_OK : (int)e;
 }
 
-// range_out (or NULL): as orp_conv1x1_bn_act_range -- zeroed here by a kernel launch, raised by one conditional atomicMax per
-// workgroup; no residual with it.
+// range_out (or NULL): the range word, as orp_c1x1::run describes it
 int orp_conv1x1_bn_act_pieces(const float* x, const void* weight_packed, const float* scale, const float* shift, const float* residual,
                               const float* scale2, const float* shift2, float* y, int batch, int c_in, int c_out, int hw, int relu,
                               uint32_t* range_out, void* stream) {
-  if (range_out && residual) return ORP_EINVAL;
-  if (!x || !weight_packed || !scale || !shift || !y || batch <= 0 || hw <= 0 || !orp_conv1x1_bn_act_pieces_ok(c_in, c_out))
-    return ORP_EINVAL;
-  if ((scale2 != nullptr) != (shift2 != nullptr) || (scale2 && !residual) || (const float*)y == x || (const float*)y == residual)
-    return ORP_EINVAL;
-  if ((uintptr_t)weight_packed & 15) return ORP_EINVAL;
-  const Tile t = pick_tile(c_out, hw, batch);
-  Args A;
-  A.x = x; A.planes = reinterpret_cast<const uint16_t*>(weight_packed); A.plane_stride = (size_t)c_in * c_out;
-  A.scale = scale; A.shift = shift; A.res = residual; A.scale2 = scale2; A.shift2 = shift2; A.y = y;
-  A.cin = c_in; A.cout = c_out; A.hw = hw; A.relu = relu ? 1 : 0;
-  A.ntm = (c_out + t.bm - 1) / t.bm; A.ntn = (hw + t.bn - 1) / t.bn;
-  A.range = range_out;
-  if ((long)A.ntm * A.ntn * batch >= (1L << 31)) return ORP_ETOOBIG;
-  const bool vec = (hw & 3) == 0 && ((uintptr_t)x & 15) == 0;
-  hipStream_t st = (hipStream_t)stream;
-  if (range_out) {
-    hipError_t fe = orp::fill_async(range_out, 0, sizeof(uint32_t), st);
-    if (fe != hipSuccess) return (int)fe;
-  }
-  if (t.bm == 64) launch<2, 2, 32>(A, batch, vec, st);        // (K steps of 64 at 128 positions would leave one workgroup per CU)
-  else if (t.bn == 128) launch<4, 4, 32>(A, batch, vec, st);
-  else if (t.bn == 64) launch<4, 2, 64>(A, batch, vec, st);
-  else launch<4, 1, 64>(A, batch, vec, st);
-  hipError_t e = hipGetLastError();
-  return e == hipSuccess ? ORP_OK : (int)e;
+  return orp_c1x1::run<Args>(x, weight_packed, scale, shift, residual, scale2, shift2, y, batch, c_in, c_out, hw, relu, range_out, stream,
+                             orp_conv1x1_bn_act_pieces_ok(c_in, c_out) != 0, pick_tile, [&](Args& A, Tile t, bool vec, hipStream_t st) {
+    A.planes = reinterpret_cast<const uint16_t*>(weight_packed); A.plane_stride = (size_t)c_in * c_out;
+    if (t.bm == 64) launch<2, 2, 32>(A, batch, vec, st);        // (K steps of 64 at 128 positions would leave one workgroup per CU)
+    else if (t.bn == 128) launch<4, 4, 32>(A, batch, vec, st);
+    else if (t.bn == 64) launch<4, 2, 64>(A, batch, vec, st);
+    else launch<4, 1, 64>(A, batch, vec, st);
+  });
 }
 
 // y = relu?( fma(conv1x1(x, w), a, b) + r ),  r = fma(conv1x1(x2 sampled at (stride2 oy, stride2 ox), w2), a2, b2) rounded to fp32: a

@@ -918,10 +918,18 @@ hipError_t pack_planes16(const float* weight, int c_out, int c_in, int taps, uin
   return hipGetLastError();
 }
 
-hipError_t pack_planes(const float* weight, int c_out, int c_in, int taps, uint16_t* planes, hipStream_t st) {
+// the three bf16 planes alone: [3][tap][c/16][2][o][8] at planes (any c_out, c_in % 16 == 0)
+hipError_t pack_planes_bf16(const float* weight, int c_out, int c_in, int taps, uint16_t* planes, hipStream_t st) {
   const long total = (long)c_out * c_in * taps;
   int blocks = (int)((total + 255) / 256); if (blocks > 4096) blocks = 4096;
   hipLaunchKernelGGL(pack_planes_kernel, dim3(blocks), dim3(256), 0, st, weight, c_out, c_in, taps, planes);
+  return hipGetLastError();
+}
+
+hipError_t pack_planes(const float* weight, int c_out, int c_in, int taps, uint16_t* planes, hipStream_t st) {
+  const long total = (long)c_out * c_in * taps;
+  hipError_t e = pack_planes_bf16(weight, c_out, c_in, taps, planes, st);
+  if (e != hipSuccess) return e;
   return pack_planes16(weight, c_out, c_in, taps, planes + 3 * total, reinterpret_cast<float*>(planes + 5 * total), st);
 }
 

@@ -66,6 +66,8 @@ size_t plane_elems(int c_out, int c_in, int taps);
 const uint16_t* planes_of(const float* packed, int c_out, int c_in, int taps, int nprod);
 const float* wscale_of(const float* packed, int c_out, int c_in, int taps);
 hipError_t pack_planes(const float* weight /* [o][c][tap] */, int c_out, int c_in, int taps, uint16_t* planes, hipStream_t st);
+// the three bf16 planes alone (3 N elements at planes; no shape_ok: any c_out, c_in % 16 == 0) -- what pack_planes does first
+hipError_t pack_planes_bf16(const float* weight, int c_out, int c_in, int taps, uint16_t* planes, hipStream_t st);
 // the two fp16 planes alone (2 N elements at planes16) and their tail (tail[0] the scale, tail[1] max |w| as float bits)
 hipError_t pack_planes16(const float* weight, int c_out, int c_in, int taps, uint16_t* planes16, float* tail, hipStream_t st);
 hipError_t launch(const Args& a, hipStream_t st);

@@ -73,9 +73,7 @@ class FPN(nn.Module):
         shape that `orp_conv_split_multi_ex` takes, GroupNorm shapes the channels-last kernels take."""
         from .. import _lib, switches
         from ..mmdet_ops.fused_norm import conv_split_ok
-        on = getattr(self, 'split_convs', None)
-        if on is None:
-            on = switches.FPN_SPLIT                           # automatic: on at every input size (ORP_FPN_SPLIT=0: off, A/B timing)
+        on = switches.of(self, 'split_convs', 'FPN_SPLIT')   # automatic: on at every input size (ORP_FPN_SPLIT=0: off, A/B timing)
         used = len(self.lateral_convs)
         if not on or _lib.lib().orp_dcn_get_split_mode() == 0 or used > 8:
             return False
@@ -96,10 +94,7 @@ class FPN(nn.Module):
         path -- only there are the NCHW laterals not needed afterwards -- and every level is exactly twice the next."""
         from .. import switches
         from ..mmdet_ops.fused_norm import fpn_topdown_ok
-        on = getattr(self, 'fuse_topdown', None)
-        if on is None:
-            on = switches.FPN_TOPDOWN_FUSE
-        return bool(on) and fpn_topdown_ok(raw, [lc.norm for lc in self.lateral_convs]) and self._split_ok(raw)
+        return switches.of(self, 'fuse_topdown', 'FPN_TOPDOWN_FUSE') and fpn_topdown_ok(raw, [lc.norm for lc in self.lateral_convs]) and self._split_ok(raw)
 
     def forward(self, inputs):
         assert len(inputs) == len(self.in_channels)

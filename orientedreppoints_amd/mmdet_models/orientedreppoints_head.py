@@ -176,13 +176,11 @@ class OrientedRepPointsHead(nn.Module):
         `orp_conv_split_multi` takes, GroupNorm shapes the channels-last kernels take."""
         from .. import _lib, switches
         from ..mmdet_ops.fused_norm import conv_split_ok
-        on = getattr(self, 'split_towers', None)
-        if on is None:
-            # automatic: on at every input size, as the reference runs its towers at every size (head :91-113, :148-171);
-            # ORP_TOWER_SPLIT=0 switches the path off (A/B timing).  (Round 4 kept pyramids below 8 x 8 off this path because
-            # graph replays there disagreed with eager: that was packed-fp32 VALU code of ANY kernel miscomputing next to dense
-            # MFMAs -- DESIGN.md 4.5 --, fixed in the library's build, not a property of this path.)
-            on = switches.TOWER_SPLIT
+        # automatic: on at every input size, as the reference runs its towers at every size (head :91-113, :148-171);
+        # ORP_TOWER_SPLIT=0 switches the path off (A/B timing).  (Round 4 kept pyramids below 8 x 8 off this path because
+        # graph replays there disagreed with eager: that was packed-fp32 VALU code of ANY kernel miscomputing next to dense
+        # MFMAs -- DESIGN.md 4.5 --, fixed in the library's build, not a property of this path.)
+        on = switches.of(self, 'split_towers', 'TOWER_SPLIT')
         if not on or _lib.lib().orp_dcn_get_split_mode() == 0 or len(self.cls_convs) != len(self.reg_convs) or len(feats) > 8:
             return False
         x = feats[0]
@@ -232,10 +230,8 @@ class OrientedRepPointsHead(nn.Module):
         cls_cur = reg_cur = cur
         from .. import switches
         from ..mmdet_ops.fused_norm import conv_split_gn, conv_split_gn_ok
-        fuse = getattr(self, 'fuse_tower_norm', None)          # None: automatic (ORP_TOWER_GN_FUSE=0 switches it off, A/B timing)
-        if fuse is None:
-            fuse = switches.TOWER_GN_FUSE
-        fuse = bool(fuse) and all(conv_split_gn_ok(a.conv, b.conv, a.norm, b.norm, cur[0]) for a, b in zip(self.cls_convs, self.reg_convs))
+        # (attribute None: automatic, ORP_TOWER_GN_FUSE=0 switches it off, A/B timing)
+        fuse = switches.of(self, 'fuse_tower_norm', 'TOWER_GN_FUSE') and all(conv_split_gn_ok(a.conv, b.conv, a.norm, b.norm, cur[0]) for a, b in zip(self.cls_convs, self.reg_convs))
         if fuse:
             # conv -> GroupNorm -> ReLU with the normalisation fused AROUND the convolution launches: statistics from the
             # convolution's epilogue, the affine + ReLU applied by the next layer as it reads (two launches per layer instead of
@@ -341,9 +337,7 @@ class OrientedRepPointsHead(nn.Module):
         # bits.  `deterministic_backward = True` on the head (or ORP_DETERMINISTIC=1) keeps the fixed-order region pass for
         # both branches: bitwise reproducible gradients at the price of that half millisecond.
         from .. import switches
-        det = getattr(self, 'deterministic_backward', None)
-        if det is None:
-            det = switches.DETERMINISTIC
+        det = switches.of(self, 'deterministic_backward', 'DETERMINISTIC')
         dcn_cls, dcn_pts = deform_conv_pair(cls_feats, pts_feats, offsets, a.weight, b.weight, a.stride, a.padding,
                                             a.dilation, sparse_grad=(False, not det))
         cls_outs = [self.reppoints_cls_out(torch.relu(c)) for c in dcn_cls]

@@ -5,6 +5,7 @@ is the part BASELINE.json says stays stock."""
 import torch
 import torch.nn as nn
 
+from .. import switches
 from .layers import build_conv_layer, build_norm_layer, constant_init, kaiming_init
 from .registry import BACKBONES
 
@@ -55,11 +56,7 @@ class Bottleneck(nn.Module):
     def _downsample_norm_fusable(self):
         """the identity branch is exactly Sequential(Conv2d, eval-mode BatchNorm2d) and the fusion is not switched off
         (`fuse_downsample_norm` attribute, or ORP_BN_DOWNSAMPLE_FUSE=0 for A/B timing)"""
-        from .. import switches
-        on = getattr(self, 'fuse_downsample_norm', None)
-        if on is None:
-            on = switches.BN_DOWNSAMPLE_FUSE
-        return bool(on) and self._downsample_is_conv_norm()
+        return switches.of(self, 'fuse_downsample_norm', 'BN_DOWNSAMPLE_FUSE') and self._downsample_is_conv_norm()
 
     def _downsample_is_conv_norm(self):
         ds = self.downsample
@@ -70,45 +67,30 @@ class Bottleneck(nn.Module):
         """conv1 / conv3 may run with their BatchNorm (+ residual) + ReLU in the convolution's epilogue where that was measured
         faster (`fuse_conv1x1` attribute, or ORP_BN_CONV1X1_FUSE=0 for A/B timing); the shapes are decided by
         `conv1x1_bn_act` (`orp_conv1x1_bn_act_pays`)"""
-        from .. import switches
-        on = getattr(self, 'fuse_conv1x1', None)
-        if on is None:
-            on = switches.BN_CONV1X1_FUSE
-        return bool(on)
+        return switches.of(self, 'fuse_conv1x1', 'BN_CONV1X1_FUSE')
 
     def _conv1x1_pieces_on(self):
         """where conv1 / conv3 run fused, the bf16-pieces kernel may take them at the shapes `orp_conv1x1_bn_act_pieces_pays` lists
         (`fuse_conv1x1_pieces` attribute, or ORP_BN_CONV1X1_PIECES=0 for A/B timing: off gives the launches of before)"""
-        from .. import switches
-        on = getattr(self, 'fuse_conv1x1_pieces', None)
-        if on is None:
-            on = switches.BN_CONV1X1_PIECES
-        return bool(on)
+        return switches.of(self, 'fuse_conv1x1_pieces', 'BN_CONV1X1_PIECES')
 
     def _downsample_conv_fusable(self):
         """where conv3 runs on the bf16-pieces kernel, the downsample convolution (and with it its BatchNorm, whatever
         `_downsample_norm_fusable` says: the launch has no form without it) may be contracted inside that launch at the shapes
         `orp_conv1x1_bn_act_pieces_dual_pays` lists (`fuse_downsample_conv` attribute, or ORP_BN_DOWNSAMPLE_CONV_FUSE=0 for A/B
         timing: off gives the launches and bits of before)"""
-        from .. import switches
-        on = getattr(self, 'fuse_downsample_conv', None)
-        if on is None:
-            on = switches.BN_DOWNSAMPLE_CONV_FUSE
-        return bool(on)
+        return switches.of(self, 'fuse_downsample_conv', 'BN_DOWNSAMPLE_CONV_FUSE')
 
     def _conv3x3_fusable(self):
         """conv2 may run on the fp16-pieces kernel with bn2 + ReLU in its epilogue where that was measured faster (`fuse_conv3x3`
         attribute, or ORP_BN_CONV3X3_FUSE=0 for A/B timing); the shapes are decided by `conv3x3_bn_act`
         (`orp_conv3x3_bn_act_ok` / `_pays`); `force_conv3x3` (attribute, tests) routes every supported shape"""
-        from .. import switches
-        on = getattr(self, 'fuse_conv3x3', None)
-        if on is None:
-            on = switches.BN_CONV3X3_FUSE
-        return bool(on) and not self.conv2_is_dcn and isinstance(self.bn2, nn.BatchNorm2d) and not self.bn2.training
+        return switches.of(self, 'fuse_conv3x3', 'BN_CONV3X3_FUSE') and not self.conv2_is_dcn and \
+            isinstance(self.bn2, nn.BatchNorm2d) and not self.bn2.training
 
     def _forward_fused(self, x):
         from ..mmdet_ops.fused_norm import bn_act, conv1x1_bn_act, conv3x3_bn_act, conv3x3_bn_act_routed, \
-            conv1x1_bn_act_dual, conv1x1_bn_act_dual_ok, conv1x1_bn_act_dual_pays
+            conv1x1_bn_act_dual, conv1x1_bn_act_dual_routed
         fuse = self._conv1x1_fusable()
         pieces = None if self._conv1x1_pieces_on() else False       # (None: conv1x1_bn_act asks its table)
 
@@ -132,21 +114,19 @@ class Bottleneck(nn.Module):
             out = bn_act(self.conv2(out).contiguous(), self.bn2, relu=True)
         ds = self.downsample
         if fuse and pieces is None and self._downsample_conv_fusable() and self._downsample_is_conv_norm() and \
-                conv1x1_bn_act_dual_ok(out, self.conv3, self.bn3, x, ds[0], ds[1]) and \
-                conv1x1_bn_act_dual_pays(out, self.conv3, x, ds[0]):
+                conv1x1_bn_act_dual_routed(out, self.conv3, self.bn3, x, ds[0], ds[1]):
             # where it was measured faster the whole identity branch rides in conv3's launch: the downsample convolution is
             # contracted in front of conv3 by the same workgroups, its output never written.  Not under ORP_BN_DOWNSAMPLE_FUSE: with
             # that switch on or off the block has the same bits, as it had before this launch existed
             return conv1x1_bn_act_dual(out, self.conv3, self.bn3, x, ds[0], ds[1], relu=True)
         if self._downsample_norm_fusable():
             # the downsample BatchNorm rides in the block's last pass: no read-modify-write pass of its own over the identity
-            return conv_bn_act(out, self.conv3, self.bn3, residual=self.downsample[0](x).contiguous(),
-                               residual_bn=self.downsample[1], relu=True)
-        if self.downsample is not None:
-            identity = bn_act(self.downsample[0](x).contiguous(), self.downsample[1], relu=False)
+            residual, residual_bn = ds[0](x).contiguous(), ds[1]
+        elif ds is not None:
+            residual, residual_bn = bn_act(ds[0](x).contiguous(), ds[1], relu=False), None
         else:
-            identity = x.contiguous()
-        return conv_bn_act(out, self.conv3, self.bn3, residual=identity, relu=True)
+            residual, residual_bn = x.contiguous(), None
+        return conv_bn_act(out, self.conv3, self.bn3, residual=residual, residual_bn=residual_bn, relu=True)
 
     def forward(self, x):
         if self._fused_ok(x):
@@ -265,15 +245,10 @@ class ResNet(nn.Module):
     def _stem_pool_fusable(self):
         """`maxpool` is exactly MaxPool2d(3, 2, 1) -- dilation 1, floor mode, no indices -- and the fusion is not switched off
         (`fuse_stem_pool` attribute, or ORP_STEM_POOL_FUSE=0 for A/B timing)"""
-        from .. import switches
-        on = getattr(self, 'fuse_stem_pool', None)
-        if on is None:
-            on = switches.STEM_POOL_FUSE
-
         def pair(v):
             return tuple(v) if isinstance(v, (tuple, list)) else (v, v)
         mp = self.maxpool
-        return bool(on) and type(mp) is nn.MaxPool2d and pair(mp.kernel_size) == (3, 3) and pair(mp.stride) == (2, 2) and \
+        return switches.of(self, 'fuse_stem_pool', 'STEM_POOL_FUSE') and type(mp) is nn.MaxPool2d and pair(mp.kernel_size) == (3, 3) and pair(mp.stride) == (2, 2) and \
             pair(mp.padding) == (1, 1) and pair(mp.dilation) == (1, 1) and not mp.ceil_mode and not mp.return_indices
 
     def forward(self, x):

@@ -16,6 +16,13 @@ class _NormLevel(ctypes.Structure):
                 ("width", ctypes.c_int)]
 
 
+def _call(name, device, *args):
+    """one launch: the library's entry point `name`, looked up at call time, under the device guard, its return code checked"""
+    with torch.cuda.device(device):
+        rc = getattr(_lib.lib(), name)(*args)
+    _lib.check(rc, name)
+
+
 def _norm_levels(ins, outs):
     """the `orp_norm_level` array of a launch: logical [B,C,H,W] tensors, outs[i] None = no such output"""
     levels = (_NormLevel * len(ins))()
@@ -87,15 +94,11 @@ def group_norm_act_multi(xs, gn, relu=True, inplace=True, nhwc=None):
         if nhwc == 'only':
             for i in range(len(xs)):
                 levels[i].output = None
-        with torch.cuda.device(x0.device):
-            rc = L.orp_groupnorm_act_multi_nhwc(levels, gam, bet, cl_ptrs, len(xs), B, C, gns[0].num_groups, float(gns[0].eps),
-                                                1 if relu else 0, _lib.ptr(ws), ws.numel(), _lib.stream_of(x0))
-        _lib.check(rc, "orp_groupnorm_act_multi_nhwc")
+        _call("orp_groupnorm_act_multi_nhwc", x0.device, levels, gam, bet, cl_ptrs, len(xs), B, C, gns[0].num_groups,
+              float(gns[0].eps), 1 if relu else 0, _lib.ptr(ws), ws.numel(), _lib.stream_of(x0))
         return cl if nhwc == 'only' else (outs, cl)
-    with torch.cuda.device(x0.device):
-        rc = L.orp_groupnorm_act_multi_ex(levels, gam, bet, len(xs), B, C, gns[0].num_groups, float(gns[0].eps),
-                                          1 if relu else 0, _lib.ptr(ws), ws.numel(), _lib.stream_of(x0))
-    _lib.check(rc, "orp_groupnorm_act_multi_ex")
+    _call("orp_groupnorm_act_multi_ex", x0.device, levels, gam, bet, len(xs), B, C, gns[0].num_groups, float(gns[0].eps),
+          1 if relu else 0, _lib.ptr(ws), ws.numel(), _lib.stream_of(x0))
     return outs
 
 
@@ -127,15 +130,11 @@ def group_norm_act_multi_cl(xs, gn, relu=True, inplace=True, amax_slots=None):
     if amax_slots is not None:
         slots = (ctypes.c_int * len(xs))(*[int(v) for v in amax_slots])
         bits = torch.empty(max(int(v) for v in amax_slots) + 1, dtype=torch.int32, device=x0.device)
-        with torch.cuda.device(x0.device):
-            rc = L.orp_groupnorm_act_multi_cl_amax(levels, gam, bet, len(xs), B, C, G, float(gns[0].eps), 1 if relu else 0, slots,
-                                                   bits.data_ptr(), bits.numel(), _lib.ptr(ws), ws.numel(), _lib.stream_of(x0))
-        _lib.check(rc, "orp_groupnorm_act_multi_cl_amax")
+        _call("orp_groupnorm_act_multi_cl_amax", x0.device, levels, gam, bet, len(xs), B, C, G, float(gns[0].eps), 1 if relu else 0,
+              slots, bits.data_ptr(), bits.numel(), _lib.ptr(ws), ws.numel(), _lib.stream_of(x0))
         return outs, bits
-    with torch.cuda.device(x0.device):
-        rc = L.orp_groupnorm_act_multi_cl(levels, gam, bet, len(xs), B, C, G, float(gns[0].eps), 1 if relu else 0,
-                                          _lib.ptr(ws), ws.numel(), _lib.stream_of(x0))
-    _lib.check(rc, "orp_groupnorm_act_multi_cl")
+    _call("orp_groupnorm_act_multi_cl", x0.device, levels, gam, bet, len(xs), B, C, G, float(gns[0].eps), 1 if relu else 0,
+          _lib.ptr(ws), ws.numel(), _lib.stream_of(x0))
     return (outs, None) if no_ranges else outs
 
 
@@ -178,24 +177,17 @@ def bn_act(x, bn, residual=None, relu=True, residual_bn=None, want_range=False):
         raise ValueError("bn_act: want_range with residual_bn")
     scale, shift = _bn_affine(bn)
     B, C, H, W = x.shape
+    head = (_lib.ptr(x), _lib.ptr(residual), _lib.ptr(scale), _lib.ptr(shift))
+    tail = (_lib.ptr(x), B, C, H * W, 1 if relu else 0)
     if want_range:
         bits = torch.empty(1, dtype=torch.int32, device=x.device)
-        with torch.cuda.device(x.device):
-            rc = _lib.lib().orp_affine_act_range(_lib.ptr(x), _lib.ptr(residual), _lib.ptr(scale), _lib.ptr(shift), _lib.ptr(x),
-                                                 B, C, H * W, 1 if relu else 0, _lib.ptr(bits), _lib.stream_of(x))
-        _lib.check(rc, "orp_affine_act_range")
+        _call("orp_affine_act_range", x.device, *head, *tail, _lib.ptr(bits), _lib.stream_of(x))
         return x, bits
     if residual_bn is not None:
         scale2, shift2 = _bn_affine(residual_bn)
-        with torch.cuda.device(x.device):
-            rc = _lib.lib().orp_affine2_act(_lib.ptr(x), _lib.ptr(residual), _lib.ptr(scale), _lib.ptr(shift), _lib.ptr(scale2),
-                                            _lib.ptr(shift2), _lib.ptr(x), B, C, H * W, 1 if relu else 0, _lib.stream_of(x))
-        _lib.check(rc, "orp_affine2_act")
+        _call("orp_affine2_act", x.device, *head, _lib.ptr(scale2), _lib.ptr(shift2), *tail, _lib.stream_of(x))
         return x
-    with torch.cuda.device(x.device):
-        rc = _lib.lib().orp_affine_act(_lib.ptr(x), _lib.ptr(residual), _lib.ptr(scale), _lib.ptr(shift), _lib.ptr(x),
-                                       B, C, H * W, 1 if relu else 0, _lib.stream_of(x))
-    _lib.check(rc, "orp_affine_act")
+    _call("orp_affine_act", x.device, *head, *tail, _lib.stream_of(x))
     return x
 
 
@@ -213,15 +205,49 @@ def _transposed_1x1_weight(weight):
     return _lib.keep_for_graph(hit)
 
 
+def _plain_conv(conv, w, ksize, strides, padding):
+    """conv, an nn.Conv2d (the caller has asked: the 1x1 rules take subclasses, the 3x3 rule the class itself) with weight w, is a
+    plain convolution: fp32 4-D weight of kernel ksize x ksize, no bias, groups 1, dilation 1, a stride of `strides`, this padding"""
+    return bool(w.dtype == torch.float32 and w.dim() == 4 and w.size(2) == ksize and w.size(3) == ksize and conv.bias is None and
+                tuple(conv.stride) in strides and tuple(conv.padding) == (padding, padding) and
+                tuple(conv.dilation) == (1, 1) and conv.groups == 1)
+
+
+def _bn_input(x, bn):
+    """bn is an eval-mode BatchNorm2d and x an fp32 CUDA tensor"""
+    return bool(isinstance(bn, torch.nn.BatchNorm2d) and not bn.training and x.is_cuda and x.dtype == torch.float32)
+
+
+def _tile_query(name, n, *shape):
+    """the n integers the library's `name`(shape..., n int pointers) fills for a launch of this shape, or None where it returns 0"""
+    v = [ctypes.c_int() for _ in range(n)]
+    if not getattr(_lib.lib(), name)(*[int(s) for s in shape], *[ctypes.byref(t) for t in v]):
+        return None
+    return tuple(t.value for t in v)
+
+
+def _packed_planes(cache, weight, size_fn, pack_fn, view):
+    """weight [Cout,Cin,k,k] -> the byte buffer the library's `pack_fn` fills from view(weight) (fp32, contiguous), `size_fn`(Cin, Cout)
+    bytes; cached on the live parameter (inference only), keyed by the tensor's storage / version state."""
+    w = weight.detach()
+    state = _packcache.tensor_state(w)
+    hit = cache.get(weight, state)
+    if hit is not None:
+        return _lib.keep_for_graph(hit)
+    cout, cin = w.size(0), w.size(1)
+    w32 = view(w)
+    packed = torch.empty((getattr(_lib.lib(), size_fn)(cin, cout),), dtype=torch.uint8, device=w.device)
+    _call(pack_fn, w.device, _lib.ptr(w32), cin, cout, _lib.ptr(packed), _lib.stream_of(w32))
+    return _lib.keep_for_graph(cache.put(weight, state, packed))
+
+
 def conv1x1_bn_act_ok(x, conv, bn):
     """conv is a bias-free 1x1 / stride 1 / groups 1 nn.Conv2d of a shape `orp_conv1x1_bn_act` takes, bn an eval-mode
     BatchNorm2d, x an fp32 CUDA [B,Cin,H,W] tensor"""
     w = conv.weight
-    return bool(isinstance(conv, torch.nn.Conv2d) and isinstance(bn, torch.nn.BatchNorm2d) and not bn.training and
-                x.is_cuda and x.dtype == torch.float32 and x.dim() == 4 and w.dtype == torch.float32 and w.dim() == 4 and
-                w.size(2) == 1 and w.size(3) == 1 and x.size(1) == w.size(1) and conv.bias is None and
-                tuple(conv.stride) == (1, 1) and tuple(conv.padding) == (0, 0) and tuple(conv.dilation) == (1, 1) and
-                conv.groups == 1 and x.size(2) * x.size(3) > 0 and _lib.lib().orp_conv1x1_bn_act_ok(w.size(1), w.size(0)))
+    return bool(isinstance(conv, torch.nn.Conv2d) and _bn_input(x, bn) and x.dim() == 4 and
+                _plain_conv(conv, w, 1, ((1, 1),), 0) and x.size(1) == w.size(1) and x.size(2) * x.size(3) > 0 and
+                _lib.lib().orp_conv1x1_bn_act_ok(w.size(1), w.size(0)))
 
 
 _packed_1x1_pieces = _packcache.new_cache("conv1x1_bn_pieces_weight")
@@ -229,28 +255,30 @@ _packed_1x1_pieces = _packcache.new_cache("conv1x1_bn_pieces_weight")
 
 def _packed_1x1_planes(weight):
     """[Cout,Cin,1,1] -> the three bf16 planes `orp_conv1x1_bn_act_pieces` reads (`orp_conv1x1_bn_pieces_pack_weight`: 6 bytes per
-    weight), cached on the live parameter (inference only), keyed by the tensor's storage / version state."""
-    w = weight.detach()
-    state = _packcache.tensor_state(w)
-    hit = _packed_1x1_pieces.get(weight, state)
-    if hit is not None:
-        return _lib.keep_for_graph(hit)
-    L = _lib.lib()
-    cout, cin = w.size(0), w.size(1)
-    w32 = w.float().reshape(cout, cin).contiguous()
-    packed = torch.empty((L.orp_conv1x1_bn_pieces_packed_bytes(cin, cout),), dtype=torch.uint8, device=w.device)
-    with torch.cuda.device(w.device):
-        _lib.check(L.orp_conv1x1_bn_pieces_pack_weight(_lib.ptr(w32), cin, cout, _lib.ptr(packed), _lib.stream_of(w32)),
-                   "orp_conv1x1_bn_pieces_pack_weight")
-    return _lib.keep_for_graph(_packed_1x1_pieces.put(weight, state, packed))
+    weight), cached as `_packed_planes` says."""
+    return _packed_planes(_packed_1x1_pieces, weight, "orp_conv1x1_bn_pieces_packed_bytes", "orp_conv1x1_bn_pieces_pack_weight",
+                          lambda w: w.float().reshape(w.size(0), w.size(1)).contiguous())
 
 
 def conv1x1_bn_act_pieces_tile(cin, cout, hw, B):
     """(tile channels, tile positions) of an `orp_conv1x1_bn_act_pieces` launch of this shape, or None"""
-    v = [ctypes.c_int() for _ in range(2)]
-    if not _lib.lib().orp_conv1x1_bn_act_pieces_tile(int(cin), int(cout), int(hw), int(B), *[ctypes.byref(t) for t in v]):
+    return _tile_query("orp_conv1x1_bn_act_pieces_tile", 2, cin, cout, hw, B)
+
+
+def _conv1x1_route(shape, force, pieces):
+    """'pieces' | 'fp32' | None: the kernel `conv1x1_bn_act` launches.  shape = (Cin, Cout, H*W, B, has_residual) of supported
+    arguments, None otherwise.  The bf16-pieces kernel is asked first: never with pieces=False or with force alone; pieces=True: at
+    every shape it takes; None: where ORP_BN_CONV1X1_PIECES is on and its table says so.  Then the fp32 kernel: force, or its table."""
+    if shape is None:
         return None
-    return tuple(t.value for t in v)
+    L = _lib.lib()
+    if not (force and pieces is None) and pieces is not False:
+        if pieces is None:
+            from .. import switches
+            pieces = bool(switches.BN_CONV1X1_PIECES) and bool(L.orp_conv1x1_bn_act_pieces_pays(*shape))
+        if bool(pieces) and bool(L.orp_conv1x1_bn_act_pieces_ok(shape[0], shape[1])):
+            return 'pieces'
+    return 'fp32' if force or bool(L.orp_conv1x1_bn_act_pays(*shape)) else None
 
 
 def conv1x1_bn_act(x, conv, bn, residual=None, residual_bn=None, relu=True, force=False, want_range=False, pieces=None):
@@ -268,37 +296,10 @@ def conv1x1_bn_act(x, conv, bn, residual=None, residual_bn=None, relu=True, forc
         raise ValueError("conv1x1_bn_act: residual_bn without a residual")
     if want_range and residual is not None:
         raise ValueError("conv1x1_bn_act: want_range with a residual")
-    L = _lib.lib()
     fused = conv1x1_bn_act_ok(x, conv, bn) and (residual_bn is None or not residual_bn.training)
     shape = (x.size(1), conv.weight.size(0), x.size(2) * x.size(3), x.size(0), 1 if residual is not None else 0) if fused else None
-    use_pieces = False
-    if fused and not (force and pieces is None) and pieces is not False:
-        if pieces is None:
-            from .. import switches
-            pieces = bool(switches.BN_CONV1X1_PIECES) and bool(L.orp_conv1x1_bn_act_pieces_pays(*shape))
-        use_pieces = bool(pieces) and bool(L.orp_conv1x1_bn_act_pieces_ok(shape[0], shape[1]))
-    if use_pieces:
-        x = x.detach().contiguous()
-        B, cin, H, W = x.shape
-        cout = conv.weight.size(0)
-        if residual is not None:
-            residual = residual.detach()
-            if not (tuple(residual.shape) == (B, cout, H, W) and residual.is_contiguous() and residual.dtype == torch.float32):
-                raise ValueError("conv1x1_bn_act: residual must be a contiguous fp32 tensor of the output's shape")
-        packed = _packed_1x1_planes(conv.weight)
-        scale, shift = _bn_affine(bn)
-        scale2, shift2 = _bn_affine(residual_bn) if residual_bn is not None else (None, None)
-        y = torch.empty((B, cout, H, W), dtype=torch.float32, device=x.device)
-        bits = torch.empty(1, dtype=torch.int32, device=x.device) if want_range else None
-        with torch.cuda.device(x.device):
-            rc = L.orp_conv1x1_bn_act_pieces(_lib.ptr(x), _lib.ptr(packed), _lib.ptr(scale), _lib.ptr(shift), _lib.ptr(residual),
-                                             _lib.ptr(scale2), _lib.ptr(shift2), _lib.ptr(y), B, cin, cout, H * W,
-                                             1 if relu else 0, _lib.ptr(bits), _lib.stream_of(x))
-        _lib.check(rc, "orp_conv1x1_bn_act_pieces")
-        return (y, bits) if want_range else y
-    if fused and not force:
-        fused = bool(L.orp_conv1x1_bn_act_pays(*shape))
-    if not fused:
+    route = _conv1x1_route(shape, force, pieces)
+    if route is None:
         return bn_act(conv(x).contiguous(), bn, residual=residual, relu=relu, residual_bn=residual_bn, want_range=want_range)
     x = x.detach().contiguous()
     B, cin, H, W = x.shape
@@ -307,23 +308,20 @@ def conv1x1_bn_act(x, conv, bn, residual=None, residual_bn=None, relu=True, forc
         residual = residual.detach()
         if not (tuple(residual.shape) == (B, cout, H, W) and residual.is_contiguous() and residual.dtype == torch.float32):
             raise ValueError("conv1x1_bn_act: residual must be a contiguous fp32 tensor of the output's shape")
-    wt = _transposed_1x1_weight(conv.weight)
+    weight = _packed_1x1_planes(conv.weight) if route == 'pieces' else _transposed_1x1_weight(conv.weight)
     scale, shift = _bn_affine(bn)
     scale2, shift2 = _bn_affine(residual_bn) if residual_bn is not None else (None, None)
     y = torch.empty((B, cout, H, W), dtype=torch.float32, device=x.device)
-    if want_range:
-        bits = torch.empty(1, dtype=torch.int32, device=x.device)
-        with torch.cuda.device(x.device):
-            rc = L.orp_conv1x1_bn_act_range(_lib.ptr(x), _lib.ptr(wt), _lib.ptr(scale), _lib.ptr(shift), None, None, None,
-                                            _lib.ptr(y), B, cin, cout, H * W, 1 if relu else 0, _lib.ptr(bits), _lib.stream_of(x))
-        _lib.check(rc, "orp_conv1x1_bn_act_range")
-        return y, bits
-    with torch.cuda.device(x.device):
-        rc = L.orp_conv1x1_bn_act(_lib.ptr(x), _lib.ptr(wt), _lib.ptr(scale), _lib.ptr(shift), _lib.ptr(residual),
-                                  _lib.ptr(scale2), _lib.ptr(shift2), _lib.ptr(y), B, cin, cout, H * W, 1 if relu else 0,
-                                  _lib.stream_of(x))
-    _lib.check(rc, "orp_conv1x1_bn_act")
-    return y
+    bits = torch.empty(1, dtype=torch.int32, device=x.device) if want_range else None
+    args = (_lib.ptr(x), _lib.ptr(weight), _lib.ptr(scale), _lib.ptr(shift), _lib.ptr(residual), _lib.ptr(scale2), _lib.ptr(shift2),
+            _lib.ptr(y), B, cin, cout, H * W, 1 if relu else 0)
+    if route == 'pieces':                                    # (one entry point, its range word optional)
+        _call("orp_conv1x1_bn_act_pieces", x.device, *args, _lib.ptr(bits), _lib.stream_of(x))
+    elif want_range:
+        _call("orp_conv1x1_bn_act_range", x.device, *args, _lib.ptr(bits), _lib.stream_of(x))
+    else:
+        _call("orp_conv1x1_bn_act", x.device, *args, _lib.stream_of(x))
+    return (y, bits) if want_range else y
 
 
 def conv1x1_bn_act_dual_ok(x, conv, bn, x2, conv2, bn2):
@@ -333,11 +331,9 @@ def conv1x1_bn_act_dual_ok(x, conv, bn, x2, conv2, bn2):
     if not conv1x1_bn_act_ok(x, conv, bn):
         return False
     w2 = getattr(conv2, 'weight', None)
-    if not (isinstance(conv2, torch.nn.Conv2d) and isinstance(bn2, torch.nn.BatchNorm2d) and not bn2.training and
-            x2.is_cuda and x2.dtype == torch.float32 and x2.dim() == 4 and x2.device == x.device and w2.dtype == torch.float32 and
-            w2.dim() == 4 and w2.size(2) == 1 and w2.size(3) == 1 and x2.size(1) == w2.size(1) and conv2.bias is None and
-            tuple(conv2.stride) in ((1, 1), (2, 2)) and tuple(conv2.padding) == (0, 0) and tuple(conv2.dilation) == (1, 1) and
-            conv2.groups == 1 and w2.size(0) == conv.weight.size(0) and x2.size(0) == x.size(0)):
+    if not (isinstance(conv2, torch.nn.Conv2d) and _bn_input(x2, bn2) and x2.dim() == 4 and x2.device == x.device and
+            _plain_conv(conv2, w2, 1, ((1, 1), (2, 2)), 0) and x2.size(1) == w2.size(1) and
+            w2.size(0) == conv.weight.size(0) and x2.size(0) == x.size(0)):
         return False
     s = conv2.stride[0]
     return bool(x2.size(2) > 0 and x2.size(3) > 0 and (x2.size(2) - 1) // s + 1 == x.size(2) and (x2.size(3) - 1) // s + 1 == x.size(3)
@@ -350,12 +346,15 @@ def conv1x1_bn_act_dual_pays(x, conv, x2, conv2):
                                                                x.size(2) * x.size(3), conv2.stride[0], x.size(0)))
 
 
+def conv1x1_bn_act_dual_routed(x, conv, bn, x2, conv2, bn2):
+    """`conv1x1_bn_act_dual` takes these (`conv1x1_bn_act_dual_ok`) and was measured faster than what it replaces
+    (`conv1x1_bn_act_dual_pays`): what a caller asks, as `conv3x3_bn_act_routed`"""
+    return conv1x1_bn_act_dual_ok(x, conv, bn, x2, conv2, bn2) and conv1x1_bn_act_dual_pays(x, conv, x2, conv2)
+
+
 def conv1x1_bn_act_dual_tile(cin, cin2, cout, hw, B):
     """(tile channels, tile positions) of an `orp_conv1x1_bn_act_pieces_dual` launch of this shape, or None"""
-    v = [ctypes.c_int() for _ in range(2)]
-    if not _lib.lib().orp_conv1x1_bn_act_pieces_dual_tile(int(cin), int(cin2), int(cout), int(hw), int(B), *[ctypes.byref(t) for t in v]):
-        return None
-    return tuple(t.value for t in v)
+    return _tile_query("orp_conv1x1_bn_act_pieces_dual_tile", 2, cin, cin2, cout, hw, B)
 
 
 def conv1x1_bn_act_dual(x, conv, bn, x2, conv2, bn2, relu=True):
@@ -364,10 +363,9 @@ def conv1x1_bn_act_dual(x, conv, bn, x2, conv2, bn2, relu=True):
     stride (1, 1) or (2, 2), padding 0) and its eval-mode BatchNorm bn2 on the block input x2 contracted in front of it; the
     downsample output is never written.  The bits of `conv1x1_bn_act(x2[:, :, ::s, ::s].contiguous(), conv2, bn2, relu=False,
     pieces=True)` followed by `conv1x1_bn_act(x, conv, bn, residual=that, relu=relu, pieces=True)`.  Inference only; unsupported
-    arguments are a ValueError (the caller asks `conv1x1_bn_act_dual_ok` and the routing table first)."""
+    arguments are a ValueError (the caller asks `conv1x1_bn_act_dual_routed` first)."""
     if not conv1x1_bn_act_dual_ok(x, conv, bn, x2, conv2, bn2):
         raise ValueError("conv1x1_bn_act_dual: unsupported modules or shapes (conv1x1_bn_act_dual_ok)")
-    L = _lib.lib()
     x, x2 = x.detach().contiguous(), x2.detach().contiguous()
     B, cin, H, W = x.shape
     cout, cin2 = conv.weight.size(0), conv2.weight.size(1)
@@ -375,11 +373,9 @@ def conv1x1_bn_act_dual(x, conv, bn, x2, conv2, bn2, relu=True):
     scale, shift = _bn_affine(bn)
     scale2, shift2 = _bn_affine(bn2)
     y = torch.empty((B, cout, H, W), dtype=torch.float32, device=x.device)
-    with torch.cuda.device(x.device):
-        rc = L.orp_conv1x1_bn_act_pieces_dual(_lib.ptr(x), _lib.ptr(packed), _lib.ptr(scale), _lib.ptr(shift), _lib.ptr(x2),
-                                              _lib.ptr(packed2), _lib.ptr(scale2), _lib.ptr(shift2), cin2, x2.size(2), x2.size(3),
-                                              conv2.stride[0], _lib.ptr(y), B, cin, cout, H, W, 1 if relu else 0, _lib.stream_of(x))
-    _lib.check(rc, "orp_conv1x1_bn_act_pieces_dual")
+    _call("orp_conv1x1_bn_act_pieces_dual", x.device, _lib.ptr(x), _lib.ptr(packed), _lib.ptr(scale), _lib.ptr(shift), _lib.ptr(x2),
+          _lib.ptr(packed2), _lib.ptr(scale2), _lib.ptr(shift2), cin2, x2.size(2), x2.size(3), conv2.stride[0], _lib.ptr(y),
+          B, cin, cout, H, W, 1 if relu else 0, _lib.stream_of(x))
     return y
 
 
@@ -389,11 +385,10 @@ def conv3x3_bn_act_ok(x, conv, bn, shape=None):
     is only a tensor of its device and dtype)"""
     w = getattr(conv, 'weight', None)
     shape = tuple(x.shape) if shape is None else tuple(shape)
-    return bool(type(conv) is torch.nn.Conv2d and isinstance(bn, torch.nn.BatchNorm2d) and not bn.training and
-                x.is_cuda and x.dtype == torch.float32 and len(shape) == 4 and w.dtype == torch.float32 and w.dim() == 4 and
-                w.size(2) == 3 and w.size(3) == 3 and shape[1] == w.size(1) and conv.bias is None and
-                tuple(conv.stride) == (1, 1) and tuple(conv.padding) == (1, 1) and tuple(conv.dilation) == (1, 1) and
-                conv.groups == 1 and shape[0] * shape[2] * shape[3] > 0 and _lib.lib().orp_conv3x3_bn_act_ok(w.size(1), w.size(0)))
+    # (the class itself: a subclass, which the 1x1 rules take, may have another forward)
+    return bool(type(conv) is torch.nn.Conv2d and _bn_input(x, bn) and len(shape) == 4 and
+                _plain_conv(conv, w, 3, ((1, 1),), 1) and shape[1] == w.size(1) and shape[0] * shape[2] * shape[3] > 0 and
+                _lib.lib().orp_conv3x3_bn_act_ok(w.size(1), w.size(0)))
 
 
 def conv3x3_bn_act_routed(x, conv, bn, force=False, shape=None):
@@ -408,10 +403,7 @@ def conv3x3_bn_act_routed(x, conv, bn, force=False, shape=None):
 
 def conv3x3_bn_act_tile(cin, cout, H, W, B):
     """(tile_h, tile_w, waves over positions, waves over channels) of an `orp_conv3x3_bn_act` launch of this shape, or None"""
-    v = [ctypes.c_int() for _ in range(4)]
-    if not _lib.lib().orp_conv3x3_bn_act_tile(int(cin), int(cout), int(H), int(W), int(B), *[ctypes.byref(t) for t in v]):
-        return None
-    return tuple(t.value for t in v)
+    return _tile_query("orp_conv3x3_bn_act_tile", 4, cin, cout, H, W, B)
 
 
 _packed_3x3 = _packcache.new_cache("conv3x3_bn_weight")
@@ -419,20 +411,9 @@ _packed_3x3 = _packcache.new_cache("conv3x3_bn_weight")
 
 def _packed_3x3_planes(weight):
     """[C,C,3,3] -> the two fp16 planes + scale `orp_conv3x3_bn_act` reads (`orp_conv3x3_bn_pack_weight`: 4 bytes per weight), cached
-    on the live parameter (inference only), keyed by the tensor's storage / version state."""
-    w = weight.detach()
-    state = _packcache.tensor_state(w)
-    hit = _packed_3x3.get(weight, state)
-    if hit is not None:
-        return _lib.keep_for_graph(hit)
-    L = _lib.lib()
-    cout, cin = w.size(0), w.size(1)
-    w32 = w.float().contiguous()
-    packed = torch.empty((L.orp_conv3x3_bn_packed_bytes(cin, cout),), dtype=torch.uint8, device=w.device)
-    with torch.cuda.device(w.device):
-        _lib.check(L.orp_conv3x3_bn_pack_weight(_lib.ptr(w32), cin, cout, _lib.ptr(packed), _lib.stream_of(w32)),
-                   "orp_conv3x3_bn_pack_weight")
-    return _lib.keep_for_graph(_packed_3x3.put(weight, state, packed))
+    as `_packed_planes` says."""
+    return _packed_planes(_packed_3x3, weight, "orp_conv3x3_bn_packed_bytes", "orp_conv3x3_bn_pack_weight",
+                          lambda w: w.float().contiguous())
 
 
 def conv3x3_bn_act(x, conv, bn, relu=True, force=False, range_bits=None):
@@ -450,10 +431,8 @@ def conv3x3_bn_act(x, conv, bn, relu=True, force=False, range_bits=None):
     packed = _packed_3x3_planes(conv.weight)
     scale, shift = _bn_affine(bn)
     y = torch.empty((B, cout, H, W), dtype=torch.float32, device=x.device)
-    with torch.cuda.device(x.device):
-        rc = _lib.lib().orp_conv3x3_bn_act(_lib.ptr(x), _lib.ptr(packed), _lib.ptr(scale), _lib.ptr(shift), _lib.ptr(range_bits),
-                                           _lib.ptr(y), B, cin, cout, H, W, 1 if relu else 0, _lib.stream_of(x))
-    _lib.check(rc, "orp_conv3x3_bn_act")
+    _call("orp_conv3x3_bn_act", x.device, _lib.ptr(x), _lib.ptr(packed), _lib.ptr(scale), _lib.ptr(shift), _lib.ptr(range_bits),
+          _lib.ptr(y), B, cin, cout, H, W, 1 if relu else 0, _lib.stream_of(x))
     return y
 
 
@@ -465,10 +444,7 @@ def bn_relu_maxpool(x, bn):
     scale, shift = _bn_affine(bn)
     B, C, H, W = x.shape
     y = torch.empty((B, C, (H - 1) // 2 + 1, (W - 1) // 2 + 1), dtype=torch.float32, device=x.device)
-    with torch.cuda.device(x.device):
-        rc = _lib.lib().orp_affine_relu_maxpool(_lib.ptr(x), _lib.ptr(scale), _lib.ptr(shift), _lib.ptr(y), B, C, H, W,
-                                                _lib.stream_of(x))
-    _lib.check(rc, "orp_affine_relu_maxpool")
+    _call("orp_affine_relu_maxpool", x.device, _lib.ptr(x), _lib.ptr(scale), _lib.ptr(shift), _lib.ptr(y), B, C, H, W, _lib.stream_of(x))
     return y
 
 
@@ -508,10 +484,8 @@ def fpn_topdown_cl(xs, gns, amax=True):
     bits = torch.empty(1, dtype=torch.int32, device=x0.device) if (amax and _ranges_wanted()) else None
     nbytes = L.orp_fpn_topdown_workspace_bytes(levels, n, B, C, gns[0].num_groups)
     ws = _lib.workspace(x0.device, nbytes)
-    with torch.cuda.device(x0.device):
-        rc = L.orp_fpn_topdown_nhwc(levels, gam, bet, n, B, C, gns[0].num_groups, float(gns[0].eps),
-                                    bits.data_ptr() if bits is not None else None, _lib.ptr(ws), ws.numel(), _lib.stream_of(x0))
-    _lib.check(rc, "orp_fpn_topdown_nhwc")
+    _call("orp_fpn_topdown_nhwc", x0.device, levels, gam, bet, n, B, C, gns[0].num_groups, float(gns[0].eps),
+          bits.data_ptr() if bits is not None else None, _lib.ptr(ws), ws.numel(), _lib.stream_of(x0))
     return outs, bits
 
 
@@ -547,10 +521,7 @@ def bias_act_multi(xs, bias, relu=False, residuals=None, sub=None):
     s = sub.detach().float().reshape(-1).contiguous() if sub is not None else None
     if (b is not None and b.numel() != C) or (s is not None and s.numel() != C):
         raise ValueError("bias_act_multi: bias / sub must have C elements")
-    with torch.cuda.device(x0.device):
-        rc = _lib.lib().orp_bias_act_multi(levels, len(xs), B, C, _lib.ptr(b), _lib.ptr(s), 1 if relu else 0,
-                                           _lib.stream_of(x0))
-    _lib.check(rc, "orp_bias_act_multi")
+    _call("orp_bias_act_multi", x0.device, levels, len(xs), B, C, _lib.ptr(b), _lib.ptr(s), 1 if relu else 0, _lib.stream_of(x0))
     return (ys, zs) if sub is not None else ys
 
 
@@ -567,9 +538,7 @@ def _packed_1x1_weight(weight):
     cout, cin = w.size(0), w.size(1)
     w2 = w.float().reshape(cout, cin).contiguous()
     packed = torch.empty((_lib.lib().orp_conv1x1_packed_floats(cin),), dtype=torch.float32, device=w.device)
-    with torch.cuda.device(w.device):
-        _lib.check(_lib.lib().orp_conv1x1_pack_weight(_lib.ptr(w2), cout, cin, _lib.ptr(packed), _lib.stream_of(w2)),
-                   "orp_conv1x1_pack_weight")
+    _call("orp_conv1x1_pack_weight", w.device, _lib.ptr(w2), cout, cin, _lib.ptr(packed), _lib.stream_of(w2))
     return _lib.keep_for_graph(_packed_1x1.put(weight, state, packed))
 
 
@@ -609,10 +578,8 @@ def conv1x1_multi(xs, conv, relu=False, residuals=None, sub=None):
     s = sub.detach().float().reshape(-1).contiguous() if sub is not None else None
     if s is not None and s.numel() != cout:
         raise ValueError("conv1x1_multi: sub must have Cout elements")
-    with torch.cuda.device(x0.device):
-        rc = _lib.lib().orp_conv1x1_multi(levels, len(xs), B, cin, cout, _lib.ptr(packed), _lib.ptr(b), _lib.ptr(s),
-                                          1 if relu else 0, _lib.stream_of(x0))
-    _lib.check(rc, "orp_conv1x1_multi")
+    _call("orp_conv1x1_multi", x0.device, levels, len(xs), B, cin, cout, _lib.ptr(packed), _lib.ptr(b), _lib.ptr(s),
+          1 if relu else 0, _lib.stream_of(x0))
     return (ys, zs) if sub is not None else ys
 
 
@@ -667,10 +634,8 @@ def conv3x3_multi(xs, conv, split_k=False):
         x0 = xs[small[0]]
         nbytes = L.orp_conv3x3_small_workspace_bytes(levels, strides, len(small), B, cout) if split_k else 0
         ws = _lib.workspace(x0.device, nbytes) if nbytes else None
-        with torch.cuda.device(x0.device):
-            rc = L.orp_conv3x3_small_multi_strided(levels, wts, strides, len(small), B, cin, cout, _lib.ptr(ws),
-                                                   ws.numel() if ws is not None else 0, _lib.stream_of(x0))
-        _lib.check(rc, "orp_conv3x3_small_multi_strided")
+        _call("orp_conv3x3_small_multi_strided", x0.device, levels, wts, strides, len(small), B, cin, cout, _lib.ptr(ws),
+              ws.numel() if ws is not None else 0, _lib.stream_of(x0))
     return outs
 
 
@@ -697,10 +662,8 @@ class _GroupNormActTrain(torch.autograd.Function):
         stats = torch.empty((n * B * groups, 2), dtype=torch.float32, device=x0.device)
         nbytes = L.orp_groupnorm_workspace_bytes(levels, n, B, C, groups)
         ws = _lib.workspace(x0.device, nbytes)
-        with torch.cuda.device(x0.device):
-            rc = L.orp_groupnorm_act_multi_train(levels, gam, bet, n, B, C, groups, float(eps), 1 if relu else 0,
-                                                 _lib.ptr(stats), _lib.ptr(ws), ws.numel(), _lib.stream_of(x0))
-        _lib.check(rc, "orp_groupnorm_act_multi_train")
+        _call("orp_groupnorm_act_multi_train", x0.device, levels, gam, bet, n, B, C, groups, float(eps), 1 if relu else 0,
+              _lib.ptr(stats), _lib.ptr(ws), ws.numel(), _lib.stream_of(x0))
         ctx.save_for_backward(stats, *xs, *gammas, *betas, *ys)      # ys: the ReLU mask (the next layer keeps them alive anyway)
         ctx.meta = (n, m, groups, bool(relu), tuple(owner))
         return tuple(ys)
@@ -725,10 +688,8 @@ class _GroupNormActTrain(torch.autograd.Function):
         dg, db = _ptrs(dgam, owner), _ptrs(dbet, owner)
         nbytes = L.orp_groupnorm_backward_workspace_bytes(levels, n, B, C, groups)
         ws = _lib.workspace(x0.device, nbytes)
-        with torch.cuda.device(x0.device):
-            rc = L.orp_groupnorm_act_multi_backward(levels, dys, dxs, gam, bet, dg, db, n, B, C, groups, 1 if relu else 0,
-                                                    _lib.ptr(stats), _lib.ptr(ws), ws.numel(), _lib.stream_of(x0))
-        _lib.check(rc, "orp_groupnorm_act_multi_backward")
+        _call("orp_groupnorm_act_multi_backward", x0.device, levels, dys, dxs, gam, bet, dg, db, n, B, C, groups, 1 if relu else 0,
+              _lib.ptr(stats), _lib.ptr(ws), ws.numel(), _lib.stream_of(x0))
         return (None, None, None, None, None) + tuple(gxs) + tuple(dgam) + tuple(dbet)
 
 
@@ -781,7 +742,6 @@ def to_channels_last_multi(xs, amax_slots=None, amax_into=None, force_ranges=Fal
     amax_slots (one slot index per tensor): also returns an int32 tensor with max |x| per slot as float bits, or None when a
     tensor passed through untouched (its range is not known here); amax_into = (bits tensor, slots): accumulate into an
     existing one instead (all tensors of xs must then be converted here or the result is None again)."""
-    L = _lib.lib()
     todo = [i for i, x in enumerate(xs) if not _is_cl(x)]
     outs = list(xs)
     want_amax = amax_slots is not None or amax_into is not None
@@ -806,14 +766,10 @@ def to_channels_last_multi(xs, amax_slots=None, amax_into=None, force_ranges=Fal
             slots_all, reset = list(amax_slots), 1
             bits = torch.empty(max(slots_all) + 1, dtype=torch.int32, device=x0.device)
         slots = (ctypes.c_int * len(todo))(*[int(slots_all[i]) for i in todo])
-        with torch.cuda.device(x0.device):
-            rc = L.orp_nchw_to_nhwc_multi_amax(levels, len(todo), B, C, slots, bits.data_ptr(), bits.numel(), reset,
-                                               _lib.stream_of(x0))
-        _lib.check(rc, "orp_nchw_to_nhwc_multi_amax")
+        _call("orp_nchw_to_nhwc_multi_amax", x0.device, levels, len(todo), B, C, slots, bits.data_ptr(), bits.numel(), reset,
+              _lib.stream_of(x0))
         return outs, bits
-    with torch.cuda.device(x0.device):
-        rc = L.orp_nchw_to_nhwc_multi(levels, len(todo), B, C, _lib.stream_of(x0))
-    _lib.check(rc, "orp_nchw_to_nhwc_multi")
+    _call("orp_nchw_to_nhwc_multi", x0.device, levels, len(todo), B, C, _lib.stream_of(x0))
     return (outs, None) if want_amax else outs
 
 
@@ -905,21 +861,15 @@ def conv_split_weights(xs_a, weights_a, xs_b=None, weight_b=None, biases_a=None,
             keep += [pk, bi]
             wts[i] = pk.data_ptr()
             bs[i] = bi.data_ptr() if bi is not None else None
-        with torch.cuda.device(x0.device):
-            rc = L.orp_conv_split_multi_ex(levels, wts, bs, n, B, cin, cout, 1 if relu else 0, kh, kw, st[0], st[1], pd[0], pd[1],
-                                           dl[0], dl[1], 1 if out_channels_last else 0, int(nprod), _lib.ptr(ws), ws.numel(),
-                                           am_ptr, _lib.stream_of(x0))
-        _lib.check(rc, "orp_conv_split_multi_ex")
+        _call("orp_conv_split_multi_ex", x0.device, levels, wts, bs, n, B, cin, cout, 1 if relu else 0, kh, kw, st[0], st[1], pd[0],
+              pd[1], dl[0], dl[1], 1 if out_channels_last else 0, int(nprod), _lib.ptr(ws), ws.numel(), am_ptr, _lib.stream_of(x0))
         return outs_a
     pa = _packed_weight(w, cache_pack)
     pb = _packed_weight(weight_b, cache_pack) if pair else None
     ba, bb = f32(biases_a), f32(bias_b) if pair else None
-    with torch.cuda.device(x0.device):
-        rc = L.orp_conv_split_multi(levels, n, B, cin, cout, _lib.ptr(pa), _lib.ptr(pb), _lib.ptr(ba), _lib.ptr(bb),
-                                    1 if relu else 0, kh, kw, st[0], st[1], pd[0], pd[1], dl[0], dl[1],
-                                    1 if out_channels_last else 0, int(nprod), _lib.ptr(ws), ws.numel(), am_ptr, am_stride,
-                                    _lib.stream_of(x0))
-    _lib.check(rc, "orp_conv_split_multi")
+    _call("orp_conv_split_multi", x0.device, levels, n, B, cin, cout, _lib.ptr(pa), _lib.ptr(pb), _lib.ptr(ba), _lib.ptr(bb),
+          1 if relu else 0, kh, kw, st[0], st[1], pd[0], pd[1], dl[0], dl[1], 1 if out_channels_last else 0, int(nprod),
+          _lib.ptr(ws), ws.numel(), am_ptr, am_stride, _lib.stream_of(x0))
     return (outs_a, outs_b) if pair else outs_a
 
 
@@ -998,29 +948,23 @@ def conv_split_gn(xs_a, conv_a, xs_b, conv_b, gn_a, gn_b, coef_in=None, amax=Non
     pa, pb = _packed_weight(conv_a.weight), _packed_weight(conv_b.weight)
     am_ptr = amax.bits.data_ptr() if amax is not None else None
     pd, dl = conv_a.padding, conv_a.dilation
-    with torch.cuda.device(x0.device):
-        rc = L.orp_conv_split_multi_gn(levels, n, B, cin, cout, _lib.ptr(pa), _lib.ptr(pb), kh, kw, pd[0], pd[1], dl[0], dl[1], int(nprod),
-                                       _lib.ptr(coef_in), 1, _lib.ptr(partials), pf, G, _lib.ptr(ws), ws.numel(), am_ptr,
-                                       int(amax.stride) if amax is not None else 0, int(amax.count) if amax is not None else 0,
-                                       _lib.stream_of(x0))
-    _lib.check(rc, "orp_conv_split_multi_gn")
+    _call("orp_conv_split_multi_gn", x0.device, levels, n, B, cin, cout, _lib.ptr(pa), _lib.ptr(pb), kh, kw, pd[0], pd[1], dl[0],
+          dl[1], int(nprod), _lib.ptr(coef_in), 1, _lib.ptr(partials), pf, G, _lib.ptr(ws), ws.numel(), am_ptr,
+          int(amax.stride) if amax is not None else 0, int(amax.count) if amax is not None else 0, _lib.stream_of(x0))
     coef = torch.empty((2 * n, B, cout, 2), dtype=torch.float32, device=x0.device)
     ranges = _ranges_wanted()
     per_set = n * B * G
     bound = torch.empty((2, per_set), dtype=torch.int32, device=x0.device) if ranges else None
     gam, bet, _gs, _bs = _affine_ptrs((gn_a, gn_b), [0] * n + [1] * n)
-    with torch.cuda.device(x0.device):
-        rc = L.orp_conv_split_gn_finish(levels, n, B, cout, G, 2, float(gn_a.eps), gam, bet, _lib.ptr(partials), _lib.ptr(coef),
-                                        bound.data_ptr() if bound is not None else None, _lib.stream_of(x0))
-    _lib.check(rc, "orp_conv_split_gn_finish")
+    _call("orp_conv_split_gn_finish", x0.device, levels, n, B, cout, G, 2, float(gn_a.eps), gam, bet, _lib.ptr(partials),
+          _lib.ptr(coef), bound.data_ptr() if bound is not None else None, _lib.stream_of(x0))
     if not materialize:
         return outs_a, outs_b, coef, (Amax(bound, per_set, per_set) if bound is not None else None)
     nl = _norm_levels(outs_a + outs_b, outs_a + outs_b)
     slots = torch.empty((2,), dtype=torch.int32, device=x0.device) if bound is not None else None
-    with torch.cuda.device(x0.device):
-        rc = L.orp_affine_act_multi_cl(nl, 2 * n, B, cout, _lib.ptr(coef), 1, bound.data_ptr() if bound is not None else None, 2,
-                                       per_set, slots.data_ptr() if slots is not None else None, _lib.stream_of(x0))
-    _lib.check(rc, "orp_affine_act_multi_cl")
+    _call("orp_affine_act_multi_cl", x0.device, nl, 2 * n, B, cout, _lib.ptr(coef), 1,
+          bound.data_ptr() if bound is not None else None, 2, per_set, slots.data_ptr() if slots is not None else None,
+          _lib.stream_of(x0))
     return outs_a, outs_b, None, (Amax(slots, 1) if slots is not None else None)
 
 
@@ -1055,11 +999,9 @@ def conv_wgrad_split(xs, grad_outs, weight_shape, padding=(1, 1), dilation=(1, 1
     nbytes = L.orp_conv_wgrad_split_workspace_bytes(levels, n, B, kh, kw)
     ws = _lib.workspace(x0.device, nbytes)
     have = amax_x is not None and amax_g is not None
-    with torch.cuda.device(x0.device):
-        rc = L.orp_conv_wgrad_split(levels, n, B, cin, cout, kh, kw, padding[0], padding[1], dilation[0], dilation[1],
-                                    amax_x.data_ptr() if have else None, amax_g.data_ptr() if have else None,
-                                    gw.data_ptr(), _lib.ptr(ws), ws.numel(), _lib.stream_of(x0))
-    _lib.check(rc, "orp_conv_wgrad_split")
+    _call("orp_conv_wgrad_split", x0.device, levels, n, B, cin, cout, kh, kw, padding[0], padding[1], dilation[0], dilation[1],
+          amax_x.data_ptr() if have else None, amax_g.data_ptr() if have else None, gw.data_ptr(), _lib.ptr(ws), ws.numel(),
+          _lib.stream_of(x0))
     return gw
 
 

@@ -26,3 +26,9 @@ STEM_POOL_FUSE = _on('ORP_STEM_POOL_FUSE')    # stem BatchNorm + ReLU + max-pool
 FPN_TOPDOWN_FUSE = _on('ORP_FPN_TOPDOWN_FUSE')  # FPN lateral GroupNorm + top-down sum + transposition as one pass (neck.fuse_topdown overrides)
 TRAIN_SPLIT = _on('ORP_TRAIN_SPLIT')          # training: tower / FPN convolutions as conv_split_train nodes
 DETERMINISTIC = _on('ORP_DETERMINISTIC', '0')  # training: fixed-order DeformConv backward for both branches (head.deterministic_backward overrides)
+
+
+def of(obj, attr, name):
+    """the switch `name` as `obj` sees it: its attribute `attr` where that is set (not None), else this module's `name`, read now"""
+    on = getattr(obj, attr, None)
+    return bool(globals()[name] if on is None else on)
