@@ -815,6 +815,30 @@ int orp_conv_wgrad_split(const orp_wgrad_level* levels_host, int nlevels, int ba
                          float* grad_weight, void* workspace, size_t workspace_bytes, void* stream);
 
 /* ---------------------------------------------------------------------------------------------------------
+ * Swin (shifted-)window attention at inference as one fp32 kernel: everything between `attn.qkv` and `attn.proj` of
+ * SwinTransformerBlock.forward (mmdet/models/backbones/swin_transformer.py:199-250, WindowAttention.forward:122-155, the mask of
+ * BasicLayer.forward:370-390) -- pad, roll, window partition, q k^T + relative-position bias + shift mask, softmax, P V, window
+ * reverse, un-roll, crop.
+ *   qkv        [batch, height * width, 3, heads, head_dim] fp32, contiguous: attn.qkv on the un-padded, un-rolled tokens
+ *   qkv_bias   [3 * heads * head_dim] or NULL: what a padded token's q / k / v are (the pad comes after norm1, so a padded token
+ *              is a zero vector in front of qkv); NULL = zeros
+ *   bias_table [(2 * window - 1)^2, heads]: the relative-position bias table
+ *   out        [batch, height * width, heads * head_dim]: the attention result of every real token in its own place, before proj
+ * Hp = ceil(height / window) * window (Wp likewise).  Position (i, j) of window (wy, wx) is the token of the padded map at
+ * ((wy * window + i + shift) mod Hp, (wx * window + j + shift) mod Wp); a row >= height or column >= width is a padded token: a key
+ * like any other, without an output.  score = scale * q.k + bias_table[(dy + window - 1) * (2 * window - 1) + (dx + window - 1), head]
+ * with (dy, dx) = query position - key position inside the window; for shift > 0, -100 (additive, as in the reference) where the two
+ * positions lie in different bands, a band per axis on the rolled coordinate r = wy * window + i: 0 for r < Hp - window, 1 for
+ * r < Hp - shift, else 2 (also when Hp == window).  Softmax over the 49 keys with the row maximum subtracted, then P V.  All fp32
+ * (fp32 products, fp32 accumulation, the device library's expf), keys in ascending order for every output: bitwise reproducible,
+ * independent of the grid and of replay.  One launch, no workspace, no host synchronisation: capturable.
+ * Supported: window == 7, 0 <= shift < 7, head_dim a multiple of 4 in [4, 32], heads / height / width / batch >= 1, 16-byte aligned
+ * qkv / qkv_bias / out; anything else is ORP_EINVAL and launches nothing.
+ * ------------------------------------------------------------------------------------------------------- */
+int orp_window_attention(const float* qkv, const float* qkv_bias, const float* bias_table, int batch, int height, int width,
+                         int heads, int head_dim, int window, int shift, float scale, float* out, void* stream);
+
+/* ---------------------------------------------------------------------------------------------------------
  * Fused test-time post-processing around the rotated NMS: replaces the tensor-op chains of
  * get_bboxes_single (orientedreppoints_head.py:707-779), multiclass_rnms (bbox_nms.py:93-182) and rbbox2result
  * (transforms.py:356-375) with fixed-shape, stream-ordered kernels -- no host synchronisation, hipGraph-capturable.

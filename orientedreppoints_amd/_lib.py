@@ -174,6 +174,7 @@ _SIGNATURES = {
     "orp_conv_split_multi_gn": (_i, [_vp, _i, _i, _i, _i, _vp, _vp] + [_i] * 7 + [_vp, _i, _vp, _sz, _i, _vp, _sz, _vp, _i, _i, _vp]),
     "orp_conv_split_gn_finish": (_i, [_vp, _i, _i, _i, _i, _i, _f, _vp, _vp, _vp, _vp, _vp, _vp]),
     "orp_affine_act_multi_cl": (_i, [_vp, _i, _i, _i, _vp, _i, _vp, _i, _i, _vp, _vp]),
+    "orp_window_attention": (_i, [_vp, _vp, _vp] + [_i] * 7 + [_f, _vp, _vp]),
 }
 
 _lib = None

@@ -5,7 +5,9 @@ keeps the backbone on the framework.  Written from the paper (Liu et al., "Swin 
 using Shifted Windows", 2021): windowed multi-head self-attention with a learned relative-position bias, every second block
 on windows shifted by half a window (cyclic roll + a mask that separates the wrapped-around regions), patch merging between
 stages.  Own layout of the computation: one `scaled_dot_product_attention` call per block over all windows with the
-(bias + shift mask) tensor as its additive mask, the shift masks built once per (resolution, device).
+(bias + shift mask) tensor as its additive mask, the shift masks built once per (resolution, device).  At inference on fp32 device
+tensors a block runs everything between `attn.qkv` and `attn.proj` as one HIP kernel on the un-padded, un-rolled tokens instead
+(`SwinBlock.fuses_attention`, mmdet_ops/window_attention.py; switch ORP_SWIN_ATTN_FUSE / `block.fuse_window_attention`).
 
 Parameter / buffer names are the released checkpoints' (`swin_tiny_patch4_window7_224.pth`): patch_embed.{proj,norm},
 layers.<i>.blocks.<j>.{norm1,attn.{relative_position_bias_table,relative_position_index,qkv,proj},norm2,mlp.{fc1,fc2}},
@@ -15,6 +17,8 @@ import torch.nn as nn
 import torch.nn.functional as F
 import torch.utils.checkpoint as cp
 
+from .. import switches
+from ..mmdet_ops.window_attention import window_attention, window_attention_ok
 from .registry import BACKBONES
 
 
@@ -95,7 +99,18 @@ class SwinBlock(nn.Module):
         self.norm2 = nn.LayerNorm(dim)
         self.mlp = Mlp(dim, int(dim * mlp_ratio), drop)
 
+    def fuses_attention(self, x):
+        """inference on fp32 device tokens: everything between attn.qkv and attn.proj as one kernel (mmdet_ops/window_attention.py)"""
+        return switches.of(self, 'fuse_window_attention', 'SWIN_ATTN_FUSE') and window_attention_ok(self.attn, x)
+
     def forward(self, x, H, W, shift_mask):
+        if self.fuses_attention(x):
+            # qkv and proj are per-token linears: both run on the un-padded, un-rolled tokens, the kernel does the index arithmetic
+            a = self.attn
+            y = window_attention(a.qkv(self.norm1(x)), a.qkv.bias, a.relative_position_bias_table, H, W, a.num_heads, self.ws,
+                                 self.shift, a.scale)
+            x = x + self.drop_path(a.proj_drop(a.proj(y)))
+            return x + self.drop_path(self.mlp(self.norm2(x)))
         B, L, C = x.shape
         ws = self.ws
         y = self.norm1(x).view(B, H, W, C)
@@ -164,7 +179,8 @@ class SwinStage(nn.Module):
         return m
 
     def forward(self, x, H, W):
-        mask = self.shift_mask(H, W, x.device)
+        # (no block that takes the fused route reads the mask: it is not evaluated for them)
+        mask = None if all(blk.fuses_attention(x) for blk in self.blocks if blk.shift) else self.shift_mask(H, W, x.device)
         for blk in self.blocks:
             if self.use_checkpoint and x.requires_grad:
                 x = cp.checkpoint(blk, x, H, W, mask, use_reentrant=False)

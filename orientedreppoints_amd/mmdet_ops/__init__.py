@@ -14,3 +14,4 @@ from .deform_conv import (DeformConv, DeformConvPack, ModulatedDeformConv, Modul
                           deform_conv, modulated_deform_conv, deform_conv_forward_multi, deform_conv_forward_multi_half, deform_conv_forward_pair,
                           deform_conv_pair)
 from .box_iou_rotated import box_iou_rotated  # noqa: F401
+from .window_attention import window_attention, window_attention_ok, window_attention_reference  # noqa: F401
