@@ -839,6 +839,42 @@ int orp_window_attention(const float* qkv, const float* qkv_bias, const float* b
                          int heads, int head_dim, int window, int shift, float scale, float* out, void* stream);
 
 /* ---------------------------------------------------------------------------------------------------------
+ * The same attention in TRAINING (csrc/orp_window_attn_train.hip): a forward that also keeps every row's log-sum-exp, and the
+ * backward.  Arguments, index arithmetic, supported set and grid (one wave per (window, head)) are orp_window_attention's.
+ * orp_window_attention_train:
+ *   out        bit for bit what orp_window_attention writes for the same arguments (same score expression, same key order, same expf)
+ *   lse        [batch, height * width, heads]: row maximum + logf(row sum) of every real token's row of scores
+ *   A padded token has no output and no lse.
+ * orp_window_attention_backward: out, lse as the forward left them, grad_out [batch, height * width, heads * head_dim].  With
+ *   P_ij = expf(s_ij - lse_i), D_i = sum_d grad_out_i,d * out_i,d and dS_ij = P_ij * (grad_out_i . V_j - D_i) over the 49 positions of a
+ *   window:
+ *   grad_qkv        [batch, height * width, 3, heads, head_dim]: dQ_i = scale * sum_j dS_ij K_j, dK_j = scale * sum_i dS_ij Q_i,
+ *                   dV_j = sum_i P_ij grad_out_i, each at the real token's own place.  Every real token lies in exactly one window:
+ *                   every element is written exactly once -- no pre-zeroing, no atomics.
+ *   grad_bias_table [(2 * window - 1)^2, heads]: the sum of dS_ij over all windows, images and pairs with the same (dy, dx)
+ *   grad_qkv_bias   [3 * heads * head_dim] or NULL (it must be NULL when qkv_bias is): a padded token's k and v ARE the qkv bias, so
+ *                   the dK_j / dV_j of padded keys are summed into the k and v thirds; a padded query has no output, hence no
+ *                   grad_out: the q third is exactly zero.  Only the padded tokens' share -- the real tokens' reaches the bias
+ *                   through the linear layer that made qkv.
+ *   A padded query contributes nothing to any gradient; the shift mask is a constant.
+ *   workspace       orp_window_attention_backward_workspace_bytes(batch, height, width, heads, head_dim, window) bytes of device
+ *                   memory (0 for an unsupported shape), 4-byte aligned: per (window, head) the 169 bin sums and the dK / dV of its
+ *                   padded keys, which a second kernel inside the same call sums over windows and images.
+ * Deterministic: every output element has ONE summation order, fixed by the source file (keys / queries ascending inside a window,
+ * padded keys ascending, windows in sixteen interleaved ascending slices, then the slices ascending); no floating-point atomics.
+ * It does not depend on the grid's scheduling, on other work on the device or on replay.  No allocation, no host synchronisation.
+ * Supported: as orp_window_attention, with 16-byte aligned qkv / qkv_bias / out / grad_out / grad_qkv; anything else, a workspace
+ * smaller than asked for included, is ORP_EINVAL and launches nothing.
+ * ------------------------------------------------------------------------------------------------------- */
+int orp_window_attention_train(const float* qkv, const float* qkv_bias, const float* bias_table, int batch, int height, int width,
+                               int heads, int head_dim, int window, int shift, float scale, float* out, float* lse, void* stream);
+size_t orp_window_attention_backward_workspace_bytes(int batch, int height, int width, int heads, int head_dim, int window);
+int orp_window_attention_backward(const float* qkv, const float* qkv_bias, const float* bias_table, const float* out, const float* lse,
+                                  const float* grad_out, int batch, int height, int width, int heads, int head_dim, int window,
+                                  int shift, float scale, float* grad_qkv, float* grad_qkv_bias, float* grad_bias_table,
+                                  void* workspace, size_t workspace_bytes, void* stream);
+
+/* ---------------------------------------------------------------------------------------------------------
  * Fused test-time post-processing around the rotated NMS: replaces the tensor-op chains of
  * get_bboxes_single (orientedreppoints_head.py:707-779), multiclass_rnms (bbox_nms.py:93-182) and rbbox2result
  * (transforms.py:356-375) with fixed-shape, stream-ordered kernels -- no host synchronisation, hipGraph-capturable.

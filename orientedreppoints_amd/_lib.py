@@ -175,6 +175,9 @@ _SIGNATURES = {
     "orp_conv_split_gn_finish": (_i, [_vp, _i, _i, _i, _i, _i, _f, _vp, _vp, _vp, _vp, _vp, _vp]),
     "orp_affine_act_multi_cl": (_i, [_vp, _i, _i, _i, _vp, _i, _vp, _i, _i, _vp, _vp]),
     "orp_window_attention": (_i, [_vp, _vp, _vp] + [_i] * 7 + [_f, _vp, _vp]),
+    "orp_window_attention_train": (_i, [_vp, _vp, _vp] + [_i] * 7 + [_f, _vp, _vp, _vp]),
+    "orp_window_attention_backward_workspace_bytes": (_sz, [_i] * 6),
+    "orp_window_attention_backward": (_i, [_vp] * 6 + [_i] * 7 + [_f, _vp, _vp, _vp, _vp, _sz, _vp]),
 }
 
 _lib = None

@@ -7,7 +7,9 @@ on windows shifted by half a window (cyclic roll + a mask that separates the wra
 stages.  Own layout of the computation: one `scaled_dot_product_attention` call per block over all windows with the
 (bias + shift mask) tensor as its additive mask, the shift masks built once per (resolution, device).  At inference on fp32 device
 tensors a block runs everything between `attn.qkv` and `attn.proj` as one HIP kernel on the un-padded, un-rolled tokens instead
-(`SwinBlock.fuses_attention`, mmdet_ops/window_attention.py; switch ORP_SWIN_ATTN_FUSE / `block.fuse_window_attention`).
+(`SwinBlock.fuses_attention`, mmdet_ops/window_attention.py; switch ORP_SWIN_ATTN_FUSE / `block.fuse_window_attention`); with
+gradients enabled the same span is `window_attention_train`, a forward kernel that keeps the rows' log-sum-exp and a backward call
+(`SwinBlock.fuses_attention_train`; switch ORP_SWIN_ATTN_TRAIN_FUSE / `block.fuse_window_attention_train`).
 
 Parameter / buffer names are the released checkpoints' (`swin_tiny_patch4_window7_224.pth`): patch_embed.{proj,norm},
 layers.<i>.blocks.<j>.{norm1,attn.{relative_position_bias_table,relative_position_index,qkv,proj},norm2,mlp.{fc1,fc2}},
@@ -18,7 +20,7 @@ import torch.nn.functional as F
 import torch.utils.checkpoint as cp
 
 from .. import switches
-from ..mmdet_ops.window_attention import window_attention, window_attention_ok
+from ..mmdet_ops.window_attention import window_attention, window_attention_ok, window_attention_train, window_attention_train_ok
 from .registry import BACKBONES
 
 
@@ -103,12 +105,16 @@ class SwinBlock(nn.Module):
         """inference on fp32 device tokens: everything between attn.qkv and attn.proj as one kernel (mmdet_ops/window_attention.py)"""
         return switches.of(self, 'fuse_window_attention', 'SWIN_ATTN_FUSE') and window_attention_ok(self.attn, x)
 
+    def fuses_attention_train(self, x):
+        """the same with gradients enabled: a forward kernel that keeps the rows' log-sum-exp, and one backward call"""
+        return switches.of(self, 'fuse_window_attention_train', 'SWIN_ATTN_TRAIN_FUSE') and window_attention_train_ok(self.attn, x)
+
     def forward(self, x, H, W, shift_mask):
-        if self.fuses_attention(x):
+        fused = window_attention if self.fuses_attention(x) else window_attention_train if self.fuses_attention_train(x) else None
+        if fused is not None:
             # qkv and proj are per-token linears: both run on the un-padded, un-rolled tokens, the kernel does the index arithmetic
             a = self.attn
-            y = window_attention(a.qkv(self.norm1(x)), a.qkv.bias, a.relative_position_bias_table, H, W, a.num_heads, self.ws,
-                                 self.shift, a.scale)
+            y = fused(a.qkv(self.norm1(x)), a.qkv.bias, a.relative_position_bias_table, H, W, a.num_heads, self.ws, self.shift, a.scale)
             x = x + self.drop_path(a.proj_drop(a.proj(y)))
             return x + self.drop_path(self.mlp(self.norm2(x)))
         B, L, C = x.shape
@@ -180,7 +186,8 @@ class SwinStage(nn.Module):
 
     def forward(self, x, H, W):
         # (no block that takes the fused route reads the mask: it is not evaluated for them)
-        mask = None if all(blk.fuses_attention(x) for blk in self.blocks if blk.shift) else self.shift_mask(H, W, x.device)
+        fused = all(blk.fuses_attention(x) or blk.fuses_attention_train(x) for blk in self.blocks if blk.shift)
+        mask = None if fused else self.shift_mask(H, W, x.device)
         for blk in self.blocks:
             if self.use_checkpoint and x.requires_grad:
                 x = cp.checkpoint(blk, x, H, W, mask, use_reentrant=False)

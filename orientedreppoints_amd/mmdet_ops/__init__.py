@@ -15,3 +15,5 @@ from .deform_conv import (DeformConv, DeformConvPack, ModulatedDeformConv, Modul
                           deform_conv_pair)
 from .box_iou_rotated import box_iou_rotated  # noqa: F401
 from .window_attention import window_attention, window_attention_ok, window_attention_reference  # noqa: F401
+from .window_attention import (window_attention_backward, window_attention_forward_lse, window_attention_train,  # noqa: F401
+                               window_attention_train_ok)

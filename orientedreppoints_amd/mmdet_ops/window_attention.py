@@ -1,4 +1,5 @@
-"""Swin's (shifted-)window attention at inference as one HIP kernel (`orp_window_attention`, include/orp_hip.h): everything between
+"""Swin's (shifted-)window attention as HIP kernels -- at inference one (`orp_window_attention`, include/orp_hip.h), in training a
+forward that keeps the rows' log-sum-exp and a backward (`orp_window_attention_train`, `orp_window_attention_backward`): everything between
 `attn.qkv` and `attn.proj` of a Swin block (mmdet/models/backbones/swin_transformer.py: SwinTransformerBlock.forward:199-250,
 WindowAttention.forward:122-155, the mask of BasicLayer.forward:370-390).
 
@@ -8,6 +9,7 @@ one); pad, roll, window partition, relative-position bias, shift mask, window re
 `window_attention_reference` states exactly that in plain torch (any dtype, any device) and is what the tests hold the kernel to.
 """
 import torch
+from torch.autograd.function import once_differentiable
 
 from .. import _lib
 
@@ -71,14 +73,122 @@ def window_attention_ok(attn_module, x):
     return all(p.dtype == torch.float32 and p.device == x.device for p in params)
 
 
+def _fp32_on(ref, tensors, optional=()):
+    """the argument rule of `window_attention` for the training calls: contiguous float32 CUDA tensors on `ref`'s device"""
+    for name, t in tensors:
+        if t is None and name in optional:
+            continue
+        _lib.require_cuda(t, name)
+        if t.dtype != torch.float32 or t.device != ref.device:
+            raise TypeError("%s must be a float32 tensor on qkv's device" % name)
+        if not t.is_contiguous():
+            raise ValueError("%s must be contiguous" % name)
+
+
+def _shaped(t, shape, name):
+    if tuple(t.shape) != tuple(shape):
+        raise ValueError("%s must be %s, got %s" % (name, list(shape), tuple(t.shape)))
+    return t
+
+
+def window_attention_forward_lse(qkv, qkv_bias, bias_table, H, W, heads, window, shift, scale, out=None, lse=None):
+    """`window_attention` for training: returns (out, lse) -- `out` bit for bit `window_attention`'s, `lse` [B, H * W, heads] the
+    log-sum-exp of every token's row of scores, which is all the backward needs besides the operands.  Not differentiable by itself
+    (`window_attention_train` is); the same argument rules, nothing written where they raise."""
+    _fp32_on(qkv, (("qkv", qkv), ("qkv_bias", qkv_bias), ("bias_table", bias_table), ("out", out), ("lse", lse)),
+             optional=("qkv_bias", "out", "lse"))
+    B, C, hd = _shapes(qkv, qkv_bias, bias_table, H, W, heads, window)
+    out = torch.empty((B, H * W, C), dtype=torch.float32, device=qkv.device) if out is None else _shaped(out, (B, H * W, C), "out")
+    lse = torch.empty((B, H * W, heads), dtype=torch.float32, device=qkv.device) if lse is None else _shaped(lse, (B, H * W, heads), "lse")
+    with torch.cuda.device(qkv.device):
+        rc = _lib.lib().orp_window_attention_train(_lib.ptr(qkv.detach()), _lib.ptr(None if qkv_bias is None else qkv_bias.detach()),
+                                                   _lib.ptr(bias_table.detach()), B, H, W, heads, hd, window, shift, float(scale),
+                                                   _lib.ptr(out), _lib.ptr(lse), _lib.stream_of(qkv))
+    _lib.check(rc, "orp_window_attention_train")
+    return out, lse
+
+
+def window_attention_backward(qkv, qkv_bias, bias_table, out, lse, grad_out, H, W, heads, window, shift, scale, grads=None,
+                              workspace=None):
+    """The gradients of `window_attention` (include/orp_hip.h: orp_window_attention_backward) from the operands, the forward's `out` and
+    `lse` and grad_out [B, H * W, C]: (grad_qkv like qkv, grad_qkv_bias [3 * C] -- the padded tokens' share; None without a qkv_bias --,
+    grad_bias_table [169, heads]).  Every element is written, in one fixed summation order.  `grads`: the three as preallocated tensors
+    (None in the bias's place without one); `workspace`: a uint8 CUDA tensor in place of the cached one."""
+    gq, gb, gt = (None, None, None) if grads is None else grads
+    _fp32_on(qkv, (("qkv", qkv), ("qkv_bias", qkv_bias), ("bias_table", bias_table), ("out", out), ("lse", lse), ("grad_out", grad_out),
+                   ("grad_qkv", gq), ("grad_qkv_bias", gb), ("grad_bias_table", gt)),
+             optional=("qkv_bias", "grad_qkv", "grad_qkv_bias", "grad_bias_table"))
+    B, C, hd = _shapes(qkv, qkv_bias, bias_table, H, W, heads, window)
+    _shaped(out, (B, H * W, C), "out"), _shaped(lse, (B, H * W, heads), "lse"), _shaped(grad_out, (B, H * W, C), "grad_out")
+    if gb is not None and qkv_bias is None:
+        raise ValueError("grad_qkv_bias without a qkv_bias")
+    gq = torch.empty_like(qkv) if gq is None else _shaped(gq, qkv.shape, "grad_qkv")
+    gt = torch.empty_like(bias_table) if gt is None else _shaped(gt, bias_table.shape, "grad_bias_table")
+    if qkv_bias is not None:
+        gb = torch.empty_like(qkv_bias) if gb is None else _shaped(gb, qkv_bias.shape, "grad_qkv_bias")
+    L = _lib.lib()
+    with torch.cuda.device(qkv.device):
+        if workspace is None:
+            workspace = _lib.workspace(qkv.device, L.orp_window_attention_backward_workspace_bytes(B, H, W, heads, hd, window))
+        elif not (isinstance(workspace, torch.Tensor) and workspace.is_cuda and workspace.dtype == torch.uint8 and workspace.is_contiguous()):
+            raise TypeError("workspace must be a contiguous uint8 CUDA tensor")
+        rc = L.orp_window_attention_backward(_lib.ptr(qkv.detach()), _lib.ptr(None if qkv_bias is None else qkv_bias.detach()),
+                                             _lib.ptr(bias_table.detach()), _lib.ptr(out.detach()), _lib.ptr(lse), _lib.ptr(grad_out), B, H, W,
+                                             heads, hd, window, shift, float(scale), _lib.ptr(gq), _lib.ptr(gb), _lib.ptr(gt),
+                                             _lib.ptr(workspace), workspace.numel(), _lib.stream_of(qkv))
+    _lib.check(rc, "orp_window_attention_backward")
+    return gq, gb, gt
+
+
+class _WindowAttentionTrain(torch.autograd.Function):
+    """saves the operands, `out` and `lse` -- nothing of size 49 x 49"""
+
+    @staticmethod
+    def forward(ctx, qkv, qkv_bias, bias_table, H, W, heads, window, shift, scale):
+        out, lse = window_attention_forward_lse(qkv, qkv_bias, bias_table, H, W, heads, window, shift, scale)
+        ctx.save_for_backward(qkv, qkv_bias, bias_table, out, lse)
+        ctx.geometry = (H, W, heads, window, shift, scale)
+        return out
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, grad_out):
+        qkv, qkv_bias, bias_table, out, lse = ctx.saved_tensors
+        gq, gb, gt = window_attention_backward(qkv, qkv_bias, bias_table, out, lse, grad_out.contiguous(), *ctx.geometry)
+        return (gq, gb, gt) + (None,) * 6
+
+
+def window_attention_train(qkv, qkv_bias, bias_table, H, W, heads, window, shift, scale):
+    """`window_attention` with a backward: gradients for qkv, qkv_bias (the padded tokens' share: their k / v are the bias) and
+    bias_table, all three always computed.  Once differentiable."""
+    return _WindowAttentionTrain.apply(qkv, qkv_bias, bias_table, H, W, heads, window, shift, scale)
+
+
+def window_attention_train_ok(attn_module, x):
+    """The routing rule of the fused Swin block in training: `window_attention_ok`'s with gradients ENABLED -- fp32 CUDA tokens and
+    parameters, window 7, a head dim the kernels have, attention dropout inactive, no autocast."""
+    if not isinstance(x, torch.Tensor) or not x.is_cuda or x.dtype != torch.float32:
+        return False
+    if not torch.is_grad_enabled() or torch.is_autocast_enabled():
+        return False
+    a = attn_module
+    if a.ws != WINDOW or a.dim % a.num_heads or (a.dim // a.num_heads) not in HEAD_DIMS:
+        return False
+    if a.training and a.attn_drop.p > 0.0:
+        return False
+    params = [a.qkv.weight, a.proj.weight, a.relative_position_bias_table] + ([] if a.qkv.bias is None else [a.qkv.bias])
+    return all(p.dtype == torch.float32 and p.device == x.device for p in params)
+
+
 def _bands(n, window, shift, device):
     """band of every rolled coordinate of an axis of padded length n: 0 below n - window, 1 below n - shift, else 2"""
     r = torch.arange(n, device=device)
     return (r >= n - window).long() + (r >= n - shift).long()
 
 
-def window_attention_reference(qkv, qkv_bias, bias_table, H, W, heads, window, shift, scale):
-    """`window_attention` in plain torch, written from the semantics in include/orp_hip.h: any dtype, any device, any window."""
+def window_attention_reference(qkv, qkv_bias, bias_table, H, W, heads, window, shift, scale, with_lse=False):
+    """`window_attention` in plain torch, written from the semantics in include/orp_hip.h: any dtype, any device, any window;
+    differentiable, which defines the backward.  with_lse: returns (out, lse [B, H * W, heads]) as `window_attention_forward_lse`."""
     B, C, hd = _shapes(qkv, qkv_bias, bias_table, H, W, heads, window)
     ws, N, dev = window, window * window, qkv.device
     Hp, Wp = -(-H // ws) * ws, -(-W // ws) * ws
@@ -100,9 +210,15 @@ def window_attention_reference(qkv, qkv_bias, bias_table, H, W, heads, window, s
         band = 3 * _bands(Hp, ws, shift, dev)[:, None] + _bands(Wp, ws, shift, dev)[None, :]          # on rolled coordinates
         band = band.view(nwy, ws, nwx, ws).permute(0, 2, 1, 3).reshape(nwy, nwx, 1, N)
         score = score + (band[..., :, None] != band[..., None, :]).to(qkv.dtype) * -100.0
-    p = torch.exp(score - score.amax(-1, keepdim=True))
+    top = score.amax(-1, keepdim=True)
+    p = torch.exp(score - top)
     o = (p / p.sum(-1, keepdim=True)) @ v                                      # [B, nwy, nwx, heads, N, hd]
-    o = o.view(B, nwy, nwx, heads, ws, ws, hd).permute(0, 1, 4, 2, 5, 3, 6).reshape(B, Hp, Wp, C)
-    back = qkv.new_empty((B, Hp, Wp, C))
-    back[:, sy[:, None], sx[None, :]] = o                                      # un-roll
-    return back[:, :H, :W].reshape(B, H * W, C)
+
+    def to_tokens(t):                                                          # [B, nwy, nwx, heads, N, last] -> [B, H * W, heads * last]
+        t = t.view(B, nwy, nwx, heads, ws, ws, -1).permute(0, 1, 4, 2, 5, 3, 6).reshape(B, Hp, Wp, -1)
+        back = torch.empty_like(t)
+        back[:, sy[:, None], sx[None, :]] = t                                  # un-roll
+        return back[:, :H, :W].reshape(B, H * W, -1)
+    if with_lse:
+        return to_tokens(o), to_tokens(top + torch.log(p.sum(-1, keepdim=True)))
+    return to_tokens(o)
