@@ -875,6 +875,47 @@ int orp_window_attention_backward(const float* qkv, const float* qkv_bias, const
                                   void* workspace, size_t workspace_bytes, void* stream);
 
 /* ---------------------------------------------------------------------------------------------------------
+ * The same attention on fp16 / bf16 OPERANDS (csrc/orp_window_attn_half.hip): what a Swin block holds between attn.qkv and attn.proj
+ * under autocast.  dtype: 1 = fp16, 2 = bf16 (the convention of orp_dcn_forward_multi_h).  The arithmetic is the fp32 calls': every
+ * product, sum, expf and logf is fp32, in the order orp_window_attention / orp_window_attention_train / orp_window_attention_backward
+ * fix; only the memory format differs.
+ *   qkv, out, grad_out, grad_qkv   16-bit elements of `dtype`, the fp32 calls' shapes; widened as they are loaded, rounded ONCE, to
+ *                                  nearest even, as they are stored
+ *   qkv_bias, bias_table, lse, grad_qkv_bias, grad_bias_table, workspace   fp32, as in the fp32 calls (fp32 parameters under autocast)
+ *   A padded token's q / k / v are the qkv bias ROUNDED TO `dtype` -- what the 16-bit linear layer emits for a zero row; the kernel
+ *   reads the fp32 bias and rounds it itself.
+ * Index arithmetic, score expression, shift mask, key order and grid are orp_window_attention's.  Hence: with fp32 copies of the same
+ * 16-bit operands and the rounded bias, the fp32 calls form the same fp32 values; `out` and `grad_qkv` here are those values rounded to
+ * `dtype`, and lse, grad_qkv_bias and grad_bias_table are the fp32 calls' bit for bit.
+ * orp_window_attention_h: the forward.
+ *   out        [batch, height * width, heads * head_dim], `dtype`: the attention result of every real token in its own place
+ *   lse        [batch, height * width, heads] fp32, or NULL: row maximum + logf(row sum) of every real token's row of scores.  One
+ *              entry serves inference under autocast (NULL: nothing kept) and training.  A padded token has no output and no lse.
+ * orp_window_attention_backward_h: out, lse as the forward left them (D_i = sum_d grad_out_i,d * out_i,d is formed from the 16-bit
+ *   `out`), grad_out [batch, height * width, heads * head_dim] of `dtype`.  P_ij, dS_ij and the three gradients are
+ *   orp_window_attention_backward's:
+ *   grad_qkv        [batch, height * width, 3, heads, head_dim], `dtype`: dQ / dK / dV of every real token at its own place; every
+ *                   element is written exactly once -- no pre-zeroing, no atomics
+ *   grad_bias_table [(2 * window - 1)^2, heads] fp32: the sum of dS_ij over all windows, images and pairs with the same (dy, dx)
+ *   grad_qkv_bias   [3 * heads * head_dim] fp32 or NULL (it must be NULL when qkv_bias is): the dK_j / dV_j of padded keys summed into
+ *                   the k and v thirds; the q third is written as exactly zero.  Only the padded tokens' share.
+ *   workspace       orp_window_attention_backward_workspace_bytes(batch, height, width, heads, head_dim, window) bytes (the fp32
+ *                   call's figure: the partials are fp32), 4-byte aligned.
+ * Deterministic: ONE summation order per output element, the fp32 call's (keys / queries ascending inside a window, padded keys
+ * ascending, windows in sixteen interleaved ascending slices, then the slices ascending); no floating-point atomics; independent of
+ * the grid's scheduling, of other work on the device and of replay.  No allocation, no host synchronisation: capturable.
+ * Supported: as orp_window_attention (window == 7, 0 <= shift < 7, head_dim a multiple of 4 in [4, 32]), dtype 1 or 2, 8-byte aligned
+ * qkv / out / grad_out / grad_qkv, 16-byte aligned qkv_bias; anything else, a workspace smaller than asked for included, is ORP_EINVAL
+ * and launches nothing.
+ * ------------------------------------------------------------------------------------------------------- */
+int orp_window_attention_h(const void* qkv, const float* qkv_bias, const float* bias_table, int batch, int height, int width, int heads,
+                           int head_dim, int window, int shift, float scale, void* out, float* lse, int dtype, void* stream);
+int orp_window_attention_backward_h(const void* qkv, const float* qkv_bias, const float* bias_table, const void* out, const float* lse,
+                                    const void* grad_out, int batch, int height, int width, int heads, int head_dim, int window,
+                                    int shift, float scale, void* grad_qkv, float* grad_qkv_bias, float* grad_bias_table,
+                                    void* workspace, size_t workspace_bytes, int dtype, void* stream);
+
+/* ---------------------------------------------------------------------------------------------------------
  * Fused test-time post-processing around the rotated NMS: replaces the tensor-op chains of
  * get_bboxes_single (orientedreppoints_head.py:707-779), multiclass_rnms (bbox_nms.py:93-182) and rbbox2result
  * (transforms.py:356-375) with fixed-shape, stream-ordered kernels -- no host synchronisation, hipGraph-capturable.

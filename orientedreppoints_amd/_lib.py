@@ -178,6 +178,8 @@ _SIGNATURES = {
     "orp_window_attention_train": (_i, [_vp, _vp, _vp] + [_i] * 7 + [_f, _vp, _vp, _vp]),
     "orp_window_attention_backward_workspace_bytes": (_sz, [_i] * 6),
     "orp_window_attention_backward": (_i, [_vp] * 6 + [_i] * 7 + [_f, _vp, _vp, _vp, _vp, _sz, _vp]),
+    "orp_window_attention_h": (_i, [_vp, _vp, _vp] + [_i] * 7 + [_f, _vp, _vp, _i, _vp]),
+    "orp_window_attention_backward_h": (_i, [_vp] * 6 + [_i] * 7 + [_f, _vp, _vp, _vp, _vp, _sz, _i, _vp]),
 }
 
 _lib = None

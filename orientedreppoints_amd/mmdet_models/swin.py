@@ -9,7 +9,9 @@ stages.  Own layout of the computation: one `scaled_dot_product_attention` call 
 tensors a block runs everything between `attn.qkv` and `attn.proj` as one HIP kernel on the un-padded, un-rolled tokens instead
 (`SwinBlock.fuses_attention`, mmdet_ops/window_attention.py; switch ORP_SWIN_ATTN_FUSE / `block.fuse_window_attention`); with
 gradients enabled the same span is `window_attention_train`, a forward kernel that keeps the rows' log-sum-exp and a backward call
-(`SwinBlock.fuses_attention_train`; switch ORP_SWIN_ATTN_TRAIN_FUSE / `block.fuse_window_attention_train`).
+(`SwinBlock.fuses_attention_train`; switch ORP_SWIN_ATTN_TRAIN_FUSE / `block.fuse_window_attention_train`).  Under fp16 / bf16
+autocast `attn.qkv` yields 16-bit q / k / v and the span is `window_attention_half` / `window_attention_train_half`: the same kernels
+on 16-bit operands, fp32 arithmetic (`SwinBlock.fuses_attention_half`; switch ORP_SWIN_ATTN_HALF_FUSE / `block.fuse_window_attention_half`).
 
 Parameter / buffer names are the released checkpoints' (`swin_tiny_patch4_window7_224.pth`): patch_embed.{proj,norm},
 layers.<i>.blocks.<j>.{norm1,attn.{relative_position_bias_table,relative_position_index,qkv,proj},norm2,mlp.{fc1,fc2}},
@@ -20,7 +22,9 @@ import torch.nn.functional as F
 import torch.utils.checkpoint as cp
 
 from .. import switches
-from ..mmdet_ops.window_attention import window_attention, window_attention_ok, window_attention_train, window_attention_train_ok
+from ..mmdet_ops.window_attention import (window_attention, window_attention_half, window_attention_half_ok, window_attention_ok,
+                                          window_attention_train, window_attention_train_half, window_attention_train_half_ok,
+                                          window_attention_train_ok)
 from .registry import BACKBONES
 
 
@@ -109,8 +113,24 @@ class SwinBlock(nn.Module):
         """the same with gradients enabled: a forward kernel that keeps the rows' log-sum-exp, and one backward call"""
         return switches.of(self, 'fuse_window_attention_train', 'SWIN_ATTN_TRAIN_FUSE') and window_attention_train_ok(self.attn, x)
 
+    def fuses_attention_half(self, x):
+        """under fp16 / bf16 autocast: `attn.qkv` yields 16-bit q / k / v and the kernels take them as they are (fp32 arithmetic);
+        `window_attention_half` without gradients, `window_attention_train_half` with"""
+        if not switches.of(self, 'fuse_window_attention_half', 'SWIN_ATTN_HALF_FUSE'):
+            return None
+        if window_attention_half_ok(self.attn, x):
+            return window_attention_half
+        return window_attention_train_half if window_attention_train_half_ok(self.attn, x) else None
+
+    def fused_attention(self, x):
+        """the operator this block runs between attn.qkv and attn.proj on `x`, or None for the stock route: fp32 inference, fp32
+        training, 16-bit inference, 16-bit training, in this order"""
+        if self.fuses_attention(x):
+            return window_attention
+        return window_attention_train if self.fuses_attention_train(x) else self.fuses_attention_half(x)
+
     def forward(self, x, H, W, shift_mask):
-        fused = window_attention if self.fuses_attention(x) else window_attention_train if self.fuses_attention_train(x) else None
+        fused = self.fused_attention(x)
         if fused is not None:
             # qkv and proj are per-token linears: both run on the un-padded, un-rolled tokens, the kernel does the index arithmetic
             a = self.attn
@@ -186,7 +206,7 @@ class SwinStage(nn.Module):
 
     def forward(self, x, H, W):
         # (no block that takes the fused route reads the mask: it is not evaluated for them)
-        fused = all(blk.fuses_attention(x) or blk.fuses_attention_train(x) for blk in self.blocks if blk.shift)
+        fused = all(blk.fused_attention(x) is not None for blk in self.blocks if blk.shift)
         mask = None if fused else self.shift_mask(H, W, x.device)
         for blk in self.blocks:
             if self.use_checkpoint and x.requires_grad:

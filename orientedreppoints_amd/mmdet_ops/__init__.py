@@ -17,3 +17,5 @@ from .box_iou_rotated import box_iou_rotated  # noqa: F401
 from .window_attention import window_attention, window_attention_ok, window_attention_reference  # noqa: F401
 from .window_attention import (window_attention_backward, window_attention_forward_lse, window_attention_train,  # noqa: F401
                                window_attention_train_ok)
+from .window_attention import (window_attention_backward_half, window_attention_forward_lse_half, window_attention_half,  # noqa: F401
+                               window_attention_half_ok, window_attention_train_half, window_attention_train_half_ok)

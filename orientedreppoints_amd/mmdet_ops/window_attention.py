@@ -7,6 +7,10 @@ The reformulation it rests on: `qkv` and `proj` are per-token linears, so both r
 the pad comes after norm1, so a padded token is a zero vector in front of `qkv` and its q / k / v are the `qkv` bias (zero without
 one); pad, roll, window partition, relative-position bias, shift mask, window reverse, un-roll and crop are index arithmetic.
 `window_attention_reference` states exactly that in plain torch (any dtype, any device) and is what the tests hold the kernel to.
+
+Under fp16 / bf16 autocast `attn.qkv` yields 16-bit q / k / v: `window_attention_half`, `window_attention_train_half` and their
+low-level calls (`orp_window_attention_h`, `orp_window_attention_backward_h`) take them as they are -- fp32 arithmetic in the fp32
+kernels' order, a padded token's q / k / v = the bias rounded to the operand type.  The fp32 functions and predicates do not change.
 """
 import torch
 from torch.autograd.function import once_differentiable
@@ -178,6 +182,139 @@ def window_attention_train_ok(attn_module, x):
         return False
     params = [a.qkv.weight, a.proj.weight, a.relative_position_bias_table] + ([] if a.qkv.bias is None else [a.qkv.bias])
     return all(p.dtype == torch.float32 and p.device == x.device for p in params)
+
+
+# ---- fp16 / bf16 operands: what a block holds between attn.qkv and attn.proj under autocast (csrc/orp_window_attn_half.hip) ----
+HALF_DTYPES = {torch.float16: 1, torch.bfloat16: 2}          # the library's dtype codes (orp_dcn_forward_multi_h's convention)
+
+
+def _half_on(qkv, halves, floats, optional=()):
+    """the argument rule of the 16-bit calls: `qkv` fp16 or bf16, `halves` of qkv's dtype, `floats` float32, all contiguous CUDA tensors
+    on qkv's device.  Returns the library's dtype code."""
+    _lib.require_cuda(qkv, "qkv")
+    if qkv.dtype not in HALF_DTYPES:
+        raise TypeError("qkv must be a float16 or bfloat16 tensor, got %s" % qkv.dtype)
+    for want, group in ((qkv.dtype, (("qkv", qkv),) + tuple(halves)), (torch.float32, floats)):
+        for name, t in group:
+            if t is None and name in optional:
+                continue
+            _lib.require_cuda(t, name)
+            if t.dtype != want or t.device != qkv.device:
+                raise TypeError("%s must be a %s tensor on qkv's device" % (name, str(want).replace("torch.", "")))
+            if not t.is_contiguous():
+                raise ValueError("%s must be contiguous" % name)
+    return HALF_DTYPES[qkv.dtype]
+
+
+def window_attention_forward_lse_half(qkv, qkv_bias, bias_table, H, W, heads, window, shift, scale, out=None, lse=None, keep_lse=True):
+    """`window_attention_forward_lse` on 16-bit operands (include/orp_hip.h: orp_window_attention_h): qkv and `out` fp16 or bf16 and
+    of one dtype, qkv_bias / bias_table / `lse` float32.  All arithmetic is fp32 in the fp32 kernel's order; a padded token's q / k / v
+    are the bias rounded to qkv's dtype; `out` is rounded once as it is stored, `lse` is the fp32 kernel's for the widened operands.
+    Returns (out, lse); keep_lse=False keeps none (lse is None).  A dtype mix raises TypeError, nothing is written where the rules raise."""
+    code = _half_on(qkv, (("out", out),), (("qkv_bias", qkv_bias), ("bias_table", bias_table), ("lse", lse)), optional=("qkv_bias", "out", "lse"))
+    B, C, hd = _shapes(qkv, qkv_bias, bias_table, H, W, heads, window)
+    out = torch.empty((B, H * W, C), dtype=qkv.dtype, device=qkv.device) if out is None else _shaped(out, (B, H * W, C), "out")
+    if keep_lse:
+        lse = torch.empty((B, H * W, heads), dtype=torch.float32, device=qkv.device) if lse is None else _shaped(lse, (B, H * W, heads), "lse")
+    elif lse is not None:
+        raise ValueError("lse given with keep_lse=False")
+    with torch.cuda.device(qkv.device):
+        rc = _lib.lib().orp_window_attention_h(_lib.ptr(qkv.detach()), _lib.ptr(None if qkv_bias is None else qkv_bias.detach()),
+                                               _lib.ptr(bias_table.detach()), B, H, W, heads, hd, window, shift, float(scale),
+                                               _lib.ptr(out), _lib.ptr(lse), code, _lib.stream_of(qkv))
+    _lib.check(rc, "orp_window_attention_h")
+    return out, lse
+
+
+def window_attention_half(qkv, qkv_bias, bias_table, H, W, heads, window, shift, scale, out=None):
+    """`window_attention` on 16-bit operands, forward only: qkv fp16 or bf16 CUDA, qkv_bias / bias_table float32 (the parameters stay
+    fp32 under autocast).  Returns [B, H * W, C] of qkv's dtype."""
+    return window_attention_forward_lse_half(qkv, qkv_bias, bias_table, H, W, heads, window, shift, scale, out=out, keep_lse=False)[0]
+
+
+def window_attention_backward_half(qkv, qkv_bias, bias_table, out, lse, grad_out, H, W, heads, window, shift, scale, grads=None,
+                                   workspace=None):
+    """`window_attention_backward` on 16-bit operands (orp_window_attention_backward_h): qkv, out, grad_out and grad_qkv of one 16-bit
+    dtype; qkv_bias, bias_table, lse, grad_qkv_bias and grad_bias_table float32.  D_i is formed from the 16-bit `out`; everything else is
+    the fp32 backward's arithmetic on the widened operands, grad_qkv rounded once as it is stored.  The workspace is the fp32 call's."""
+    gq, gb, gt = (None, None, None) if grads is None else grads
+    code = _half_on(qkv, (("out", out), ("grad_out", grad_out), ("grad_qkv", gq)),
+                    (("qkv_bias", qkv_bias), ("bias_table", bias_table), ("lse", lse), ("grad_qkv_bias", gb), ("grad_bias_table", gt)),
+                    optional=("qkv_bias", "grad_qkv", "grad_qkv_bias", "grad_bias_table"))
+    B, C, hd = _shapes(qkv, qkv_bias, bias_table, H, W, heads, window)
+    _shaped(out, (B, H * W, C), "out"), _shaped(lse, (B, H * W, heads), "lse"), _shaped(grad_out, (B, H * W, C), "grad_out")
+    if gb is not None and qkv_bias is None:
+        raise ValueError("grad_qkv_bias without a qkv_bias")
+    gq = torch.empty_like(qkv) if gq is None else _shaped(gq, qkv.shape, "grad_qkv")
+    gt = torch.empty_like(bias_table) if gt is None else _shaped(gt, bias_table.shape, "grad_bias_table")
+    if qkv_bias is not None:
+        gb = torch.empty_like(qkv_bias) if gb is None else _shaped(gb, qkv_bias.shape, "grad_qkv_bias")
+    L = _lib.lib()
+    with torch.cuda.device(qkv.device):
+        if workspace is None:
+            workspace = _lib.workspace(qkv.device, L.orp_window_attention_backward_workspace_bytes(B, H, W, heads, hd, window))
+        elif not (isinstance(workspace, torch.Tensor) and workspace.is_cuda and workspace.dtype == torch.uint8 and workspace.is_contiguous()):
+            raise TypeError("workspace must be a contiguous uint8 CUDA tensor")
+        rc = L.orp_window_attention_backward_h(_lib.ptr(qkv.detach()), _lib.ptr(None if qkv_bias is None else qkv_bias.detach()),
+                                               _lib.ptr(bias_table.detach()), _lib.ptr(out.detach()), _lib.ptr(lse), _lib.ptr(grad_out), B, H, W,
+                                               heads, hd, window, shift, float(scale), _lib.ptr(gq), _lib.ptr(gb), _lib.ptr(gt),
+                                               _lib.ptr(workspace), workspace.numel(), code, _lib.stream_of(qkv))
+    _lib.check(rc, "orp_window_attention_backward_h")
+    return gq, gb, gt
+
+
+class _WindowAttentionTrainHalf(torch.autograd.Function):
+    """saves the 16-bit operands and `out` and the fp32 `lse` -- nothing of size 49 x 49"""
+
+    @staticmethod
+    def forward(ctx, qkv, qkv_bias, bias_table, H, W, heads, window, shift, scale):
+        out, lse = window_attention_forward_lse_half(qkv, qkv_bias, bias_table, H, W, heads, window, shift, scale)
+        ctx.save_for_backward(qkv, qkv_bias, bias_table, out, lse)
+        ctx.geometry = (H, W, heads, window, shift, scale)
+        return out
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, grad_out):
+        qkv, qkv_bias, bias_table, out, lse = ctx.saved_tensors
+        gq, gb, gt = window_attention_backward_half(qkv, qkv_bias, bias_table, out, lse, grad_out.to(out.dtype).contiguous(), *ctx.geometry)
+        return (gq, gb, gt) + (None,) * 6
+
+
+def window_attention_train_half(qkv, qkv_bias, bias_table, H, W, heads, window, shift, scale):
+    """`window_attention_half` with a backward: a 16-bit gradient for qkv, fp32 gradients for qkv_bias (the padded tokens' share) and
+    bias_table, all three always computed.  Once differentiable."""
+    return _WindowAttentionTrainHalf.apply(qkv, qkv_bias, bias_table, H, W, heads, window, shift, scale)
+
+
+def _half_route_ok(attn_module, x, grad):
+    if not isinstance(x, torch.Tensor) or not x.is_cuda:
+        return False
+    if torch.is_grad_enabled() != grad or not torch.is_autocast_enabled() or torch.get_autocast_dtype('cuda') not in HALF_DTYPES:
+        return False
+    if x.dtype not in (torch.float32, torch.get_autocast_dtype('cuda')):
+        return False
+    a = attn_module
+    if a.ws != WINDOW or a.dim % a.num_heads or (a.dim // a.num_heads) not in HEAD_DIMS:
+        return False
+    if a.training and a.attn_drop.p > 0.0:
+        return False
+    params = [a.qkv.weight, a.proj.weight, a.relative_position_bias_table] + ([] if a.qkv.bias is None else [a.qkv.bias])
+    return all(p.dtype == torch.float32 and p.device == x.device for p in params)
+
+
+def window_attention_half_ok(attn_module, x):
+    """The routing rule of the fused Swin block at inference under autocast: CUDA tokens, fp32 parameters on their device, CUDA
+    autocast ENABLED with dtype fp16 or bf16 (so `attn.qkv` yields 16-bit q / k / v and `attn.proj` takes a 16-bit operand), window 7, a
+    head dim the kernels have, attention dropout inactive, gradients disabled.  The tokens are fp32 or of the autocast dtype: the
+    first stage's are fp32, but PatchMerging's linear layer hands every later stage 16-bit tokens (norm1 widens them again).  A
+    `model.half()` model (16-bit parameters, no autocast) is not detected and keeps the stock route."""
+    return _half_route_ok(attn_module, x, grad=False)
+
+
+def window_attention_train_half_ok(attn_module, x):
+    """`window_attention_half_ok` with gradients ENABLED: the routing rule of `window_attention_train_half`."""
+    return _half_route_ok(attn_module, x, grad=True)
 
 
 def _bands(n, window, shift, device):

@@ -25,6 +25,7 @@ BN_CONV3X3_FUSE = _on('ORP_BN_CONV3X3_FUSE')  # bottleneck conv2 (3x3, stride 1)
 STEM_POOL_FUSE = _on('ORP_STEM_POOL_FUSE')    # stem BatchNorm + ReLU + max-pool as one kernel (backbone.fuse_stem_pool overrides)
 SWIN_ATTN_FUSE = _on('ORP_SWIN_ATTN_FUSE')    # Swin inference: pad / roll / windows / bias / mask / softmax / P V / un-roll / crop as one fp32 kernel (block.fuse_window_attention overrides)
 SWIN_ATTN_TRAIN_FUSE = _on('ORP_SWIN_ATTN_TRAIN_FUSE')  # Swin training: the same between attn.qkv and attn.proj as one fp32 forward kernel that keeps the rows' log-sum-exp, and one backward call (block.fuse_window_attention_train overrides)
+SWIN_ATTN_HALF_FUSE = _on('ORP_SWIN_ATTN_HALF_FUSE')  # Swin under fp16 / bf16 autocast, inference and training: the same span on 16-bit operands with fp32 arithmetic, one forward kernel (+ one backward call) (block.fuse_window_attention_half overrides)
 FPN_TOPDOWN_FUSE = _on('ORP_FPN_TOPDOWN_FUSE')  # FPN lateral GroupNorm + top-down sum + transposition as one pass (neck.fuse_topdown overrides)
 TRAIN_SPLIT = _on('ORP_TRAIN_SPLIT')          # training: tower / FPN convolutions as conv_split_train nodes
 DETERMINISTIC = _on('ORP_DETERMINISTIC', '0')  # training: fixed-order DeformConv backward for both branches (head.deterministic_backward overrides)
