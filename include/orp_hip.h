@@ -839,7 +839,7 @@ int orp_window_attention(const float* qkv, const float* qkv_bias, const float* b
                          int heads, int head_dim, int window, int shift, float scale, float* out, void* stream);
 
 /* ---------------------------------------------------------------------------------------------------------
- * The same attention in TRAINING (csrc/orp_window_attn_train.hip): a forward that also keeps every row's log-sum-exp, and the
+ * The same attention in TRAINING (csrc/orp_window_attn.hip, the same forward kernel): a forward that also keeps every row's log-sum-exp, and the
  * backward.  Arguments, index arithmetic, supported set and grid (one wave per (window, head)) are orp_window_attention's.
  * orp_window_attention_train:
  *   out        bit for bit what orp_window_attention writes for the same arguments (same score expression, same key order, same expf)
@@ -875,8 +875,8 @@ int orp_window_attention_backward(const float* qkv, const float* qkv_bias, const
                                   void* workspace, size_t workspace_bytes, void* stream);
 
 /* ---------------------------------------------------------------------------------------------------------
- * The same attention on fp16 / bf16 OPERANDS (csrc/orp_window_attn_half.hip): what a Swin block holds between attn.qkv and attn.proj
- * under autocast.  dtype: 1 = fp16, 2 = bf16 (the convention of orp_dcn_forward_multi_h).  The arithmetic is the fp32 calls': every
+ * The same attention on fp16 / bf16 OPERANDS (csrc/orp_window_attn.hip, the same kernels on another operand type): what a Swin
+ * block holds between attn.qkv and attn.proj under autocast.  dtype: 1 = fp16, 2 = bf16 (the convention of orp_dcn_forward_multi_h).  The arithmetic is the fp32 calls': every
  * product, sum, expf and logf is fp32, in the order orp_window_attention / orp_window_attention_train / orp_window_attention_backward
  * fix; only the memory format differs.
  *   qkv, out, grad_out, grad_qkv   16-bit elements of `dtype`, the fp32 calls' shapes; widened as they are loaded, rounded ONCE, to

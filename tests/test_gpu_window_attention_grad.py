@@ -1,5 +1,5 @@
 """GPU: Swin's (shifted-)window attention in training -- `orp_window_attention_train` (the forward that keeps the rows' log-sum-exp) and
-`orp_window_attention_backward` (csrc/orp_window_attn_train.hip) -- and the route SwinBlock.forward takes through them.
+`orp_window_attention_backward` (csrc/orp_window_attn.hip) -- and the route SwinBlock.forward takes through them.
 
 One accuracy gate for every gradient tensor g: max |g - g64| <= 2e-5 * max(1, max |g64|), this project's Swin tolerance
 (tests/test_gpu_window_attention.py).  g64 comes from torch.autograd.grad through `window_attention_reference` in float64, which

@@ -1,5 +1,5 @@
 """GPU: Swin's (shifted-)window attention on fp16 / bf16 operands -- `orp_window_attention_h` and `orp_window_attention_backward_h`
-(csrc/orp_window_attn_half.hip) -- and the route SwinBlock.forward takes through them under autocast.
+(csrc/orp_window_attn.hip) -- and the route SwinBlock.forward takes through them under autocast.
 
 The accuracy argument has two parts.
   * Bit for bit: the 16-bit kernels are the fp32 kernels' arithmetic between a widening load and one rounded store.  So on fp32 copies

@@ -5,18 +5,13 @@ tokens, a padded token's q / k / v = the qkv bias, pad / roll / windows / relati
 arithmetic, proj after the crop.  Held here in float64 against the stock SwinBlock (pad, roll, to_windows, scaled_dot_product_attention
 with the materialised mask, from_windows, roll, crop): both are float64 evaluations of the same real function and only the order of
 the sums differs, so they agree to 1e-12 of the output's maximum."""
-import os
-import re
-import shutil
-import subprocess
-import tempfile
-
 import pytest
 import torch
 
 from orientedreppoints_amd import switches
 from orientedreppoints_amd.mmdet_models.swin import SwinStage, SwinTransformer
 from orientedreppoints_amd.mmdet_ops import window_attention_ok, window_attention_reference
+from window_attention_metadata import instantiations
 
 DIMS = [(24, 2), (96, 4), (96, 3)]                                  # (channels, heads): head dims 12, 24, 32
 MAPS = [(2, 14, 14), (1, 15, 20), (1, 5, 9), (1, 38, 51)]            # whole windows; padded on both axes; smaller than a window; many
@@ -112,25 +107,10 @@ def test_cpu_forward_is_bit_identical_with_the_switch_on_and_off(monkeypatch):
 
 
 def test_window_attention_kernels_spill_nothing_and_use_no_scratch():
-    """Code-object metadata of the built library: every head-dim instantiation of window_attn_kernel (4, 8, ..., 32) keeps its query,
-    its accumulators and a window row's key pieces in registers -- no spilled VGPR, no scratch memory -- at three waves per SIMD or
-    more (at most 168 registers)."""
-    from orientedreppoints_amd import build, _lib
-    objdump, readelf = "/opt/rocm/lib/llvm/bin/llvm-objdump", "/opt/rocm/lib/llvm/bin/llvm-readelf"
-    assert os.path.exists(objdump) and os.path.exists(readelf), "the llvm tools of the toolchain that builds the library"
-    build.build_hip()
-    seen = {}
-    with tempfile.TemporaryDirectory() as tmp:
-        so = os.path.join(tmp, "liborp_hip.so")
-        shutil.copy(_lib.LIB_PATH, so)
-        subprocess.run([objdump, "--offloading", so], cwd=tmp, stdout=subprocess.DEVNULL, stderr=subprocess.DEVNULL, check=True)
-        for b in [f for f in os.listdir(tmp) if f.endswith("gfx950")]:
-            notes = subprocess.run([readelf, "--notes", os.path.join(tmp, b)], stdout=subprocess.PIPE, universal_newlines=True, check=True).stdout
-            for blk in notes.split("- .agpr_count")[1:]:
-                name = re.search(r"\.name:\s+(\S+)", blk).group(1)
-                if "window_attn_kernel" in name:
-                    seen[name] = tuple(int(re.search(r"\.%s:\s+(\d+)" % k, blk).group(1))
-                                       for k in ("vgpr_spill_count", "private_segment_fixed_size", "vgpr_count"))
-    assert sorted(int(re.search(r"window_attn_kernelILi(\d+)E", n).group(1)) for n in seen) == list(range(4, 33, 4)), sorted(seen)
-    for name, (spill, scratch, vgprs) in seen.items():
-        assert spill == 0 and scratch == 0 and vgprs <= 168, (name, spill, scratch, vgprs)
+    """Code-object metadata of the built library: every head-dim instantiation of the forward kernel on fp32 operands (4, 8, ..., 32)
+    keeps its query, its accumulators and a window row's key pieces in registers -- no spilled VGPR, no scratch memory -- at three
+    waves per SIMD or more (at most 168 registers)."""
+    seen = {key: meta for key, meta in instantiations().items() if key[0] == "wattn_fwd_kernel" and key[2] == 0}
+    assert sorted(hd for _, hd, _ in seen) == list(range(4, 33, 4)), sorted(seen)
+    for key, (spill, scratch, vgprs, _) in seen.items():
+        assert spill == 0 and scratch == 0 and vgprs <= 168, (key, spill, scratch, vgprs)

@@ -5,17 +5,12 @@ differentiable plain torch.  Held here in float64 against the stock SwinBlock's 
 scaled_dot_product_attention with the materialised mask, from_windows, roll, crop): gradients with respect to the input tokens,
 qkv.weight, qkv.bias, proj.weight and the bias table.  Both are float64 evaluations of the same real function and only the order of
 the sums differs, so they agree to 1e-10 of each gradient's maximum."""
-import os
-import re
-import shutil
-import subprocess
-import tempfile
-
 import pytest
 import torch
 
 from orientedreppoints_amd.mmdet_ops import window_attention_ok, window_attention_train_ok
 from test_window_attention_cpu import DIMS, MAPS, make_stage, reexpressed
+from window_attention_metadata import instantiations
 
 
 def check_block_gradients(st, shape, shift, seed):
@@ -66,25 +61,9 @@ def test_training_routing_rule_on_the_cpu():
 
 
 def test_training_kernels_spill_nothing_and_use_no_scratch():
-    """Code-object metadata of the built library: the eight head-dim instantiations each of the training forward and of the backward
-    spill no VGPR and use no scratch memory, at or under the 168 registers their `amdgpu_waves_per_eu(3)` declares."""
-    from orientedreppoints_amd import build, _lib
-    objdump, readelf = "/opt/rocm/lib/llvm/bin/llvm-objdump", "/opt/rocm/lib/llvm/bin/llvm-readelf"
-    assert os.path.exists(objdump) and os.path.exists(readelf), "the llvm tools of the toolchain that builds the library"
-    build.build_hip()
-    seen = {}
-    with tempfile.TemporaryDirectory() as tmp:
-        so = os.path.join(tmp, "liborp_hip.so")
-        shutil.copy(_lib.LIB_PATH, so)
-        subprocess.run([objdump, "--offloading", so], cwd=tmp, stdout=subprocess.DEVNULL, stderr=subprocess.DEVNULL, check=True)
-        for b in [f for f in os.listdir(tmp) if f.endswith("gfx950")]:
-            notes = subprocess.run([readelf, "--notes", os.path.join(tmp, b)], stdout=subprocess.PIPE, universal_newlines=True, check=True).stdout
-            for blk in notes.split("- .agpr_count")[1:]:
-                name = re.search(r"\.name:\s+(\S+)", blk).group(1)
-                m = re.search(r"(wattn_train_fwd_kernel|wattn_bwd_kernel)ILi(\d+)E", name)
-                if m:
-                    seen[(m.group(1), int(m.group(2)))] = tuple(int(re.search(r"\.%s:\s+(\d+)" % k, blk).group(1))
-                                                                for k in ("vgpr_spill_count", "private_segment_fixed_size", "vgpr_count"))
-    assert sorted(seen) == [(k, hd) for k in ("wattn_bwd_kernel", "wattn_train_fwd_kernel") for hd in range(4, 33, 4)], sorted(seen)
-    for key, (spill, scratch, vgprs) in seen.items():
+    """Code-object metadata of the built library: the eight head-dim instantiations each of the forward and of the backward on fp32
+    operands spill no VGPR and use no scratch memory, at or under the 168 registers their `amdgpu_waves_per_eu(3)` declares."""
+    seen = {key[:2]: meta for key, meta in instantiations().items() if key[2] == 0}
+    assert sorted(seen) == [(k, hd) for k in ("wattn_bwd_kernel", "wattn_fwd_kernel") for hd in range(4, 33, 4)], sorted(seen)
+    for key, (spill, scratch, vgprs, _) in seen.items():
         assert spill == 0 and scratch == 0 and vgprs <= 168, (key, spill, scratch, vgprs)

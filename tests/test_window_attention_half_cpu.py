@@ -1,5 +1,5 @@
 """CPU: what the 16-bit Swin attention route (mmdet_ops/window_attention.py: window_attention_half / window_attention_train_half,
-csrc/orp_window_attn_half.hip) rests on: its routing rules, the rounding rule for padded tokens and the kernels' register budget.
+csrc/orp_window_attn.hip) rests on: its routing rules, the rounding rule for padded tokens and the kernels' register budget.
 
 The rounding rule.  Under autocast `attn.qkv` is a 16-bit linear layer on fp32 parameters: it emits 16-bit q / k / v, and for the zero
 row of a padded token exactly the bias ROUNDED to that type.  The kernels read the fp32 bias and round it themselves, so the float64
@@ -7,12 +7,6 @@ reference that the GPU tests hold them to must be fed the rounded bias: `window_
 bias.to(dt).double(), ...)`.  Held here against the stock SwinBlock in float64 whose qkv layer emits 16-bit values (float64 product,
 rounded to the type, widened): two float64 evaluations of the same real function, 1e-12 of the output's maximum as in
 tests/test_window_attention_cpu.py.  With the un-rounded bias in its place the two differ by orders of magnitude more."""
-import os
-import re
-import shutil
-import subprocess
-import tempfile
-
 import pytest
 import torch
 import torch.nn as nn
@@ -21,9 +15,9 @@ import torch.nn.functional as F
 from orientedreppoints_amd.mmdet_ops import (window_attention_half_ok, window_attention_ok, window_attention_reference,
                                              window_attention_train_half_ok, window_attention_train_ok)
 from test_window_attention_cpu import make_stage
+from window_attention_metadata import HEAD_DIMS, KERNELS, OPERANDS, VGPR_CAP, instantiations
 
 DTYPES = [torch.float16, torch.bfloat16]
-VGPR_CAP = 168                                    # every instantiation declares amdgpu_waves_per_eu(3), as the fp32 kernels
 
 
 def test_half_routing_rules_on_the_cpu():
@@ -87,35 +81,14 @@ def test_padded_tokens_carry_the_bias_rounded_to_the_operand_type(shape, shift, 
 
 
 def test_half_kernels_are_all_there_spill_nothing_and_use_no_scratch():
-    """Code-object metadata of the built library: the forward and the backward on 16-bit operands, eight head dims times two operand
-    types each and nothing else under these names, spill no VGPR and use no scratch memory at or under the 168 registers their
-    `amdgpu_waves_per_eu(3)` declares; the LDS of every instantiation is the fp32 kernels' (K / V staged as fp32)."""
-    from orientedreppoints_amd import build, _lib
-    objdump, readelf = "/opt/rocm/lib/llvm/bin/llvm-objdump", "/opt/rocm/lib/llvm/bin/llvm-readelf"
-    assert os.path.exists(objdump) and os.path.exists(readelf), "the llvm tools of the toolchain that builds the library"
-    build.build_hip()
-    seen, lds32 = {}, {}
-    with tempfile.TemporaryDirectory() as tmp:
-        so = os.path.join(tmp, "liborp_hip.so")
-        shutil.copy(_lib.LIB_PATH, so)
-        subprocess.run([objdump, "--offloading", so], cwd=tmp, stdout=subprocess.DEVNULL, stderr=subprocess.DEVNULL, check=True)
-        for b in [f for f in os.listdir(tmp) if f.endswith("gfx950")]:
-            notes = subprocess.run([readelf, "--notes", os.path.join(tmp, b)], stdout=subprocess.PIPE, universal_newlines=True, check=True).stdout
-            for blk in notes.split("- .agpr_count")[1:]:
-                name = re.search(r"\.name:\s+(\S+)", blk).group(1)
-                field = lambda k: int(re.search(r"\.%s:\s+(\d+)" % k, blk).group(1))                       # noqa: E731
-                m = re.search(r"(wattn_h_fwd_kernel|wattn_h_bwd_kernel)ILi(\d+)ELi(\d+)E", name)
-                if m:
-                    key = (m.group(1), int(m.group(2)), int(m.group(3)))
-                    assert key not in seen, name
-                    seen[key] = tuple(field(k) for k in ("vgpr_spill_count", "private_segment_fixed_size", "vgpr_count", "group_segment_fixed_size"))
-                else:
-                    assert "wattn_h_fwd" not in name and "wattn_h_bwd" not in name, name
-                m = re.search(r"(wattn_train_fwd_kernel|wattn_bwd_kernel)ILi(\d+)E", name)
-                if m:
-                    lds32[(m.group(1), int(m.group(2)))] = field("group_segment_fixed_size")
-    assert sorted(seen) == [(k, hd, dt) for k in ("wattn_h_bwd_kernel", "wattn_h_fwd_kernel") for hd in range(4, 33, 4) for dt in (1, 2)], sorted(seen)
-    twin = {"wattn_h_fwd_kernel": "wattn_train_fwd_kernel", "wattn_h_bwd_kernel": "wattn_bwd_kernel"}
+    """Code-object metadata of the built library: the forward and the backward kernel, eight head dims times three operand types each
+    (fp32, fp16, bf16) and nothing else under these names; the sixteen instantiations each on fp16 and on bf16 operands spill no VGPR and
+    use no scratch memory at or under the 168 registers their `amdgpu_waves_per_eu(3)` declares; the LDS of every one of them is the
+    fp32 instantiation's (K / V staged as fp32)."""
+    seen = instantiations()
+    assert sorted(seen) == [(k, hd, dt) for k in KERNELS for hd in HEAD_DIMS for dt in OPERANDS], sorted(seen)
     for (kernel, hd, dt), (spill, scratch, vgprs, lds) in seen.items():
+        if dt == 0:
+            continue                                   # the fp32 budget: tests/test_window_attention_cpu.py, test_window_attention_grad_cpu.py
         assert spill == 0 and scratch == 0 and vgprs <= VGPR_CAP, (kernel, hd, dt, spill, scratch, vgprs)
-        assert lds == lds32[(twin[kernel], hd)], (kernel, hd, dt, lds)
+        assert lds == seen[(kernel, hd, 0)][3], (kernel, hd, dt, lds)
