@@ -701,6 +701,21 @@ int orp_conv3x3_bn_pack_weight(const float* weight, int c_in, int c_out, void* p
 int orp_conv3x3_bn_act(const float* x, const void* weight_packed, const float* scale, const float* shift, const uint32_t* range_in,
                        float* y, int batch, int c_in, int c_out, int height, int width, int relu, void* stream);
 
+/* orp_conv3x3_bn_deep: the same operator for the 512 -> 512 channel conv2 of stage 4, stride 1 or 2 (padding 1; height / width are the
+ *   INPUT's, the output is ((height - 1) / stride + 1) x ((width - 1) / stride + 1)), in the same arithmetic and with the same packed
+ *   format and range word: a second route beside orp_conv3x3_bn_act, whose answers do not change.  A workgroup covers a 2 x 16 output
+ *   tile and 64 (stride 1) or 128 (stride 2) output channels and splits K between four or two groups of its waves, reduced in LDS in
+ *   a fixed order: deterministic, no atomics (csrc/orp_conv3x3_bn_deep.hip).
+ *   orp_conv3x3_bn_deep_ok: Cin == Cout == 512 and stride in {1, 2}; anything else is ORP_EINVAL.
+ *   orp_conv3x3_bn_deep_pays: 1 where the launch was MEASURED faster than library convolution + pass on MI355X (closed table,
+ *   docs/notebook/round23.md), else 0. */
+int orp_conv3x3_bn_deep_ok(int c_in, int c_out, int stride);
+int orp_conv3x3_bn_deep_pays(int c_in, int c_out, int height, int width, int stride, int batch);
+size_t orp_conv3x3_bn_deep_packed_bytes(int c_in, int c_out);
+int orp_conv3x3_bn_deep_pack_weight(const float* weight, int c_in, int c_out, void* packed, void* stream);
+int orp_conv3x3_bn_deep(const float* x, const void* weight_packed, const float* scale, const float* shift, const uint32_t* range_in,
+                        float* y, int batch, int c_in, int c_out, int height, int width, int stride, int relu, void* stream);
+
 
 /* orp_conv3x3_small_multi: 3x3 / stride 1 / pad 1 convolution (no bias) of the SMALL FPN levels -- the 32^2 / 16^2 / 8^2
  *   maps the head's seven 256->256 convolutions (orientedreppoints_head.py:91-132) also visit -- all levels in ONE
