@@ -716,6 +716,22 @@ int orp_conv3x3_bn_deep_pack_weight(const float* weight, int c_in, int c_out, vo
 int orp_conv3x3_bn_deep(const float* x, const void* weight_packed, const float* scale, const float* shift, const uint32_t* range_in,
                         float* y, int batch, int c_in, int c_out, int height, int width, int stride, int relu, void* stream);
 
+/* orp_conv3x3_bn_s2: the same operator for the STRIDE-2 conv2 of the first bottleneck of stages 2 and 3 (128 -> 128 and 256 -> 256
+ *   channels, padding 1; height / width are the INPUT's, the output is ((height - 1) / 2 + 1) x ((width - 1) / 2 + 1)), in the same
+ *   arithmetic and with the same packed format and range word: a third route beside orp_conv3x3_bn_act and orp_conv3x3_bn_deep, whose
+ *   answers do not change.  A workgroup covers a 2 x 16 output tile and 128 output channels, stages the 5 x 33 halo 64 channels at a
+ *   time (two workgroups per CU) and splits K between two groups of its waves, reduced in LDS in a fixed order: deterministic, no
+ *   atomics (csrc/orp_conv3x3_bn_s2.hip).
+ *   orp_conv3x3_bn_s2_ok: Cin == Cout in {128, 256}; anything else is ORP_EINVAL.
+ *   orp_conv3x3_bn_s2_pays: 1 where the launch was MEASURED faster than library convolution + pass on MI355X (closed table,
+ *   docs/notebook/round24.md), else 0. */
+int orp_conv3x3_bn_s2_ok(int c_in, int c_out);
+int orp_conv3x3_bn_s2_pays(int c_in, int c_out, int height, int width, int batch);
+size_t orp_conv3x3_bn_s2_packed_bytes(int c_in, int c_out);
+int orp_conv3x3_bn_s2_pack_weight(const float* weight, int c_in, int c_out, void* packed, void* stream);
+int orp_conv3x3_bn_s2(const float* x, const void* weight_packed, const float* scale, const float* shift, const uint32_t* range_in,
+                      float* y, int batch, int c_in, int c_out, int height, int width, int relu, void* stream);
+
 
 /* orp_conv3x3_small_multi: 3x3 / stride 1 / pad 1 convolution (no bias) of the SMALL FPN levels -- the 32^2 / 16^2 / 8^2
  *   maps the head's seven 256->256 convolutions (orientedreppoints_head.py:91-132) also visit -- all levels in ONE

@@ -96,9 +96,18 @@ class Bottleneck(nn.Module):
         return switches.of(self, 'fuse_conv3x3_deep', 'BN_CONV3X3_DEEP_FUSE') and not self.conv2_is_dcn and \
             isinstance(self.bn2, nn.BatchNorm2d) and not self.bn2.training
 
+    def _conv3x3_s2_fusable(self):
+        """where neither `conv3x3_bn_act` nor `conv3x3_bn_deep` takes conv2, the narrow-pass fp16-pieces kernel may (128 and 256
+        channels, stride 2) where that was measured faster (`fuse_conv3x3_s2` attribute, or ORP_BN_CONV3X3_S2_FUSE=0 for A/B timing:
+        off gives the launches and bits of before); the shapes are decided by `conv3x3_bn_s2` (`orp_conv3x3_bn_s2_ok` / `_pays`);
+        `force_conv3x3_s2` (attribute, tests) routes every supported shape.  The other routes' attributes do not touch this one."""
+        return switches.of(self, 'fuse_conv3x3_s2', 'BN_CONV3X3_S2_FUSE') and not self.conv2_is_dcn and \
+            isinstance(self.bn2, nn.BatchNorm2d) and not self.bn2.training
+
     def _forward_fused(self, x):
         from ..mmdet_ops.fused_norm import bn_act, conv1x1_bn_act, conv3x3_bn_act, conv3x3_bn_act_routed, \
-            conv3x3_bn_deep, conv3x3_bn_deep_routed, conv1x1_bn_act_dual, conv1x1_bn_act_dual_routed
+            conv3x3_bn_deep, conv3x3_bn_deep_routed, conv3x3_bn_s2, conv3x3_bn_s2_routed, conv1x1_bn_act_dual, \
+            conv1x1_bn_act_dual_routed
         fuse = self._conv1x1_fusable()
         pieces = None if self._conv1x1_pieces_on() else False       # (None: conv1x1_bn_act asks its table)
 
@@ -120,12 +129,21 @@ class Bottleneck(nn.Module):
             # the second route (stage 4's 512 channels, stride 1 and 2), asked only where the first said no, in front of conv1 as well
             deep3 = conv3x3_bn_deep_routed(x, self.conv2, self.bn2, force3d,
                                            shape=(x.size(0), self.conv1.out_channels, x.size(2), x.size(3)))
+        force3s = bool(getattr(self, 'force_conv3x3_s2', False))
+        s23 = False
+        if not fuse3 and not deep3 and self._conv3x3_s2_fusable() and tuple(self.conv1.stride) == (1, 1):
+            # the third route (the stride-2 conv2 of stages 2 and 3), asked only where the first two said no, in front of conv1 as well
+            s23 = conv3x3_bn_s2_routed(x, self.conv2, self.bn2, force3s,
+                                       shape=(x.size(0), self.conv1.out_channels, x.size(2), x.size(3)))
         if fuse3:
             out, bits = conv_bn_act(x, self.conv1, self.bn1, relu=True, want_range=True)
             out = conv3x3_bn_act(out, self.conv2, self.bn2, relu=True, force=force3, range_bits=bits)
         elif deep3:
             out, bits = conv_bn_act(x, self.conv1, self.bn1, relu=True, want_range=True)
             out = conv3x3_bn_deep(out, self.conv2, self.bn2, relu=True, force=force3d, range_bits=bits)
+        elif s23:
+            out, bits = conv_bn_act(x, self.conv1, self.bn1, relu=True, want_range=True)
+            out = conv3x3_bn_s2(out, self.conv2, self.bn2, relu=True, force=force3s, range_bits=bits)
         else:
             out = conv_bn_act(x, self.conv1, self.bn1, relu=True)
             out = bn_act(self.conv2(out).contiguous(), self.bn2, relu=True)

@@ -482,6 +482,53 @@ def conv3x3_bn_deep(x, conv, bn, relu=True, force=False, range_bits=None):
     return y
 
 
+def conv3x3_bn_s2_ok(x, conv, bn, shape=None):
+    """conv is a bias-free 3x3 / stride 2 / padding 1 / dilation 1 / groups 1 nn.Conv2d of a shape `orp_conv3x3_bn_s2` takes
+    (Cin == Cout in {128, 256}), bn an eval-mode BatchNorm2d, x an fp32 CUDA [B,Cin,H,W] tensor (shape: as `conv3x3_bn_act_ok`)"""
+    w = getattr(conv, 'weight', None)
+    shape = tuple(x.shape) if shape is None else tuple(shape)
+    return bool(type(conv) is torch.nn.Conv2d and _bn_input(x, bn) and len(shape) == 4 and
+                _plain_conv(conv, w, 3, ((2, 2),), 1) and shape[1] == w.size(1) and shape[0] * shape[2] * shape[3] > 0 and
+                _lib.lib().orp_conv3x3_bn_s2_ok(w.size(1), w.size(0)))
+
+
+def conv3x3_bn_s2_routed(x, conv, bn, force=False, shape=None):
+    """`conv3x3_bn_s2` would run its launch for this input, given its range: supported (`conv3x3_bn_s2_ok`) and either forced or
+    measured faster (`orp_conv3x3_bn_s2_pays`).  Asked BEFORE the input is produced, as `conv3x3_bn_act_routed`."""
+    if not conv3x3_bn_s2_ok(x, conv, bn, shape):
+        return False
+    B, _c, H, W = tuple(x.shape) if shape is None else tuple(shape)
+    return bool(force or _lib.lib().orp_conv3x3_bn_s2_pays(conv.weight.size(1), conv.weight.size(0), H, W, B))
+
+
+_packed_3x3_s2 = _packcache.new_cache("conv3x3_bn_s2_weight")
+
+
+def _packed_3x3_s2_planes(weight):
+    """[C,C,3,3] -> the two fp16 planes + scale `orp_conv3x3_bn_s2` reads (`orp_conv3x3_bn_s2_pack_weight`), cached as
+    `_packed_planes` says."""
+    return _packed_planes(_packed_3x3_s2, weight, "orp_conv3x3_bn_s2_packed_bytes", "orp_conv3x3_bn_s2_pack_weight",
+                          lambda w: w.float().contiguous())
+
+
+def conv3x3_bn_s2(x, conv, bn, relu=True, force=False, range_bits=None):
+    """relu?(BatchNorm_eval(conv(x))) for the stride-2 conv2 of the first bottleneck of stages 2 and 3 (128 and 256 channels) as a new
+    contiguous tensor: the third route beside `conv3x3_bn_act` and `conv3x3_bn_deep`, with the same contract.  Where
+    `conv3x3_bn_s2_routed` says so and the input's range is known (range_bits) this is ONE launch of `orp_conv3x3_bn_s2`; everywhere
+    else `bn_act(conv(x).contiguous(), bn)`."""
+    if range_bits is None or not conv3x3_bn_s2_routed(x, conv, bn, force):
+        return bn_act(conv(x).contiguous(), bn, relu=relu)
+    x = x.detach().contiguous()
+    B, cin, H, W = x.shape
+    cout = conv.weight.size(0)
+    packed = _packed_3x3_s2_planes(conv.weight)
+    scale, shift = _bn_affine(bn)
+    y = torch.empty((B, cout, (H - 1) // 2 + 1, (W - 1) // 2 + 1), dtype=torch.float32, device=x.device)
+    _call("orp_conv3x3_bn_s2", x.device, _lib.ptr(x), _lib.ptr(packed), _lib.ptr(scale), _lib.ptr(shift), _lib.ptr(range_bits),
+          _lib.ptr(y), B, cin, cout, H, W, 1 if relu else 0, _lib.stream_of(x))
+    return y
+
+
 def bn_relu_maxpool(x, bn):
     """max_pool2d(relu(BatchNorm_eval(x)), kernel 3, stride 2, padding 1) as ONE kernel (`orp_affine_relu_maxpool`, the ResNet
     stem): x [B,C,H,W] fp32 CUDA, contiguous, left as it is; returns a new [B,C,(H-1)//2+1,(W-1)//2+1] tensor."""
