@@ -732,6 +732,25 @@ int orp_conv3x3_bn_s2_pack_weight(const float* weight, int c_in, int c_out, void
 int orp_conv3x3_bn_s2(const float* x, const void* weight_packed, const float* scale, const float* shift, const uint32_t* range_in,
                       float* y, int batch, int c_in, int c_out, int height, int width, int relu, void* stream);
 
+/* orp_stem_conv_bn_relu_pool: the ResNet stem as ONE launch, inference only (csrc/orp_stem.hip):
+ *     y = maxpool3x3/s2/p1(relu(conv7x7/s2/p3(x, w) * scale[c] + shift[c]))
+ *   x [batch,3,height,width] fp32 NCHW, y [batch,64,(Ho-1)/2+1,(Wo-1)/2+1] fp32 NCHW with Ho = (height-1)/2+1, Wo = (width-1)/2+1.
+ *   Exact fp32 MFMA, one accumulator per output, K in the weight tensor's own (channel, ky, kx) order: deterministic, independent of
+ *   the tile an output falls in and of the batch size.  BatchNorm, ReLU and the pooling windows (clipped to the conv map) are those of
+ *   orp_affine_relu_maxpool, bit for bit on the same raw values.  pool = 0 ("raw mode"): y [batch,64,Ho,Wo] is the convolution itself,
+ *   scale / shift unused (may be NULL).
+ *   orp_stem_ok: 3 -> 64 channels, kernel 7, stride 2, padding 3; the launch refuses anything else, null pointers and non-positive
+ *   sizes with ORP_EINVAL.
+ *   orp_stem_pays: 1 where the launch was MEASURED faster than library convolution + orp_affine_relu_maxpool on MI355X (closed table of
+ *   image sides and batch sizes, docs/notebook/round25.md), else 0.
+ *   weight_packed: orp_stem_packed_bytes(3, 64) bytes filled by orp_stem_pack_weight from the [64,3,7,7] fp32 weight. */
+int orp_stem_ok(int c_in, int c_out, int kernel, int stride, int padding);
+int orp_stem_pays(int height, int width, int batch);
+size_t orp_stem_packed_bytes(int c_in, int c_out);
+int orp_stem_pack_weight(const float* weight, int c_in, int c_out, void* packed, void* stream);
+int orp_stem_conv_bn_relu_pool(const float* x, const void* weight_packed, const float* scale, const float* shift, float* y, int batch,
+                               int c_in, int c_out, int height, int width, int kernel, int stride, int padding, int pool, void* stream);
+
 
 /* orp_conv3x3_small_multi: 3x3 / stride 1 / pad 1 convolution (no bias) of the SMALL FPN levels -- the 32^2 / 16^2 / 8^2
  *   maps the head's seven 256->256 convolutions (orientedreppoints_head.py:91-132) also visit -- all levels in ONE

@@ -135,6 +135,11 @@ _SIGNATURES = {
     "orp_conv3x3_bn_s2_packed_bytes": (_sz, [_i, _i]),
     "orp_conv3x3_bn_s2_pack_weight": (_i, [_vp, _i, _i, _vp, _vp]),
     "orp_conv3x3_bn_s2": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _vp]),
+    "orp_stem_ok": (_i, [_i, _i, _i, _i, _i]),
+    "orp_stem_pays": (_i, [_i, _i, _i]),
+    "orp_stem_packed_bytes": (_sz, [_i, _i]),
+    "orp_stem_pack_weight": (_i, [_vp, _i, _i, _vp, _vp]),
+    "orp_stem_conv_bn_relu_pool": (_i, [_vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _i, _i, _i, _vp]),
     "orp_pp_select_scratch_bytes": (_sz, [_i, _i, _i]),
     "orp_pp_select": (_i, [_vp, _i, _i, _vp, _i, _i, _vp, _vp, _sz, _vp]),
     "orp_pp_gather": (_i, [_vp, _vp, _i, _i, _vp, _vp, _vp, _i, _vp, _vp, _vp, _vp, _vp]),

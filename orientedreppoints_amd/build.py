@@ -49,6 +49,7 @@ SOURCES = [
     ("orp_conv3x3_bn.hip", []),
     ("orp_conv3x3_bn_deep.hip", []),
     ("orp_conv3x3_bn_s2.hip", []),
+    ("orp_stem.hip", []),
     ("orp_dcn.hip", []),
     ("orp_dcn_split.hip", ["-ffp-contract=off"]),    # the bilinear combine is the reference's unfused float expression
     ("orp_conv_split.hip", []),

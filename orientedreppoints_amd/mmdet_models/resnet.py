@@ -289,8 +289,13 @@ class ResNet(nn.Module):
     def forward(self, x):
         if (not torch.is_grad_enabled()) and x.is_cuda and x.dtype == torch.float32 and \
                 isinstance(self.bn1, nn.BatchNorm2d) and not self.bn1.training:
-            from ..mmdet_ops.fused_norm import bn_act, bn_relu_maxpool
-            if self._stem_pool_fusable():
+            from ..mmdet_ops.fused_norm import bn_act, bn_relu_maxpool, stem_conv_bn_relu_maxpool, stem_conv_routed
+            # the whole stem as one launch (`fuse_stem_conv` attribute, or ORP_STEM_CONV_FUSE=0 for A/B timing) at the shapes where it was
+            # measured faster; `force_stem_conv` (attribute, tests) routes every supported shape
+            if switches.of(self, 'fuse_stem_conv', 'STEM_CONV_FUSE') and \
+                    stem_conv_routed(x, self.conv1, self.bn1, self.maxpool, bool(getattr(self, 'force_stem_conv', False))):
+                x = stem_conv_bn_relu_maxpool(x, self.conv1, self.bn1)
+            elif self._stem_pool_fusable():
                 x = bn_relu_maxpool(self.conv1(x).contiguous(), self.bn1)      # BatchNorm + ReLU applied while pooling
             else:
                 x = self.maxpool(bn_act(self.conv1(x).contiguous(), self.bn1, relu=True))

@@ -541,6 +541,74 @@ def bn_relu_maxpool(x, bn):
     return y
 
 
+def _pair(v):
+    return tuple(v) if isinstance(v, (tuple, list)) else (v, v)
+
+
+def stem_conv_ok(x, conv, bn=None, maxpool=None):
+    """conv is the bias-free 7x7 / stride 2 / padding 3 fp32 nn.Conv2d 3 -> 64 that `orp_stem_conv_bn_relu_pool` takes and x an fp32 CUDA
+    [B,3,H,W] tensor; bn (where given) an eval-mode BatchNorm2d; maxpool (where given) exactly MaxPool2d(3, 2, 1): dilation 1, floor mode,
+    no indices"""
+    w = getattr(conv, 'weight', None)
+    if not (type(conv) is torch.nn.Conv2d and x.is_cuda and x.dtype == torch.float32 and x.dim() == 4 and x.numel() > 0 and
+            _plain_conv(conv, w, 7, ((2, 2),), 3) and x.size(1) == w.size(1) and
+            _lib.lib().orp_stem_ok(w.size(1), w.size(0), 7, 2, 3)):
+        return False
+    if bn is not None and not _bn_input(x, bn):
+        return False
+    mp = maxpool
+    return bool(mp is None or (type(mp) is torch.nn.MaxPool2d and _pair(mp.kernel_size) == (3, 3) and _pair(mp.stride) == (2, 2) and
+                               _pair(mp.padding) == (1, 1) and _pair(mp.dilation) == (1, 1) and not mp.ceil_mode and
+                               not mp.return_indices))
+
+
+def stem_conv_routed(x, conv, bn, maxpool, force=False):
+    """`stem_conv_bn_relu_maxpool` is what runs for this stem and input: supported (`stem_conv_ok`), no gradient wanted, and either
+    forced or measured faster than library convolution + `bn_relu_maxpool` (`orp_stem_pays`)"""
+    if torch.is_grad_enabled() or not stem_conv_ok(x, conv, bn, maxpool):
+        return False
+    return bool(force or _lib.lib().orp_stem_pays(x.size(2), x.size(3), x.size(0)))
+
+
+_packed_stem = _packcache.new_cache("stem_weight")
+
+
+def _packed_stem_weight(weight):
+    """[64,3,7,7] -> the per-lane MFMA operand order `orp_stem_conv_bn_relu_pool` reads (`orp_stem_pack_weight`), cached as
+    `_packed_planes` says."""
+    return _packed_planes(_packed_stem, weight, "orp_stem_packed_bytes", "orp_stem_pack_weight", lambda w: w.float().contiguous())
+
+
+def _stem_launch(x, conv, bn, pool):
+    if not stem_conv_ok(x, conv, bn):
+        raise ValueError("the stem kernel takes a bias-free 7x7 / 2 / 3 fp32 convolution 3 -> 64 (and an eval-mode BatchNorm2d) on an "
+                         "fp32 CUDA [B,3,H,W] tensor")
+    x = x.detach().contiguous()
+    B, cin, H, W = x.shape
+    cout = conv.weight.size(0)
+    packed = _packed_stem_weight(conv.weight)
+    scale, shift = _bn_affine(bn) if pool else (None, None)
+    ho, wo = (H - 1) // 2 + 1, (W - 1) // 2 + 1
+    if pool:
+        ho, wo = (ho - 1) // 2 + 1, (wo - 1) // 2 + 1
+    y = torch.empty((B, cout, ho, wo), dtype=torch.float32, device=x.device)
+    _call("orp_stem_conv_bn_relu_pool", x.device, _lib.ptr(x), _lib.ptr(packed), _lib.ptr(scale), _lib.ptr(shift), _lib.ptr(y), B, cin,
+          cout, H, W, 7, 2, 3, 1 if pool else 0, _lib.stream_of(x))
+    return y
+
+
+def stem_conv_bn_relu_maxpool(x, conv, bn):
+    """max_pool2d(relu(BatchNorm_eval(conv(x))), 3, 2, 1) of the ResNet stem as ONE launch of `orp_stem_conv_bn_relu_pool` (exact fp32
+    MFMA; the raw conv map stays on the CU): x [B,3,H,W] fp32 CUDA; returns a new [B,64,Hp,Wp] tensor.  The caller has asked
+    `stem_conv_routed`; an unsupported stem is an error here."""
+    return _stem_launch(x, conv, bn, True)
+
+
+def stem_conv_raw(x, conv):
+    """conv(x) by the same launch in raw mode (no BatchNorm / ReLU / pooling): what the tests compare contraction and epilogue through"""
+    return _stem_launch(x, conv, None, False)
+
+
 def fpn_topdown_ok(xs, gns):
     """the laterals (raw convolution outputs, finest first) and their GroupNorms are what `fpn_topdown_cl` takes: at most four
     fp32 CUDA [B,C,H,W] tensors, each exactly twice the next in H and W, channel tiles of 32 that hold whole groups"""

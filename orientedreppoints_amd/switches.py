@@ -25,6 +25,7 @@ BN_CONV3X3_FUSE = _on('ORP_BN_CONV3X3_FUSE')  # bottleneck conv2 (3x3, stride 1)
 BN_CONV3X3_DEEP_FUSE = _on('ORP_BN_CONV3X3_DEEP_FUSE')  # stage 4 conv2 (512 channels, stride 1 and 2) on the K-split fp16-pieces kernel with BatchNorm + ReLU in the epilogue where measured faster; asked only where the kernel above said no (block.fuse_conv3x3_deep overrides)
 BN_CONV3X3_S2_FUSE = _on('ORP_BN_CONV3X3_S2_FUSE')  # the stride-2 conv2 of stages 2 and 3 (128 and 256 channels) on the narrow-pass fp16-pieces kernel with BatchNorm + ReLU in the epilogue where measured faster; asked only where the two kernels above said no (block.fuse_conv3x3_s2 overrides)
 STEM_POOL_FUSE = _on('ORP_STEM_POOL_FUSE')    # stem BatchNorm + ReLU + max-pool as one kernel (backbone.fuse_stem_pool overrides)
+STEM_CONV_FUSE = _on('ORP_STEM_CONV_FUSE')    # the whole stem (7x7 convolution + BatchNorm + ReLU + max-pool) as one exact-fp32 MFMA launch where measured faster than library convolution + the kernel above; asked first, does not consult that switch (backbone.fuse_stem_conv overrides)
 SWIN_ATTN_FUSE = _on('ORP_SWIN_ATTN_FUSE')    # Swin inference: pad / roll / windows / bias / mask / softmax / P V / un-roll / crop as one fp32 kernel (block.fuse_window_attention overrides)
 SWIN_ATTN_TRAIN_FUSE = _on('ORP_SWIN_ATTN_TRAIN_FUSE')  # Swin training: the same between attn.qkv and attn.proj as one fp32 forward kernel that keeps the rows' log-sum-exp, and one backward call (block.fuse_window_attention_train overrides)
 SWIN_ATTN_HALF_FUSE = _on('ORP_SWIN_ATTN_HALF_FUSE')  # Swin under fp16 / bf16 autocast, inference and training: the same span on 16-bit operands with fp32 arithmetic, one forward kernel (+ one backward call) (block.fuse_window_attention_half overrides)
