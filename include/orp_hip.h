@@ -493,6 +493,57 @@ int orp_scene_collect(const float* packed, int num_tiles, int max_rows, const in
                       int capacity_rows, double* dets, int32_t* seg_offsets, int32_t* src, int32_t* flag, void* workspace,
                       size_t workspace_bytes, void* stream);
 
+/* Training data on the device: the image half of the train pipelines (RotateResize / PolyResize with keep_ratio ->
+ * RotateRandomFlip / PolyRandomFlip -> [PolyRandomRotate] -> Normalize and Pad in either order -> the collate's padding to the
+ * batch shape) for the B raw images of a batch, each with its own geometry.  The draws and the box half stay on the host.
+ *
+ * images: uint8 ON THE DEVICE, the B source images (HWC, 3 channels, rows contiguous) back to back; image b starts at byte
+ * src_offset.  desc: one orp_train_image_desc per image ON THE DEVICE; desc_host: the same table on the host (the argument checks and
+ * the launch shapes are taken from it; the kernels read desc).  inv_affine: [B, 6] float64 ON THE DEVICE, rows i00 i01 i02 i10 i11
+ * i12 of the inverse of the rotation's 2 x 3 matrix (read for rotating images only).  axis_i0 / axis_w1: int32 / float32 ON THE
+ * DEVICE, axis_len entries each, the concatenated axis tables of orp_scene_tiles_resized (same formula); image b's column table
+ * is the new_w entries from x_table, its row table the new_h entries from y_table.  out: [B, 3, out_h, out_w] float32, contiguous,
+ * 16-byte aligned, out_w % 4 == 0.
+ *
+ * Stage A (one launch): image b is resampled to new_w x new_h in orp_scene_tiles_resized's arithmetic to the bit (i1 = min(i0 + 1,
+ * in - 1), w0 = 1 - w1, top = w0x*a + w1x*b, bot = w0x*c + w1x*d, v = w0y*top + w1y*bot, every product and sum rounded to fp32,
+ * rint with ties to even, clamp to [0, 255]).  flip 1 (horizontal) gives output column x the table entry of column new_w - 1 - x,
+ * flip 2 (vertical) gives row y the entry of row new_h - 1 - y: every value is the unflipped image's.  An image with rotate == 0 is
+ * normalised (channels reversed when to_rgb, (float32(v) - mean[c]) / std[c] with IEEE division, mean / std per OUTPUT channel)
+ * and written to out[b]; one with rotate != 0 is written as uint8 HWC to scratch at scratch_offset, rows
+ * (3 * new_w + 3) & ~3 bytes apart.
+ * Stage B (a second launch, only if some image rotates): output pixel (x, y) of a rotating image, in float64 with every operation
+ * rounded on its own: sx = (i00*x + i01*y) + i02, sy = (i10*x + i11*y) + i12, x0 = floor(sx), fx = (float)(sx - x0), y0 and fy
+ * likewise; in fp32 with every product and sum rounded on its own: top = (1 - fx)*a + fx*b, bot = (1 - fx)*c + fx*d,
+ * v = (1 - fy)*top + fy*bot over the scratch bytes a (x0, y0), b (x0 + 1, y0), c (x0, y0 + 1), d (x0 + 1, y0 + 1), a tap outside
+ * the new_w x new_h image being 0 (cv2's constant border); rint, clamp, the normalisation.  The output size is new_w x new_h.
+ * Padding of out[b]: inside (pad_h, pad_w) but outside (new_h, new_w) 0 when pad_before_normalize == 0 and
+ * (0 - mean[c]) / std[c] otherwise; beyond (pad_h, pad_w) up to (out_h, out_w) 0.  Every element of out is written exactly once.
+ * No allocation, no synchronisation, no memset: the call can be captured.
+ *
+ * orp_train_images_scratch_bytes(new_w, new_h): bytes of one rotating image's scratch (a multiple of 256); the caller lays the
+ * images' scratch out back to back, non-overlapping, at offsets that are multiples of 4.  scratch may be NULL when no image rotates.
+ * ORP_EINVAL: a null pointer, out_w % 4 != 0, num_images > 65535, a non-positive size, flip outside 0..2, an image whose pad shape
+ * exceeds (out_h, out_w) or is smaller than its resized shape, an image or table that does not lie inside images_bytes / axis_len,
+ * a scratch image that does not lie inside scratch_bytes.  ORP_ETOOBIG: out_h > 524280. */
+typedef struct orp_train_image_desc {
+  int64_t src_offset;      /* byte offset of the source image in images */
+  int64_t scratch_offset;  /* byte offset of the resized image in scratch (rotating images) */
+  int32_t src_h, src_w;    /* source size */
+  int32_t new_h, new_w;    /* resized size (img_shape) */
+  int32_t pad_h, pad_w;    /* pad_shape */
+  int32_t flip;            /* 0 none, 1 horizontal, 2 vertical */
+  int32_t rotate;          /* 0 no, 1 yes */
+  int32_t x_table, y_table;/* first entries of the column and row axis tables in axis_i0 / axis_w1 */
+  int32_t reserved[2];     /* 0 */
+} orp_train_image_desc;    /* 64 bytes */
+size_t orp_train_images_scratch_bytes(int new_w, int new_h);
+int orp_train_images(const uint8_t* images, size_t images_bytes, const orp_train_image_desc* desc_host,
+                     const orp_train_image_desc* desc, int num_images, const double* inv_affine, const int32_t* axis_i0,
+                     const float* axis_w1, int axis_len, const float* mean_host, const float* std_host, int to_rgb,
+                     int pad_before_normalize, float* out, int out_h, int out_w, void* scratch, size_t scratch_bytes,
+                     void* stream);
+
 /* Detection -> ground-truth matching of the DOTA Task1 evaluation (DOTA_devkit/dota_evaluation_task1.py:160-206, the
  * per-detection python loop of voc_eval): for detection d of image det_image[d], over the ground truths
  * gts[gt_offsets[img] .. gt_offsets[img + 1]) that pass the fp64 horizontal-box pre-filter (`overlaps > 0`, "+ 1." pixel

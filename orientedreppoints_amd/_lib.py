@@ -98,7 +98,9 @@ _SIGNATURES = {
                                           _vp, _i, _i, _vp, _vp]),
     "orp_scene_collect_workspace_bytes": (_sz, [_i, _i]),
     "orp_scene_collect": (_i, [_vp, _i, _i, _vp, ctypes.c_double, _i, _i, _vp, _vp, _vp, _vp, _vp, _sz, _vp]),
-    "orp_soft_rnms_host": (_i, [_vp, _i, _f, _i, _f, _f, _vp, _vp]),
+    "orp_train_images_scratch_bytes": (_sz, [_i, _i]),
+    "orp_train_images": (_i, [_vp, _sz, _vp, _vp, _i, _vp, _vp, _vp, _i, _vp, _vp, _i, _i, _vp, _i, _i, _vp, _sz, _vp]),
+    "orp_soft_rnms_host":(_i, [_vp, _i, _f, _i, _f, _f, _vp, _vp]),
     "orp_conv1x1_packed_floats": (_sz, [_i]),
     "orp_conv1x1_ok": (_i, [_i, _i]),
     "orp_conv1x1_pack_weight": (_i, [_vp, _i, _i, _vp, _vp]),

@@ -39,6 +39,7 @@ SOURCES = [
     ("orp_postproc.hip", ["-ffp-contract=off"]),
     ("orp_soft_rnms.hip", ["-ffp-contract=off"]),
     ("orp_scene.hip", ["-ffp-contract=off"]),
+    ("orp_train_images.hip", ["-ffp-contract=off"]),
     ("orp_eval.hip", ["-ffp-contract=off"]),
     ("orp_train.hip", ["-ffp-contract=off"]),
     ("orp_norm.hip", []),

@@ -79,10 +79,15 @@ def imnormalize(img, mean, std, to_rgb=True):
     return (img - np.asarray(mean, np.float32)) / np.asarray(std, np.float32)
 
 
+def invert_affine(M):
+    """The 2 x 3 float64 inverse of a 2 x 3 affine matrix, as `warp_affine` uses it."""
+    return np.linalg.inv(np.vstack([np.asarray(M, np.float64), [0, 0, 1]]))[:2]
+
+
 def warp_affine(img, M, dsize, interpolation='bilinear'):
     """cv2.warpAffine(img, M, (w, h)): dst(x, y) = src(M^-1 [x, y, 1]); constant-0 border; pixel centres at integers."""
     w, h = int(dsize[0]), int(dsize[1])
-    Minv = np.linalg.inv(np.vstack([np.asarray(M, np.float64), [0, 0, 1]]))[:2]
+    Minv = invert_affine(M)
     ys, xs = np.meshgrid(np.arange(h, dtype=np.float64), np.arange(w, dtype=np.float64), indexing='ij')
     sx = Minv[0, 0] * xs + Minv[0, 1] * ys + Minv[0, 2]
     sy = Minv[1, 0] * xs + Minv[1, 1] * ys + Minv[1, 2]

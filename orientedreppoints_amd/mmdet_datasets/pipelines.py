@@ -189,19 +189,25 @@ class RotateResize(object):
             scale, scale_idx = self.random_select(self.img_scale)
         results['scale'], results['scale_idx'] = scale, scale_idx
 
-    def _resize_img(self, results):
+    def _resize_meta(self, results):
+        """The resize without the image: the new shape and the scale factor, from the shape of the image as loaded."""
+        h, w = results['img'].shape[:2]
         if self.keep_ratio:
-            img, scale_factor = imops.imrescale(results['img'], results['scale'], return_scale=True,
-                                                interpolation=self.interpolation)
+            new_w, new_h, scale_factor = imops.rescale_size((w, h), results['scale'])
         else:
-            img, w_scale, h_scale = imops.imresize(results['img'], results['scale'], return_scale=True,
-                                                   interpolation=self.interpolation)
+            new_w, new_h = results['scale']
+            w_scale, h_scale = new_w / w, new_h / h
             scale_factor = np.array([w_scale, h_scale, w_scale, h_scale], dtype=np.float32)
-        results['img'] = img
-        results['img_shape'] = img.shape
-        results['pad_shape'] = img.shape
+        shape = (int(new_h), int(new_w)) + tuple(results['img'].shape[2:])
+        results['img_shape'] = shape
+        results['pad_shape'] = shape
         results['scale_factor'] = scale_factor
         results['keep_ratio'] = self.keep_ratio
+
+    def _resize_img(self, results):
+        """The image step: resample to the `img_shape` `_resize_meta` wrote."""
+        new_h, new_w = results['img_shape'][:2]
+        results['img'] = imops.imresize(results['img'], (new_w, new_h), interpolation=self.interpolation)
 
     def _resize_bboxes(self, results, clamp_rbbox=True):
         img_shape = results['img_shape']
@@ -212,11 +218,22 @@ class RotateResize(object):
                 bboxes[:, 1::2] = np.clip(bboxes[:, 1::2], 0, img_shape[0] - 1)
             results[key] = bboxes
 
-    def _one(self, results):
+    def _draw_scale(self, results):
         if 'scale' not in results:
             self._random_scale(results)
-        self._resize_img(results)
+
+    def plan(self, results):
+        """The draw and box step: everything `_one` does except the image (`_resize_img`)."""
+        self._draw_scale(results)
+        self._resize_meta(results)
         self._resize_bboxes(results, self.clamp_rbbox)
+        return results
+
+    apply_image = _resize_img
+
+    def _one(self, results):
+        self.plan(results)
+        self.apply_image(results)
         return results
 
     def __call__(self, results):
@@ -229,7 +246,7 @@ class RotateResize(object):
 class PolyResize(RotateResize):
     """poly_transforms.py:86-247: RotateResize plus the test-time random edge re-draw when `scale` is preset (:207-216)."""
 
-    def _one(self, results):
+    def _draw_scale(self, results):
         if 'scale' not in results:
             self._random_scale(results)
         else:
@@ -237,13 +254,17 @@ class PolyResize(RotateResize):
             edge1 = np.random.randint(min(results['scale']), max(results['scale']) + 1)
             edge2 = np.random.randint(min(results['scale']), max(results['scale']) + 1)
             results['scale'] = (max(edge1, edge2) + 1, min(edge1, edge2))
-        self._resize_img(results)
+
+    def _one_preset(self, results):
+        RotateResize._draw_scale(self, results)
+        self._resize_meta(results)
         self._resize_bboxes(results, self.clamp_rbbox)
+        self.apply_image(results)
         return results
 
     def __call__(self, results):
         if isinstance(results, list):            # mosaic lists keep a preset scale (multi_img_call :221-228)
-            return [RotateResize._one(self, r) for r in results]
+            return [self._one_preset(r) for r in results]
         return self._one(results)
 
 
@@ -293,16 +314,29 @@ class RotateRandomFlip(object):
         if 'flip_direction' not in results:
             results['flip_direction'] = np.random.choice(self.direction, 1)
 
-    def _one(self, results):
+    @staticmethod
+    def direction_of(results):
+        d = results['flip_direction']
+        return d if isinstance(d, str) else str(np.asarray(d).reshape(-1)[0])
+
+    def plan(self, results):
+        """The draw and box step: everything `_one` does except the image (`apply_image`)."""
         if 'flip' not in results:
             results['flip'] = True if np.random.rand() < self.flip_ratio else False
         self._draw_direction(results)
         if results['flip']:
-            d = results['flip_direction']
-            d = d if isinstance(d, str) else str(np.asarray(d).reshape(-1)[0])
-            results['img'] = imops.imflip(results['img'], direction=d)
+            d = self.direction_of(results)
             for key in results.get('bbox_fields', []):
                 results[key] = rbbox_flip(results[key], results['img_shape'], d)
+        return results
+
+    def apply_image(self, results):
+        if results['flip']:
+            results['img'] = imops.imflip(results['img'], direction=self.direction_of(results))
+
+    def _one(self, results):
+        self.plan(results)
+        self.apply_image(results)
         return results
 
     def __call__(self, results):
@@ -358,7 +392,9 @@ class PolyRandomRotate(object):
         x_ctr, y_ctr, w_bbox, h_bbox = bboxes[:, 0], bboxes[:, 1], bboxes[:, 2], bboxes[:, 3]
         return (x_ctr > 0) & (x_ctr < w) & (y_ctr > 0) & (y_ctr < h) & (w_bbox > 5) & (h_bbox > 5)
 
-    def _one(self, results):
+    def plan(self, results):
+        """The draw and box step: the draws, the two matrices, `img_shape` and the surviving boxes; None when no box survives.
+        The image step (`apply_image`) warps with `rm_image` to the `img_shape` written here."""
         if not self.is_rotate:
             results['rotate'] = False
             angle = 0
@@ -375,7 +411,6 @@ class PolyRandomRotate(object):
             bound_w, bound_h = w, h
         self.rm_coords = self.create_rotation_matrix(image_center, angle, bound_h, bound_w)
         self.rm_image = self.create_rotation_matrix(image_center, angle, bound_h, bound_w, offset=-0.5)
-        results['img'] = imops.warp_affine(results['img'], self.rm_image, (bound_w, bound_h))
         results['img_shape'] = (bound_h, bound_w, c)
         gt_bboxes = results.get('gt_bboxes', np.zeros((0, 8), np.float32))
         labels = results.get('gt_labels', np.zeros((0,), np.int64))
@@ -387,6 +422,16 @@ class PolyRandomRotate(object):
             return None
         results['gt_bboxes'] = rbox2poly(rb).astype(np.float32)
         results['gt_labels'] = labels
+        return results
+
+    def apply_image(self, results):
+        bound_h, bound_w = results['img_shape'][:2]
+        results['img'] = imops.warp_affine(results['img'], self.rm_image, (bound_w, bound_h))
+
+    def _one(self, results):
+        if self.plan(results) is None:
+            return None
+        self.apply_image(results)
         return results
 
     def __call__(self, results):
@@ -409,16 +454,24 @@ class HSVAugment(object):
             np.random.uniform(-1, 1, 3)
         return results
 
+    plan = __call__                               # (there is no image step)
+
 
 @PIPELINES.register_module
 class Normalize(object):
     def __init__(self, mean, std, to_rgb=True):
         self.mean, self.std, self.to_rgb = np.array(mean, np.float32), np.array(std, np.float32), to_rgb
 
-    def __call__(self, results):
-        results['img'] = imops.imnormalize(results['img'], self.mean, self.std, self.to_rgb)
+    def plan(self, results):
         results['img_norm_cfg'] = dict(mean=self.mean, std=self.std, to_rgb=self.to_rgb)
         return results
+
+    def apply_image(self, results):
+        results['img'] = imops.imnormalize(results['img'], self.mean, self.std, self.to_rgb)
+
+    def __call__(self, results):
+        self.apply_image(results)
+        return self.plan(results)
 
 
 @PIPELINES.register_module
@@ -427,6 +480,17 @@ class Pad(object):
         self.size, self.size_divisor, self.pad_val = size, size_divisor, pad_val
         assert size is not None or size_divisor is not None
         assert size is None or size_divisor is None
+
+    def plan(self, results):
+        """The pad without the image: `pad_shape` from `img_shape`, which is the image's shape wherever `img_shape` is kept."""
+        h, w = results['img_shape'][:2]
+        if self.size is not None:
+            pad_h, pad_w = self.size
+        else:
+            pad_h, pad_w = int(np.ceil(h / self.size_divisor)) * self.size_divisor, int(np.ceil(w / self.size_divisor)) * self.size_divisor
+        results['pad_shape'] = (pad_h, pad_w) + tuple(results['img_shape'][2:])
+        results['pad_fixed_size'], results['pad_size_divisor'] = self.size, self.size_divisor
+        return results
 
     def __call__(self, results):
         img = imops.impad(results['img'], self.size, self.pad_val) if self.size is not None else \
