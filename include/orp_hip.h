@@ -635,6 +635,27 @@ int orp_affine2_act(const float* x, const float* residual, const float* scale, c
                     const float* shift2, float* y, int batch, int channels, int hw, int relu, void* stream);
 int orp_affine_relu_maxpool(const float* x, const float* scale, const float* shift, float* y, int batch, int channels,
                             int height, int width, void* stream);
+/* Training: the backward of orp_affine_act / orp_affine2_act for an eval-mode BatchNorm with trainable weight / bias,
+ *   y = relu?(x*a[c] + b[c] (+ r | + x2*a2[c] + b2[c])),  a = weight*rstd, b = bias - mean*a, rstd = rsqrt(running_var + eps).
+ *   g = grad_y where y > 0, else 0 (y: the forward's OUTPUT, its sign is the ReLU mask; y NULL = no ReLU, g = grad_y);
+ *   grad_x = g*a[c] (scale = a);  grad_x2 = g*a2[c] (scale2 = a2; NULL = not wanted);  grad_res = g (NULL = not wanted; may alias
+ *   grad_y);  dbias[c] = sum over images and positions of g;  dweight[c] = sum of g*((x - mean[c])*rstd[c]);  dweight2 / dbias2 the
+ *   same with x2, mean2, rstd2 (dbias2 = dbias).
+ *   dweight / dbias are NULL together (that BatchNorm's parameters want no gradient): x, mean, rstd are then not read and may be
+ *   NULL; likewise dweight2 / dbias2 and x2, mean2, rstd2.  grad_x (and grad_x2) must not alias grad_y.
+ *   Kernel launches on `stream` only (no allocation, no synchronisation, no memset, no atomics): one pass over the tensors, and
+ *   where a dweight is wanted a second small kernel that adds the workgroups' partial sums per channel in float64; every sum is
+ *   formed in one fixed order (the same data give the same bits).  workspace (16-byte aligned, orp_affine_act_backward_workspace_bytes
+ *   bytes) is read and written only where a dweight is wanted and may be NULL otherwise.
+ *   ORP_EINVAL without a launch: batch, channels or hw <= 0, a missing or too small workspace, dweight without dbias or x. */
+size_t orp_affine_act_backward_workspace_bytes(int batch, int channels, int hw);
+int orp_affine_act_backward(const float* grad_y, const float* y, const float* x, const float* scale, const float* mean,
+                            const float* rstd, float* grad_x, float* grad_res, float* dweight, float* dbias, int batch, int channels,
+                            int hw, void* workspace, size_t workspace_bytes, void* stream);
+int orp_affine2_act_backward(const float* grad_y, const float* y, const float* x, const float* scale, const float* mean,
+                             const float* rstd, const float* x2, const float* scale2, const float* mean2, const float* rstd2,
+                             float* grad_x, float* grad_x2, float* grad_res, float* dweight, float* dbias, float* dweight2,
+                             float* dbias2, int batch, int channels, int hw, void* workspace, size_t workspace_bytes, void* stream);
 size_t orp_fpn_topdown_workspace_bytes(const orp_norm_level* levels, int nlevels, int batch, int channels, int groups);
 int orp_fpn_topdown_nhwc(const orp_norm_level* levels, const float* const* gammas_host, const float* const* betas_host,
                          int nlevels, int batch, int channels, int groups, float eps, uint32_t* amax_out, void* workspace,

@@ -161,6 +161,9 @@ _SIGNATURES = {
     "orp_affine_act": (_i, [_vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _vp]),
     "orp_affine2_act": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _vp]),
     "orp_affine_relu_maxpool": (_i, [_vp, _vp, _vp, _vp, _i, _i, _i, _i, _vp]),
+    "orp_affine_act_backward_workspace_bytes": (_sz, [_i, _i, _i]),
+    "orp_affine_act_backward": (_i, [_vp] * 10 + [_i, _i, _i, _vp, _sz, _vp]),
+    "orp_affine2_act_backward": (_i, [_vp] * 17 + [_i, _i, _i, _vp, _sz, _vp]),
     "orp_fpn_topdown_workspace_bytes": (_sz, [_vp, _i, _i, _i, _i]),
     "orp_fpn_topdown_nhwc": (_i, [_vp, _vp, _vp, _i, _i, _i, _i, _f, _vp, _vp, _sz, _vp]),
     "orp_bias_act_multi": (_i, [_vp, _i, _i, _i, _vp, _vp, _i, _vp]),

@@ -16,6 +16,8 @@
 //   orp_affine_act          : y = relu?(x * scale[c] + shift[c] (+ residual)) -- eval-mode BatchNorm folded to a
 //               per-channel affine, fused with the bottleneck's residual add and ReLU; in place allowed.
 //   orp_affine2_act         : the same pass with a second affine on the residual (the downsample branch's BatchNorm);
+//   orp_affine_act_backward / orp_affine2_act_backward : training, the backward of the two passes above with the BatchNorm's
+//               dweight / dbias: one pass that leaves per-workgroup partial sums, one small kernel that adds them in float64;
 //   orp_affine_relu_maxpool : the stem's BatchNorm + ReLU applied inside its 3x3 / stride-2 max-pool, one read of the input;
 //   orp_fpn_topdown_nhwc    : the FPN laterals' GroupNorm + top-down sum + transposition as one pass behind the statistics.
 //   orp_bias_act_multi      : y = relu?(x + bias[c] (+ residual)), y2 = y - sub[c], all FPN levels in one launch -- the
@@ -472,6 +474,114 @@ affine2_act_kernel(const float* __restrict__ x, const float* __restrict__ res, c
     for (int i = blockIdx.x * blockDim.x + threadIdx.x; i < hw; i += gridDim.x * blockDim.x) {
       y[base + i] = affine_res_act(x[base + i], a, b, affine_act(res[base + i], a2, b2, 0), relu);
     }
+  }
+}
+
+// Training: the backward of affine_act_kernel / affine2_act_kernel, one read of grad_y, y and x (orp_affine_act_backward,
+// orp_affine2_act_backward).  g = grad_y where y > 0 (y: the forward's output is the ReLU mask; NULL = no ReLU), grad_x = g a[c],
+// grad_x2 = g a2[c], grad_res = g (may alias grad_y: a thread reads its elements before it writes them).  The launch has the forward's
+// shape -- grid.y = (image, channel) plane, grid.x = plane_blocks(hw) -- so the channel's constants are block-uniform.
+// STATS: a BatchNorm's parameters want their gradient.  Each workgroup leaves (sum g, sum g xhat, sum g xhat2) of its elements,
+// xhat = (x - mean[c]) rstd[c], in part[plane * gridDim.x + blockIdx.x]: the thread's elements in loop order, the wave by butterfly,
+// the four waves in order (block_sum).  x / x2 are NULL where that BatchNorm wants nothing, and are then not read.
+struct AffineBwd {
+  const float* gy; const float* y; const float* x; const float* x2;
+  const float* scale; const float* mean; const float* rstd;
+  const float* scale2; const float* mean2; const float* rstd2;
+  float* gx; float* gx2; float* gres;
+  float4* part;
+  int C, hw, vec;
+};
+
+template <bool STATS>
+__global__ void __launch_bounds__(kThreads)
+affine_act_bwd_kernel(const AffineBwd P) {
+  const int plane = blockIdx.y;                       // b * C + c
+  const int c = plane % P.C;
+  const float a = P.scale[c];
+  const float a2 = P.gx2 ? P.scale2[c] : 0.f;
+  float m = 0.f, r = 0.f, m2 = 0.f, r2 = 0.f;
+  if (STATS) {
+    if (P.x) { m = P.mean[c]; r = P.rstd[c]; }
+    if (P.x2) { m2 = P.mean2[c]; r2 = P.rstd2[c]; }
+  }
+  float sg = 0.f, sx = 0.f, sx2 = 0.f;
+  const size_t base = (size_t)plane * P.hw;
+  if (P.vec) {
+    const int hw4 = P.hw >> 2;
+    const float4* g4 = reinterpret_cast<const float4*>(P.gy + base);
+    const float4* y4 = P.y ? reinterpret_cast<const float4*>(P.y + base) : nullptr;
+    const float4* x4 = (STATS && P.x) ? reinterpret_cast<const float4*>(P.x + base) : nullptr;
+    const float4* x24 = (STATS && P.x2) ? reinterpret_cast<const float4*>(P.x2 + base) : nullptr;
+    float4* gx4 = reinterpret_cast<float4*>(P.gx + base);
+    float4* gx24 = P.gx2 ? reinterpret_cast<float4*>(P.gx2 + base) : nullptr;
+    float4* gr4 = P.gres ? reinterpret_cast<float4*>(P.gres + base) : nullptr;
+    for (int i = blockIdx.x * blockDim.x + threadIdx.x; i < hw4; i += gridDim.x * blockDim.x) {
+      float4 g = g4[i];
+      if (y4) {
+        const float4 t = y4[i];
+        g.x = t.x > 0.f ? g.x : 0.f; g.y = t.y > 0.f ? g.y : 0.f; g.z = t.z > 0.f ? g.z : 0.f; g.w = t.w > 0.f ? g.w : 0.f;
+      }
+      if (gr4) gr4[i] = g;
+      gx4[i] = make_float4(g.x * a, g.y * a, g.z * a, g.w * a);
+      if (gx24) gx24[i] = make_float4(g.x * a2, g.y * a2, g.z * a2, g.w * a2);
+      if (STATS) {
+        sg += g.x; sg += g.y; sg += g.z; sg += g.w;
+        if (x4) {
+          const float4 t = x4[i];
+          sx += g.x * ((t.x - m) * r); sx += g.y * ((t.y - m) * r); sx += g.z * ((t.z - m) * r); sx += g.w * ((t.w - m) * r);
+        }
+        if (x24) {
+          const float4 t = x24[i];
+          sx2 += g.x * ((t.x - m2) * r2); sx2 += g.y * ((t.y - m2) * r2); sx2 += g.z * ((t.z - m2) * r2); sx2 += g.w * ((t.w - m2) * r2);
+        }
+      }
+    }
+  } else {
+    for (int i = blockIdx.x * blockDim.x + threadIdx.x; i < P.hw; i += gridDim.x * blockDim.x) {
+      float g = P.gy[base + i];
+      if (P.y) g = P.y[base + i] > 0.f ? g : 0.f;
+      if (P.gres) P.gres[base + i] = g;
+      P.gx[base + i] = g * a;
+      if (P.gx2) P.gx2[base + i] = g * a2;
+      if (STATS) {
+        sg += g;
+        if (P.x) sx += g * ((P.x[base + i] - m) * r);
+        if (P.x2) sx2 += g * ((P.x2[base + i] - m2) * r2);
+      }
+    }
+  }
+  if (STATS) {
+    __shared__ float red[4];
+    sg = block_sum(sg, red);
+    sx = block_sum(sx, red);
+    sx2 = block_sum(sx2, red);
+    if (threadIdx.x == 0) P.part[(size_t)plane * gridDim.x + blockIdx.x] = make_float4(sg, sx, sx2, 0.f);
+  }
+}
+
+// one wave per channel adds the channel's B * bx partials in float64: lane l takes partials l, l + 64, ... in that order (image-major,
+// then block), then the butterfly over the lanes -- one fixed order, so the same data give the same bits.  dbias2 is dbias's sum.
+__global__ void __launch_bounds__(kThreads)
+affine_act_bwd_finish_kernel(const float4* __restrict__ part, int B, int C, int bx, float* __restrict__ dw, float* __restrict__ db,
+                             float* __restrict__ dw2, float* __restrict__ db2) {
+  const int lane = threadIdx.x & 63;
+  const int c = blockIdx.x * (kThreads / 64) + (threadIdx.x >> 6);
+  if (c >= C) return;                                 // (wave-uniform; no barrier below)
+  double sg = 0., sx = 0., sx2 = 0.;
+  const int n = B * bx;
+  for (int j = lane; j < n; j += 64) {
+    const int b = j / bx, k = j - b * bx;
+    const float4 p = part[((size_t)b * C + c) * bx + k];
+    sg += (double)p.x; sx += (double)p.y; sx2 += (double)p.z;
+  }
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) {
+    sg += __shfl_xor(sg, o, 64); sx += __shfl_xor(sx, o, 64); sx2 += __shfl_xor(sx2, o, 64);
+  }
+  if (lane == 0) {
+    if (dw) { dw[c] = (float)sx; db[c] = (float)sg; }
+    if (dw2) { dw2[c] = (float)sx2; db2[c] = (float)sg; }
   }
 }
 
@@ -1166,6 +1276,55 @@ int orp_affine2_act(const float* x, const float* residual, const float* scale, c
   hipLaunchKernelGGL(affine2_act_kernel, dim3(plane_blocks(hw), batch * channels), dim3(kThreads), 0, (hipStream_t)stream, x, residual,
                      scale, shift, scale2, shift2, y, channels, hw, relu);
   return launch_status();
+}
+
+size_t orp_affine_act_backward_workspace_bytes(int batch, int channels, int hw) {
+  if (batch <= 0 || channels <= 0 || hw <= 0) return sizeof(float4);
+  return sizeof(float4) * (size_t)batch * (size_t)channels * (size_t)plane_blocks(hw);
+}
+
+int orp_affine2_act_backward(const float* grad_y, const float* y, const float* x, const float* scale, const float* mean,
+                             const float* rstd, const float* x2, const float* scale2, const float* mean2, const float* rstd2,
+                             float* grad_x, float* grad_x2, float* grad_res, float* dweight, float* dbias, float* dweight2,
+                             float* dbias2, int batch, int channels, int hw, void* workspace, size_t workspace_bytes, void* stream) {
+  if (!grad_y || !scale || !grad_x || batch <= 0 || channels <= 0 || hw <= 0) return ORP_EINVAL;
+  if ((dweight == nullptr) != (dbias == nullptr) || (dweight2 == nullptr) != (dbias2 == nullptr)) return ORP_EINVAL;
+  if (dweight && (!x || !mean || !rstd)) return ORP_EINVAL;
+  if (dweight2 && (!x2 || !mean2 || !rstd2)) return ORP_EINVAL;
+  if (grad_x2 && !scale2) return ORP_EINVAL;
+  if (grad_x == grad_y || (grad_x2 && (grad_x2 == grad_y || grad_x2 == grad_x || grad_x2 == grad_res)) || grad_res == grad_x) return ORP_EINVAL;
+  if ((long)batch * channels > 65535L * 1024) return ORP_ETOOBIG;
+  const bool stats = dweight || dweight2;
+  if (stats && (!workspace || ((uintptr_t)workspace & 15) != 0 ||
+                workspace_bytes < orp_affine_act_backward_workspace_bytes(batch, channels, hw)))
+    return ORP_EINVAL;
+  AffineBwd P;
+  P.gy = grad_y; P.y = y; P.x = dweight ? x : nullptr; P.x2 = dweight2 ? x2 : nullptr;
+  P.scale = scale; P.mean = mean; P.rstd = rstd; P.scale2 = scale2; P.mean2 = mean2; P.rstd2 = rstd2;
+  P.gx = grad_x; P.gx2 = grad_x2; P.gres = grad_res;
+  P.part = reinterpret_cast<float4*>(workspace);
+  P.C = channels; P.hw = hw;
+  const uintptr_t bits = (uintptr_t)P.gy | (uintptr_t)P.y | (uintptr_t)P.x | (uintptr_t)P.x2 | (uintptr_t)P.gx | (uintptr_t)P.gx2 |
+                         (uintptr_t)P.gres;
+  P.vec = ((hw & 3) == 0 && (bits & 15) == 0) ? 1 : 0;
+  const int bx = plane_blocks(hw);
+  const dim3 grid(bx, batch * channels);
+  hipStream_t st = (hipStream_t)stream;
+  if (stats) {
+    hipLaunchKernelGGL(affine_act_bwd_kernel<true>, grid, dim3(kThreads), 0, st, P);
+    hipLaunchKernelGGL(affine_act_bwd_finish_kernel, dim3((channels + kThreads / 64 - 1) / (kThreads / 64)), dim3(kThreads), 0, st,
+                       (const float4*)P.part, batch, channels, bx, dweight, dbias, dweight2, dbias2);
+  } else {
+    hipLaunchKernelGGL(affine_act_bwd_kernel<false>, grid, dim3(kThreads), 0, st, P);
+  }
+  return launch_status();
+}
+
+int orp_affine_act_backward(const float* grad_y, const float* y, const float* x, const float* scale, const float* mean,
+                            const float* rstd, float* grad_x, float* grad_res, float* dweight, float* dbias, int batch, int channels,
+                            int hw, void* workspace, size_t workspace_bytes, void* stream) {
+  return orp_affine2_act_backward(grad_y, y, x, scale, mean, rstd, nullptr, nullptr, nullptr, nullptr, grad_x, nullptr, grad_res,
+                                  dweight, dbias, nullptr, nullptr, batch, channels, hw, workspace, workspace_bytes, stream);
 }
 
 int orp_affine_relu_maxpool(const float* x, const float* scale, const float* shift, float* y, int batch, int channels,

@@ -53,6 +53,52 @@ class Bottleneck(nn.Module):
         return (not torch.is_grad_enabled()) and x.is_cuda and x.dtype == torch.float32 and \
             isinstance(self.bn1, nn.BatchNorm2d) and not self.bn1.training and not self.bn3.training
 
+    def _norms_are_eval_bn(self):
+        """bn1 / bn2 / bn3 and the downsample norm (where the identity branch has one: then it is exactly Sequential(Conv2d, BatchNorm2d))
+        are eval-mode BatchNorm2d"""
+        return all(isinstance(bn, nn.BatchNorm2d) and not bn.training for bn in (self.bn1, self.bn2, self.bn3)) and \
+            (self.downsample is None or self._downsample_is_conv_norm())
+
+    def _frozen_ok(self, x):
+        """training with this block frozen (`frozen_stages`): gradients are enabled, but no parameter of the block and not its input
+        requires one, so nothing here needs autograd and the block runs the inference route as it is, under that route's switches
+        (`fuse_bn_frozen` attribute, or ORP_BN_FROZEN_FUSE=0 for A/B timing: off gives the stock modules).  Not under autocast."""
+        return torch.is_grad_enabled() and not torch.is_autocast_enabled() and x.is_cuda and x.dtype == torch.float32 and \
+            not x.requires_grad and not getattr(self, 'with_cp', False) and \
+            isinstance(self.bn1, nn.BatchNorm2d) and not self.bn1.training and not self.bn3.training and \
+            switches.of(self, 'fuse_bn_frozen', 'BN_FROZEN_FUSE') and not any(p.requires_grad for p in self.parameters())
+
+    def _train_fused_ok(self, x):
+        """training with this block trainable and its norms frozen statistics (`norm_eval`): each BatchNorm (+ residual) + ReLU behind a
+        convolution is one differentiable pass (`bn_act_train`) on contiguous fp32 CUDA tensors (`fuse_bn_train` attribute, or
+        ORP_BN_TRAIN_FUSE=0 for A/B timing: off gives the stock modules).  Not under autocast (16-bit convolution outputs), not with
+        checkpointing."""
+        return torch.is_grad_enabled() and not torch.is_autocast_enabled() and x.is_cuda and x.dtype == torch.float32 and \
+            x.dim() == 4 and x.is_contiguous() and not getattr(self, 'with_cp', False) and self._norms_are_eval_bn() and \
+            switches.of(self, 'fuse_bn_train', 'BN_TRAIN_FUSE')
+
+    def route(self, x):
+        """the route `forward` takes for x: 'fused' (inference kernels, gradients disabled), 'frozen' (the same, in a training step's
+        frozen stage), 'train' (differentiable fused passes) or 'stock' (the modules as written)"""
+        if self._fused_ok(x):
+            return 'fused'
+        if self._frozen_ok(x):
+            return 'frozen'
+        if self._train_fused_ok(x):
+            return 'train'
+        return 'stock'
+
+    def _forward_train_fused(self, x):
+        from ..mmdet_ops.fused_norm import bn_act_train
+        out = bn_act_train(self.conv1(x).contiguous(), self.bn1, relu=True)
+        out = bn_act_train(self.conv2(out).contiguous(), self.bn2, relu=True)
+        out = self.conv3(out).contiguous()
+        ds = self.downsample
+        if ds is not None:
+            # the downsample BatchNorm rides in the block's last pass, forward and backward
+            return bn_act_train(out, self.bn3, residual=ds[0](x).contiguous(), residual_bn=ds[1], relu=True)
+        return bn_act_train(out, self.bn3, residual=x, relu=True)
+
     def _downsample_norm_fusable(self):
         """the identity branch is exactly Sequential(Conv2d, eval-mode BatchNorm2d) and the fusion is not switched off
         (`fuse_downsample_norm` attribute, or ORP_BN_DOWNSAMPLE_FUSE=0 for A/B timing)"""
@@ -164,8 +210,14 @@ class Bottleneck(nn.Module):
         return conv_bn_act(out, self.conv3, self.bn3, residual=residual, residual_bn=residual_bn, relu=True)
 
     def forward(self, x):
-        if self._fused_ok(x):
+        route = self.route(x)
+        if route == 'fused':
             return self._forward_fused(x)
+        if route == 'frozen':
+            with torch.no_grad():       # nothing here has a gradient: the result requires none, as on the stock route
+                return self._forward_fused(x)
+        if route == 'train':
+            return self._forward_train_fused(x)
         identity = x
         out = self.relu(self.bn1(self.conv1(x)))
         out = self.relu(self.bn2(self.conv2(out)))
@@ -286,19 +338,37 @@ class ResNet(nn.Module):
         return switches.of(self, 'fuse_stem_pool', 'STEM_POOL_FUSE') and type(mp) is nn.MaxPool2d and pair(mp.kernel_size) == (3, 3) and pair(mp.stride) == (2, 2) and \
             pair(mp.padding) == (1, 1) and pair(mp.dilation) == (1, 1) and not mp.ceil_mode and not mp.return_indices
 
+    def stem_route(self, x):
+        """the route `forward` takes through the stem for x: 'fused' (inference kernels, gradients disabled), 'frozen' (the same in a
+        training step whose stem is frozen -- neither conv1 / bn1 nor the image requires a gradient; `fuse_bn_frozen` attribute, or
+        ORP_BN_FROZEN_FUSE=0 for A/B timing; not under autocast) or 'stock'"""
+        if not (x.is_cuda and x.dtype == torch.float32 and isinstance(self.bn1, nn.BatchNorm2d) and not self.bn1.training):
+            return 'stock'
+        if not torch.is_grad_enabled():
+            return 'fused'
+        if not torch.is_autocast_enabled() and not x.requires_grad and switches.of(self, 'fuse_bn_frozen', 'BN_FROZEN_FUSE') and \
+                not any(p.requires_grad for m in (self.conv1, self.bn1) for p in m.parameters()):
+            return 'frozen'
+        return 'stock'
+
+    def _forward_stem_fused(self, x):
+        from ..mmdet_ops.fused_norm import bn_act, bn_relu_maxpool, stem_conv_bn_relu_maxpool, stem_conv_routed
+        # the whole stem as one launch (`fuse_stem_conv` attribute, or ORP_STEM_CONV_FUSE=0 for A/B timing) at the shapes where it was
+        # measured faster; `force_stem_conv` (attribute, tests) routes every supported shape
+        if switches.of(self, 'fuse_stem_conv', 'STEM_CONV_FUSE') and \
+                stem_conv_routed(x, self.conv1, self.bn1, self.maxpool, bool(getattr(self, 'force_stem_conv', False))):
+            return stem_conv_bn_relu_maxpool(x, self.conv1, self.bn1)
+        if self._stem_pool_fusable():
+            return bn_relu_maxpool(self.conv1(x).contiguous(), self.bn1)      # BatchNorm + ReLU applied while pooling
+        return self.maxpool(bn_act(self.conv1(x).contiguous(), self.bn1, relu=True))
+
     def forward(self, x):
-        if (not torch.is_grad_enabled()) and x.is_cuda and x.dtype == torch.float32 and \
-                isinstance(self.bn1, nn.BatchNorm2d) and not self.bn1.training:
-            from ..mmdet_ops.fused_norm import bn_act, bn_relu_maxpool, stem_conv_bn_relu_maxpool, stem_conv_routed
-            # the whole stem as one launch (`fuse_stem_conv` attribute, or ORP_STEM_CONV_FUSE=0 for A/B timing) at the shapes where it was
-            # measured faster; `force_stem_conv` (attribute, tests) routes every supported shape
-            if switches.of(self, 'fuse_stem_conv', 'STEM_CONV_FUSE') and \
-                    stem_conv_routed(x, self.conv1, self.bn1, self.maxpool, bool(getattr(self, 'force_stem_conv', False))):
-                x = stem_conv_bn_relu_maxpool(x, self.conv1, self.bn1)
-            elif self._stem_pool_fusable():
-                x = bn_relu_maxpool(self.conv1(x).contiguous(), self.bn1)      # BatchNorm + ReLU applied while pooling
-            else:
-                x = self.maxpool(bn_act(self.conv1(x).contiguous(), self.bn1, relu=True))
+        route = self.stem_route(x)
+        if route == 'fused':
+            x = self._forward_stem_fused(x)
+        elif route == 'frozen':
+            with torch.no_grad():       # nothing in the stem has a gradient: the result requires none, as on the stock route
+                x = self._forward_stem_fused(x)
         else:
             x = self.maxpool(self.relu(self.bn1(self.conv1(x))))
         outs = []

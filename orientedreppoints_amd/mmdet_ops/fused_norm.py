@@ -3,7 +3,9 @@
 eval-mode BatchNorm (+ residual) + ReLU of the ResNet bottlenecks as one pass, and the bias / ReLU / residual / base-offset
 passes around the head's output convolutions for all levels in one launch.  Those are inference-only (callers use them
 under torch.no_grad()).  Training: `group_norm_act_train` is the autograd-capable GroupNorm(+ReLU) over a list of tensors
-(one launch pair forward, one pair + a parameter reduction backward, `orp_groupnorm_act_multi_train / _backward`)."""
+(one launch pair forward, one pair + a parameter reduction backward, `orp_groupnorm_act_multi_train / _backward`);
+`bn_act_train` the autograd-capable eval-mode BatchNorm (+ residual) + ReLU of the bottlenecks (the inference pass forward, one
+pass + a per-channel reduction backward, `orp_affine_act_backward` / `orp_affine2_act_backward`)."""
 import ctypes
 
 import torch
@@ -144,19 +146,30 @@ _affine_cache = _packcache.new_cache("bn_affine")
 def _bn_affine(bn):
     """eval-mode BatchNorm as (scale, shift): y = x*scale + shift; cached on the live module (_packcache.OwnerCache:
     weak reference + identity check), keyed by the storage / version state of its four tensors."""
+    hit = _bn_affine_stats(bn)
+    return _lib.keep_for_graph(hit[0]), _lib.keep_for_graph(hit[1])
+
+
+def _bn_affine_stats(bn, cache=True):
+    """(scale, shift, mean, rstd) of an eval-mode BatchNorm, fp32 and contiguous: `_bn_affine`'s pair and the statistics it is
+    made of, which the training backward (`bn_act_train`) reads.  One arithmetic, one cache entry.  cache=False: computed now and not
+    kept -- inside a stream capture of a module whose parameters train, so that the replay recomputes them from the live weights."""
     def st(t):
         return _packcache.tensor_state(t) if t is not None else None
     state = (st(bn.weight), st(bn.bias), st(bn.running_mean), st(bn.running_var), float(bn.eps))
-    hit = _affine_cache.get(bn, state)
+    hit = _affine_cache.get(bn, state) if cache else None
     if hit is None:
         with torch.no_grad():
             rstd = torch.rsqrt(bn.running_var.float() + bn.eps)
             w = bn.weight.float() if bn.weight is not None else torch.ones_like(rstd)
             b = bn.bias.float() if bn.bias is not None else torch.zeros_like(rstd)
+            mean = bn.running_mean.float().contiguous()
             scale = (w * rstd).contiguous()
-            shift = (b - bn.running_mean.float() * scale).contiguous()
-        hit = _affine_cache.put(bn, state, (scale, shift))
-    return _lib.keep_for_graph(hit[0]), _lib.keep_for_graph(hit[1])
+            shift = (b - mean * scale).contiguous()
+        hit = (scale, shift, mean, rstd.contiguous())
+        if cache:
+            _affine_cache.put(bn, state, hit)
+    return hit
 
 
 def bn_act(x, bn, residual=None, relu=True, residual_bn=None, want_range=False):
@@ -861,6 +874,110 @@ def group_norm_act_train(xs, gn, relu=True):
     outs = _GroupNormActTrain.apply(len(xs), gns[0].num_groups, gns[0].eps, bool(relu), tuple(owner), *xs,
                                     *[d.weight for d in distinct], *[d.bias for d in distinct])
     return list(outs)
+
+
+def bn_act_train_ok(x, bn):
+    """`bn_act_train` takes these: x a contiguous fp32 CUDA [B,C,H,W] tensor with elements, bn an eval-mode nn.BatchNorm2d of C
+    channels with fp32 running statistics (and parameters, where it has them)"""
+    if not (isinstance(x, torch.Tensor) and x.is_cuda and x.dtype == torch.float32 and x.dim() == 4 and x.is_contiguous() and
+            x.numel() > 0):
+        return False
+    if not (isinstance(bn, torch.nn.BatchNorm2d) and not bn.training and bn.running_var is not None and
+            bn.running_mean is not None and bn.num_features == x.size(1)):
+        return False
+    return all(t is None or (t.dtype == torch.float32 and t.device == x.device)
+               for t in (bn.weight, bn.bias, bn.running_mean, bn.running_var))
+
+
+class _BnActTrain(torch.autograd.Function):
+    """y = relu?(BatchNorm_eval(x) (+ residual | + BatchNorm2_eval(residual))) with autograd: forward = the inference pass
+    (`orp_affine_act` / `orp_affine2_act`) into a new tensor; backward = one pass for grad_x, the residual's gradient and the
+    workgroups' partial sums, one small kernel for dweight / dbias (`orp_affine_act_backward` / `orp_affine2_act_backward`).
+    Inputs: x, residual | None, bn.weight, bn.bias, residual_bn.weight, residual_bn.bias (None where there is none: autograd sees the
+    parameters here), then bn, residual_bn | None, relu."""
+
+    @staticmethod
+    def forward(ctx, x, residual, weight, bias, weight2, bias2, bn, residual_bn, relu):
+        # inside a capture (dist_utils.graph_backbone) the affine of parameters that train is computed in the graph, not cached
+        capturing = torch.cuda.is_current_stream_capturing()
+        needs = ctx.needs_input_grad
+        want1, want2 = bool(needs[2] or needs[3]), bool(needs[4] or needs[5])
+        scale, shift, mean, rstd = _bn_affine_stats(bn, cache=not (capturing and want1))
+        B, C, H, W = x.shape
+        y = torch.empty_like(x)
+        head = (_lib.ptr(x), _lib.ptr(residual), _lib.ptr(scale), _lib.ptr(shift))
+        tail = (_lib.ptr(y), B, C, H * W, 1 if relu else 0, _lib.stream_of(x))
+        keep = [scale, mean, rstd]
+        if residual_bn is not None:
+            scale2, shift2, mean2, rstd2 = _bn_affine_stats(residual_bn, cache=not (capturing and want2))
+            _call("orp_affine2_act", x.device, *head, _lib.ptr(scale2), _lib.ptr(shift2), *tail)
+            keep += [scale2, mean2, rstd2]
+        else:
+            _call("orp_affine_act", x.device, *head, *tail)
+        # only what the backward reads: y is the ReLU mask, x / the raw residual feed that BatchNorm's dweight
+        ctx.save_for_backward(y if relu else None, x if want1 else None, residual if want2 else None, *keep)
+        ctx.meta = (bool(relu), residual_bn is not None, want1, want2)
+        return y
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, gy):
+        relu, two, want1, want2 = ctx.meta
+        saved = ctx.saved_tensors
+        y, x, x2 = saved[:3]
+        scale, mean, rstd = saved[3:6]
+        scale2, mean2, rstd2 = saved[6:9] if two else (None, None, None)
+        gy = gy.detach().float().contiguous()
+        B, C, H, W = gy.shape
+        want_res = ctx.needs_input_grad[1]
+        gx = torch.empty_like(gy)
+        gx2 = torch.empty_like(gy) if (two and want_res) else None
+        # without the ReLU the residual's gradient IS grad_y: no copy; with it, a new tensor (a gradient is never written in place)
+        gres = torch.empty_like(gy) if (want_res and not two and relu) else None
+        dw = torch.empty_like(scale) if want1 else None
+        db = torch.empty_like(scale) if want1 else None
+        dw2 = torch.empty_like(scale) if want2 else None
+        db2 = torch.empty_like(scale) if want2 else None
+        ws, nbytes = None, 0
+        if want1 or want2:
+            # torch's allocator, so that a capture of the backward (make_graphed_callables) owns it
+            nbytes = _lib.lib().orp_affine_act_backward_workspace_bytes(B, C, H * W)
+            ws = torch.empty(nbytes, dtype=torch.uint8, device=gy.device)
+        p = _lib.ptr
+        dims = (B, C, H * W, p(ws), nbytes, _lib.stream_of(gy))
+        if two:
+            _call("orp_affine2_act_backward", gy.device, p(gy), p(y), p(x), p(scale), p(mean), p(rstd), p(x2), p(scale2), p(mean2),
+                  p(rstd2), p(gx), p(gx2), None, p(dw), p(db), p(dw2), p(db2), *dims)
+        else:
+            _call("orp_affine_act_backward", gy.device, p(gy), p(y), p(x), p(scale), p(mean), p(rstd), p(gx), p(gres), p(dw), p(db),
+                  *dims)
+        if two:
+            gr = gx2
+        else:
+            gr = (gres if relu else gy) if want_res else None
+        needs = ctx.needs_input_grad
+        return (gx, gr, dw if needs[2] else None, db if needs[3] else None, dw2 if needs[4] else None, db2 if needs[5] else None,
+                None, None, None)
+
+
+def bn_act_train(x, bn, residual=None, relu=True, residual_bn=None):
+    """relu?(BatchNorm_eval(x) (+ residual)) with autograd, as a NEW tensor: the values of `bn_act` on a copy of x, bit for bit, one pass
+    forward; one pass (+ a per-channel reduction where bn.weight / bn.bias require a gradient) backward, giving the gradients of x, of
+    the residual and of the BatchNorm's parameters.  residual_bn: the residual is a RAW convolution output with this eval-mode
+    BatchNorm applied while it is read (`orp_affine2_act`), whose parameters get their gradients from the same launch.
+    x (and the residual): contiguous fp32 CUDA [B,C,H,W]; bn (residual_bn): eval-mode nn.BatchNorm2d.  Anything else -- 16-bit
+    tensors under autocast, float64, channels-last, a BatchNorm in training mode -- is a ValueError: the caller keeps the stock route."""
+    if not bn_act_train_ok(x, bn):
+        raise ValueError("bn_act_train expects a contiguous fp32 CUDA [B,C,H,W] tensor and an eval-mode BatchNorm2d of its channels")
+    if residual_bn is not None and residual is None:
+        raise ValueError("bn_act_train: residual_bn without a residual")
+    if residual is not None and not (isinstance(residual, torch.Tensor) and residual.shape == x.shape and residual.is_cuda and
+                                     residual.device == x.device and residual.dtype == torch.float32 and residual.is_contiguous()):
+        raise ValueError("bn_act_train: residual must be a contiguous fp32 tensor of x's shape and device")
+    if residual_bn is not None and not bn_act_train_ok(residual, residual_bn):
+        raise ValueError("bn_act_train: residual_bn must be an eval-mode BatchNorm2d of the residual's channels")
+    return _BnActTrain.apply(x, residual, bn.weight, bn.bias, residual_bn.weight if residual_bn is not None else None,
+                             residual_bn.bias if residual_bn is not None else None, bn, residual_bn, bool(relu))
 
 
 # ---- channels-last tower path (round 4): conv_split_multi -> group_norm_act_multi_cl -> ... -----------------------------------

@@ -24,6 +24,8 @@ BN_DOWNSAMPLE_CONV_FUSE = _on('ORP_BN_DOWNSAMPLE_CONV_FUSE')  # the downsample c
 BN_CONV3X3_FUSE = _on('ORP_BN_CONV3X3_FUSE')  # bottleneck conv2 (3x3, stride 1) on the fp16-pieces kernel with BatchNorm + ReLU in the epilogue where measured faster (block.fuse_conv3x3 overrides)
 BN_CONV3X3_DEEP_FUSE = _on('ORP_BN_CONV3X3_DEEP_FUSE')  # stage 4 conv2 (512 channels, stride 1 and 2) on the K-split fp16-pieces kernel with BatchNorm + ReLU in the epilogue where measured faster; asked only where the kernel above said no (block.fuse_conv3x3_deep overrides)
 BN_CONV3X3_S2_FUSE = _on('ORP_BN_CONV3X3_S2_FUSE')  # the stride-2 conv2 of stages 2 and 3 (128 and 256 channels) on the narrow-pass fp16-pieces kernel with BatchNorm + ReLU in the epilogue where measured faster; asked only where the two kernels above said no (block.fuse_conv3x3_s2 overrides)
+BN_TRAIN_FUSE = _on('ORP_BN_TRAIN_FUSE')      # training, stages that train: eval-mode BatchNorm (+ residual) + ReLU behind the bottleneck convolutions as one forward pass and one backward pass with dweight / dbias (block.fuse_bn_train overrides)
+BN_FROZEN_FUSE = _on('ORP_BN_FROZEN_FUSE')    # training, frozen stem / stages (no parameter and no input that requires a gradient): the inference route, under its own switches above and below (block.fuse_bn_frozen / backbone.fuse_bn_frozen override)
 STEM_POOL_FUSE = _on('ORP_STEM_POOL_FUSE')    # stem BatchNorm + ReLU + max-pool as one kernel (backbone.fuse_stem_pool overrides)
 STEM_CONV_FUSE = _on('ORP_STEM_CONV_FUSE')    # the whole stem (7x7 convolution + BatchNorm + ReLU + max-pool) as one exact-fp32 MFMA launch where measured faster than library convolution + the kernel above; asked first, does not consult that switch (backbone.fuse_stem_conv overrides)
 SWIN_ATTN_FUSE = _on('ORP_SWIN_ATTN_FUSE')    # Swin inference: pad / roll / windows / bias / mask / softmax / P V / un-roll / crop as one fp32 kernel (block.fuse_window_attention overrides)
