@@ -29,16 +29,12 @@
 #include "../../include/orp_hip.h"
 #include "orp_affine.hpp"
 #include "orp_range.hpp"
-#include "orp_launch.hpp"
-#include "orp_dcn_split.hpp"
+#include "orp_conv3x3_bn_host.hpp"
 
 namespace {
 
-typedef float floatx16 __attribute__((ext_vector_type(16)));
-typedef _Float16 h8 __attribute__((ext_vector_type(8)));
-typedef _Float16 h2 __attribute__((ext_vector_type(2)));
+using namespace orp_conv3x3;       // floatx16 / h8 / h2, kThreads and the host helpers
 
-constexpr int kThreads = 512;
 constexpr int TW = 16;             // tile width
 constexpr int HWID = TW + 2;       // halo width
 constexpr int NCH = 4;             // 16-channel chunks per phase (64 channels of one tap)
@@ -237,12 +233,8 @@ bool layout_of(int c, Layout& l) {
 
 template <int C, int WM, int MT>
 hipError_t launch(const Args& A, long tiles, hipStream_t st) {
-  using K = Cfg<C, WM, MT>;
   struct Tag {};
-  hipError_t e = orp::set_max_dynamic_lds_once<Tag>(reinterpret_cast<const void*>(&conv3x3_bn_act_kernel<C, WM, MT>), K::smem);
-  if (e != hipSuccess) return e;
-  hipLaunchKernelGGL((conv3x3_bn_act_kernel<C, WM, MT>), dim3((unsigned)tiles), dim3(kThreads), K::smem, st, A);
-  return hipGetLastError();
+  return launch_with_lds<Tag>(&conv3x3_bn_act_kernel<C, WM, MT>, tiles, Cfg<C, WM, MT>::smem, st, A);
 }
 
 }  // namespace
@@ -253,17 +245,10 @@ int orp_conv3x3_bn_act_ok(int c_in, int c_out) {
   return (c_in == c_out && (c_in == 64 || c_in == 128 || c_in == 256)) ? 1 : 0;
 }
 
-// the packed weight: two fp16 planes [2][tap][C/16][2][C][8] (4 bytes per weight), then 16 bytes that hold the planes' scale
-size_t orp_conv3x3_bn_packed_bytes(int c_in, int c_out) {
-  return orp_conv3x3_bn_act_ok(c_in, c_out) ? (size_t)4 * c_in * c_out * 9 + 16 : 0;
-}
+size_t orp_conv3x3_bn_packed_bytes(int c_in, int c_out) { return packed_bytes(orp_conv3x3_bn_act_ok(c_in, c_out), c_in, c_out); }
 
 int orp_conv3x3_bn_pack_weight(const float* weight, int c_in, int c_out, void* packed, void* stream) {
-  if (!weight || !packed || ((uintptr_t)packed & 15) || !orp_conv3x3_bn_act_ok(c_in, c_out)) return ORP_EINVAL;
-  uint16_t* planes = reinterpret_cast<uint16_t*>(packed);
-  const size_t n = (size_t)c_in * c_out * 9;
-  hipError_t e = orp_split::pack_planes16(weight, c_out, c_in, 9, planes, reinterpret_cast<float*>(planes + 2 * n), (hipStream_t)stream);
-  return e == hipSuccess ? ORP_OK : (int)e;
+  return pack_weight(orp_conv3x3_bn_act_ok(c_in, c_out), weight, c_in, c_out, packed, stream);
 }
 
 int orp_conv3x3_bn_act_tile(int c_in, int c_out, int height, int width, int batch, int* tile_h, int* tile_w, int* waves_pos,
@@ -288,29 +273,22 @@ int orp_conv3x3_bn_act_pays(int c_in, int c_out, int height, int width, int batc
   if (!orp_conv3x3_bn_act_ok(c_in, c_out) || height <= 0 || width <= 0 || batch <= 0) return 0;
   // (channels, map side at 1024^2, at 1536^2, images): height and width each inside [side_min, side_max] -- only square maps were
   // timed, so a map is routed where BOTH sides lie between the timed corners' and no further
-  static const struct { int c, side_min, side_max, batch; } paid[] = {
+  static const PaidSquare rows[] = {
       {64, 256, 384, 1},  {64, 256, 256, 2},                         // stage 1: blocks 0 - 2
       {128, 128, 192, 1}, {128, 128, 128, 2},                        // stage 2: blocks 1 - 3
       {256, 64, 96, 1},   {256, 64, 64, 2},                          // stage 3: blocks 1 - 5
   };
-  for (const auto& s : paid)
-    if (s.c == c_in && s.batch == batch && height >= s.side_min && height <= s.side_max && width >= s.side_min && width <= s.side_max)
-      return 1;
-  return 0;
+  return paid(rows, c_in, height, width, batch);
 }
 
 int orp_conv3x3_bn_act(const float* x, const void* weight_packed, const float* scale, const float* shift, const uint32_t* range_in,
                        float* y, int batch, int c_in, int c_out, int height, int width, int relu, void* stream) {
   Layout l;
-  if (!x || !weight_packed || ((uintptr_t)weight_packed & 15) || !scale || !shift || !range_in || !y || (const float*)y == x || batch <= 0 || height <= 0 || width <= 0 ||
-      !orp_conv3x3_bn_act_ok(c_in, c_out) || !layout_of(c_in, l))
+  if (bad_launch_args(x, weight_packed, scale, shift, range_in, y, batch, height, width) || !orp_conv3x3_bn_act_ok(c_in, c_out) ||
+      !layout_of(c_in, l))
     return ORP_EINVAL;
   Args A;
-  A.x = x; A.scale = scale; A.shift = shift; A.y = y; A.range = range_in;
-  A.planes = reinterpret_cast<const uint16_t*>(weight_packed);
-  A.plane_stride = (size_t)c_out * c_in * 9;
-  A.wscale = reinterpret_cast<const float*>(A.planes + 2 * A.plane_stride);
-  A.H = height; A.W = width; A.relu = relu ? 1 : 0;
+  fill_common(A, x, weight_packed, scale, shift, range_in, y, c_in, c_out, height, width, relu);
   A.tiles_x = (width + TW - 1) / TW;
   const long tpi = (long)A.tiles_x * ((height + l.th - 1) / l.th);
   if (tpi * batch >= (1L << 31) || (long)height * width >= (1L << 31)) return ORP_ETOOBIG;

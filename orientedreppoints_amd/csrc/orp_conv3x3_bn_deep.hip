@@ -34,16 +34,12 @@
 #include "../../include/orp_hip.h"
 #include "orp_affine.hpp"
 #include "orp_range.hpp"
-#include "orp_launch.hpp"
-#include "orp_dcn_split.hpp"
+#include "orp_conv3x3_bn_host.hpp"
 
 namespace {
 
-typedef float floatx16 __attribute__((ext_vector_type(16)));
-typedef _Float16 h8 __attribute__((ext_vector_type(8)));
-typedef _Float16 h2 __attribute__((ext_vector_type(2)));
+using namespace orp_conv3x3;       // floatx16 / h8 / h2, kThreads and the host helpers
 
-constexpr int kThreads = 512;
 constexpr int C = 512;             // input = output channels
 constexpr int TH = 2, TW = 16;     // output tile: one 32-position MFMA block
 constexpr int NCH = 4;             // 16-channel chunks per phase (64 channels of one tap)
@@ -245,10 +241,7 @@ template <int S, int KS>
 hipError_t launch(const Args& A, long tiles, hipStream_t st) {
   using K = Cfg<S, KS>;
   struct Tag {};
-  hipError_t e = orp::set_max_dynamic_lds_once<Tag>(reinterpret_cast<const void*>(&conv3x3_bn_deep_kernel<S, KS>), K::smem);
-  if (e != hipSuccess) return e;
-  hipLaunchKernelGGL((conv3x3_bn_deep_kernel<S, KS>), dim3((unsigned)(tiles * (C / K::CG))), dim3(kThreads), K::smem, st, A);
-  return hipGetLastError();
+  return launch_with_lds<Tag>(&conv3x3_bn_deep_kernel<S, KS>, tiles * (C / K::CG), K::smem, st, A);
 }
 
 }  // namespace
@@ -259,46 +252,31 @@ int orp_conv3x3_bn_deep_ok(int c_in, int c_out, int stride) {
   return (c_in == C && c_out == C && (stride == 1 || stride == 2)) ? 1 : 0;
 }
 
-// the packed weight: two fp16 planes [2][tap][C/16][2][C][8] (4 bytes per weight), then 16 bytes that hold the planes' scale
-size_t orp_conv3x3_bn_deep_packed_bytes(int c_in, int c_out) {
-  return orp_conv3x3_bn_deep_ok(c_in, c_out, 1) ? (size_t)4 * c_in * c_out * 9 + 16 : 0;
-}
+size_t orp_conv3x3_bn_deep_packed_bytes(int c_in, int c_out) { return packed_bytes(orp_conv3x3_bn_deep_ok(c_in, c_out, 1), c_in, c_out); }
 
 int orp_conv3x3_bn_deep_pack_weight(const float* weight, int c_in, int c_out, void* packed, void* stream) {
-  if (!weight || !packed || ((uintptr_t)packed & 15) || !orp_conv3x3_bn_deep_ok(c_in, c_out, 1)) return ORP_EINVAL;
-  uint16_t* planes = reinterpret_cast<uint16_t*>(packed);
-  const size_t n = (size_t)c_in * c_out * 9;
-  hipError_t e = orp_split::pack_planes16(weight, c_out, c_in, 9, planes, reinterpret_cast<float*>(planes + 2 * n), (hipStream_t)stream);
-  return e == hipSuccess ? ORP_OK : (int)e;
+  return pack_weight(orp_conv3x3_bn_deep_ok(c_in, c_out, 1), weight, c_in, c_out, packed, stream);
 }
 
 // THE routing rule of this launch: where it was measured faster than library convolution + pass on MI355X, slowest new run plus what
-// the range word costs conv1 against the fastest library run (tests/checks/time_bottleneck_3x3_deep.py; docs/notebook/round23.md has
-// the tables).  A closed table of (stride, INPUT map side, images) filled from timed corners only: square maps, both sides inside
+// the range word costs conv1 against the fastest library run (tests/checks/time_bottleneck_3x3.py --kernel deep; docs/notebook/round23.md
+// has the tables).  A closed table of (stride, INPUT map side, images) filled from timed corners only: square maps, both sides inside
 // [side_min, side_max].
 int orp_conv3x3_bn_deep_pays(int c_in, int c_out, int height, int width, int stride, int batch) {
   if (!orp_conv3x3_bn_deep_ok(c_in, c_out, stride) || height <= 0 || width <= 0 || batch <= 0) return 0;
-  static const struct { int stride, side_min, side_max, batch; } paid[] = {
+  static const PaidSquare rows[] = {
       {1, 32, 48, 1}, {1, 32, 32, 2},                        // blocks 1 and 2: the 1024^2 image's map to the 1536^2 image's; two images
       {2, 64, 96, 1}, {2, 64, 64, 2},                        // block 0 (input map)
   };
-  for (const auto& s : paid)
-    if (s.stride == stride && s.batch == batch && height >= s.side_min && height <= s.side_max && width >= s.side_min && width <= s.side_max)
-      return 1;
-  return 0;
+  return paid(rows, stride, height, width, batch);
 }
 
 int orp_conv3x3_bn_deep(const float* x, const void* weight_packed, const float* scale, const float* shift, const uint32_t* range_in,
                         float* y, int batch, int c_in, int c_out, int height, int width, int stride, int relu, void* stream) {
-  if (!x || !weight_packed || ((uintptr_t)weight_packed & 15) || !scale || !shift || !range_in || !y || (const float*)y == x || batch <= 0 ||
-      height <= 0 || width <= 0 || !orp_conv3x3_bn_deep_ok(c_in, c_out, stride))
+  if (bad_launch_args(x, weight_packed, scale, shift, range_in, y, batch, height, width) || !orp_conv3x3_bn_deep_ok(c_in, c_out, stride))
     return ORP_EINVAL;
   Args A;
-  A.x = x; A.scale = scale; A.shift = shift; A.y = y; A.range = range_in;
-  A.planes = reinterpret_cast<const uint16_t*>(weight_packed);
-  A.plane_stride = (size_t)c_out * c_in * 9;
-  A.wscale = reinterpret_cast<const float*>(A.planes + 2 * A.plane_stride);
-  A.H = height; A.W = width; A.relu = relu ? 1 : 0;
+  fill_common(A, x, weight_packed, scale, shift, range_in, y, c_in, c_out, height, width, relu);
   A.Ho = (height - 1) / stride + 1; A.Wo = (width - 1) / stride + 1;
   A.tiles_x = (A.Wo + TW - 1) / TW;
   const long tpi = (long)A.tiles_x * ((A.Ho + TH - 1) / TH);

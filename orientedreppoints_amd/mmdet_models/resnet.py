@@ -2,6 +2,8 @@
 out_indices, frozen_stages, norm_cfg, style, norm_eval).  Parameter names follow torchvision / the released
 checkpoints (conv1, bn1, layer{1..4}.{i}.conv{1,2,3}, bn{1,2,3}, downsample.{0,1}).  Out of the HIP hot path: this
 is the part BASELINE.json says stays stock."""
+import functools
+
 import torch
 import torch.nn as nn
 
@@ -127,32 +129,26 @@ class Bottleneck(nn.Module):
         timing: off gives the launches and bits of before)"""
         return switches.of(self, 'fuse_downsample_conv', 'BN_DOWNSAMPLE_CONV_FUSE')
 
-    def _conv3x3_fusable(self):
-        """conv2 may run on the fp16-pieces kernel with bn2 + ReLU in its epilogue where that was measured faster (`fuse_conv3x3`
-        attribute, or ORP_BN_CONV3X3_FUSE=0 for A/B timing); the shapes are decided by `conv3x3_bn_act`
-        (`orp_conv3x3_bn_act_ok` / `_pays`); `force_conv3x3` (attribute, tests) routes every supported shape"""
-        return switches.of(self, 'fuse_conv3x3', 'BN_CONV3X3_FUSE') and not self.conv2_is_dcn and \
+    def _conv3x3_fusable(self, kind='act'):
+        """conv2 may run on the fused fp16-pieces kernel `kind` of `fused_norm.CONV3X3_KERNELS` -- bn2 + ReLU in its epilogue -- where
+        that was measured faster: the kernel's block attribute (`fuse_conv3x3`, `fuse_conv3x3_deep`, `fuse_conv3x3_s2`) or its switch
+        (ORP_BN_CONV3X3_FUSE / _DEEP_FUSE / _S2_FUSE = 0 for A/B timing: off gives the launches and bits of before).  The shapes are
+        decided by the kernel's `ok` / `pays`; its force attribute (`force_conv3x3`..., tests) routes every supported shape.  One
+        kernel's attributes do not touch another's."""
+        from ..mmdet_ops.fused_norm import conv3x3_kernel
+        k = conv3x3_kernel(kind)
+        return switches.of(self, k.fuse_attr, k.switch) and not self.conv2_is_dcn and \
             isinstance(self.bn2, nn.BatchNorm2d) and not self.bn2.training
 
-    def _conv3x3_deep_fusable(self):
-        """where `conv3x3_bn_act` does not take conv2, the K-split fp16-pieces kernel may (512 channels, stride 1 and 2) where that
-        was measured faster (`fuse_conv3x3_deep` attribute, or ORP_BN_CONV3X3_DEEP_FUSE=0 for A/B timing: off gives the launches and
-        bits of before); the shapes are decided by `conv3x3_bn_deep` (`orp_conv3x3_bn_deep_ok` / `_pays`); `force_conv3x3_deep`
-        (attribute, tests) routes every supported shape.  `fuse_conv3x3` / `force_conv3x3` do not touch this route."""
-        return switches.of(self, 'fuse_conv3x3_deep', 'BN_CONV3X3_DEEP_FUSE') and not self.conv2_is_dcn and \
-            isinstance(self.bn2, nn.BatchNorm2d) and not self.bn2.training
+    _conv3x3_deep_fusable = functools.partialmethod(_conv3x3_fusable, 'deep')
+    _conv3x3_s2_fusable = functools.partialmethod(_conv3x3_fusable, 's2')
 
-    def _conv3x3_s2_fusable(self):
-        """where neither `conv3x3_bn_act` nor `conv3x3_bn_deep` takes conv2, the narrow-pass fp16-pieces kernel may (128 and 256
-        channels, stride 2) where that was measured faster (`fuse_conv3x3_s2` attribute, or ORP_BN_CONV3X3_S2_FUSE=0 for A/B timing:
-        off gives the launches and bits of before); the shapes are decided by `conv3x3_bn_s2` (`orp_conv3x3_bn_s2_ok` / `_pays`);
-        `force_conv3x3_s2` (attribute, tests) routes every supported shape.  The other routes' attributes do not touch this one."""
-        return switches.of(self, 'fuse_conv3x3_s2', 'BN_CONV3X3_S2_FUSE') and not self.conv2_is_dcn and \
-            isinstance(self.bn2, nn.BatchNorm2d) and not self.bn2.training
+    def _conv3x3_forced(self, kind):
+        from ..mmdet_ops.fused_norm import conv3x3_kernel
+        return bool(getattr(self, conv3x3_kernel(kind).force_attr, False))
 
     def _forward_fused(self, x):
-        from ..mmdet_ops.fused_norm import bn_act, conv1x1_bn_act, conv3x3_bn_act, conv3x3_bn_act_routed, \
-            conv3x3_bn_deep, conv3x3_bn_deep_routed, conv3x3_bn_s2, conv3x3_bn_s2_routed, conv1x1_bn_act_dual, \
+        from ..mmdet_ops.fused_norm import bn_act, conv1x1_bn_act, conv3x3_bn_route, _conv3x3_launch, conv1x1_bn_act_dual, \
             conv1x1_bn_act_dual_routed
         fuse = self._conv1x1_fusable()
         pieces = None if self._conv1x1_pieces_on() else False       # (None: conv1x1_bn_act asks its table)
@@ -163,33 +159,15 @@ class Bottleneck(nn.Module):
             if fuse:
                 return conv1x1_bn_act(t, conv, bn, pieces=pieces, **kw)
             return bn_act(conv(t).contiguous(), bn, **kw)
-        force3 = bool(getattr(self, 'force_conv3x3', False))
-        fuse3 = False
-        if self._conv3x3_fusable() and tuple(self.conv1.stride) == (1, 1):
-            # decided in front of conv1 (whose output has x's positions), so that conv1's kernel leaves the range word conv2 reads
-            fuse3 = conv3x3_bn_act_routed(x, self.conv2, self.bn2, force3,
-                                          shape=(x.size(0), self.conv1.out_channels, x.size(2), x.size(3)))
-        force3d = bool(getattr(self, 'force_conv3x3_deep', False))
-        deep3 = False
-        if not fuse3 and self._conv3x3_deep_fusable() and tuple(self.conv1.stride) == (1, 1):
-            # the second route (stage 4's 512 channels, stride 1 and 2), asked only where the first said no, in front of conv1 as well
-            deep3 = conv3x3_bn_deep_routed(x, self.conv2, self.bn2, force3d,
-                                           shape=(x.size(0), self.conv1.out_channels, x.size(2), x.size(3)))
-        force3s = bool(getattr(self, 'force_conv3x3_s2', False))
-        s23 = False
-        if not fuse3 and not deep3 and self._conv3x3_s2_fusable() and tuple(self.conv1.stride) == (1, 1):
-            # the third route (the stride-2 conv2 of stages 2 and 3), asked only where the first two said no, in front of conv1 as well
-            s23 = conv3x3_bn_s2_routed(x, self.conv2, self.bn2, force3s,
-                                       shape=(x.size(0), self.conv1.out_channels, x.size(2), x.size(3)))
-        if fuse3:
+        kind = None
+        if tuple(self.conv1.stride) == (1, 1):
+            # conv2's kernel -- the first of the table that says yes -- is decided in front of conv1 (whose output has x's positions),
+            # so that conv1's kernel leaves the range word conv2 reads
+            kind = conv3x3_bn_route(x, self.conv2, self.bn2, (x.size(0), self.conv1.out_channels, x.size(2), x.size(3)),
+                                    self._conv3x3_fusable, self._conv3x3_forced)
+        if kind is not None:
             out, bits = conv_bn_act(x, self.conv1, self.bn1, relu=True, want_range=True)
-            out = conv3x3_bn_act(out, self.conv2, self.bn2, relu=True, force=force3, range_bits=bits)
-        elif deep3:
-            out, bits = conv_bn_act(x, self.conv1, self.bn1, relu=True, want_range=True)
-            out = conv3x3_bn_deep(out, self.conv2, self.bn2, relu=True, force=force3d, range_bits=bits)
-        elif s23:
-            out, bits = conv_bn_act(x, self.conv1, self.bn1, relu=True, want_range=True)
-            out = conv3x3_bn_s2(out, self.conv2, self.bn2, relu=True, force=force3s, range_bits=bits)
+            out = _conv3x3_launch(kind, out, self.conv2, self.bn2, relu=True, force=self._conv3x3_forced(kind), range_bits=bits)
         else:
             out = conv_bn_act(x, self.conv1, self.bn1, relu=True)
             out = bn_act(self.conv2(out).contiguous(), self.bn2, relu=True)
@@ -332,11 +310,8 @@ class ResNet(nn.Module):
     def _stem_pool_fusable(self):
         """`maxpool` is exactly MaxPool2d(3, 2, 1) -- dilation 1, floor mode, no indices -- and the fusion is not switched off
         (`fuse_stem_pool` attribute, or ORP_STEM_POOL_FUSE=0 for A/B timing)"""
-        def pair(v):
-            return tuple(v) if isinstance(v, (tuple, list)) else (v, v)
-        mp = self.maxpool
-        return switches.of(self, 'fuse_stem_pool', 'STEM_POOL_FUSE') and type(mp) is nn.MaxPool2d and pair(mp.kernel_size) == (3, 3) and pair(mp.stride) == (2, 2) and \
-            pair(mp.padding) == (1, 1) and pair(mp.dilation) == (1, 1) and not mp.ceil_mode and not mp.return_indices
+        from ..mmdet_ops.fused_norm import is_maxpool_3_2_1
+        return switches.of(self, 'fuse_stem_pool', 'STEM_POOL_FUSE') and is_maxpool_3_2_1(self.maxpool)
 
     def stem_route(self, x):
         """the route `forward` takes through the stem for x: 'fused' (inference kernels, gradients disabled), 'frozen' (the same in a

@@ -6,7 +6,9 @@ under torch.no_grad()).  Training: `group_norm_act_train` is the autograd-capabl
 (one launch pair forward, one pair + a parameter reduction backward, `orp_groupnorm_act_multi_train / _backward`);
 `bn_act_train` the autograd-capable eval-mode BatchNorm (+ residual) + ReLU of the bottlenecks (the inference pass forward, one
 pass + a per-channel reduction backward, `orp_affine_act_backward` / `orp_affine2_act_backward`)."""
+import collections
 import ctypes
+import functools
 
 import torch
 
@@ -392,154 +394,122 @@ def conv1x1_bn_act_dual(x, conv, bn, x2, conv2, bn2, relu=True):
     return y
 
 
-def conv3x3_bn_act_ok(x, conv, bn, shape=None):
-    """conv is a bias-free 3x3 / stride 1 / padding 1 / dilation 1 / groups 1 nn.Conv2d of a shape `orp_conv3x3_bn_act` takes
-    (Cin == Cout in {64, 128, 256}), bn an eval-mode BatchNorm2d, x an fp32 CUDA [B,Cin,H,W] tensor (shape: the input's shape where x
-    is only a tensor of its device and dtype)"""
+_Conv3x3Kernel = collections.namedtuple("_Conv3x3Kernel", "kind strides ok pays packed_bytes pack_weight launch takes_stride "
+                                                           "switch fuse_attr force_attr")
+# The fused fp16-pieces kernels of a bottleneck's conv2, in the order they are asked: the first that says yes runs.  Per kernel: the
+# conv strides it takes; the library's names of its channel rule, its routing table, its packer pair and its launch; whether those
+# calls carry the stride -- behind (c_in, c_out) in `ok`, behind (height, width) in `pays` and in the launch; the switch (a name in
+# `switches`) and the block attributes that turn it off / route every supported shape.  A shape is taken by at most one `ok`
+# (tests/test_conv3x3_route_table.py).  To add a kernel: its .hip file, a row here, a switch.
+CONV3X3_KERNELS = (
+    _Conv3x3Kernel("act", ((1, 1),), "orp_conv3x3_bn_act_ok", "orp_conv3x3_bn_act_pays", "orp_conv3x3_bn_packed_bytes",
+                   "orp_conv3x3_bn_pack_weight", "orp_conv3x3_bn_act", False, "BN_CONV3X3_FUSE", "fuse_conv3x3", "force_conv3x3"),
+    _Conv3x3Kernel("deep", ((1, 1), (2, 2)), "orp_conv3x3_bn_deep_ok", "orp_conv3x3_bn_deep_pays", "orp_conv3x3_bn_deep_packed_bytes",
+                   "orp_conv3x3_bn_deep_pack_weight", "orp_conv3x3_bn_deep", True, "BN_CONV3X3_DEEP_FUSE", "fuse_conv3x3_deep",
+                   "force_conv3x3_deep"),
+    _Conv3x3Kernel("s2", ((2, 2),), "orp_conv3x3_bn_s2_ok", "orp_conv3x3_bn_s2_pays", "orp_conv3x3_bn_s2_packed_bytes",
+                   "orp_conv3x3_bn_s2_pack_weight", "orp_conv3x3_bn_s2", False, "BN_CONV3X3_S2_FUSE", "fuse_conv3x3_s2", "force_conv3x3_s2"),
+)
+_CONV3X3 = {k.kind: k for k in CONV3X3_KERNELS}
+
+
+def conv3x3_kernel(kind):
+    """the row of `CONV3X3_KERNELS` of this kind ('act' | 'deep' | 's2')"""
+    return _CONV3X3[kind]
+
+
+def _stride_arg(k, conv):
+    return (conv.stride[0],) if k.takes_stride else ()
+
+
+def _conv3x3_ok(kind, x, conv, bn, shape=None):
+    """conv is a bias-free 3x3 / padding 1 / dilation 1 / groups 1 nn.Conv2d of a stride and a shape the kernel `kind` takes (its `ok`
+    symbol), bn an eval-mode BatchNorm2d, x an fp32 CUDA [B,Cin,H,W] tensor (shape: the input's shape where x is only a tensor of its
+    device and dtype)"""
+    k = _CONV3X3[kind]
     w = getattr(conv, 'weight', None)
     shape = tuple(x.shape) if shape is None else tuple(shape)
     # (the class itself: a subclass, which the 1x1 rules take, may have another forward)
     return bool(type(conv) is torch.nn.Conv2d and _bn_input(x, bn) and len(shape) == 4 and
-                _plain_conv(conv, w, 3, ((1, 1),), 1) and shape[1] == w.size(1) and shape[0] * shape[2] * shape[3] > 0 and
-                _lib.lib().orp_conv3x3_bn_act_ok(w.size(1), w.size(0)))
+                _plain_conv(conv, w, 3, k.strides, 1) and shape[1] == w.size(1) and shape[0] * shape[2] * shape[3] > 0 and
+                getattr(_lib.lib(), k.ok)(w.size(1), w.size(0), *_stride_arg(k, conv)))
 
 
-def conv3x3_bn_act_routed(x, conv, bn, force=False, shape=None):
-    """`conv3x3_bn_act` would run the fused launch for this input, given its range: supported (`conv3x3_bn_act_ok`) and either
-    forced or measured faster (`orp_conv3x3_bn_act_pays`).  A caller asks BEFORE it produces the input (shape = its shape, x any
-    tensor of its device and dtype), so that the producer leaves the range word."""
-    if not conv3x3_bn_act_ok(x, conv, bn, shape):
+def _conv3x3_routed(kind, x, conv, bn, force=False, shape=None):
+    """`_conv3x3_launch` would run the kernel `kind` for this input, given its range: supported (`_conv3x3_ok`) and either forced or
+    measured faster (its `pays` symbol).  A caller asks BEFORE it produces the input (shape = its shape, x any tensor of its device and
+    dtype), so that the producer leaves the range word."""
+    if not _conv3x3_ok(kind, x, conv, bn, shape):
         return False
+    k = _CONV3X3[kind]
     B, _c, H, W = tuple(x.shape) if shape is None else tuple(shape)
-    return bool(force or _lib.lib().orp_conv3x3_bn_act_pays(conv.weight.size(1), conv.weight.size(0), H, W, B))
+    return bool(force or getattr(_lib.lib(), k.pays)(conv.weight.size(1), conv.weight.size(0), H, W, *_stride_arg(k, conv), B))
+
+
+def conv3x3_bn_route(x, conv, bn, shape, enabled, forced):
+    """the kind of the first kernel of `CONV3X3_KERNELS` that is switched on (enabled(kind)) and whose `_conv3x3_routed` says yes for an
+    input of this shape (forced(kind): its force), or None.  A kernel's table is asked only where every kernel before it said no."""
+    for k in CONV3X3_KERNELS:
+        if enabled(k.kind) and _conv3x3_routed(k.kind, x, conv, bn, forced(k.kind), shape):
+            return k.kind
+    return None
+
+
+_packed_3x3_cache = _packcache.new_cache("conv3x3_bn_weight")
+
+
+def _packed_3x3(kind, weight):
+    """[C,C,3,3] -> the two fp16 planes + scale the kernel `kind` reads (its packer: 4 bytes per weight + 16), cached as `_packed_planes`
+    says.  One cache for every kind: the packers write one format, and a weight's shape is taken by one kind only."""
+    k = _CONV3X3[kind]
+    return _packed_planes(_packed_3x3_cache, weight, k.packed_bytes, k.pack_weight, lambda w: w.float().contiguous())
+
+
+def _conv3x3_launch(kind, x, conv, bn, relu=True, force=False, range_bits=None):
+    """relu?(BatchNorm_eval(conv(x))) for a bottleneck's conv2 as a new contiguous tensor.  Where `_conv3x3_routed` says so and the
+    input's range is known -- range_bits: the one-element int32 tensor its producer left (`conv1x1_bn_act(want_range=True)`,
+    `bn_act(want_range=True)`) -- this is ONE launch of the kernel `kind`: the fp16-pieces arithmetic of the towers' convolutions with
+    the BatchNorm and the ReLU in the epilogue, NCHW in and out, [B,C,(H-1)//s+1,(W-1)//s+1] for stride s.  Everywhere else it is
+    `bn_act(conv(x).contiguous(), bn)`: the library's convolution and the pass.  The weight planes are packed once per weight
+    (`_packed_3x3`: cached on the live parameter by storage / version state); nothing else is cached.  Inference only."""
+    if range_bits is None or not _conv3x3_routed(kind, x, conv, bn, force):
+        return bn_act(conv(x).contiguous(), bn, relu=relu)
+    k = _CONV3X3[kind]
+    x = x.detach().contiguous()
+    B, cin, H, W = x.shape
+    cout, s = conv.weight.size(0), conv.stride[0]
+    packed = _packed_3x3(kind, conv.weight)
+    scale, shift = _bn_affine(bn)
+    y = torch.empty((B, cout, (H - 1) // s + 1, (W - 1) // s + 1), dtype=torch.float32, device=x.device)
+    _call(k.launch, x.device, _lib.ptr(x), _lib.ptr(packed), _lib.ptr(scale), _lib.ptr(shift), _lib.ptr(range_bits), _lib.ptr(y),
+          B, cin, cout, H, W, *_stride_arg(k, conv), 1 if relu else 0, _lib.stream_of(x))
+    return y
+
+
+def _of_kind(fn, kind, doc):
+    """fn with its first argument bound to `kind`, under a docstring of its own"""
+    bound = functools.partial(fn, kind)
+    bound.__doc__ = doc
+    return bound
+
+
+conv3x3_bn_act_ok = _of_kind(_conv3x3_ok, "act", "`_conv3x3_ok` of `orp_conv3x3_bn_act`: Cin == Cout in {64, 128, 256}, stride 1")
+conv3x3_bn_act_routed = _of_kind(_conv3x3_routed, "act", "`_conv3x3_routed` of `orp_conv3x3_bn_act` (`orp_conv3x3_bn_act_pays`)")
+conv3x3_bn_act = _of_kind(_conv3x3_launch, "act", "`_conv3x3_launch` of `orp_conv3x3_bn_act`: 64 / 128 / 256 channels, stride 1")
+_packed_3x3_planes = _of_kind(_packed_3x3, "act", "`_packed_3x3` by `orp_conv3x3_bn_pack_weight`")
+conv3x3_bn_deep_ok = _of_kind(_conv3x3_ok, "deep", "`_conv3x3_ok` of `orp_conv3x3_bn_deep`: Cin == Cout == 512, stride 1 or 2")
+conv3x3_bn_deep_routed = _of_kind(_conv3x3_routed, "deep", "`_conv3x3_routed` of `orp_conv3x3_bn_deep` (`orp_conv3x3_bn_deep_pays`)")
+conv3x3_bn_deep = _of_kind(_conv3x3_launch, "deep", "`_conv3x3_launch` of `orp_conv3x3_bn_deep`: stage 4's 512 channels, stride 1 and 2")
+_packed_3x3_deep_planes = _of_kind(_packed_3x3, "deep", "`_packed_3x3` by `orp_conv3x3_bn_deep_pack_weight`")
+conv3x3_bn_s2_ok = _of_kind(_conv3x3_ok, "s2", "`_conv3x3_ok` of `orp_conv3x3_bn_s2`: Cin == Cout in {128, 256}, stride 2")
+conv3x3_bn_s2_routed = _of_kind(_conv3x3_routed, "s2", "`_conv3x3_routed` of `orp_conv3x3_bn_s2` (`orp_conv3x3_bn_s2_pays`)")
+conv3x3_bn_s2 = _of_kind(_conv3x3_launch, "s2", "`_conv3x3_launch` of `orp_conv3x3_bn_s2`: block 0 of stages 2 and 3, 128 / 256 channels, stride 2")
+_packed_3x3_s2_planes = _of_kind(_packed_3x3, "s2", "`_packed_3x3` by `orp_conv3x3_bn_s2_pack_weight`")
 
 
 def conv3x3_bn_act_tile(cin, cout, H, W, B):
     """(tile_h, tile_w, waves over positions, waves over channels) of an `orp_conv3x3_bn_act` launch of this shape, or None"""
     return _tile_query("orp_conv3x3_bn_act_tile", 4, cin, cout, H, W, B)
-
-
-_packed_3x3 = _packcache.new_cache("conv3x3_bn_weight")
-
-
-def _packed_3x3_planes(weight):
-    """[C,C,3,3] -> the two fp16 planes + scale `orp_conv3x3_bn_act` reads (`orp_conv3x3_bn_pack_weight`: 4 bytes per weight), cached
-    as `_packed_planes` says."""
-    return _packed_planes(_packed_3x3, weight, "orp_conv3x3_bn_packed_bytes", "orp_conv3x3_bn_pack_weight",
-                          lambda w: w.float().contiguous())
-
-
-def conv3x3_bn_act(x, conv, bn, relu=True, force=False, range_bits=None):
-    """relu?(BatchNorm_eval(conv(x))) for a bottleneck's conv2 as a new contiguous tensor.  Where `conv3x3_bn_act_routed` says so and
-    the input's range is known -- range_bits: the one-element int32 tensor its producer left (`conv1x1_bn_act(want_range=True)`,
-    `bn_act(want_range=True)`) -- this is ONE launch of `orp_conv3x3_bn_act`: the fp16-pieces arithmetic of the towers' convolutions
-    with the BatchNorm and the ReLU in the epilogue, NCHW in and out.  Everywhere else it is `bn_act(conv(x).contiguous(), bn)`:
-    the library's convolution and the pass.  The weight planes are packed once per weight (`_packed_3x3_planes`: cached on the live
-    parameter by storage / version state); nothing else is cached.  Inference only."""
-    if range_bits is None or not conv3x3_bn_act_routed(x, conv, bn, force):
-        return bn_act(conv(x).contiguous(), bn, relu=relu)
-    x = x.detach().contiguous()
-    B, cin, H, W = x.shape
-    cout = conv.weight.size(0)
-    packed = _packed_3x3_planes(conv.weight)
-    scale, shift = _bn_affine(bn)
-    y = torch.empty((B, cout, H, W), dtype=torch.float32, device=x.device)
-    _call("orp_conv3x3_bn_act", x.device, _lib.ptr(x), _lib.ptr(packed), _lib.ptr(scale), _lib.ptr(shift), _lib.ptr(range_bits),
-          _lib.ptr(y), B, cin, cout, H, W, 1 if relu else 0, _lib.stream_of(x))
-    return y
-
-
-def conv3x3_bn_deep_ok(x, conv, bn, shape=None):
-    """conv is a bias-free 3x3 / stride 1 or 2 / padding 1 / dilation 1 / groups 1 nn.Conv2d of a shape `orp_conv3x3_bn_deep` takes
-    (Cin == Cout == 512), bn an eval-mode BatchNorm2d, x an fp32 CUDA [B,Cin,H,W] tensor (shape: as `conv3x3_bn_act_ok`)"""
-    w = getattr(conv, 'weight', None)
-    shape = tuple(x.shape) if shape is None else tuple(shape)
-    return bool(type(conv) is torch.nn.Conv2d and _bn_input(x, bn) and len(shape) == 4 and
-                _plain_conv(conv, w, 3, ((1, 1), (2, 2)), 1) and shape[1] == w.size(1) and shape[0] * shape[2] * shape[3] > 0 and
-                _lib.lib().orp_conv3x3_bn_deep_ok(w.size(1), w.size(0), conv.stride[0]))
-
-
-def conv3x3_bn_deep_routed(x, conv, bn, force=False, shape=None):
-    """`conv3x3_bn_deep` would run its launch for this input, given its range: supported (`conv3x3_bn_deep_ok`) and either forced or
-    measured faster (`orp_conv3x3_bn_deep_pays`).  Asked BEFORE the input is produced, as `conv3x3_bn_act_routed`."""
-    if not conv3x3_bn_deep_ok(x, conv, bn, shape):
-        return False
-    B, _c, H, W = tuple(x.shape) if shape is None else tuple(shape)
-    return bool(force or _lib.lib().orp_conv3x3_bn_deep_pays(conv.weight.size(1), conv.weight.size(0), H, W, conv.stride[0], B))
-
-
-_packed_3x3_deep = _packcache.new_cache("conv3x3_bn_deep_weight")
-
-
-def _packed_3x3_deep_planes(weight):
-    """[512,512,3,3] -> the two fp16 planes + scale `orp_conv3x3_bn_deep` reads (`orp_conv3x3_bn_deep_pack_weight`), cached as
-    `_packed_planes` says."""
-    return _packed_planes(_packed_3x3_deep, weight, "orp_conv3x3_bn_deep_packed_bytes", "orp_conv3x3_bn_deep_pack_weight",
-                          lambda w: w.float().contiguous())
-
-
-def conv3x3_bn_deep(x, conv, bn, relu=True, force=False, range_bits=None):
-    """relu?(BatchNorm_eval(conv(x))) for the 512-channel conv2 of a stage 4 bottleneck (stride 1 or 2) as a new contiguous tensor: the
-    second route beside `conv3x3_bn_act`, with the same contract.  Where `conv3x3_bn_deep_routed` says so and the input's range is
-    known (range_bits) this is ONE launch of `orp_conv3x3_bn_deep`; everywhere else `bn_act(conv(x).contiguous(), bn)`."""
-    if range_bits is None or not conv3x3_bn_deep_routed(x, conv, bn, force):
-        return bn_act(conv(x).contiguous(), bn, relu=relu)
-    x = x.detach().contiguous()
-    B, cin, H, W = x.shape
-    cout, s = conv.weight.size(0), conv.stride[0]
-    packed = _packed_3x3_deep_planes(conv.weight)
-    scale, shift = _bn_affine(bn)
-    y = torch.empty((B, cout, (H - 1) // s + 1, (W - 1) // s + 1), dtype=torch.float32, device=x.device)
-    _call("orp_conv3x3_bn_deep", x.device, _lib.ptr(x), _lib.ptr(packed), _lib.ptr(scale), _lib.ptr(shift), _lib.ptr(range_bits),
-          _lib.ptr(y), B, cin, cout, H, W, s, 1 if relu else 0, _lib.stream_of(x))
-    return y
-
-
-def conv3x3_bn_s2_ok(x, conv, bn, shape=None):
-    """conv is a bias-free 3x3 / stride 2 / padding 1 / dilation 1 / groups 1 nn.Conv2d of a shape `orp_conv3x3_bn_s2` takes
-    (Cin == Cout in {128, 256}), bn an eval-mode BatchNorm2d, x an fp32 CUDA [B,Cin,H,W] tensor (shape: as `conv3x3_bn_act_ok`)"""
-    w = getattr(conv, 'weight', None)
-    shape = tuple(x.shape) if shape is None else tuple(shape)
-    return bool(type(conv) is torch.nn.Conv2d and _bn_input(x, bn) and len(shape) == 4 and
-                _plain_conv(conv, w, 3, ((2, 2),), 1) and shape[1] == w.size(1) and shape[0] * shape[2] * shape[3] > 0 and
-                _lib.lib().orp_conv3x3_bn_s2_ok(w.size(1), w.size(0)))
-
-
-def conv3x3_bn_s2_routed(x, conv, bn, force=False, shape=None):
-    """`conv3x3_bn_s2` would run its launch for this input, given its range: supported (`conv3x3_bn_s2_ok`) and either forced or
-    measured faster (`orp_conv3x3_bn_s2_pays`).  Asked BEFORE the input is produced, as `conv3x3_bn_act_routed`."""
-    if not conv3x3_bn_s2_ok(x, conv, bn, shape):
-        return False
-    B, _c, H, W = tuple(x.shape) if shape is None else tuple(shape)
-    return bool(force or _lib.lib().orp_conv3x3_bn_s2_pays(conv.weight.size(1), conv.weight.size(0), H, W, B))
-
-
-_packed_3x3_s2 = _packcache.new_cache("conv3x3_bn_s2_weight")
-
-
-def _packed_3x3_s2_planes(weight):
-    """[C,C,3,3] -> the two fp16 planes + scale `orp_conv3x3_bn_s2` reads (`orp_conv3x3_bn_s2_pack_weight`), cached as
-    `_packed_planes` says."""
-    return _packed_planes(_packed_3x3_s2, weight, "orp_conv3x3_bn_s2_packed_bytes", "orp_conv3x3_bn_s2_pack_weight",
-                          lambda w: w.float().contiguous())
-
-
-def conv3x3_bn_s2(x, conv, bn, relu=True, force=False, range_bits=None):
-    """relu?(BatchNorm_eval(conv(x))) for the stride-2 conv2 of the first bottleneck of stages 2 and 3 (128 and 256 channels) as a new
-    contiguous tensor: the third route beside `conv3x3_bn_act` and `conv3x3_bn_deep`, with the same contract.  Where
-    `conv3x3_bn_s2_routed` says so and the input's range is known (range_bits) this is ONE launch of `orp_conv3x3_bn_s2`; everywhere
-    else `bn_act(conv(x).contiguous(), bn)`."""
-    if range_bits is None or not conv3x3_bn_s2_routed(x, conv, bn, force):
-        return bn_act(conv(x).contiguous(), bn, relu=relu)
-    x = x.detach().contiguous()
-    B, cin, H, W = x.shape
-    cout = conv.weight.size(0)
-    packed = _packed_3x3_s2_planes(conv.weight)
-    scale, shift = _bn_affine(bn)
-    y = torch.empty((B, cout, (H - 1) // 2 + 1, (W - 1) // 2 + 1), dtype=torch.float32, device=x.device)
-    _call("orp_conv3x3_bn_s2", x.device, _lib.ptr(x), _lib.ptr(packed), _lib.ptr(scale), _lib.ptr(shift), _lib.ptr(range_bits),
-          _lib.ptr(y), B, cin, cout, H, W, 1 if relu else 0, _lib.stream_of(x))
-    return y
 
 
 def bn_relu_maxpool(x, bn):
@@ -558,6 +528,12 @@ def _pair(v):
     return tuple(v) if isinstance(v, (tuple, list)) else (v, v)
 
 
+def is_maxpool_3_2_1(mp):
+    """mp is exactly MaxPool2d(3, 2, 1): dilation 1, floor mode, no indices"""
+    return bool(type(mp) is torch.nn.MaxPool2d and _pair(mp.kernel_size) == (3, 3) and _pair(mp.stride) == (2, 2) and
+                _pair(mp.padding) == (1, 1) and _pair(mp.dilation) == (1, 1) and not mp.ceil_mode and not mp.return_indices)
+
+
 def stem_conv_ok(x, conv, bn=None, maxpool=None):
     """conv is the bias-free 7x7 / stride 2 / padding 3 fp32 nn.Conv2d 3 -> 64 that `orp_stem_conv_bn_relu_pool` takes and x an fp32 CUDA
     [B,3,H,W] tensor; bn (where given) an eval-mode BatchNorm2d; maxpool (where given) exactly MaxPool2d(3, 2, 1): dilation 1, floor mode,
@@ -569,10 +545,7 @@ def stem_conv_ok(x, conv, bn=None, maxpool=None):
         return False
     if bn is not None and not _bn_input(x, bn):
         return False
-    mp = maxpool
-    return bool(mp is None or (type(mp) is torch.nn.MaxPool2d and _pair(mp.kernel_size) == (3, 3) and _pair(mp.stride) == (2, 2) and
-                               _pair(mp.padding) == (1, 1) and _pair(mp.dilation) == (1, 1) and not mp.ceil_mode and
-                               not mp.return_indices))
+    return maxpool is None or is_maxpool_3_2_1(maxpool)
 
 
 def stem_conv_routed(x, conv, bn, maxpool, force=False):

@@ -3,7 +3,7 @@ written and read back) against the one launch of `stem_conv_bn_relu_maxpool` at 
 
     python tests/checks/time_stem.py [--out FILE.jsonl] [--calls 20] [--rounds 2] [--batch 1] [--size 1024]
 
-Each side as time_bottleneck_3x3_s2.py times it: HIP events around ONE captured graph of `calls` calls (at least 20) after a warm-up pass,
+Each side as time_bottleneck_3x3.py --kernel s2 times it: HIP events around ONE captured graph of `calls` calls (at least 20) after a warm-up pass,
 cycling through enough distinct input / output buffers (more than 320 MiB in total) that no call finds its image in a cache; the sides
 alternate `rounds` times.  Run it twice (two processes) at each corner the project uses (--size 1024, --size 1024 --batch 2, --size 1536)
 and route a corner only where the SLOWEST new figure of all rounds beats the FASTEST library figure.  Prints (and with --out appends)
