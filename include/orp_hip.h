@@ -1038,6 +1038,35 @@ int orp_window_attention_backward_h(const void* qkv, const float* qkv_bias, cons
                                     void* workspace, size_t workspace_bytes, int dtype, void* stream);
 
 /* ---------------------------------------------------------------------------------------------------------
+ * A per-token linear layer with its epilogue on the bf16 matrix pipe (csrc/orp_token_linear.hip, inference): what a Swin block runs
+ * as attn.qkv, attn.proj, mlp.fc1 and mlp.fc2, and PatchMerging as its reduction.
+ *   y[t][n] = act(sum_k x[t][k] * w[n][k] + bias[n]) + residual[t][n]
+ *   x        [tokens][k] fp32, rows contiguous
+ *   weight   [n][k] fp32 (nn.Linear's layout), packed once by orp_token_linear_pack_weight into orp_token_linear_packed_bytes bytes
+ *            (16-byte aligned): three bf16 planes [3][k/16][2][n][8]
+ *   bias     [n] or NULL (nothing added);  residual [tokens][n] or NULL (nothing added);  y [tokens][n]
+ *   act      0 = identity, 1 = the exact GELU 0.5 * u * (1 + erff(u * sqrt(1/2)))
+ * Arithmetic: that of orp_conv1x1_bn_act_pieces -- every fp32 operand split exactly into three bf16 pieces by truncation, the six
+ * products x2 w0, x0 w2, x1 w1, x1 w0, x0 w1, x0 w0 in this order per 16-wide chunk of k, chunks ascending, ONE fp32 accumulator per output:
+ * no split-K, no atomics; the value of an output does not depend on `tokens`, on the tile it falls in or on the launch it is part of.
+ * The epilogue is plain fp32 in the order written.  Held to float64 inside the first-order bound by tests/test_gpu_token_linear.py,
+ * bit-identical on exact data.  An infinite x gives NaN where fp32 gives inf, in that token's row only.  One launch, no workspace,
+ * no host synchronisation: capturable.
+ * Supported (the _ok query): k % 32 == 0 in [32, 8192], n % 32 == 0 in [32, 16384]; `tokens` is arbitrary (0: ORP_OK, nothing
+ * launched).  ORP_EINVAL without a launch: a NULL x / weight / y, a pointer that is not 16-byte aligned, tokens < 0, a shape the query
+ * refuses, act outside {0, 1}, y == x or y == residual.
+ * The _pays query: 1 where this launch was MEASURED faster than the library's GEMM plus its GELU / residual kernels on MI355X
+ * (closed table, docs/notebook/round29.md; 0 for every shape, token count or epilogue outside it).  epilogue: bit 0 = bias, bit 1 =
+ * GELU, bit 2 = residual.  The three queries are host functions that answer without a device.
+ * ------------------------------------------------------------------------------------------------------- */
+int orp_token_linear_ok(int k, int n);
+int orp_token_linear_pays(long tokens, int k, int n, int epilogue);
+size_t orp_token_linear_packed_bytes(int k, int n);
+int orp_token_linear_pack_weight(const float* weight, int k, int n, void* packed, void* stream);
+int orp_token_linear(const float* x, const void* weight_packed, const float* bias, const float* residual, float* y, long tokens, int k,
+                     int n, int act, void* stream);
+
+/* ---------------------------------------------------------------------------------------------------------
  * Fused test-time post-processing around the rotated NMS: replaces the tensor-op chains of
  * get_bboxes_single (orientedreppoints_head.py:707-779), multiclass_rnms (bbox_nms.py:93-182) and rbbox2result
  * (transforms.py:356-375) with fixed-shape, stream-ordered kernels -- no host synchronisation, hipGraph-capturable.

@@ -200,6 +200,11 @@ _SIGNATURES = {
     "orp_window_attention_backward": (_i, [_vp] * 6 + [_i] * 7 + [_f, _vp, _vp, _vp, _vp, _sz, _vp]),
     "orp_window_attention_h": (_i, [_vp, _vp, _vp] + [_i] * 7 + [_f, _vp, _vp, _i, _vp]),
     "orp_window_attention_backward_h": (_i, [_vp] * 6 + [_i] * 7 + [_f, _vp, _vp, _vp, _vp, _sz, _i, _vp]),
+    "orp_token_linear_ok": (_i, [_i, _i]),
+    "orp_token_linear_pays": (_i, [ctypes.c_long, _i, _i, _i]),
+    "orp_token_linear_packed_bytes": (_sz, [_i, _i]),
+    "orp_token_linear_pack_weight": (_i, [_vp, _i, _i, _vp, _vp]),
+    "orp_token_linear": (_i, [_vp, _vp, _vp, _vp, _vp, ctypes.c_long, _i, _i, _i, _vp]),
 }
 
 _lib = None

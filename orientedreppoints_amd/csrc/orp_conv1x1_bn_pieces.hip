@@ -85,20 +85,7 @@ struct DualArgs : Args {
   int cin2, hw2, w2, wo, s2;       // input plane and row length, output row length, stride (1 | 2)
 };
 
-// two fp32 values whose low 16 bits are zero -> one dword of two bf16: (a >> 16) | (b & 0xffff0000)
-__device__ __forceinline__ unsigned pack_hi16(float a, float b) {
-  return __builtin_amdgcn_perm(__float_as_uint(b), __float_as_uint(a), 0x07060302u);
-}
-
-// rows k (a) and k + 1 (b) of one position -> the packed dword of each plane
-__device__ __forceinline__ void split_pair(float a, float b, unsigned (&d)[3]) {
-  const float a0 = __uint_as_float(__float_as_uint(a) & 0xffff0000u), b0 = __uint_as_float(__float_as_uint(b) & 0xffff0000u);
-  const float ar = a - a0, br = b - b0;
-  const float a1 = __uint_as_float(__float_as_uint(ar) & 0xffff0000u), b1 = __uint_as_float(__float_as_uint(br) & 0xffff0000u);
-  d[0] = pack_hi16(a0, b0);
-  d[1] = pack_hi16(a1, b1);
-  d[2] = pack_hi16(ar - a1, br - b1);
-}
+using orp_split::split_pair;      // rows k and k + 1 of one position -> the packed dword of each plane (orp_dcn_split.hpp)
 
 // WCH waves over channels (32 each) x 4 / WCH waves over positions (32 WN each).  VEC: hw % 4 == 0 and x 16-byte aligned.  MODE: the
 // residual term (0 nothing, 1 res, 2 res with its own affine, 3 contracted here out of x2 in front of the main contraction, with

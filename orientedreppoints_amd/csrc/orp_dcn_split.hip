@@ -167,11 +167,7 @@ __global__ void pack_planes16_kernel(const float* __restrict__ w, int cout, int 
   }
 }
 
-// two fp32 values whose low 16 bits are zero (or may be dropped) -> one dword of two bf16: (a >> 16) | (b & 0xffff0000)
-__device__ __forceinline__ unsigned pack_hi16(float a, float b) {
-  return __builtin_amdgcn_perm(__float_as_uint(b), __float_as_uint(a), 0x07060302u);
-}
-
+// (pack_hi16: orp_dcn_split.hpp)
 // partial products (A plane, W plane), smallest first: 0 = hi, 1 = mid, 2 = lo.  Base-3 digit strings, so that the unrolled
 // loop indexes registers with compile-time constants (a constexpr array would be materialised in scratch memory)
 __device__ __forceinline__ constexpr int prod_a(int t) { const int tab[9] = {2, 2, 1, 2, 0, 1, 1, 0, 0}; return tab[t]; }

@@ -74,4 +74,20 @@ hipError_t launch(const Args& a, hipStream_t st);
 // dev aid (orp_debug_amax_log): returns the number of launches logged since the previous call
 int set_amax_log(unsigned* log, int capacity_launches);
 
+// ---- the exact three-piece bf16 split in registers, shared by every kernel that stages fp32 operands for v_mfma_f32_32x32x16_bf16 ----
+// two fp32 values whose low 16 bits are zero (or may be dropped) -> one dword of two bf16: (a >> 16) | (b & 0xffff0000)
+__device__ __forceinline__ unsigned pack_hi16(float a, float b) {
+  return __builtin_amdgcn_perm(__float_as_uint(b), __float_as_uint(a), 0x07060302u);
+}
+
+// elements k (a) and k + 1 (b) of one row -> the packed dword of each plane
+__device__ __forceinline__ void split_pair(float a, float b, unsigned (&d)[3]) {
+  const float a0 = __uint_as_float(__float_as_uint(a) & 0xffff0000u), b0 = __uint_as_float(__float_as_uint(b) & 0xffff0000u);
+  const float ar = a - a0, br = b - b0;
+  const float a1 = __uint_as_float(__float_as_uint(ar) & 0xffff0000u), b1 = __uint_as_float(__float_as_uint(br) & 0xffff0000u);
+  d[0] = pack_hi16(a0, b0);
+  d[1] = pack_hi16(a1, b1);
+  d[2] = pack_hi16(ar - a1, br - b1);
+}
+
 }  // namespace orp_split

@@ -12,6 +12,10 @@ gradients enabled the same span is `window_attention_train`, a forward kernel th
 (`SwinBlock.fuses_attention_train`; switch ORP_SWIN_ATTN_TRAIN_FUSE / `block.fuse_window_attention_train`).  Under fp16 / bf16
 autocast `attn.qkv` yields 16-bit q / k / v and the span is `window_attention_half` / `window_attention_train_half`: the same kernels
 on 16-bit operands, fp32 arithmetic (`SwinBlock.fuses_attention_half`; switch ORP_SWIN_ATTN_HALF_FUSE / `block.fuse_window_attention_half`).
+An eval-mode block on the fp32 inference route also runs its four linears -- `attn.qkv`, `attn.proj` with the block input as residual,
+`mlp.fc1` with the GELU, `mlp.fc2` with its residual -- and `PatchMerging` its `reduction` as bf16-pieces launches with the epilogue
+fused, each where measured faster (`SwinBlock.fuses_linears`, mmdet_ops/token_linear.py; switch ORP_SWIN_LINEAR_FUSE /
+`fuse_token_linear`); the LayerNorms stay stock.
 
 Parameter / buffer names are the released checkpoints' (`swin_tiny_patch4_window7_224.pth`): patch_embed.{proj,norm},
 layers.<i>.blocks.<j>.{norm1,attn.{relative_position_bias_table,relative_position_index,qkv,proj},norm2,mlp.{fc1,fc2}},
@@ -22,10 +26,24 @@ import torch.nn.functional as F
 import torch.utils.checkpoint as cp
 
 from .. import switches
+from ..mmdet_ops.token_linear import token_linear, token_linear_ok, token_linear_routed
 from ..mmdet_ops.window_attention import (window_attention, window_attention_half, window_attention_half_ok, window_attention_ok,
                                           window_attention_train, window_attention_train_half, window_attention_train_half_ok,
                                           window_attention_train_ok)
 from .registry import BACKBONES
+
+
+def _linear(owner, linear, x, act=None, residual=None):
+    """act(linear(x)) + residual for a module whose linears go through `token_linear`: one launch where the routing table says so
+    (`owner.force_token_linear`, tests: at every shape the kernel takes), else the library's launches with their bits"""
+    force = bool(getattr(owner, 'force_token_linear', False))
+    res_ok = residual is None or (residual.is_contiguous() and residual.dtype == torch.float32)
+    if res_ok and (token_linear_ok(linear, x) if force else token_linear_routed(linear, x, act, residual)):
+        return token_linear(x, linear, act, residual, force=True)
+    y = linear(x)
+    if act == 'gelu':
+        y = F.gelu(y)
+    return y if residual is None else residual + y
 
 
 class StochasticDepth(nn.Module):
@@ -129,7 +147,19 @@ class SwinBlock(nn.Module):
             return window_attention
         return window_attention_train if self.fuses_attention_train(x) else self.fuses_attention_half(x)
 
+    def fuses_linears(self, x):
+        """an eval-mode block (dropout and drop_path are identities) on the fp32 inference attention route, contiguous tokens: qkv,
+        proj + residual, fc1 + GELU and fc2 + residual through `token_linear`, each where routed"""
+        return bool(not self.training and switches.of(self, 'fuse_token_linear', 'SWIN_LINEAR_FUSE') and self.fuses_attention(x) and
+                    x.is_contiguous())
+
     def forward(self, x, H, W, shift_mask):
+        if self.fuses_linears(x):
+            a, m = self.attn, self.mlp
+            y = window_attention(_linear(self, a.qkv, self.norm1(x)), a.qkv.bias, a.relative_position_bias_table, H, W, a.num_heads,
+                                 self.ws, self.shift, a.scale)
+            x = _linear(self, a.proj, y, None, x)
+            return _linear(self, m.fc2, _linear(self, m.fc1, self.norm2(x), 'gelu'), None, x)
         fused = self.fused_attention(x)
         if fused is not None:
             # qkv and proj are per-token linears: both run on the un-padded, un-rolled tokens, the kernel does the index arithmetic
@@ -171,7 +201,10 @@ class PatchMerging(nn.Module):
             x = F.pad(x, (0, 0, 0, W % 2, 0, H % 2))
         # channel order of the released weights: (even row, even col), (odd, even), (even, odd), (odd, odd)
         x = torch.cat([x[:, 0::2, 0::2], x[:, 1::2, 0::2], x[:, 0::2, 1::2], x[:, 1::2, 1::2]], -1)
-        return self.reduction(self.norm(x.view(B, -1, 4 * C)))
+        x = self.norm(x.view(B, -1, 4 * C))
+        if not self.training and switches.of(self, 'fuse_token_linear', 'SWIN_LINEAR_FUSE'):
+            return _linear(self, self.reduction, x)       # (fp32 inference on CUDA tokens, where routed; else the module as written)
+        return self.reduction(x)
 
 
 class SwinStage(nn.Module):
