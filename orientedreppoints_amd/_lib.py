@@ -2,216 +2,122 @@
 
 The product path has NO CPU fallback: if the HIP library is missing the import of any operator fails loudly.
 PyTorch is used for device memory, the current stream and (elsewhere) torch.distributed only.
+
+The header is the only declaration of the ABI: the signatures, the argument structs and the ORP_* constants below are parsed
+from it at import (`parse_header`), and a declaration the parser cannot map is an error, never a skipped entry.
 """
 import ctypes
 import os
+import re
 
 import torch
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("ORP_HIP_LIB") or os.path.join(_HERE, "csrc", "liborp_hip.so")   # ORP_HIP_LIB: dev aid (instrumented builds)
-
-ORP_OK, ORP_EINVAL, ORP_EWORKSPACE, ORP_ETOOBIG = 0, -1, -2, -3
-ORP_NMS_MAX_BOXES = 131072
-
-_vp = ctypes.c_void_p
-_i = ctypes.c_int
-_f = ctypes.c_float
-_sz = ctypes.c_size_t
-
-# name -> (restype, argtypes); mirrors include/orp_hip.h one to one
-_SIGNATURES = {
-    "orp_version": (ctypes.c_char_p, []),
-    "orp_rnms_workspace_bytes": (_sz, [_i]),
-    "orp_rnms": (_i, [_vp, _i, _f, _i, _i, _i, _vp, _vp, _vp, _sz, _vp]),
-    "orp_rnms_batched_workspace_bytes": (_sz, [_i, _i, _i]),
-    "orp_rnms_batched": (_i, [_vp, _i, _vp, _i, _i, _f, _i, _vp, _vp, _vp, _sz, _vp]),
-    "_poly_nms": (None, [_vp, _vp, _vp, _i, _i, _f, _i]),
-    "_overlaps": (None, [_vp, _vp, _vp, _i, _i, _i]),
-    "orp_quad_iou_matrix": (_i, [_vp, _i, _vp, _i, _i, _i, _vp, _vp]),
-    "orp_poly_overlaps": (_i, [_vp, _i, _vp, _i, _vp, _vp]),
-    "orp_box_iou_rotated": (_i, [_vp, _i, _vp, _i, _vp, _vp]),
-    "orp_box_iou_rotated_host": (_i, [_vp, _i, _vp, _i, _vp]),
-    "orp_minarearect": (_i, [_vp, _i, _vp, _vp]),
-    "orp_minarearect_decode": (_i, [_vp, _i, _vp, _vp, _vp, _vp]),
-    "orp_libm_eval": (_i, [_vp, _vp, ctypes.c_long, _i, _vp, _vp]),
-    "orp_convex_iou": (_i, [_vp, _i, _vp, _i, _vp, _vp]),
-    "orp_convex_giou": (_i, [_vp, _vp, _i, _vp, _vp]),
-    "orp_points_justify": (_i, [_vp, _i, _vp, _i, _vp, _vp]),
-    "orp_points_in_quad_aligned": (_i, [_vp, _vp, _i, _vp, _vp]),
-    "orp_chamfer2d_forward": (_i, [_vp, _vp, _i, _i, _i, _vp, _vp, _vp, _vp, _vp]),
-    "orp_chamfer2d_backward": (_i, [_vp, _vp, _i, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
-    "orp_sigmoid_focal_loss_forward": (_i, [_vp, _vp, _i, _i, _f, _f, _vp, _vp]),
-    "orp_sigmoid_focal_loss_backward": (_i, [_vp, _vp, _vp, _i, _i, _f, _f, _vp, _vp]),
-    "orp_sigmoid_focal_loss_forward_f64": (_i, [_vp, _vp, _i, _i, _f, _f, _vp, _vp]),
-    "orp_sigmoid_focal_loss_backward_f64": (_i, [_vp, _vp, _vp, _i, _i, _f, _f, _vp, _vp]),
-    "orp_point_assign_workspace_bytes": (_sz, [_i]),
-    "orp_point_assign": (_i, [_vp, _i, _vp, _i, _f, _i, _vp, _vp, _sz, _vp]),
-    "orp_max_iou_assign_workspace_bytes": (_sz, [_i]),
-    "orp_max_iou_assign": (_i, [_vp, _i, _i, _f, _f, _f, _f, _i, _vp, _vp, _vp, _sz, _vp]),
-    "orp_apaa_feature_dissimilarity": (_i, [_vp, _vp, _vp, _vp, _i, _i, _vp, _vp, _vp, _i, _vp, _vp]),
-    "orp_apaa_select": (_i, [_vp, _vp, _vp, _i, _i, _i, _i, ctypes.c_double, _vp, _vp]),
-    "orp_pointset_target": (_i, [_vp, _vp, _i, _i, _vp, _vp, _vp, _vp, _i, _f, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
-    "orp_points_from_offsets": (_i, [_vp, _i, _i, _i, _i, _vp, _vp]),
-    "orp_gather_levels": (_i, [_vp, _i, _i, _i, _vp, _i, _i, _vp, _vp]),
-    "orp_gather_levels_backward": (_i, [_vp, _i, _i, _i, _vp, _i, _i, _vp, _vp]),
-    "orp_outline_samples": (_i, [_vp, _i, _i, _vp, _vp, _vp]),
-    "orp_profile_enable": (_i, [_i]),
-    "orp_profile_read": (_i, [_i, _vp, _vp, _i]),
-    "orp_dcn_fast_path_ok": (_i, [_i, _i, _i, _i, _i, _i]),
-    "orp_dcn_pack_weight": (_i, [_vp, _i, _i, _i, _i, _vp, _vp]),
-    "orp_dcn_packed_weight_floats": (_sz, [_i, _i, _i, _i]),
-    "orp_dcn_set_split_mode": (_i, [_i]),
-    "orp_dcn_get_split_mode": (_i, []),
-    "orp_dcn_forward_workspace_bytes": (_sz, [_vp, _i, _i, _i, _i]),
-    "orp_dcn_forward_multi": (_i, [_vp, _i, _i, _i, _i, _vp] + [_i] * 10 + [_vp, _sz, _vp]),
-    "orp_dcn_forward_multi_ex": (_i, [_vp, _vp, _i, _i, _i, _i, _vp, _vp] + [_i] * 11 + [_vp, _sz, _vp]),
-    "orp_dcn_forward_pair": (_i, [_vp, _vp, _vp, _i, _i, _i, _i, _vp, _vp, _vp, _vp] + [_i] * 11 + [_vp, _sz, _vp]),
-    "orp_dcn_head_packed_floats": (_sz, []),
-    "orp_dcn_pack_head_weight": (_i, [_vp, _i, _vp, _vp]),
-    "orp_dcn_forward_pair_heads": (_i, [_vp, _vp, _i, _i, _vp, _vp, _vp] + [_i] * 9 + [_vp, _sz, _vp]),
-    "orp_dcn_half_path_ok": (_i, [_i, _i, _i, _i, _i, _i]),
-    "orp_dcn_pack_weight_h": (_i, [_vp, _i, _i, _i, _i, _vp, _i, _vp]),
-    "orp_dcn_forward_h_tile_rows": (_i, [ctypes.c_long, _i]),
-    "orp_dcn_forward_h_wave_specialised": (_i, []),
-    "orp_dcn_forward_h_workspace_bytes": (_sz, [_vp, _i, _i, _i, _i]),
-    "orp_dcn_forward_multi_h": (_i, [_vp, _vp, _i, _i, _i, _i, _vp, _vp] + [_i] * 12 + [_vp, _sz, _vp]),
-    "orp_dcn_im2col": (_i, [_vp, _vp, _vp] + [_i] * 13 + [_vp, _vp]),
-    "orp_dcn_col2im": (_i, [_vp, _vp, _vp, _vp] + [_i] * 13 + [_vp, _vp, _vp, _vp]),
-    "orp_dcn_im2col_f64": (_i, [_vp, _vp, _vp] + [_i] * 13 + [_vp, _vp]),
-    "orp_dcn_col2im_f64": (_i, [_vp, _vp, _vp, _vp] + [_i] * 13 + [_vp, _vp, _vp, _vp]),
-    "orp_dcn_col2im_nhwc": (_i, [_vp, _vp, _vp] + [_i] * 12 + [_vp, _vp, _vp]),
-    "orp_dcn_forward_direct": (_i, [_vp] * 6 + [_i] * 15 + [_vp]),
-    "orp_dcn_backward_mfma_ok": (_i, [_i] * 6),
-    "orp_dcn_backward_workspace_bytes": (_sz, [_vp] + [_i] * 10),
-    "orp_dcn_backward_multi": (_i, [_vp, _i, _i, _i, _i, _vp, _vp] + [_i] * 9 + [_vp, _sz, _vp]),
-    "orp_dcn_backward_multi_ex": (_i, [_vp, _vp, _vp, _i, _i, _i, _i, _i, _vp, _vp] + [_i] * 9 + [_vp, _sz, _vp]),
-    "orp_poly_nms_f64_workspace_bytes": (_sz, [_i]),
-    "orp_poly_nms_f64": (_i, [_vp, _i, ctypes.c_double, _vp, _vp, _vp, _sz, _vp]),
-    "orp_poly_nms_f64_batched_workspace_bytes": (_sz, [_i, _i, _i]),
-    "orp_poly_nms_f64_batched": (_i, [_vp, _i, _vp, _i, _i, ctypes.c_double, _i, _i, _vp, _vp, _vp, _sz, _vp]),
-    "orp_scene_tiles": (_i, [_vp, _i, _i, ctypes.c_longlong, _vp, _i, _i, _vp, _vp, _i, _i, _vp, _vp]),
-    "orp_scene_tiles_resized": (_i, [_vp, _i, _i, ctypes.c_longlong, _vp, _i, _i, _i, _i, _i, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp, _i,
-                                     _i, _vp, _vp]),
-    "orp_scene_tiles_flip": (_i, [_vp, _i, _i, ctypes.c_longlong, _vp, _i, _i, _vp, _vp, _i, _i, _vp, _vp]),
-    "orp_scene_tiles_resized_flip": (_i, [_vp, _i, _i, ctypes.c_longlong, _vp, _i, _i, _i, _i, _i, _i, _i, _vp, _vp, _vp, _vp, _vp,
-                                          _vp, _i, _i, _vp, _vp]),
-    "orp_scene_collect_workspace_bytes": (_sz, [_i, _i]),
-    "orp_scene_collect": (_i, [_vp, _i, _i, _vp, ctypes.c_double, _i, _i, _vp, _vp, _vp, _vp, _vp, _sz, _vp]),
-    "orp_train_images_scratch_bytes": (_sz, [_i, _i]),
-    "orp_train_images": (_i, [_vp, _sz, _vp, _vp, _i, _vp, _vp, _vp, _i, _vp, _vp, _i, _i, _vp, _i, _i, _vp, _sz, _vp]),
-    "orp_soft_rnms_host":(_i, [_vp, _i, _f, _i, _f, _f, _vp, _vp]),
-    "orp_conv1x1_packed_floats": (_sz, [_i]),
-    "orp_conv1x1_ok": (_i, [_i, _i]),
-    "orp_conv1x1_pack_weight": (_i, [_vp, _i, _i, _vp, _vp]),
-    "orp_conv1x1_multi": (_i, [_vp, _i, _i, _i, _i, _vp, _vp, _vp, _i, _vp]),
-    "orp_conv1x1_bn_act_ok": (_i, [_i, _i]),
-    "orp_conv1x1_bn_act_pays": (_i, [_i, _i, _i, _i, _i]),
-    "orp_conv1x1_bn_act_tile": (_i, [_i, _i, _i, _i, _vp, _vp]),
-    "orp_conv1x1_bn_act": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _vp]),
-    "orp_conv1x1_bn_act_range": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _vp, _vp]),
-    "orp_affine_act_range": (_i, [_vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _vp, _vp]),
-    "orp_conv1x1_bn_act_pieces_ok": (_i, [_i, _i]),
-    "orp_conv1x1_bn_act_pieces_pays": (_i, [_i, _i, _i, _i, _i]),
-    "orp_conv1x1_bn_act_pieces_tile": (_i, [_i, _i, _i, _i, _vp, _vp]),
-    "orp_conv1x1_bn_pieces_packed_bytes": (_sz, [_i, _i]),
-    "orp_conv1x1_bn_pieces_pack_weight": (_i, [_vp, _i, _i, _vp, _vp]),
-    "orp_conv1x1_bn_act_pieces": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _vp, _vp]),
-    "orp_conv1x1_bn_act_pieces_dual_ok": (_i, [_i, _i, _i]),
-    "orp_conv1x1_bn_act_pieces_dual_pays": (_i, [_i, _i, _i, _i, _i, _i]),
-    "orp_conv1x1_bn_act_pieces_dual_tile": (_i, [_i, _i, _i, _i, _i, _vp, _vp]),
-    "orp_conv1x1_bn_act_pieces_dual": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _vp, _i, _i, _i, _i, _i, _i, _vp]),
-    "orp_conv3x3_bn_act_ok": (_i, [_i, _i]),
-    "orp_conv3x3_bn_act_pays": (_i, [_i, _i, _i, _i, _i]),
-    "orp_conv3x3_bn_act_tile": (_i, [_i, _i, _i, _i, _i, _vp, _vp, _vp, _vp]),
-    "orp_conv3x3_bn_packed_bytes": (_sz, [_i, _i]),
-    "orp_conv3x3_bn_pack_weight": (_i, [_vp, _i, _i, _vp, _vp]),
-    "orp_conv3x3_bn_act": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _vp]),
-    "orp_conv3x3_bn_deep_ok": (_i, [_i, _i, _i]),
-    "orp_conv3x3_bn_deep_pays": (_i, [_i, _i, _i, _i, _i, _i]),
-    "orp_conv3x3_bn_deep_packed_bytes": (_sz, [_i, _i]),
-    "orp_conv3x3_bn_deep_pack_weight": (_i, [_vp, _i, _i, _vp, _vp]),
-    "orp_conv3x3_bn_deep": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _i, _vp]),
-    "orp_conv3x3_bn_s2_ok": (_i, [_i, _i]),
-    "orp_conv3x3_bn_s2_pays": (_i, [_i, _i, _i, _i, _i]),
-    "orp_conv3x3_bn_s2_packed_bytes": (_sz, [_i, _i]),
-    "orp_conv3x3_bn_s2_pack_weight": (_i, [_vp, _i, _i, _vp, _vp]),
-    "orp_conv3x3_bn_s2": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _vp]),
-    "orp_stem_ok": (_i, [_i, _i, _i, _i, _i]),
-    "orp_stem_pays": (_i, [_i, _i, _i]),
-    "orp_stem_packed_bytes": (_sz, [_i, _i]),
-    "orp_stem_pack_weight": (_i, [_vp, _i, _i, _vp, _vp]),
-    "orp_stem_conv_bn_relu_pool": (_i, [_vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _i, _i, _i, _vp]),
-    "orp_pp_select_scratch_bytes": (_sz, [_i, _i, _i]),
-    "orp_pp_select": (_i, [_vp, _i, _i, _vp, _i, _i, _vp, _vp, _sz, _vp]),
-    "orp_pp_gather": (_i, [_vp, _vp, _i, _i, _vp, _vp, _vp, _i, _vp, _vp, _vp, _vp, _vp]),
-    "orp_pp_compact_scratch_bytes": (_sz, [_i]),
-    "orp_pp_compact": (_i, [_vp, _vp, _i, _i, _i, _vp, _f, _i, _vp, _vp, _vp, _vp, _vp, _vp, _sz, _vp]),
-    "orp_pp_compact_views_scratch_bytes": (_sz, [_i]),
-    "orp_pp_compact_views": (_i, [_vp, _i, _i, _f, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _sz, _vp]),
-    "orp_pp_pack": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _vp, _vp]),
-    "orp_groupnorm_workspace_bytes": (_sz, [_vp, _i, _i, _i, _i]),
-    "orp_groupnorm_act_multi": (_i, [_vp, _i, _i, _i, _i, _vp, _vp, _f, _i, _vp, _sz, _vp]),
-    "orp_groupnorm_act_multi_ex": (_i, [_vp, _vp, _vp, _i, _i, _i, _i, _f, _i, _vp, _sz, _vp]),
-    "orp_groupnorm_act_multi_nhwc": (_i, [_vp, _vp, _vp, _vp, _i, _i, _i, _i, _f, _i, _vp, _sz, _vp]),
-    "orp_groupnorm_act_multi_train": (_i, [_vp, _vp, _vp, _i, _i, _i, _i, _f, _i, _vp, _vp, _sz, _vp]),
-    "orp_groupnorm_backward_workspace_bytes": (_sz, [_vp, _i, _i, _i, _i]),
-    "orp_groupnorm_act_multi_backward": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _vp, _vp, _sz, _vp]),
-    "orp_voc_best_match_f64": (_i, [_vp, _vp, _i, _vp, _vp, _i, _vp, _vp, _vp]),
-    "orp_affine_act": (_i, [_vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _vp]),
-    "orp_affine2_act": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _vp]),
-    "orp_affine_relu_maxpool": (_i, [_vp, _vp, _vp, _vp, _i, _i, _i, _i, _vp]),
-    "orp_affine_act_backward_workspace_bytes": (_sz, [_i, _i, _i]),
-    "orp_affine_act_backward": (_i, [_vp] * 10 + [_i, _i, _i, _vp, _sz, _vp]),
-    "orp_affine2_act_backward": (_i, [_vp] * 17 + [_i, _i, _i, _vp, _sz, _vp]),
-    "orp_fpn_topdown_workspace_bytes": (_sz, [_vp, _i, _i, _i, _i]),
-    "orp_fpn_topdown_nhwc": (_i, [_vp, _vp, _vp, _i, _i, _i, _i, _f, _vp, _vp, _sz, _vp]),
-    "orp_bias_act_multi": (_i, [_vp, _i, _i, _i, _vp, _vp, _i, _vp]),
-    "orp_conv3x3_small_ok": (_i, [_i, _i]),
-    "orp_conv3x3_small_multi": (_i, [_vp, _i, _i, _i, _i, _vp, _vp]),
-    "orp_conv3x3_small_multi_ex": (_i, [_vp, _vp, _i, _i, _i, _i, _vp]),
-    "orp_border_rows": (_i, [_vp, _vp, _vp, _i, _vp, _vp, _vp, _vp]),
-    "orp_giou_rows": (_i, [_vp, _vp, _vp, _vp, _vp, _i, _f, _vp, _vp, _vp]),
-    "orp_segment_finish": (_i, [_vp, _vp, _vp, _i, _i, _vp, _f, _i, _vp, _vp, _vp]),
-    "orp_conv3x3_small_workspace_bytes": (ctypes.c_size_t, [_vp, _vp, _i, _i, _i]),
-    "orp_conv3x3_small_multi_strided": (_i, [_vp, _vp, _vp, _i, _i, _i, _i, _vp, ctypes.c_size_t, _vp]),
-    "orp_conv_split_ok": (_i, [_i, _i, _i, _i]),
-    "orp_conv_split_multi": (_i, [_vp, _i, _i, _i, _i, _vp, _vp, _vp, _vp] + [_i] * 11 + [_vp, _sz, _vp, _i, _vp]),
-    "orp_conv_split_multi_ex": (_i, [_vp, _vp, _vp, _i, _i, _i, _i] + [_i] * 11 + [_vp, _sz, _vp, _vp]),
-    "orp_conv_split_set_halo": (_i, [_i]),
-    "orp_conv_split_halo_tile": (_i, [_vp] + [_i] * 10 + [_vp, _vp]),
-    "orp_conv_wgrad_split_ok": (_i, [_i, _i, _i, _i]),
-    "orp_conv_wgrad_split_workspace_bytes": (_sz, [_vp, _i, _i, _i, _i]),
-    "orp_conv_wgrad_split": (_i, [_vp, _i, _i, _i, _i, _i, _i, _i, _i, _i, _i, _vp, _vp, _vp, _vp, _sz, _vp]),
-    "orp_nchw_to_nhwc_multi_amax": (_i, [_vp, _i, _i, _i, _vp, _vp, _i, _i, _vp]),
-    "orp_groupnorm_act_multi_cl_amax": (_i, [_vp, _vp, _vp, _i, _i, _i, _i, _f, _i, _vp, _vp, _i, _vp, _sz, _vp]),
-    "orp_dcn_forward_pair_amax": (_i, [_vp, _vp, _vp, _i, _i, _i, _i, _vp, _vp, _vp, _vp] + [_i] * 11 + [_vp, _sz, _vp, _i, _vp]),
-    "orp_nchw_to_nhwc_multi": (_i, [_vp, _i, _i, _i, _vp]),
-    "orp_groupnorm_cl_workspace_bytes": (_sz, [_vp, _i, _i, _i, _i]),
-    "orp_groupnorm_act_multi_cl": (_i, [_vp, _vp, _vp, _i, _i, _i, _i, _f, _i, _vp, _sz, _vp]),
-    "orp_debug_amax_log": (_i, [_vp, _i]),
-    "orp_conv_split_gn_partial_floats": (_sz, [_vp, _i, _i, _i, _i]),
-    "orp_conv_split_multi_gn": (_i, [_vp, _i, _i, _i, _i, _vp, _vp] + [_i] * 7 + [_vp, _i, _vp, _sz, _i, _vp, _sz, _vp, _i, _i, _vp]),
-    "orp_conv_split_gn_finish": (_i, [_vp, _i, _i, _i, _i, _i, _f, _vp, _vp, _vp, _vp, _vp, _vp]),
-    "orp_affine_act_multi_cl": (_i, [_vp, _i, _i, _i, _vp, _i, _vp, _i, _i, _vp, _vp]),
-    "orp_window_attention": (_i, [_vp, _vp, _vp] + [_i] * 7 + [_f, _vp, _vp]),
-    "orp_window_attention_train": (_i, [_vp, _vp, _vp] + [_i] * 7 + [_f, _vp, _vp, _vp]),
-    "orp_window_attention_backward_workspace_bytes": (_sz, [_i] * 6),
-    "orp_window_attention_backward": (_i, [_vp] * 6 + [_i] * 7 + [_f, _vp, _vp, _vp, _vp, _sz, _vp]),
-    "orp_window_attention_h": (_i, [_vp, _vp, _vp] + [_i] * 7 + [_f, _vp, _vp, _i, _vp]),
-    "orp_window_attention_backward_h": (_i, [_vp] * 6 + [_i] * 7 + [_f, _vp, _vp, _vp, _vp, _sz, _i, _vp]),
-    "orp_token_linear_ok": (_i, [_i, _i]),
-    "orp_token_linear_pays": (_i, [ctypes.c_long, _i, _i, _i]),
-    "orp_token_linear_packed_bytes": (_sz, [_i, _i]),
-    "orp_token_linear_pack_weight": (_i, [_vp, _i, _i, _vp, _vp]),
-    "orp_token_linear": (_i, [_vp, _vp, _vp, _vp, _vp, ctypes.c_long, _i, _i, _i, _vp]),
-}
-
-_lib = None
+HEADER_PATH = os.path.join(os.path.dirname(_HERE), "include", "orp_hip.h")
 
 
 class OrpHipError(RuntimeError):
     pass
+
+
+_SCALARS = {"int": ctypes.c_int, "int32_t": ctypes.c_int, "uint32_t": ctypes.c_uint32, "float": ctypes.c_float,
+            "double": ctypes.c_double, "size_t": ctypes.c_size_t, "long": ctypes.c_long, "long long": ctypes.c_longlong,
+            "int64_t": ctypes.c_longlong}
+_POINTEES = set(_SCALARS) | {"void", "char", "uint8_t"}
+
+
+def _ctype(spec, structs, decl, field=False, result=False):
+    """ctypes type of the C type `spec` (no declarator) as an argument, a struct field or a function's result.  Pointers are
+    c_void_p, except a field that points to a parsed struct and a `char*` result; `decl` is what the error quotes."""
+    base = " ".join(w for w in spec.replace("*", " ").split() if w != "const")
+    stars = spec.count("*")
+    if result and (base, stars) in (("void", 0), ("char", 1)):
+        return ctypes.c_char_p if stars else None
+    if stars == 0 and base in _SCALARS:
+        return _SCALARS[base]
+    if stars and not result and (base in _POINTEES or base in structs):
+        return ctypes.POINTER(structs[base]) if field and stars == 1 and base in structs else ctypes.c_void_p
+    raise OrpHipError("orp_hip.h: cannot map the type `%s` in `%s`" % (spec.strip(), decl))
+
+
+def _declarator(text, decl):
+    """`<type> <name>` or `<type> <name>[<n>]` -> (type, name, n or None)."""
+    m = re.fullmatch(r"([\w\s*]*[\s*])(\w+)\s*(?:\[\s*(\d+)\s*\])?", text.strip())
+    if not m or m.group(2) in _POINTEES or m.group(2) == "const":     # (an unnamed `long long` is not a `long` called long)
+        raise OrpHipError("orp_hip.h: cannot parse `%s` in `%s`" % (text.strip(), decl))
+    return m.group(1), m.group(2), m.group(3) and int(m.group(3))
+
+
+def parse_header(text):
+    """C header text -> (signatures {name: (restype, argtypes)}, structs {name: ctypes.Structure}, constants {ORP_*: int})."""
+    text = re.sub(r"/\*.*?\*/|//[^\n]*", " ", text, flags=re.S)
+    signatures, structs, constants = {}, {}, {}
+    for name, value in re.findall(r"^[ \t]*#[ \t]*define[ \t]+(ORP_\w+)[ \t]+(\S.*?)[ \t]*$", text, flags=re.M):
+        m = re.fullmatch(r"\(\s*(-?\s*\w+)\s*\)|(-?\s*\w+)", value)
+        try:
+            constants[name] = int((m.group(1) or m.group(2)).replace(" ", ""), 0)
+        except (AttributeError, ValueError):
+            raise OrpHipError("orp_hip.h: `#define %s %s` is not an integer" % (name, value))
+    text = re.sub(r"^[ \t]*#.*$", " ", text, flags=re.M)
+    text = re.sub(r'extern\s+"C"\s*\{(.*)\}', r"\1", text, flags=re.S)
+    depth, start, decls = 0, 0, []
+    for m in re.finditer(r"[{};]", text):       # a declaration ends at a `;` outside braces
+        depth += (m.group() == "{") - (m.group() == "}")
+        if m.group() == ";" and depth == 0:
+            decls.append(" ".join(text[start:m.start()].split()))
+            start = m.end()
+    if text[start:].strip():
+        raise OrpHipError("orp_hip.h: unfinished declaration `%s`" % " ".join(text[start:].split()))
+    for decl in decls:
+        st = re.fullmatch(r"typedef struct(?: \w+)? ?\{([^{}]*)\} ?(\w+)", decl)
+        fn = re.fullmatch(r"([\w\s*]*[\s*])(\w+) ?\(([^()]*)\)", decl)
+        if (st and st.group(2) in structs) or (fn and fn.group(2) in signatures):
+            raise OrpHipError("orp_hip.h: declared twice: `%s`" % decl)
+        if st:
+            fields = []
+            for line in filter(None, (f.strip() for f in st.group(1).split(";"))):
+                first, *more = line.split(",")
+                spec = _declarator(first, line)[0]
+                if more and "*" in line:        # `float *a, *b` / `float* a, b`: the star binds to one name only
+                    raise OrpHipError("orp_hip.h: a pointer in the comma list `%s`" % line)
+                for d in [first] + [spec + " " + other for other in more]:
+                    _, name, n = _declarator(d, line)
+                    t = _ctype(spec, structs, line, field=True)
+                    fields.append((name, t if n is None else t * n))
+            structs[st.group(2)] = type(st.group(2), (ctypes.Structure,), {"_fields_": fields})
+        elif fn:
+            args = []
+            for p in ([] if fn.group(3).strip() == "void" else fn.group(3).split(",")):
+                spec, _, n = _declarator(p, decl)
+                if n is not None:
+                    raise OrpHipError("orp_hip.h: an array argument `%s` in `%s`" % (p.strip(), decl))
+                args.append(_ctype(spec, structs, decl))
+            signatures[fn.group(2)] = (_ctype(fn.group(1), structs, decl, result=True), args)
+        else:
+            raise OrpHipError("orp_hip.h: cannot parse the declaration `%s`" % decl)
+    return signatures, structs, constants
+
+
+def _load_header():
+    if not os.path.exists(HEADER_PATH):
+        raise OrpHipError("orientedreppoints_amd: the C header %s is missing; the binding is derived from it" % HEADER_PATH)
+    with open(HEADER_PATH) as f:
+        return parse_header(f.read())
+
+
+# name -> (restype, argtypes); name -> ctypes.Structure; ORP_* -> int: include/orp_hip.h, parsed once per process
+_SIGNATURES, _STRUCTS, _CONSTANTS = _load_header()
+ORP_OK, ORP_EINVAL, ORP_EWORKSPACE, ORP_ETOOBIG = (_CONSTANTS[k] for k in ("ORP_OK", "ORP_EINVAL", "ORP_EWORKSPACE", "ORP_ETOOBIG"))
+ORP_NMS_MAX_BOXES = _CONSTANTS["ORP_NMS_MAX_BOXES"]
+
+
+def struct(name):
+    """The ctypes.Structure of the header's `typedef struct { ... } name;` (field names and order as declared)."""
+    return _STRUCTS[name]
+
+
+_lib = None
 
 
 def lib():

@@ -62,7 +62,8 @@ SOURCES = [
     ("orp_token_linear.hip", []),
     ("orp_prof.hip", []),
 ]
-HEADERS = ["orp_affine.hpp", "orp_geom.hpp", "orp_quadfast.hpp", "orp_tile.hpp", "orp_hull.hpp", "orp_libm.hpp", "orp_prof.hpp", "orp_launch.hpp", "orp_dcn_split.hpp", "orp_dcn_common.hpp", "orp_range.hpp", "orp_conv1x1_bn_host.hpp", "orp_conv3x3_bn_host.hpp", os.path.join("..", "..", "include", "orp_hip.h")]
+# every header of csrc/ and the C ABI: each object depends on all of them, and build_id() hashes them
+HEADERS = sorted(f for f in os.listdir(CSRC) if f.endswith(".hpp")) + [os.path.join("..", "..", "include", "orp_hip.h")]
 
 
 def _stale(target, deps):

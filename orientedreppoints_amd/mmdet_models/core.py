@@ -293,10 +293,7 @@ def fused_postprocess(cls_scores, points_preds, strides, cfg, num_points=9, scal
     return _nms_and_pack(compact, sig, m0, C, cfg, boxes, rep)
 
 
-class PpView(ctypes.Structure):
-    """`orp_pp_view` of include/orp_hip.h."""
-    _fields_ = [(k, ctypes.c_void_p) for k in ('sig_all', 'cand', 'boxes', 'reppoints')] + \
-               [(k, ctypes.c_int) for k in ('m0', 'n', 'flip', 'img_width')] + [('scale', ctypes.c_double)]
+PpView = _lib.struct("orp_pp_view")
 
 
 def compact_views(views, num_classes, score_thr, capacity, boxes_all, rep_all, dets, sel_cand, sel_label, seg, total):

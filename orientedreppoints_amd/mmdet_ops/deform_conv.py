@@ -20,10 +20,7 @@ from torch.nn.modules.utils import _pair, _single
 from .. import _lib, _packcache
 
 
-class _DcnLevel(ctypes.Structure):
-    _fields_ = [("input", ctypes.c_void_p), ("offset", ctypes.c_void_p), ("output", ctypes.c_void_p),
-                ("height", ctypes.c_int), ("width", ctypes.c_int)]
-
+_DcnLevel = _lib.struct("orp_dcn_level")
 
 _packed_cache = _packcache.new_cache("dcn_weight_fp32")
 
@@ -186,10 +183,7 @@ def deform_conv_forward_multi_half(inputs, offsets, weight, stride, padding, dil
     nhwc = all(x.dim() == 4 and x.is_contiguous(memory_format=torch.channels_last) and not x.is_contiguous()
                for x in inputs)
     packed = _packed_weight_h(weight, cache_pack)
-
-    class _LevelH(ctypes.Structure):
-        _fields_ = [("input", ctypes.c_void_p), ("offset", ctypes.c_void_p), ("output", ctypes.c_void_p),
-                    ("height", ctypes.c_int), ("width", ctypes.c_int)]
+    _LevelH = _lib.struct("orp_dcn_level_h")
     levels = (_LevelH * len(inputs))()
     keep, outs = [], []
     for i, (x, off) in enumerate(zip(inputs, offsets)):
@@ -295,15 +289,8 @@ def deform_conv_forward_pair(inputs_a, inputs_b, offsets, weight_a, weight_b, st
     return outs_a, outs_b
 
 
-class _DcnHeadLevel(ctypes.Structure):
-    _fields_ = [("output_a", ctypes.c_void_p), ("output_b", ctypes.c_void_p), ("residual_b", ctypes.c_void_p)]
-
-
-class _DcnHeads(ctypes.Structure):
-    _fields_ = [("weight_a_packed", ctypes.c_void_p), ("bias_a", ctypes.c_void_p), ("k_a", ctypes.c_int),
-                ("weight_b_packed", ctypes.c_void_p), ("bias_b", ctypes.c_void_p), ("k_b", ctypes.c_int),
-                ("levels", ctypes.POINTER(_DcnHeadLevel))]
-
+_DcnHeadLevel = _lib.struct("orp_dcn_head_level")
+_DcnHeads = _lib.struct("orp_dcn_heads")
 
 _packed_heads = _packcache.new_cache("dcn_head_1x1")
 

@@ -10,12 +10,7 @@ import torch
 
 from .. import _lib
 
-
-class _BwdLevel(ctypes.Structure):
-    _fields_ = [("input", ctypes.c_void_p), ("offset", ctypes.c_void_p), ("grad_output", ctypes.c_void_p),
-                ("grad_input", ctypes.c_void_p), ("grad_offset", ctypes.c_void_p), ("height", ctypes.c_int),
-                ("width", ctypes.c_int)]
-
+_BwdLevel = _lib.struct("orp_dcn_bwd_level")
 
 USE_MFMA = True          # False: force the column formulation (comparisons in tests / tools)
 

@@ -15,9 +15,7 @@ import torch
 from .. import _lib, _packcache
 
 
-class _NormLevel(ctypes.Structure):
-    _fields_ = [("input", ctypes.c_void_p), ("output", ctypes.c_void_p), ("height", ctypes.c_int),
-                ("width", ctypes.c_int)]
+_NormLevel = _lib.struct("orp_norm_level")
 
 
 def _call(name, device, *args):
@@ -636,9 +634,7 @@ def fpn_topdown_cl(xs, gns, amax=True):
     return outs, bits
 
 
-class _BiasLevel(ctypes.Structure):
-    _fields_ = [("input", ctypes.c_void_p), ("residual", ctypes.c_void_p), ("output", ctypes.c_void_p),
-                ("output2", ctypes.c_void_p), ("height", ctypes.c_int), ("width", ctypes.c_int)]
+_BiasLevel = _lib.struct("orp_bias_level")
 
 
 def bias_act_multi(xs, bias, relu=False, residuals=None, sub=None):
@@ -955,9 +951,7 @@ def bn_act_train(x, bn, residual=None, relu=True, residual_bn=None):
 
 # ---- channels-last tower path (round 4): conv_split_multi -> group_norm_act_multi_cl -> ... -----------------------------------
 
-class _ConvLevel(ctypes.Structure):
-    _fields_ = [("input_a", ctypes.c_void_p), ("input_b", ctypes.c_void_p), ("output_a", ctypes.c_void_p),
-                ("output_b", ctypes.c_void_p), ("height", ctypes.c_int), ("width", ctypes.c_int)]
+_ConvLevel = _lib.struct("orp_conv_level")
 
 
 def _is_cl(x):
@@ -1219,8 +1213,7 @@ def conv_split_gn(xs_a, conv_a, xs_b, conv_b, gn_a, gn_b, coef_in=None, amax=Non
     return outs_a, outs_b, None, (Amax(slots, 1) if slots is not None else None)
 
 
-class _WgradLevel(ctypes.Structure):
-    _fields_ = [("input", ctypes.c_void_p), ("grad_output", ctypes.c_void_p), ("height", ctypes.c_int), ("width", ctypes.c_int)]
+_WgradLevel = _lib.struct("orp_wgrad_level")
 
 
 def conv_wgrad_split_ok(weight, padding, dilation):

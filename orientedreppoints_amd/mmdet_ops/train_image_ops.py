@@ -13,9 +13,7 @@ from .. import _lib
 from .scene_ops import resize_axis
 
 # orp_train_image_desc of include/orp_hip.h, 64 bytes
-DESC_DTYPE = np.dtype([('src_offset', '<i8'), ('scratch_offset', '<i8'), ('src_h', '<i4'), ('src_w', '<i4'), ('new_h', '<i4'),
-                       ('new_w', '<i4'), ('pad_h', '<i4'), ('pad_w', '<i4'), ('flip', '<i4'), ('rotate', '<i4'),
-                       ('x_table', '<i4'), ('y_table', '<i4'), ('reserved', '<i4', (2,))])
+DESC_DTYPE = np.dtype(_lib.struct("orp_train_image_desc"))
 assert DESC_DTYPE.itemsize == 64
 
 FLIP_CODES = {None: 0, 'horizontal': 1, 'vertical': 2}

@@ -2,18 +2,13 @@
 `orp_gather_levels`, `orp_outline_samples`; csrc/orp_train.hip).  No counterpart module in the reference: there this work
 is per-image / per-level Python loops of small tensor operations inside pointset_target.py and
 orientedreppoints_head.py (loss, offset_to_pts, sampling_points)."""
-import ctypes
-
 import torch
 from torch.autograd import Function
 from torch.autograd.function import once_differentiable
 
 from .. import _lib
 
-
-class _LevelDesc(ctypes.Structure):
-    _fields_ = [("data", ctypes.c_void_p), ("grad", ctypes.c_void_p), ("height", ctypes.c_int), ("width", ctypes.c_int),
-                ("stride", ctypes.c_float)]
+_LevelDesc = _lib.struct("orp_level_desc")
 
 
 def _level_table(levels, strides, grads=None):
