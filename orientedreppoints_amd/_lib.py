@@ -144,6 +144,21 @@ def check(rc, what):
         raise OrpHipError("%s failed: %s" % (what, names.get(rc, "hipError %d" % rc)))
 
 
+def call(name, device, *args):
+    """one launch: the library's entry point `name`, looked up at call time, under the device guard, its return code checked"""
+    with torch.cuda.device(device):
+        rc = getattr(lib(), name)(*args)
+    check(rc, name)
+
+
+def tile_query(name, n, *shape):
+    """the n integers the library's `name`(shape..., n int pointers) fills for a launch of this shape, or None where it returns 0"""
+    v = [ctypes.c_int() for _ in range(n)]
+    if not getattr(lib(), name)(*[int(s) for s in shape], *[ctypes.byref(t) for t in v]):
+        return None
+    return tuple(t.value for t in v)
+
+
 def ptr(t):
     """Device (or host) address of a contiguous tensor, or NULL."""
     if t is None:

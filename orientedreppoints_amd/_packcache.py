@@ -14,6 +14,10 @@ An entry belongs to ONE live Python object (an nn.Parameter or an nn.Module):
 """
 import weakref
 
+import torch
+
+from . import _lib
+
 
 class OwnerCache:
     def __init__(self, name):
@@ -68,3 +72,30 @@ def stats():
 
 def tensor_state(t):
     return (t.data_ptr(), t._version, tuple(t.shape), t.dtype, t.device.index)
+
+
+def packed(cache, owner, build, state=None, store=True):
+    """The cache protocol of every pack: `cache`'s entry of the live `owner` in this `state` (default: the tensor's storage / version
+    state), made by build() on a miss; hit or miss, handed to a graph that is being captured (`_lib.keep_for_graph`), which must
+    outlive the entry.  store=False (training: optimizers write through `.data`): build() now, nothing looked up, kept or registered."""
+    if not store:
+        return build()
+    if state is None:
+        state = tensor_state(owner.detach())
+    hit = cache.get(owner, state)
+    if hit is None:
+        hit = cache.put(owner, state, build())
+    return _lib.keep_for_graph(hit)
+
+
+def packed_planes(cache, weight, size_fn, pack_fn, view):
+    """weight [Cout,Cin,...] -> the byte buffer the library's `pack_fn` fills from view(weight) (fp32, contiguous), `size_fn`(Cin, Cout)
+    bytes; cached on the live parameter as `packed` says (inference only)."""
+    def build():
+        w = weight.detach()
+        cout, cin = w.size(0), w.size(1)
+        w32 = view(w)
+        planes = torch.empty((getattr(_lib.lib(), size_fn)(cin, cout),), dtype=torch.uint8, device=w.device)
+        _lib.call(pack_fn, w.device, _lib.ptr(w32), cin, cout, _lib.ptr(planes), _lib.stream_of(w32))
+        return planes
+    return packed(cache, weight, build)

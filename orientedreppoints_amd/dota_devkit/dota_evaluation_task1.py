@@ -62,11 +62,8 @@ def best_match_gpu(BB, det_img, gts, gt_off, device=None):
     go = torch.from_numpy(np.ascontiguousarray(gt_off, np.int32)).to(dev)
     ov = torch.empty((nd,), dtype=torch.float64, device=dev)
     jm = torch.empty((nd,), dtype=torch.int32, device=dev)
-    with torch.cuda.device(dev):
-        rc = _lib.lib().orp_voc_best_match_f64(_lib.ptr(d), _lib.ptr(di), nd, _lib.ptr(g) if g.numel() else None,
-                                               _lib.ptr(go), int(go.numel()) - 1, _lib.ptr(ov), _lib.ptr(jm),
-                                               _lib.stream_of(d))
-    _lib.check(rc, "orp_voc_best_match_f64")
+    _lib.call("orp_voc_best_match_f64", dev, _lib.ptr(d), _lib.ptr(di), nd, _lib.ptr(g) if g.numel() else None, _lib.ptr(go),
+              int(go.numel()) - 1, _lib.ptr(ov), _lib.ptr(jm), _lib.stream_of(d))
     return ov.cpu().numpy(), jm.cpu().numpy()
 
 

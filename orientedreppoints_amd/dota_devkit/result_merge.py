@@ -32,10 +32,8 @@ def py_gpu_nms_poly(dets, thresh, device=None):
     keep = torch.empty((n,), dtype=torch.long, device=dev)
     num = torch.empty((1,), dtype=torch.int32, device=dev)
     ws = _lib.workspace(dev, L.orp_poly_nms_f64_workspace_bytes(n))
-    with torch.cuda.device(dev):
-        rc = L.orp_poly_nms_f64(_lib.ptr(d), n, float(thresh), _lib.ptr(keep), _lib.ptr(num), _lib.ptr(ws), ws.numel(),
-                                _lib.stream_of(d))
-    _lib.check(rc, "orp_poly_nms_f64")
+    _lib.call("orp_poly_nms_f64", dev, _lib.ptr(d), n, float(thresh), _lib.ptr(keep), _lib.ptr(num), _lib.ptr(ws), ws.numel(),
+              _lib.stream_of(d))
     k = keep[:int(num.item())].cpu().numpy()
     return [int(i) for i in order[k]]
 

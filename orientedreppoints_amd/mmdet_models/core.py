@@ -200,7 +200,6 @@ def _decode_candidates(cls_scores, points_preds, strides, cfg, num_points=9):
     Returns (sig [C, N], cand [m0] int64, boxes [m0, 8], reppoints [m0, 18]), fp32, boxes and rep-points in the image's own scale."""
     from ..mmdet_ops.minarea_rect import minaerarect_decode
     assert num_points == 9
-    L = _lib.lib()
     dev = cls_scores[0].device
     C = cls_scores[0].size(0)
     sizes = [int(c.size(1)) * int(c.size(2)) for c in cls_scores]
@@ -235,16 +234,14 @@ def _decode_candidates(cls_scores, points_preds, strides, cfg, num_points=9):
     lo = (ctypes.c_int * len(sizes))(*[int(o) for o in offs[:-1]])
     lw = (ctypes.c_int * len(sizes))(*widths)
     ls = (ctypes.c_float * len(sizes))(*[float(s) for s in strides])
-    with torch.cuda.device(dev):
-        _lib.check(L.orp_pp_gather(_lib.ptr(pts_all), _lib.ptr(cand), m0, N, lo, lw, ls, len(sizes), _lib.ptr(pts_xy),
-                                   _lib.ptr(centers), _lib.ptr(strd), _lib.ptr(rep), _lib.stream_of(sig)), "orp_pp_gather")
+    _lib.call("orp_pp_gather", dev, _lib.ptr(pts_all), _lib.ptr(cand), m0, N, lo, lw, ls, len(sizes), _lib.ptr(pts_xy), _lib.ptr(centers),
+              _lib.ptr(strd), _lib.ptr(rep), _lib.stream_of(sig))
     return sig, cand, minaerarect_decode(pts_xy, centers, strd), rep
 
 
 def _nms_and_pack(compact, sig, m0, C, cfg, boxes, rep):
     """The back of the fused post-processing: `compact(cap, dets, sel_cand, sel_label, seg, total)` fills the detections of
     m0 candidate rows, then one `rnms_batched_device` and one `orp_pp_pack` over `boxes` / `rep`.  Returns packed [m + 1, 28]."""
-    L = _lib.lib()
     dev = sig.device
     f32 = dict(dtype=torch.float32, device=dev)
     cap = int(min(cfg.get('static_capacity', 8192), m0 * C))
@@ -260,10 +257,8 @@ def _nms_and_pack(compact, sig, m0, C, cfg, boxes, rep):
     compact(cap, dets, sel_cand, sel_label, seg, total)
     keep, num = nms_wrapper.rnms_batched_device(dets, seg, cap, nms_cfg_.get('iou_thr', 0.4))
     packed = torch.empty((m + 1, 28), **f32)
-    with torch.cuda.device(dev):
-        _lib.check(L.orp_pp_pack(_lib.ptr(keep), _lib.ptr(num), _lib.ptr(dets), _lib.ptr(sel_cand), _lib.ptr(sel_label),
-                                 _lib.ptr(boxes), _lib.ptr(rep), _lib.ptr(total), cap, m, _lib.ptr(packed),
-                                 _lib.stream_of(sig)), "orp_pp_pack")
+    _lib.call("orp_pp_pack", dev, _lib.ptr(keep), _lib.ptr(num), _lib.ptr(dets), _lib.ptr(sel_cand), _lib.ptr(sel_label), _lib.ptr(boxes),
+              _lib.ptr(rep), _lib.ptr(total), cap, m, _lib.ptr(packed), _lib.stream_of(sig))
     return packed
 
 
@@ -284,12 +279,10 @@ def fused_postprocess(cls_scores, points_preds, strides, cfg, num_points=9, scal
         rep /= scale
 
     def compact(cap, dets, sel_cand, sel_label, seg, total):
-        with torch.cuda.device(dev):
-            scratch = torch.empty((L.orp_pp_compact_scratch_bytes(m0),), dtype=torch.uint8, device=dev)
-            _lib.check(L.orp_pp_compact(_lib.ptr(sig), _lib.ptr(cand), m0, N, C, _lib.ptr(boxes), float(cfg.score_thr), cap,
-                                        _lib.ptr(dets), _lib.ptr(sel_cand), _lib.ptr(sel_label), _lib.ptr(seg),
-                                        _lib.ptr(total), _lib.ptr(scratch), scratch.numel(), _lib.stream_of(sig)),
-                       "orp_pp_compact")
+        scratch = torch.empty((L.orp_pp_compact_scratch_bytes(m0),), dtype=torch.uint8, device=dev)
+        _lib.call("orp_pp_compact", dev, _lib.ptr(sig), _lib.ptr(cand), m0, N, C, _lib.ptr(boxes), float(cfg.score_thr), cap, _lib.ptr(dets),
+                  _lib.ptr(sel_cand), _lib.ptr(sel_label), _lib.ptr(seg), _lib.ptr(total), _lib.ptr(scratch), scratch.numel(),
+                  _lib.stream_of(sig))
     return _nms_and_pack(compact, sig, m0, C, cfg, boxes, rep)
 
 
@@ -309,12 +302,10 @@ def compact_views(views, num_classes, score_thr, capacity, boxes_all, rep_all, d
     m_all = sum(v[1].numel() for v in views)
     if tuple(boxes_all.shape) != (m_all, 8) or tuple(rep_all.shape) != (m_all, 18):
         raise ValueError("compact_views: boxes_all / rep_all must hold the %d rows of all views" % m_all)
-    with torch.cuda.device(dev):
-        scratch = torch.empty((L.orp_pp_compact_views_scratch_bytes(m_all),), dtype=torch.uint8, device=dev)
-        _lib.check(L.orp_pp_compact_views(arr, len(views), int(num_classes), float(score_thr), int(capacity), _lib.ptr(boxes_all),
-                                          _lib.ptr(rep_all), _lib.ptr(dets), _lib.ptr(sel_cand), _lib.ptr(sel_label),
-                                          _lib.ptr(seg), _lib.ptr(total), _lib.ptr(scratch), scratch.numel(),
-                                          _lib.stream_of(dets)), "orp_pp_compact_views")
+    scratch = torch.empty((L.orp_pp_compact_views_scratch_bytes(m_all),), dtype=torch.uint8, device=dev)
+    _lib.call("orp_pp_compact_views", dev, arr, len(views), int(num_classes), float(score_thr), int(capacity), _lib.ptr(boxes_all),
+              _lib.ptr(rep_all), _lib.ptr(dets), _lib.ptr(sel_cand), _lib.ptr(sel_label), _lib.ptr(seg), _lib.ptr(total),
+              _lib.ptr(scratch), scratch.numel(), _lib.stream_of(dets))
 
 
 def fused_postprocess_views(outs_per_view, strides, cfg, metas, rescale=False, num_points=9):
@@ -354,10 +345,9 @@ def select_candidates(sig, offs, nms_pre):
     cand = torch.empty((m0,), dtype=torch.int64, device=sig.device)
     lo = (ctypes.c_int * nlev)(*[int(o) for o in offs[:-1]])
     nbytes = L.orp_pp_select_scratch_bytes(N, nms_pre, nlev)
-    with torch.cuda.device(sig.device):
-        scratch = torch.empty((nbytes,), dtype=torch.uint8, device=sig.device)
-        _lib.check(L.orp_pp_select(_lib.ptr(sig), C, N, lo, nlev, int(nms_pre), _lib.ptr(cand), _lib.ptr(scratch), nbytes,
-                                   _lib.stream_of(sig)), "orp_pp_select")
+    scratch = torch.empty((nbytes,), dtype=torch.uint8, device=sig.device)
+    _lib.call("orp_pp_select", sig.device, _lib.ptr(sig), C, N, lo, nlev, int(nms_pre), _lib.ptr(cand), _lib.ptr(scratch), nbytes,
+              _lib.stream_of(sig))
     return cand
 
 

@@ -16,10 +16,8 @@ def point_assign(points, gt_rbboxes, scale=4, pos_num=1):
     out = torch.empty((n,), dtype=torch.long, device=p.device)
     L = _lib.lib()
     ws = _lib.workspace(p.device, L.orp_point_assign_workspace_bytes(n))
-    with torch.cuda.device(p.device):
-        rc = L.orp_point_assign(_lib.ptr(p), n, _lib.ptr(g), k, float(scale), int(pos_num), _lib.ptr(out),
-                                _lib.ptr(ws), ws.numel(), _lib.stream_of(p))
-    _lib.check(rc, "orp_point_assign")
+    _lib.call("orp_point_assign", p.device, _lib.ptr(p), n, _lib.ptr(g), k, float(scale), int(pos_num), _lib.ptr(out), _lib.ptr(ws),
+              ws.numel(), _lib.stream_of(p))
     return out
 
 
@@ -36,11 +34,8 @@ def max_iou_assign(overlaps_nk, pos_iou_thr, neg_iou_thr, min_pos_iou=0.0, gt_ma
     max_ov = torch.empty((n,), dtype=torch.float32, device=ov.device)
     L = _lib.lib()
     ws = _lib.workspace(ov.device, L.orp_max_iou_assign_workspace_bytes(k))
-    with torch.cuda.device(ov.device):
-        rc = L.orp_max_iou_assign(_lib.ptr(ov), n, k, float(pos_iou_thr), lo, hi, float(min_pos_iou),
-                                  int(bool(gt_max_assign_all)), _lib.ptr(gt_inds), _lib.ptr(max_ov), _lib.ptr(ws),
-                                  ws.numel(), _lib.stream_of(ov))
-    _lib.check(rc, "orp_max_iou_assign")
+    _lib.call("orp_max_iou_assign", ov.device, _lib.ptr(ov), n, k, float(pos_iou_thr), lo, hi, float(min_pos_iou),
+              int(bool(gt_max_assign_all)), _lib.ptr(gt_inds), _lib.ptr(max_ov), _lib.ptr(ws), ws.numel(), _lib.stream_of(ov))
     return gt_inds, max_ov
 
 
@@ -59,10 +54,8 @@ def apaa_feature_dissimilarity(feats, strides, pts18, img_index, level_index):
     st = (ctypes.c_float * nl)(*[float(s) for s in strides])
     ii = img_index.to(device=p.device, dtype=torch.int32).contiguous()
     li = level_index.to(device=p.device, dtype=torch.int32).contiguous()
-    with torch.cuda.device(p.device):
-        rc = _lib.lib().orp_apaa_feature_dissimilarity(ptrs, hs, wsz, st, nl, fs[0].size(1), _lib.ptr(p), _lib.ptr(ii),
-                                                       _lib.ptr(li), P, _lib.ptr(out), _lib.stream_of(p))
-    _lib.check(rc, "orp_apaa_feature_dissimilarity")
+    _lib.call("orp_apaa_feature_dissimilarity", p.device, ptrs, hs, wsz, st, nl, fs[0].size(1), _lib.ptr(p), _lib.ptr(ii), _lib.ptr(li), P,
+              _lib.ptr(out), _lib.stream_of(p))
     return out
 
 
@@ -75,8 +68,6 @@ def apaa_select(quality, pos_gt_inds, pos_level, num_gt, num_level, per_level_to
         return keep.bool()
     g = pos_gt_inds.to(torch.long).contiguous()
     lv = pos_level.to(torch.int32).contiguous()
-    with torch.cuda.device(q.device):
-        rc = _lib.lib().orp_apaa_select(_lib.ptr(q), _lib.ptr(g), _lib.ptr(lv), P, int(num_gt), int(num_level),
-                                        int(per_level_topk), float(top_ratio), _lib.ptr(keep), _lib.stream_of(q))
-    _lib.check(rc, "orp_apaa_select")
+    _lib.call("orp_apaa_select", q.device, _lib.ptr(q), _lib.ptr(g), _lib.ptr(lv), P, int(num_gt), int(num_level), int(per_level_topk),
+              float(top_ratio), _lib.ptr(keep), _lib.stream_of(q))
     return keep.bool()

@@ -19,8 +19,5 @@ def box_iou_rotated(boxes1, boxes2):
         rc = _lib.lib().orp_box_iou_rotated_host(_lib.ptr(a), a.size(0), _lib.ptr(b), b.size(0), _lib.ptr(out))
         _lib.check(rc, "orp_box_iou_rotated_host")
         return out
-    with torch.cuda.device(a.device):
-        rc = _lib.lib().orp_box_iou_rotated(_lib.ptr(a), a.size(0), _lib.ptr(b), b.size(0), _lib.ptr(out),
-                                            _lib.stream_of(a))
-    _lib.check(rc, "orp_box_iou_rotated")
+    _lib.call("orp_box_iou_rotated", a.device, _lib.ptr(a), a.size(0), _lib.ptr(b), b.size(0), _lib.ptr(out), _lib.stream_of(a))
     return out

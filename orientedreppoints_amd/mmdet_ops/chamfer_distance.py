@@ -16,22 +16,16 @@ class _Chamfer2dExt(object):
             _lib.require_cuda(t, n)
         b, n, _ = xyz1.size()
         m = xyz2.size(1)
-        with torch.cuda.device(xyz1.device):
-            rc = _lib.lib().orp_chamfer2d_forward(_lib.ptr(xyz1), _lib.ptr(xyz2), b, n, m, _lib.ptr(dist1),
-                                                  _lib.ptr(dist2), _lib.ptr(idx1), _lib.ptr(idx2),
-                                                  _lib.stream_of(xyz1))
-        _lib.check(rc, "orp_chamfer2d_forward")
+        _lib.call("orp_chamfer2d_forward", xyz1.device, _lib.ptr(xyz1), _lib.ptr(xyz2), b, n, m, _lib.ptr(dist1), _lib.ptr(dist2),
+                  _lib.ptr(idx1), _lib.ptr(idx2), _lib.stream_of(xyz1))
         return 1
 
     @staticmethod
     def backward(xyz1, xyz2, gradxyz1, gradxyz2, graddist1, graddist2, idx1, idx2):
         b, n, _ = xyz1.size()
         m = xyz2.size(1)
-        with torch.cuda.device(xyz1.device):
-            rc = _lib.lib().orp_chamfer2d_backward(_lib.ptr(xyz1), _lib.ptr(xyz2), b, n, m, _lib.ptr(graddist1),
-                                                   _lib.ptr(graddist2), _lib.ptr(idx1), _lib.ptr(idx2),
-                                                   _lib.ptr(gradxyz1), _lib.ptr(gradxyz2), _lib.stream_of(xyz1))
-        _lib.check(rc, "orp_chamfer2d_backward")
+        _lib.call("orp_chamfer2d_backward", xyz1.device, _lib.ptr(xyz1), _lib.ptr(xyz2), b, n, m, _lib.ptr(graddist1), _lib.ptr(graddist2),
+                  _lib.ptr(idx1), _lib.ptr(idx2), _lib.ptr(gradxyz1), _lib.ptr(gradxyz2), _lib.stream_of(xyz1))
         return 1
 
 

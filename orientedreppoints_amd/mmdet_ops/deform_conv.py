@@ -33,21 +33,13 @@ def _packed_weight(weight, cache=True):
     gradient -- decided from `ctx.needs_input_grad`, because grad mode is always off inside Function.forward): the pack
     is rebuilt on every call, so an optimizer / EMA / `reset_parameters` writing through `.data` (no version bump) can
     never make forward and backward disagree (the pack costs ~1 % of the conv)."""
-    w = weight.detach()
-    state = _packcache.tensor_state(w)
-    if cache:
-        hit = _packed_cache.get(weight, state)
-        if hit is not None:
-            return _lib.keep_for_graph(hit)
-    w = w.float().contiguous()
-    cout, cin, kh, kw = w.shape
-    packed = torch.empty((_lib.lib().orp_dcn_packed_weight_floats(cout, cin, kh, kw),), dtype=torch.float32, device=w.device)
-    with torch.cuda.device(w.device):
-        rc = _lib.lib().orp_dcn_pack_weight(_lib.ptr(w), cout, cin, kh, kw, _lib.ptr(packed), _lib.stream_of(w))
-    _lib.check(rc, "orp_dcn_pack_weight")
-    if not cache:
+    def build():
+        w = weight.detach().float().contiguous()
+        cout, cin, kh, kw = w.shape
+        packed = torch.empty((_lib.lib().orp_dcn_packed_weight_floats(cout, cin, kh, kw),), dtype=torch.float32, device=w.device)
+        _lib.call("orp_dcn_pack_weight", w.device, _lib.ptr(w), cout, cin, kh, kw, _lib.ptr(packed), _lib.stream_of(w))
         return packed
-    return _lib.keep_for_graph(_packed_cache.put(weight, state, packed))
+    return _packcache.packed(_packed_cache, weight, build, store=cache)
 
 
 def invalidate_packed_weights():
@@ -113,12 +105,9 @@ def deform_conv_forward_multi(inputs, offsets, weight, stride, padding, dilation
     layout = 1 if nhwc else 0
     nbytes = L.orp_dcn_forward_workspace_bytes(levels, len(inputs), B, cin, layout)
     ws = _lib.workspace(x0.device, nbytes)
-    with torch.cuda.device(x0.device):
-        rc = L.orp_dcn_forward_multi_ex(levels, mask_ptrs, len(inputs), B, cin, cout, _lib.ptr(packed), _lib.ptr(b),
-                                        1 if relu else 0, kh, kw, stride[0], stride[1], padding[0], padding[1],
-                                        dilation[0], dilation[1], layout, layout, _lib.ptr(ws), ws.numel(),
-                                        _lib.stream_of(x0))
-    _lib.check(rc, "orp_dcn_forward_multi_ex")
+    _lib.call("orp_dcn_forward_multi_ex", x0.device, levels, mask_ptrs, len(inputs), B, cin, cout, _lib.ptr(packed), _lib.ptr(b),
+              1 if relu else 0, kh, kw, stride[0], stride[1], padding[0], padding[1], dilation[0], dilation[1], layout, layout,
+              _lib.ptr(ws), ws.numel(), _lib.stream_of(x0))
     return outs
 
 
@@ -128,22 +117,14 @@ _packed_cache_h = _packcache.new_cache("dcn_weight_half")
 
 def _packed_weight_h(weight, cache=True):
     """[Cout,Cin,kh,kw] fp16 / bf16 -> [tap][Cin/16][2][Cout][8] (orp_dcn_pack_weight_h), cached like the fp32 pack."""
-    w = weight.detach()
-    state = _packcache.tensor_state(w)
-    if cache:
-        hit = _packed_cache_h.get(weight, state)
-        if hit is not None:
-            return _lib.keep_for_graph(hit)
-    w = w.contiguous()
-    cout, cin, kh, kw = w.shape
-    packed = torch.empty((cout * cin * kh * kw,), dtype=w.dtype, device=w.device)
-    with torch.cuda.device(w.device):
-        rc = _lib.lib().orp_dcn_pack_weight_h(_lib.ptr(w), cout, cin, kh, kw, _lib.ptr(packed), _HALF_CODES[w.dtype],
-                                              _lib.stream_of(w))
-    _lib.check(rc, "orp_dcn_pack_weight_h")
-    if not cache:
+    def build():
+        w = weight.detach().contiguous()
+        cout, cin, kh, kw = w.shape
+        packed = torch.empty((cout * cin * kh * kw,), dtype=w.dtype, device=w.device)
+        _lib.call("orp_dcn_pack_weight_h", w.device, _lib.ptr(w), cout, cin, kh, kw, _lib.ptr(packed), _HALF_CODES[w.dtype],
+                  _lib.stream_of(w))
         return packed
-    return _lib.keep_for_graph(_packed_cache_h.put(weight, state, packed))
+    return _packcache.packed(_packed_cache_h, weight, build, store=cache)
 
 
 def half_path_ok(weight, groups, deformable_groups):
@@ -211,12 +192,9 @@ def deform_conv_forward_multi_half(inputs, offsets, weight, stride, padding, dil
     layout = 1 if nhwc else 0
     nbytes = L.orp_dcn_forward_h_workspace_bytes(levels, len(inputs), B, cin, layout)
     ws = _lib.workspace(x0.device, nbytes)
-    with torch.cuda.device(x0.device):
-        rc = L.orp_dcn_forward_multi_h(levels, mask_ptrs, len(inputs), B, cin, cout, _lib.ptr(packed), _lib.ptr(b),
-                                       1 if relu else 0, kh, kw, stride[0], stride[1], padding[0], padding[1],
-                                       dilation[0], dilation[1], layout, layout, code, _lib.ptr(ws), ws.numel(),
-                                       _lib.stream_of(x0))
-    _lib.check(rc, "orp_dcn_forward_multi_h")
+    _lib.call("orp_dcn_forward_multi_h", x0.device, levels, mask_ptrs, len(inputs), B, cin, cout, _lib.ptr(packed), _lib.ptr(b),
+              1 if relu else 0, kh, kw, stride[0], stride[1], padding[0], padding[1], dilation[0], dilation[1], layout, layout, code,
+              _lib.ptr(ws), ws.numel(), _lib.stream_of(x0))
     return outs
 
 
@@ -274,18 +252,12 @@ def deform_conv_forward_pair(inputs_a, inputs_b, offsets, weight_a, weight_b, st
     layout = 1 if nhwc else 0
     nbytes = 2 * L.orp_dcn_forward_workspace_bytes(lev_a, n, B, cin, layout)
     ws = _lib.workspace(x0.device, nbytes)
-    with torch.cuda.device(x0.device):
-        if amax is not None and nhwc:
-            rc = L.orp_dcn_forward_pair_amax(lev_a, lev_b, mask_ptrs, n, B, cin, cout, _lib.ptr(pa), _lib.ptr(pb), _lib.ptr(ba),
-                                             _lib.ptr(bb), 1 if relu else 0, kh, kw, stride[0], stride[1], padding[0],
-                                             padding[1], dilation[0], dilation[1], layout, 1 if out_cl else 0, _lib.ptr(ws),
-                                             ws.numel(), amax.bits.data_ptr(), int(amax.stride), _lib.stream_of(x0))
-        else:
-            rc = L.orp_dcn_forward_pair(lev_a, lev_b, mask_ptrs, n, B, cin, cout, _lib.ptr(pa), _lib.ptr(pb), _lib.ptr(ba),
-                                        _lib.ptr(bb), 1 if relu else 0, kh, kw, stride[0], stride[1], padding[0], padding[1],
-                                        dilation[0], dilation[1], layout, 1 if out_cl else 0, _lib.ptr(ws), ws.numel(),
-                                        _lib.stream_of(x0))
-    _lib.check(rc, "orp_dcn_forward_pair")
+    args = (lev_a, lev_b, mask_ptrs, n, B, cin, cout, _lib.ptr(pa), _lib.ptr(pb), _lib.ptr(ba), _lib.ptr(bb), 1 if relu else 0, kh, kw,
+            stride[0], stride[1], padding[0], padding[1], dilation[0], dilation[1], layout, 1 if out_cl else 0, _lib.ptr(ws), ws.numel())
+    if amax is not None and nhwc:
+        _lib.call("orp_dcn_forward_pair_amax", x0.device, *args, amax.bits.data_ptr(), int(amax.stride), _lib.stream_of(x0))
+    else:
+        _lib.call("orp_dcn_forward_pair", x0.device, *args, _lib.stream_of(x0))
     return outs_a, outs_b
 
 
@@ -297,18 +269,14 @@ _packed_heads = _packcache.new_cache("dcn_head_1x1")
 
 def _packed_head_weight(weight):
     """[k,256,1,1] -> the [256][20] pack of orp_dcn_forward_pair_heads, cached on the live parameter (inference only)."""
-    w = weight.detach()
-    state = _packcache.tensor_state(w)
-    hit = _packed_heads.get(weight, state)
-    if hit is not None:
-        return _lib.keep_for_graph(hit)
-    k = w.size(0)
-    w2 = w.float().reshape(k, 256).contiguous()
-    packed = torch.empty((_lib.lib().orp_dcn_head_packed_floats(),), dtype=torch.float32, device=w.device)
-    with torch.cuda.device(w.device):
-        _lib.check(_lib.lib().orp_dcn_pack_head_weight(_lib.ptr(w2), k, _lib.ptr(packed), _lib.stream_of(w2)),
-                   "orp_dcn_pack_head_weight")
-    return _lib.keep_for_graph(_packed_heads.put(weight, state, packed))
+    def build():
+        w = weight.detach()
+        k = w.size(0)
+        w2 = w.float().reshape(k, 256).contiguous()
+        packed = torch.empty((_lib.lib().orp_dcn_head_packed_floats(),), dtype=torch.float32, device=w.device)
+        _lib.call("orp_dcn_pack_head_weight", w.device, _lib.ptr(w2), k, _lib.ptr(packed), _lib.stream_of(w2))
+        return packed
+    return _packcache.packed(_packed_heads, weight, build)
 
 
 def pair_heads_ok(conv_a, conv_b, head_a, head_b, x):
@@ -363,11 +331,8 @@ def deform_conv_forward_pair_heads(inputs_a, inputs_b, offsets, conv_a, conv_b, 
                       bb.data_ptr() if bb is not None else None, kb, hl)
     nbytes = 2 * L.orp_dcn_forward_workspace_bytes(lev_a, n, B, 256, 0)
     ws = _lib.workspace(x0.device, nbytes)
-    with torch.cuda.device(x0.device):
-        rc = L.orp_dcn_forward_pair_heads(lev_a, lev_b, n, B, _lib.ptr(pa), _lib.ptr(pb), ctypes.byref(heads), kh, kw,
-                                          stride[0], stride[1], padding[0], padding[1], dilation[0], dilation[1], 0,
-                                          _lib.ptr(ws), ws.numel(), _lib.stream_of(x0))
-    _lib.check(rc, "orp_dcn_forward_pair_heads")
+    _lib.call("orp_dcn_forward_pair_heads", x0.device, lev_a, lev_b, n, B, _lib.ptr(pa), _lib.ptr(pb), ctypes.byref(heads), kh, kw,
+              stride[0], stride[1], padding[0], padding[1], dilation[0], dilation[1], 0, _lib.ptr(ws), ws.numel(), _lib.stream_of(x0))
     return outs_a, outs_b
 
 
@@ -381,12 +346,9 @@ def _forward_direct(input, offset, mask, weight, bias, stride, padding, dilation
     cout, _, kh, kw = w.shape
     ho, wo = _out_hw(H, W, w, stride, padding, dilation)
     out = torch.empty((B, cout, ho, wo), dtype=torch.float32, device=x.device)
-    with torch.cuda.device(x.device):
-        rc = _lib.lib().orp_dcn_forward_direct(_lib.ptr(x), _lib.ptr(off), _lib.ptr(m), _lib.ptr(w), _lib.ptr(b),
-                                               _lib.ptr(out), B, cin, H, W, cout, kh, kw, stride[0], stride[1],
-                                               padding[0], padding[1], dilation[0], dilation[1], groups,
-                                               deformable_groups, _lib.stream_of(x))
-    _lib.check(rc, "orp_dcn_forward_direct")
+    _lib.call("orp_dcn_forward_direct", x.device, _lib.ptr(x), _lib.ptr(off), _lib.ptr(m), _lib.ptr(w), _lib.ptr(b), _lib.ptr(out),
+              B, cin, H, W, cout, kh, kw, stride[0], stride[1], padding[0], padding[1], dilation[0], dilation[1], groups,
+              deformable_groups, _lib.stream_of(x))
     return out
 
 

@@ -67,13 +67,11 @@ def backward_mfma(inputs, offsets, weight, grad_outputs, stride, padding, dilati
                                                 dilation[0], dilation[1])
     if nbytes == 0:
         raise ValueError("orp_dcn_backward_workspace_bytes: invalid geometry")
-    with torch.cuda.device(w.device):
+    with torch.cuda.device(w.device):                              # (workspace asks whether the current device's stream is capturing)
         ws = _lib.workspace(w.device, nbytes)
-        rc = L.orp_dcn_backward_multi_ex(levels, mptr, gmptr, _IO_CODES[dt], n, B, cin, cout, _lib.ptr(w), _lib.ptr(gw),
-                                         (1 | (2 if sparse_grad else 0)) if need_input else 0, kh, kw,
-                                         stride[0], stride[1], padding[0], padding[1], dilation[0], dilation[1],
-                                         _lib.ptr(ws), nbytes, _lib.stream_of(w))
-    _lib.check(rc, "orp_dcn_backward_multi_ex")
+    _lib.call("orp_dcn_backward_multi_ex", w.device, levels, mptr, gmptr, _IO_CODES[dt], n, B, cin, cout, _lib.ptr(w), _lib.ptr(gw),
+              (1 | (2 if sparse_grad else 0)) if need_input else 0, kh, kw, stride[0], stride[1], padding[0], padding[1], dilation[0],
+              dilation[1], _lib.ptr(ws), nbytes, _lib.stream_of(w))
     if dt != torch.float32:                                        # the small gradients follow their tensors' type
         gos = [g.to(offsets[i].dtype) if g is not None else None for i, g in enumerate(gos)]
         gms = [g.to(masks[i].dtype) if g is not None else None for i, g in enumerate(gms)]
@@ -92,12 +90,9 @@ def _geo(input, weight, stride, padding, dilation):
 def _im2col(input, offset, mask, weight, stride, padding, dilation, dg):
     B, C, H, W, kh, kw, Ho, Wo = _geo(input, weight, stride, padding, dilation)
     col = torch.empty((C * kh * kw, B * Ho * Wo), dtype=input.dtype, device=input.device)
-    fn = _lib.lib().orp_dcn_im2col_f64 if input.dtype == torch.float64 else _lib.lib().orp_dcn_im2col
-    with torch.cuda.device(input.device):
-        rc = fn(_lib.ptr(input), _lib.ptr(offset), _lib.ptr(mask), B, C, H, W, kh, kw, stride[0],
-                                       stride[1], padding[0], padding[1], dilation[0], dilation[1], dg, _lib.ptr(col),
-                                       _lib.stream_of(input))
-    _lib.check(rc, "orp_dcn_im2col")
+    _lib.call("orp_dcn_im2col_f64" if input.dtype == torch.float64 else "orp_dcn_im2col", input.device, _lib.ptr(input), _lib.ptr(offset),
+              _lib.ptr(mask), B, C, H, W, kh, kw, stride[0], stride[1], padding[0], padding[1], dilation[0], dilation[1], dg, _lib.ptr(col),
+              _lib.stream_of(input))
     return col
 
 
@@ -114,13 +109,9 @@ def _col2im(gcol, input, offset, mask, weight, stride, padding, dilation, dg):
     grad_input = torch.zeros_like(input)
     grad_offset = torch.empty_like(offset)
     grad_mask = torch.empty_like(mask) if mask is not None else None
-    fn = _lib.lib().orp_dcn_col2im_f64 if input.dtype == torch.float64 else _lib.lib().orp_dcn_col2im
-    with torch.cuda.device(input.device):
-        rc = fn(_lib.ptr(gcol), _lib.ptr(input), _lib.ptr(offset), _lib.ptr(mask), B, C, H, W, kh,
-                                       kw, stride[0], stride[1], padding[0], padding[1], dilation[0], dilation[1], dg,
-                                       _lib.ptr(grad_input), _lib.ptr(grad_offset), _lib.ptr(grad_mask),
-                                       _lib.stream_of(input))
-    _lib.check(rc, "orp_dcn_col2im")
+    _lib.call("orp_dcn_col2im_f64" if input.dtype == torch.float64 else "orp_dcn_col2im", input.device, _lib.ptr(gcol), _lib.ptr(input),
+              _lib.ptr(offset), _lib.ptr(mask), B, C, H, W, kh, kw, stride[0], stride[1], padding[0], padding[1], dilation[0], dilation[1], dg,
+              _lib.ptr(grad_input), _lib.ptr(grad_offset), _lib.ptr(grad_mask), _lib.stream_of(input))
     return grad_input, grad_offset, grad_mask
 
 
@@ -159,11 +150,8 @@ def _backward_input_nhwc(input, offset, weight, grad_output, stride, padding, di
     x_nhwc = input.permute(0, 2, 3, 1).contiguous()
     gx_nhwc = torch.zeros_like(x_nhwc)
     grad_offset = torch.empty_like(offset)
-    with torch.cuda.device(input.device):
-        rc = _lib.lib().orp_dcn_col2im_nhwc(_lib.ptr(gcol_t), _lib.ptr(x_nhwc), _lib.ptr(offset), B, C, H, W, kh, kw,
-                                            stride[0], stride[1], padding[0], padding[1], dilation[0], dilation[1],
-                                            _lib.ptr(gx_nhwc), _lib.ptr(grad_offset), _lib.stream_of(input))
-    _lib.check(rc, "orp_dcn_col2im_nhwc")
+    _lib.call("orp_dcn_col2im_nhwc", input.device, _lib.ptr(gcol_t), _lib.ptr(x_nhwc), _lib.ptr(offset), B, C, H, W, kh, kw, stride[0],
+              stride[1], padding[0], padding[1], dilation[0], dilation[1], _lib.ptr(gx_nhwc), _lib.ptr(grad_offset), _lib.stream_of(input))
     return gx_nhwc.permute(0, 3, 1, 2).contiguous(), grad_offset
 
 

@@ -18,13 +18,6 @@ from .. import _lib, _packcache
 _NormLevel = _lib.struct("orp_norm_level")
 
 
-def _call(name, device, *args):
-    """one launch: the library's entry point `name`, looked up at call time, under the device guard, its return code checked"""
-    with torch.cuda.device(device):
-        rc = getattr(_lib.lib(), name)(*args)
-    _lib.check(rc, name)
-
-
 def _norm_levels(ins, outs):
     """the `orp_norm_level` array of a launch: logical [B,C,H,W] tensors, outs[i] None = no such output"""
     levels = (_NormLevel * len(ins))()
@@ -96,11 +89,11 @@ def group_norm_act_multi(xs, gn, relu=True, inplace=True, nhwc=None):
         if nhwc == 'only':
             for i in range(len(xs)):
                 levels[i].output = None
-        _call("orp_groupnorm_act_multi_nhwc", x0.device, levels, gam, bet, cl_ptrs, len(xs), B, C, gns[0].num_groups,
-              float(gns[0].eps), 1 if relu else 0, _lib.ptr(ws), ws.numel(), _lib.stream_of(x0))
+        _lib.call("orp_groupnorm_act_multi_nhwc", x0.device, levels, gam, bet, cl_ptrs, len(xs), B, C, gns[0].num_groups,
+                  float(gns[0].eps), 1 if relu else 0, _lib.ptr(ws), ws.numel(), _lib.stream_of(x0))
         return cl if nhwc == 'only' else (outs, cl)
-    _call("orp_groupnorm_act_multi_ex", x0.device, levels, gam, bet, len(xs), B, C, gns[0].num_groups, float(gns[0].eps),
-          1 if relu else 0, _lib.ptr(ws), ws.numel(), _lib.stream_of(x0))
+    _lib.call("orp_groupnorm_act_multi_ex", x0.device, levels, gam, bet, len(xs), B, C, gns[0].num_groups, float(gns[0].eps),
+              1 if relu else 0, _lib.ptr(ws), ws.numel(), _lib.stream_of(x0))
     return outs
 
 
@@ -132,11 +125,11 @@ def group_norm_act_multi_cl(xs, gn, relu=True, inplace=True, amax_slots=None):
     if amax_slots is not None:
         slots = (ctypes.c_int * len(xs))(*[int(v) for v in amax_slots])
         bits = torch.empty(max(int(v) for v in amax_slots) + 1, dtype=torch.int32, device=x0.device)
-        _call("orp_groupnorm_act_multi_cl_amax", x0.device, levels, gam, bet, len(xs), B, C, G, float(gns[0].eps), 1 if relu else 0,
-              slots, bits.data_ptr(), bits.numel(), _lib.ptr(ws), ws.numel(), _lib.stream_of(x0))
+        _lib.call("orp_groupnorm_act_multi_cl_amax", x0.device, levels, gam, bet, len(xs), B, C, G, float(gns[0].eps), 1 if relu else 0,
+                  slots, bits.data_ptr(), bits.numel(), _lib.ptr(ws), ws.numel(), _lib.stream_of(x0))
         return outs, bits
-    _call("orp_groupnorm_act_multi_cl", x0.device, levels, gam, bet, len(xs), B, C, G, float(gns[0].eps), 1 if relu else 0,
-          _lib.ptr(ws), ws.numel(), _lib.stream_of(x0))
+    _lib.call("orp_groupnorm_act_multi_cl", x0.device, levels, gam, bet, len(xs), B, C, G, float(gns[0].eps), 1 if relu else 0,
+              _lib.ptr(ws), ws.numel(), _lib.stream_of(x0))
     return (outs, None) if no_ranges else outs
 
 
@@ -194,13 +187,13 @@ def bn_act(x, bn, residual=None, relu=True, residual_bn=None, want_range=False):
     tail = (_lib.ptr(x), B, C, H * W, 1 if relu else 0)
     if want_range:
         bits = torch.empty(1, dtype=torch.int32, device=x.device)
-        _call("orp_affine_act_range", x.device, *head, *tail, _lib.ptr(bits), _lib.stream_of(x))
+        _lib.call("orp_affine_act_range", x.device, *head, *tail, _lib.ptr(bits), _lib.stream_of(x))
         return x, bits
     if residual_bn is not None:
         scale2, shift2 = _bn_affine(residual_bn)
-        _call("orp_affine2_act", x.device, *head, _lib.ptr(scale2), _lib.ptr(shift2), *tail, _lib.stream_of(x))
+        _lib.call("orp_affine2_act", x.device, *head, _lib.ptr(scale2), _lib.ptr(shift2), *tail, _lib.stream_of(x))
         return x
-    _call("orp_affine_act", x.device, *head, *tail, _lib.stream_of(x))
+    _lib.call("orp_affine_act", x.device, *head, *tail, _lib.stream_of(x))
     return x
 
 
@@ -211,11 +204,7 @@ def _transposed_1x1_weight(weight):
     """[Cout,Cin,1,1] -> the [Cin][Cout] layout orp_conv1x1_bn_act reads, cached on the live parameter (inference only), keyed
     by the tensor's storage / version state."""
     w = weight.detach()
-    state = _packcache.tensor_state(w)
-    hit = _packed_1x1_t.get(weight, state)
-    if hit is None:
-        hit = _packed_1x1_t.put(weight, state, w.float().reshape(w.size(0), w.size(1)).t().contiguous())
-    return _lib.keep_for_graph(hit)
+    return _packcache.packed(_packed_1x1_t, weight, lambda: w.float().reshape(w.size(0), w.size(1)).t().contiguous())
 
 
 def _plain_conv(conv, w, ksize, strides, padding):
@@ -229,29 +218,6 @@ def _plain_conv(conv, w, ksize, strides, padding):
 def _bn_input(x, bn):
     """bn is an eval-mode BatchNorm2d and x an fp32 CUDA tensor"""
     return bool(isinstance(bn, torch.nn.BatchNorm2d) and not bn.training and x.is_cuda and x.dtype == torch.float32)
-
-
-def _tile_query(name, n, *shape):
-    """the n integers the library's `name`(shape..., n int pointers) fills for a launch of this shape, or None where it returns 0"""
-    v = [ctypes.c_int() for _ in range(n)]
-    if not getattr(_lib.lib(), name)(*[int(s) for s in shape], *[ctypes.byref(t) for t in v]):
-        return None
-    return tuple(t.value for t in v)
-
-
-def _packed_planes(cache, weight, size_fn, pack_fn, view):
-    """weight [Cout,Cin,k,k] -> the byte buffer the library's `pack_fn` fills from view(weight) (fp32, contiguous), `size_fn`(Cin, Cout)
-    bytes; cached on the live parameter (inference only), keyed by the tensor's storage / version state."""
-    w = weight.detach()
-    state = _packcache.tensor_state(w)
-    hit = cache.get(weight, state)
-    if hit is not None:
-        return _lib.keep_for_graph(hit)
-    cout, cin = w.size(0), w.size(1)
-    w32 = view(w)
-    packed = torch.empty((getattr(_lib.lib(), size_fn)(cin, cout),), dtype=torch.uint8, device=w.device)
-    _call(pack_fn, w.device, _lib.ptr(w32), cin, cout, _lib.ptr(packed), _lib.stream_of(w32))
-    return _lib.keep_for_graph(cache.put(weight, state, packed))
 
 
 def conv1x1_bn_act_ok(x, conv, bn):
@@ -268,14 +234,14 @@ _packed_1x1_pieces = _packcache.new_cache("conv1x1_bn_pieces_weight")
 
 def _packed_1x1_planes(weight):
     """[Cout,Cin,1,1] -> the three bf16 planes `orp_conv1x1_bn_act_pieces` reads (`orp_conv1x1_bn_pieces_pack_weight`: 6 bytes per
-    weight), cached as `_packed_planes` says."""
-    return _packed_planes(_packed_1x1_pieces, weight, "orp_conv1x1_bn_pieces_packed_bytes", "orp_conv1x1_bn_pieces_pack_weight",
+    weight), cached as `_packcache.packed_planes` says."""
+    return _packcache.packed_planes(_packed_1x1_pieces, weight, "orp_conv1x1_bn_pieces_packed_bytes", "orp_conv1x1_bn_pieces_pack_weight",
                           lambda w: w.float().reshape(w.size(0), w.size(1)).contiguous())
 
 
 def conv1x1_bn_act_pieces_tile(cin, cout, hw, B):
     """(tile channels, tile positions) of an `orp_conv1x1_bn_act_pieces` launch of this shape, or None"""
-    return _tile_query("orp_conv1x1_bn_act_pieces_tile", 2, cin, cout, hw, B)
+    return _lib.tile_query("orp_conv1x1_bn_act_pieces_tile", 2, cin, cout, hw, B)
 
 
 def _conv1x1_route(shape, force, pieces):
@@ -329,11 +295,11 @@ def conv1x1_bn_act(x, conv, bn, residual=None, residual_bn=None, relu=True, forc
     args = (_lib.ptr(x), _lib.ptr(weight), _lib.ptr(scale), _lib.ptr(shift), _lib.ptr(residual), _lib.ptr(scale2), _lib.ptr(shift2),
             _lib.ptr(y), B, cin, cout, H * W, 1 if relu else 0)
     if route == 'pieces':                                    # (one entry point, its range word optional)
-        _call("orp_conv1x1_bn_act_pieces", x.device, *args, _lib.ptr(bits), _lib.stream_of(x))
+        _lib.call("orp_conv1x1_bn_act_pieces", x.device, *args, _lib.ptr(bits), _lib.stream_of(x))
     elif want_range:
-        _call("orp_conv1x1_bn_act_range", x.device, *args, _lib.ptr(bits), _lib.stream_of(x))
+        _lib.call("orp_conv1x1_bn_act_range", x.device, *args, _lib.ptr(bits), _lib.stream_of(x))
     else:
-        _call("orp_conv1x1_bn_act", x.device, *args, _lib.stream_of(x))
+        _lib.call("orp_conv1x1_bn_act", x.device, *args, _lib.stream_of(x))
     return (y, bits) if want_range else y
 
 
@@ -367,7 +333,7 @@ def conv1x1_bn_act_dual_routed(x, conv, bn, x2, conv2, bn2):
 
 def conv1x1_bn_act_dual_tile(cin, cin2, cout, hw, B):
     """(tile channels, tile positions) of an `orp_conv1x1_bn_act_pieces_dual` launch of this shape, or None"""
-    return _tile_query("orp_conv1x1_bn_act_pieces_dual_tile", 2, cin, cin2, cout, hw, B)
+    return _lib.tile_query("orp_conv1x1_bn_act_pieces_dual_tile", 2, cin, cin2, cout, hw, B)
 
 
 def conv1x1_bn_act_dual(x, conv, bn, x2, conv2, bn2, relu=True):
@@ -386,9 +352,9 @@ def conv1x1_bn_act_dual(x, conv, bn, x2, conv2, bn2, relu=True):
     scale, shift = _bn_affine(bn)
     scale2, shift2 = _bn_affine(bn2)
     y = torch.empty((B, cout, H, W), dtype=torch.float32, device=x.device)
-    _call("orp_conv1x1_bn_act_pieces_dual", x.device, _lib.ptr(x), _lib.ptr(packed), _lib.ptr(scale), _lib.ptr(shift), _lib.ptr(x2),
-          _lib.ptr(packed2), _lib.ptr(scale2), _lib.ptr(shift2), cin2, x2.size(2), x2.size(3), conv2.stride[0], _lib.ptr(y),
-          B, cin, cout, H, W, 1 if relu else 0, _lib.stream_of(x))
+    _lib.call("orp_conv1x1_bn_act_pieces_dual", x.device, _lib.ptr(x), _lib.ptr(packed), _lib.ptr(scale), _lib.ptr(shift), _lib.ptr(x2),
+              _lib.ptr(packed2), _lib.ptr(scale2), _lib.ptr(shift2), cin2, x2.size(2), x2.size(3), conv2.stride[0], _lib.ptr(y),
+              B, cin, cout, H, W, 1 if relu else 0, _lib.stream_of(x))
     return y
 
 
@@ -457,10 +423,10 @@ _packed_3x3_cache = _packcache.new_cache("conv3x3_bn_weight")
 
 
 def _packed_3x3(kind, weight):
-    """[C,C,3,3] -> the two fp16 planes + scale the kernel `kind` reads (its packer: 4 bytes per weight + 16), cached as `_packed_planes`
+    """[C,C,3,3] -> the two fp16 planes + scale the kernel `kind` reads (its packer: 4 bytes per weight + 16), cached as `_packcache.packed_planes`
     says.  One cache for every kind: the packers write one format, and a weight's shape is taken by one kind only."""
     k = _CONV3X3[kind]
-    return _packed_planes(_packed_3x3_cache, weight, k.packed_bytes, k.pack_weight, lambda w: w.float().contiguous())
+    return _packcache.packed_planes(_packed_3x3_cache, weight, k.packed_bytes, k.pack_weight, lambda w: w.float().contiguous())
 
 
 def _conv3x3_launch(kind, x, conv, bn, relu=True, force=False, range_bits=None):
@@ -479,8 +445,8 @@ def _conv3x3_launch(kind, x, conv, bn, relu=True, force=False, range_bits=None):
     packed = _packed_3x3(kind, conv.weight)
     scale, shift = _bn_affine(bn)
     y = torch.empty((B, cout, (H - 1) // s + 1, (W - 1) // s + 1), dtype=torch.float32, device=x.device)
-    _call(k.launch, x.device, _lib.ptr(x), _lib.ptr(packed), _lib.ptr(scale), _lib.ptr(shift), _lib.ptr(range_bits), _lib.ptr(y),
-          B, cin, cout, H, W, *_stride_arg(k, conv), 1 if relu else 0, _lib.stream_of(x))
+    _lib.call(k.launch, x.device, _lib.ptr(x), _lib.ptr(packed), _lib.ptr(scale), _lib.ptr(shift), _lib.ptr(range_bits), _lib.ptr(y),
+              B, cin, cout, H, W, *_stride_arg(k, conv), 1 if relu else 0, _lib.stream_of(x))
     return y
 
 
@@ -507,7 +473,7 @@ _packed_3x3_s2_planes = _of_kind(_packed_3x3, "s2", "`_packed_3x3` by `orp_conv3
 
 def conv3x3_bn_act_tile(cin, cout, H, W, B):
     """(tile_h, tile_w, waves over positions, waves over channels) of an `orp_conv3x3_bn_act` launch of this shape, or None"""
-    return _tile_query("orp_conv3x3_bn_act_tile", 4, cin, cout, H, W, B)
+    return _lib.tile_query("orp_conv3x3_bn_act_tile", 4, cin, cout, H, W, B)
 
 
 def bn_relu_maxpool(x, bn):
@@ -518,7 +484,7 @@ def bn_relu_maxpool(x, bn):
     scale, shift = _bn_affine(bn)
     B, C, H, W = x.shape
     y = torch.empty((B, C, (H - 1) // 2 + 1, (W - 1) // 2 + 1), dtype=torch.float32, device=x.device)
-    _call("orp_affine_relu_maxpool", x.device, _lib.ptr(x), _lib.ptr(scale), _lib.ptr(shift), _lib.ptr(y), B, C, H, W, _lib.stream_of(x))
+    _lib.call("orp_affine_relu_maxpool", x.device, _lib.ptr(x), _lib.ptr(scale), _lib.ptr(shift), _lib.ptr(y), B, C, H, W, _lib.stream_of(x))
     return y
 
 
@@ -559,8 +525,8 @@ _packed_stem = _packcache.new_cache("stem_weight")
 
 def _packed_stem_weight(weight):
     """[64,3,7,7] -> the per-lane MFMA operand order `orp_stem_conv_bn_relu_pool` reads (`orp_stem_pack_weight`), cached as
-    `_packed_planes` says."""
-    return _packed_planes(_packed_stem, weight, "orp_stem_packed_bytes", "orp_stem_pack_weight", lambda w: w.float().contiguous())
+    `_packcache.packed_planes` says."""
+    return _packcache.packed_planes(_packed_stem, weight, "orp_stem_packed_bytes", "orp_stem_pack_weight", lambda w: w.float().contiguous())
 
 
 def _stem_launch(x, conv, bn, pool):
@@ -576,8 +542,8 @@ def _stem_launch(x, conv, bn, pool):
     if pool:
         ho, wo = (ho - 1) // 2 + 1, (wo - 1) // 2 + 1
     y = torch.empty((B, cout, ho, wo), dtype=torch.float32, device=x.device)
-    _call("orp_stem_conv_bn_relu_pool", x.device, _lib.ptr(x), _lib.ptr(packed), _lib.ptr(scale), _lib.ptr(shift), _lib.ptr(y), B, cin,
-          cout, H, W, 7, 2, 3, 1 if pool else 0, _lib.stream_of(x))
+    _lib.call("orp_stem_conv_bn_relu_pool", x.device, _lib.ptr(x), _lib.ptr(packed), _lib.ptr(scale), _lib.ptr(shift), _lib.ptr(y), B, cin,
+              cout, H, W, 7, 2, 3, 1 if pool else 0, _lib.stream_of(x))
     return y
 
 
@@ -629,8 +595,8 @@ def fpn_topdown_cl(xs, gns, amax=True):
     bits = torch.empty(1, dtype=torch.int32, device=x0.device) if (amax and _ranges_wanted()) else None
     nbytes = L.orp_fpn_topdown_workspace_bytes(levels, n, B, C, gns[0].num_groups)
     ws = _lib.workspace(x0.device, nbytes)
-    _call("orp_fpn_topdown_nhwc", x0.device, levels, gam, bet, n, B, C, gns[0].num_groups, float(gns[0].eps),
-          bits.data_ptr() if bits is not None else None, _lib.ptr(ws), ws.numel(), _lib.stream_of(x0))
+    _lib.call("orp_fpn_topdown_nhwc", x0.device, levels, gam, bet, n, B, C, gns[0].num_groups, float(gns[0].eps),
+              bits.data_ptr() if bits is not None else None, _lib.ptr(ws), ws.numel(), _lib.stream_of(x0))
     return outs, bits
 
 
@@ -664,7 +630,7 @@ def bias_act_multi(xs, bias, relu=False, residuals=None, sub=None):
     s = sub.detach().float().reshape(-1).contiguous() if sub is not None else None
     if (b is not None and b.numel() != C) or (s is not None and s.numel() != C):
         raise ValueError("bias_act_multi: bias / sub must have C elements")
-    _call("orp_bias_act_multi", x0.device, levels, len(xs), B, C, _lib.ptr(b), _lib.ptr(s), 1 if relu else 0, _lib.stream_of(x0))
+    _lib.call("orp_bias_act_multi", x0.device, levels, len(xs), B, C, _lib.ptr(b), _lib.ptr(s), 1 if relu else 0, _lib.stream_of(x0))
     return (ys, zs) if sub is not None else ys
 
 
@@ -673,16 +639,14 @@ _packed_1x1 = _packcache.new_cache("conv1x1_weight")
 
 def _packed_1x1_weight(weight):
     """[Cout,Cin,1,1] -> the [Cin][32] pack of orp_conv1x1_multi, cached on the live parameter (inference only)."""
-    w = weight.detach()
-    state = _packcache.tensor_state(w)
-    hit = _packed_1x1.get(weight, state)
-    if hit is not None:
-        return _lib.keep_for_graph(hit)
-    cout, cin = w.size(0), w.size(1)
-    w2 = w.float().reshape(cout, cin).contiguous()
-    packed = torch.empty((_lib.lib().orp_conv1x1_packed_floats(cin),), dtype=torch.float32, device=w.device)
-    _call("orp_conv1x1_pack_weight", w.device, _lib.ptr(w2), cout, cin, _lib.ptr(packed), _lib.stream_of(w2))
-    return _lib.keep_for_graph(_packed_1x1.put(weight, state, packed))
+    def build():
+        w = weight.detach()
+        cout, cin = w.size(0), w.size(1)
+        w2 = w.float().reshape(cout, cin).contiguous()
+        packed = torch.empty((_lib.lib().orp_conv1x1_packed_floats(cin),), dtype=torch.float32, device=w.device)
+        _lib.call("orp_conv1x1_pack_weight", w.device, _lib.ptr(w2), cout, cin, _lib.ptr(packed), _lib.stream_of(w2))
+        return packed
+    return _packcache.packed(_packed_1x1, weight, build)
 
 
 def conv1x1_ok(conv, x):
@@ -721,8 +685,8 @@ def conv1x1_multi(xs, conv, relu=False, residuals=None, sub=None):
     s = sub.detach().float().reshape(-1).contiguous() if sub is not None else None
     if s is not None and s.numel() != cout:
         raise ValueError("conv1x1_multi: sub must have Cout elements")
-    _call("orp_conv1x1_multi", x0.device, levels, len(xs), B, cin, cout, _lib.ptr(packed), _lib.ptr(b), _lib.ptr(s),
-          1 if relu else 0, _lib.stream_of(x0))
+    _lib.call("orp_conv1x1_multi", x0.device, levels, len(xs), B, cin, cout, _lib.ptr(packed), _lib.ptr(b), _lib.ptr(s),
+              1 if relu else 0, _lib.stream_of(x0))
     return (ys, zs) if sub is not None else ys
 
 
@@ -777,8 +741,8 @@ def conv3x3_multi(xs, conv, split_k=False):
         x0 = xs[small[0]]
         nbytes = L.orp_conv3x3_small_workspace_bytes(levels, strides, len(small), B, cout) if split_k else 0
         ws = _lib.workspace(x0.device, nbytes) if nbytes else None
-        _call("orp_conv3x3_small_multi_strided", x0.device, levels, wts, strides, len(small), B, cin, cout, _lib.ptr(ws),
-              ws.numel() if ws is not None else 0, _lib.stream_of(x0))
+        _lib.call("orp_conv3x3_small_multi_strided", x0.device, levels, wts, strides, len(small), B, cin, cout, _lib.ptr(ws),
+                  ws.numel() if ws is not None else 0, _lib.stream_of(x0))
     return outs
 
 
@@ -805,8 +769,8 @@ class _GroupNormActTrain(torch.autograd.Function):
         stats = torch.empty((n * B * groups, 2), dtype=torch.float32, device=x0.device)
         nbytes = L.orp_groupnorm_workspace_bytes(levels, n, B, C, groups)
         ws = _lib.workspace(x0.device, nbytes)
-        _call("orp_groupnorm_act_multi_train", x0.device, levels, gam, bet, n, B, C, groups, float(eps), 1 if relu else 0,
-              _lib.ptr(stats), _lib.ptr(ws), ws.numel(), _lib.stream_of(x0))
+        _lib.call("orp_groupnorm_act_multi_train", x0.device, levels, gam, bet, n, B, C, groups, float(eps), 1 if relu else 0,
+                  _lib.ptr(stats), _lib.ptr(ws), ws.numel(), _lib.stream_of(x0))
         ctx.save_for_backward(stats, *xs, *gammas, *betas, *ys)      # ys: the ReLU mask (the next layer keeps them alive anyway)
         ctx.meta = (n, m, groups, bool(relu), tuple(owner))
         return tuple(ys)
@@ -831,8 +795,8 @@ class _GroupNormActTrain(torch.autograd.Function):
         dg, db = _ptrs(dgam, owner), _ptrs(dbet, owner)
         nbytes = L.orp_groupnorm_backward_workspace_bytes(levels, n, B, C, groups)
         ws = _lib.workspace(x0.device, nbytes)
-        _call("orp_groupnorm_act_multi_backward", x0.device, levels, dys, dxs, gam, bet, dg, db, n, B, C, groups, 1 if relu else 0,
-              _lib.ptr(stats), _lib.ptr(ws), ws.numel(), _lib.stream_of(x0))
+        _lib.call("orp_groupnorm_act_multi_backward", x0.device, levels, dys, dxs, gam, bet, dg, db, n, B, C, groups, 1 if relu else 0,
+                  _lib.ptr(stats), _lib.ptr(ws), ws.numel(), _lib.stream_of(x0))
         return (None, None, None, None, None) + tuple(gxs) + tuple(dgam) + tuple(dbet)
 
 
@@ -879,10 +843,10 @@ class _BnActTrain(torch.autograd.Function):
         keep = [scale, mean, rstd]
         if residual_bn is not None:
             scale2, shift2, mean2, rstd2 = _bn_affine_stats(residual_bn, cache=not (capturing and want2))
-            _call("orp_affine2_act", x.device, *head, _lib.ptr(scale2), _lib.ptr(shift2), *tail)
+            _lib.call("orp_affine2_act", x.device, *head, _lib.ptr(scale2), _lib.ptr(shift2), *tail)
             keep += [scale2, mean2, rstd2]
         else:
-            _call("orp_affine_act", x.device, *head, *tail)
+            _lib.call("orp_affine_act", x.device, *head, *tail)
         # only what the backward reads: y is the ReLU mask, x / the raw residual feed that BatchNorm's dweight
         ctx.save_for_backward(y if relu else None, x if want1 else None, residual if want2 else None, *keep)
         ctx.meta = (bool(relu), residual_bn is not None, want1, want2)
@@ -915,11 +879,11 @@ class _BnActTrain(torch.autograd.Function):
         p = _lib.ptr
         dims = (B, C, H * W, p(ws), nbytes, _lib.stream_of(gy))
         if two:
-            _call("orp_affine2_act_backward", gy.device, p(gy), p(y), p(x), p(scale), p(mean), p(rstd), p(x2), p(scale2), p(mean2),
-                  p(rstd2), p(gx), p(gx2), None, p(dw), p(db), p(dw2), p(db2), *dims)
+            _lib.call("orp_affine2_act_backward", gy.device, p(gy), p(y), p(x), p(scale), p(mean), p(rstd), p(x2), p(scale2), p(mean2),
+                      p(rstd2), p(gx), p(gx2), None, p(dw), p(db), p(dw2), p(db2), *dims)
         else:
-            _call("orp_affine_act_backward", gy.device, p(gy), p(y), p(x), p(scale), p(mean), p(rstd), p(gx), p(gres), p(dw), p(db),
-                  *dims)
+            _lib.call("orp_affine_act_backward", gy.device, p(gy), p(y), p(x), p(scale), p(mean), p(rstd), p(gx), p(gres), p(dw), p(db),
+                      *dims)
         if two:
             gr = gx2
         else:
@@ -1011,10 +975,10 @@ def to_channels_last_multi(xs, amax_slots=None, amax_into=None, force_ranges=Fal
             slots_all, reset = list(amax_slots), 1
             bits = torch.empty(max(slots_all) + 1, dtype=torch.int32, device=x0.device)
         slots = (ctypes.c_int * len(todo))(*[int(slots_all[i]) for i in todo])
-        _call("orp_nchw_to_nhwc_multi_amax", x0.device, levels, len(todo), B, C, slots, bits.data_ptr(), bits.numel(), reset,
-              _lib.stream_of(x0))
+        _lib.call("orp_nchw_to_nhwc_multi_amax", x0.device, levels, len(todo), B, C, slots, bits.data_ptr(), bits.numel(), reset,
+                  _lib.stream_of(x0))
         return outs, bits
-    _call("orp_nchw_to_nhwc_multi", x0.device, levels, len(todo), B, C, _lib.stream_of(x0))
+    _lib.call("orp_nchw_to_nhwc_multi", x0.device, levels, len(todo), B, C, _lib.stream_of(x0))
     return (outs, None) if want_amax else outs
 
 
@@ -1106,15 +1070,15 @@ def conv_split_weights(xs_a, weights_a, xs_b=None, weight_b=None, biases_a=None,
             keep += [pk, bi]
             wts[i] = pk.data_ptr()
             bs[i] = bi.data_ptr() if bi is not None else None
-        _call("orp_conv_split_multi_ex", x0.device, levels, wts, bs, n, B, cin, cout, 1 if relu else 0, kh, kw, st[0], st[1], pd[0],
-              pd[1], dl[0], dl[1], 1 if out_channels_last else 0, int(nprod), _lib.ptr(ws), ws.numel(), am_ptr, _lib.stream_of(x0))
+        _lib.call("orp_conv_split_multi_ex", x0.device, levels, wts, bs, n, B, cin, cout, 1 if relu else 0, kh, kw, st[0], st[1], pd[0],
+                  pd[1], dl[0], dl[1], 1 if out_channels_last else 0, int(nprod), _lib.ptr(ws), ws.numel(), am_ptr, _lib.stream_of(x0))
         return outs_a
     pa = _packed_weight(w, cache_pack)
     pb = _packed_weight(weight_b, cache_pack) if pair else None
     ba, bb = f32(biases_a), f32(bias_b) if pair else None
-    _call("orp_conv_split_multi", x0.device, levels, n, B, cin, cout, _lib.ptr(pa), _lib.ptr(pb), _lib.ptr(ba), _lib.ptr(bb),
-          1 if relu else 0, kh, kw, st[0], st[1], pd[0], pd[1], dl[0], dl[1], 1 if out_channels_last else 0, int(nprod),
-          _lib.ptr(ws), ws.numel(), am_ptr, am_stride, _lib.stream_of(x0))
+    _lib.call("orp_conv_split_multi", x0.device, levels, n, B, cin, cout, _lib.ptr(pa), _lib.ptr(pb), _lib.ptr(ba), _lib.ptr(bb),
+              1 if relu else 0, kh, kw, st[0], st[1], pd[0], pd[1], dl[0], dl[1], 1 if out_channels_last else 0, int(nprod),
+              _lib.ptr(ws), ws.numel(), am_ptr, am_stride, _lib.stream_of(x0))
     return (outs_a, outs_b) if pair else outs_a
 
 
@@ -1193,23 +1157,23 @@ def conv_split_gn(xs_a, conv_a, xs_b, conv_b, gn_a, gn_b, coef_in=None, amax=Non
     pa, pb = _packed_weight(conv_a.weight), _packed_weight(conv_b.weight)
     am_ptr = amax.bits.data_ptr() if amax is not None else None
     pd, dl = conv_a.padding, conv_a.dilation
-    _call("orp_conv_split_multi_gn", x0.device, levels, n, B, cin, cout, _lib.ptr(pa), _lib.ptr(pb), kh, kw, pd[0], pd[1], dl[0],
-          dl[1], int(nprod), _lib.ptr(coef_in), 1, _lib.ptr(partials), pf, G, _lib.ptr(ws), ws.numel(), am_ptr,
-          int(amax.stride) if amax is not None else 0, int(amax.count) if amax is not None else 0, _lib.stream_of(x0))
+    _lib.call("orp_conv_split_multi_gn", x0.device, levels, n, B, cin, cout, _lib.ptr(pa), _lib.ptr(pb), kh, kw, pd[0], pd[1], dl[0],
+              dl[1], int(nprod), _lib.ptr(coef_in), 1, _lib.ptr(partials), pf, G, _lib.ptr(ws), ws.numel(), am_ptr,
+              int(amax.stride) if amax is not None else 0, int(amax.count) if amax is not None else 0, _lib.stream_of(x0))
     coef = torch.empty((2 * n, B, cout, 2), dtype=torch.float32, device=x0.device)
     ranges = _ranges_wanted()
     per_set = n * B * G
     bound = torch.empty((2, per_set), dtype=torch.int32, device=x0.device) if ranges else None
     gam, bet, _gs, _bs = _affine_ptrs((gn_a, gn_b), [0] * n + [1] * n)
-    _call("orp_conv_split_gn_finish", x0.device, levels, n, B, cout, G, 2, float(gn_a.eps), gam, bet, _lib.ptr(partials),
-          _lib.ptr(coef), bound.data_ptr() if bound is not None else None, _lib.stream_of(x0))
+    _lib.call("orp_conv_split_gn_finish", x0.device, levels, n, B, cout, G, 2, float(gn_a.eps), gam, bet, _lib.ptr(partials),
+              _lib.ptr(coef), bound.data_ptr() if bound is not None else None, _lib.stream_of(x0))
     if not materialize:
         return outs_a, outs_b, coef, (Amax(bound, per_set, per_set) if bound is not None else None)
     nl = _norm_levels(outs_a + outs_b, outs_a + outs_b)
     slots = torch.empty((2,), dtype=torch.int32, device=x0.device) if bound is not None else None
-    _call("orp_affine_act_multi_cl", x0.device, nl, 2 * n, B, cout, _lib.ptr(coef), 1,
-          bound.data_ptr() if bound is not None else None, 2, per_set, slots.data_ptr() if slots is not None else None,
-          _lib.stream_of(x0))
+    _lib.call("orp_affine_act_multi_cl", x0.device, nl, 2 * n, B, cout, _lib.ptr(coef), 1,
+              bound.data_ptr() if bound is not None else None, 2, per_set, slots.data_ptr() if slots is not None else None,
+              _lib.stream_of(x0))
     return outs_a, outs_b, None, (Amax(slots, 1) if slots is not None else None)
 
 
@@ -1243,9 +1207,9 @@ def conv_wgrad_split(xs, grad_outs, weight_shape, padding=(1, 1), dilation=(1, 1
     nbytes = L.orp_conv_wgrad_split_workspace_bytes(levels, n, B, kh, kw)
     ws = _lib.workspace(x0.device, nbytes)
     have = amax_x is not None and amax_g is not None
-    _call("orp_conv_wgrad_split", x0.device, levels, n, B, cin, cout, kh, kw, padding[0], padding[1], dilation[0], dilation[1],
-          amax_x.data_ptr() if have else None, amax_g.data_ptr() if have else None, gw.data_ptr(), _lib.ptr(ws), ws.numel(),
-          _lib.stream_of(x0))
+    _lib.call("orp_conv_wgrad_split", x0.device, levels, n, B, cin, cout, kh, kw, padding[0], padding[1], dilation[0], dilation[1],
+              amax_x.data_ptr() if have else None, amax_g.data_ptr() if have else None, gw.data_ptr(), _lib.ptr(ws), ws.numel(),
+              _lib.stream_of(x0))
     return gw
 
 

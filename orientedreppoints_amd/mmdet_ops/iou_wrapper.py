@@ -13,14 +13,11 @@ class _ConvexIouCuda(object):
         _lib.require_cuda(target, "target")
         if pred.numel() == 0 or target.numel() == 0:
             return torch.empty((0,), dtype=torch.float32, device="cpu")
-        L = _lib.lib()
         p = pred.detach().float().reshape(-1, 18).contiguous()
         g = target.detach().float().reshape(-1, 8).contiguous()
         n, k = p.size(0), g.size(0)
         out = torch.empty((n * k,), dtype=torch.float32, device=p.device)
-        with torch.cuda.device(p.device):
-            rc = L.orp_convex_iou(_lib.ptr(p), n, _lib.ptr(g), k, _lib.ptr(out), _lib.stream_of(p))
-        _lib.check(rc, "orp_convex_iou")
+        _lib.call("orp_convex_iou", p.device, _lib.ptr(p), n, _lib.ptr(g), k, _lib.ptr(out), _lib.stream_of(p))
         return out
 
 
@@ -40,9 +37,7 @@ class _ConvexGiouCuda(object):
         g = target.detach().float().reshape(-1, 8).contiguous()
         assert p.size(0) == g.size(0), "ex_boxes must equal to gt_boxes"
         out = torch.empty((p.size(0) * 19,), dtype=torch.float32, device=p.device)
-        with torch.cuda.device(p.device):
-            rc = _lib.lib().orp_convex_giou(_lib.ptr(p), _lib.ptr(g), p.size(0), _lib.ptr(out), _lib.stream_of(p))
-        _lib.check(rc, "orp_convex_giou")
+        _lib.call("orp_convex_giou", p.device, _lib.ptr(p), _lib.ptr(g), p.size(0), _lib.ptr(out), _lib.stream_of(p))
         return out
 
 

@@ -16,7 +16,6 @@ def minareabbox(pred):
 def minaerarect_decode(pred, centers, scales):
     """minaerarect with the optional fused decode `rect * scale + centre` (orientedreppoints_head.py:746-749).
     Stream-ordered; the result stays on the device."""
-    L = _lib.lib()
     p = pred.detach()
     if p.dtype != torch.float32:
         p = p.float()
@@ -28,9 +27,7 @@ def minaerarect_decode(pred, centers, scales):
         c = centers.detach().float().reshape(-1, 2).contiguous()
         s = scales.detach().float().reshape(-1).contiguous()
         assert c.size(0) == m and s.numel() == m
-    with torch.cuda.device(p.device):
-        rc = L.orp_minarearect_decode(_lib.ptr(p), m, _lib.ptr(c), _lib.ptr(s), _lib.ptr(out), _lib.stream_of(p))
-    _lib.check(rc, "orp_minarearect")
+    _lib.call("orp_minarearect_decode", p.device, _lib.ptr(p), m, _lib.ptr(c), _lib.ptr(s), _lib.ptr(out), _lib.stream_of(p))
     return out
 
 

@@ -41,10 +41,8 @@ def rnms_device(dets, iou_thr, flavor=0, presorted=False, order_out=0):
     num = torch.empty((1,), dtype=torch.int32, device=d.device)
     nbytes = L.orp_rnms_workspace_bytes(n)
     ws = _lib.workspace(d.device, nbytes)
-    with torch.cuda.device(d.device):
-        rc = L.orp_rnms(_lib.ptr(d), n, float(iou_thr), int(flavor), int(bool(presorted)), int(order_out),
-                        _lib.ptr(keep), _lib.ptr(num), _lib.ptr(ws), ws.numel(), _lib.stream_of(d))
-    _lib.check(rc, "orp_rnms")
+    _lib.call("orp_rnms", d.device, _lib.ptr(d), n, float(iou_thr), int(flavor), int(bool(presorted)), int(order_out), _lib.ptr(keep),
+              _lib.ptr(num), _lib.ptr(ws), ws.numel(), _lib.stream_of(d))
     return keep, num
 
 
@@ -59,10 +57,8 @@ def rnms_batched_device(dets, seg_offsets, max_seg, iou_thr, flavor=0):
     num = torch.zeros((max(nseg, 1),), dtype=torch.int32, device=d.device)
     nbytes = L.orp_rnms_batched_workspace_bytes(n, nseg, int(max_seg))
     ws = _lib.workspace(d.device, nbytes)
-    with torch.cuda.device(d.device):
-        rc = L.orp_rnms_batched(_lib.ptr(d), n, _lib.ptr(so), nseg, int(max_seg), float(iou_thr), int(flavor),
-                                _lib.ptr(keep), _lib.ptr(num), _lib.ptr(ws), ws.numel(), _lib.stream_of(d))
-    _lib.check(rc, "orp_rnms_batched")
+    _lib.call("orp_rnms_batched", d.device, _lib.ptr(d), n, _lib.ptr(so), nseg, int(max_seg), float(iou_thr), int(flavor), _lib.ptr(keep),
+              _lib.ptr(num), _lib.ptr(ws), ws.numel(), _lib.stream_of(d))
     return keep, num[:nseg]
 
 
@@ -85,11 +81,8 @@ def poly_nms_f64_batched_device(dets, seg_offsets, max_seg, iou_thr, hbb_prefilt
     num = torch.zeros((max(nseg, 1),), dtype=torch.int32, device=d.device)
     nbytes = L.orp_poly_nms_f64_batched_workspace_bytes(n, nseg, int(max_seg))
     ws = _lib.workspace(d.device, nbytes)
-    with torch.cuda.device(d.device):
-        rc = L.orp_poly_nms_f64_batched(_lib.ptr(d), n, _lib.ptr(so), nseg, int(max_seg), float(iou_thr),
-                                        int(bool(hbb_prefilter)), int(bool(presorted)), _lib.ptr(keep), _lib.ptr(num),
-                                        _lib.ptr(ws), ws.numel(), _lib.stream_of(d))
-    _lib.check(rc, "orp_poly_nms_f64_batched")
+    _lib.call("orp_poly_nms_f64_batched", d.device, _lib.ptr(d), n, _lib.ptr(so), nseg, int(max_seg), float(iou_thr),
+              int(bool(hbb_prefilter)), int(bool(presorted)), _lib.ptr(keep), _lib.ptr(num), _lib.ptr(ws), ws.numel(), _lib.stream_of(d))
     return keep[:n], num[:nseg]
 
 

@@ -27,10 +27,8 @@ def pointsJf(points, polygons, output):
     if dts != {torch.float32}:
         raise TypeError("pointsJf: float32 (or all-float64) tensors only")
     rows, cols = points.size(0), polygons.size(0)
-    with torch.cuda.device(points.device):
-        rc = _lib.lib().orp_points_justify(_lib.ptr(points), rows, _lib.ptr(polygons), cols, _lib.ptr(output),
-                                           _lib.stream_of(points))
-    _lib.check(rc, "orp_points_justify")
+    _lib.call("orp_points_justify", points.device, _lib.ptr(points), rows, _lib.ptr(polygons), cols, _lib.ptr(output),
+              _lib.stream_of(points))
     return 1
 
 
@@ -41,8 +39,5 @@ def points_in_quad_aligned(pts18, quads):
     q = quads.detach().float().reshape(-1, 8).contiguous()
     assert p.size(0) == q.size(0)
     out = torch.empty((p.size(0), 9), dtype=torch.float32, device=p.device)
-    with torch.cuda.device(p.device):
-        rc = _lib.lib().orp_points_in_quad_aligned(_lib.ptr(p), _lib.ptr(q), p.size(0), _lib.ptr(out),
-                                                   _lib.stream_of(p))
-    _lib.check(rc, "orp_points_in_quad_aligned")
+    _lib.call("orp_points_in_quad_aligned", p.device, _lib.ptr(p), _lib.ptr(q), p.size(0), _lib.ptr(out), _lib.stream_of(p))
     return out

@@ -30,11 +30,8 @@ def scene_tiles(scene, origins, out, mean, std, to_rgb=True, _entry="orp_scene_t
         raise ValueError("out holds %d tiles, origins %d" % (out.size(0), origins.size(0)))
     m = (ctypes.c_float * 3)(*[float(v) for v in np.asarray(mean, np.float32).reshape(3)])
     s = (ctypes.c_float * 3)(*[float(v) for v in np.asarray(std, np.float32).reshape(3)])
-    with torch.cuda.device(out.device):
-        rc = getattr(_lib.lib(), _entry)(ctypes.c_void_p(scene.data_ptr()), scene.size(0), scene.size(1), scene.stride(0),
-                                         _lib.ptr(origins), origins.size(0), out.size(2), m, s, int(bool(to_rgb)),
-                                         _DTYPES[out.dtype], _lib.ptr(out), _lib.stream_of(out))
-    _lib.check(rc, _entry)
+    _lib.call(_entry, out.device, ctypes.c_void_p(scene.data_ptr()), scene.size(0), scene.size(1), scene.stride(0), _lib.ptr(origins),
+              origins.size(0), out.size(2), m, s, int(bool(to_rgb)), _DTYPES[out.dtype], _lib.ptr(out), _lib.stream_of(out))
     return out
 
 
@@ -100,12 +97,9 @@ def scene_tiles_resized(scene, origins, src_size, new_size, out, mean, std, to_r
     y_i0, y_w1 = resize_tables(src_h, new_h, out.device)
     m = (ctypes.c_float * 3)(*[float(v) for v in np.asarray(mean, np.float32).reshape(3)])
     s = (ctypes.c_float * 3)(*[float(v) for v in np.asarray(std, np.float32).reshape(3)])
-    with torch.cuda.device(out.device):
-        rc = getattr(_lib.lib(), _entry)(ctypes.c_void_p(scene.data_ptr()), scene.size(0), scene.size(1), scene.stride(0),
-                                         _lib.ptr(origins), origins.size(0), src_w, src_h, new_w, new_h, out.size(3),
-                                         out.size(2), _lib.ptr(x_i0), _lib.ptr(x_w1), _lib.ptr(y_i0), _lib.ptr(y_w1), m, s,
-                                         int(bool(to_rgb)), _DTYPES[out.dtype], _lib.ptr(out), _lib.stream_of(out))
-    _lib.check(rc, _entry)
+    _lib.call(_entry, out.device, ctypes.c_void_p(scene.data_ptr()), scene.size(0), scene.size(1), scene.stride(0), _lib.ptr(origins),
+              origins.size(0), src_w, src_h, new_w, new_h, out.size(3), out.size(2), _lib.ptr(x_i0), _lib.ptr(x_w1), _lib.ptr(y_i0),
+              _lib.ptr(y_w1), m, s, int(bool(to_rgb)), _DTYPES[out.dtype], _lib.ptr(out), _lib.stream_of(out))
     return out
 
 
@@ -134,9 +128,6 @@ def scene_collect(packed, origins, rate, num_classes):
     table = torch.empty((C + 2,), dtype=torch.int32, device=dev)
     L = _lib.lib()
     ws = _lib.workspace(dev, L.orp_scene_collect_workspace_bytes(T, C))
-    with torch.cuda.device(dev):
-        rc = L.orp_scene_collect(_lib.ptr(packed), T, m, _lib.ptr(origins), float(rate), C, T * m, _lib.ptr(dets),
-                                 _lib.ptr(table), _lib.ptr(src), ctypes.c_void_p(table.data_ptr() + 4 * (C + 1)),
-                                 _lib.ptr(ws), ws.numel(), _lib.stream_of(packed))
-    _lib.check(rc, "orp_scene_collect")
+    _lib.call("orp_scene_collect", dev, _lib.ptr(packed), T, m, _lib.ptr(origins), float(rate), C, T * m, _lib.ptr(dets), _lib.ptr(table),
+              _lib.ptr(src), ctypes.c_void_p(table.data_ptr() + 4 * (C + 1)), _lib.ptr(ws), ws.numel(), _lib.stream_of(packed))
     return dets, table, src

@@ -21,11 +21,8 @@ class _FocalExt(object):
         if t.dtype != torch.long:
             t = t.long()
         losses = torch.empty_like(x)
-        fn = _lib.lib().orp_sigmoid_focal_loss_forward if x.dtype == torch.float32 else _lib.lib().orp_sigmoid_focal_loss_forward_f64
-        with torch.cuda.device(x.device):
-            rc = fn(_lib.ptr(x), _lib.ptr(t), x.size(0), x.size(1), float(gamma), float(alpha), _lib.ptr(losses),
-                    _lib.stream_of(x))
-        _lib.check(rc, "orp_sigmoid_focal_loss_forward")
+        _lib.call("orp_sigmoid_focal_loss_forward" if x.dtype == torch.float32 else "orp_sigmoid_focal_loss_forward_f64", x.device,
+                  _lib.ptr(x), _lib.ptr(t), x.size(0), x.size(1), float(gamma), float(alpha), _lib.ptr(losses), _lib.stream_of(x))
         return losses
 
     @staticmethod
@@ -41,11 +38,9 @@ class _FocalExt(object):
             raise TypeError("sigmoid_focal_loss: float32 / float64 logits only")
         g = d_losses.to(x.dtype).contiguous()
         d_logits = torch.zeros_like(x)
-        fn = _lib.lib().orp_sigmoid_focal_loss_backward if x.dtype == torch.float32 else _lib.lib().orp_sigmoid_focal_loss_backward_f64
-        with torch.cuda.device(x.device):
-            rc = fn(_lib.ptr(x), _lib.ptr(t), _lib.ptr(g), x.size(0), x.size(1), float(gamma), float(alpha),
-                    _lib.ptr(d_logits), _lib.stream_of(x))
-        _lib.check(rc, "orp_sigmoid_focal_loss_backward")
+        _lib.call("orp_sigmoid_focal_loss_backward" if x.dtype == torch.float32 else "orp_sigmoid_focal_loss_backward_f64", x.device,
+                  _lib.ptr(x), _lib.ptr(t), _lib.ptr(g), x.size(0), x.size(1), float(gamma), float(alpha), _lib.ptr(d_logits),
+                  _lib.stream_of(x))
         return d_logits
 
 

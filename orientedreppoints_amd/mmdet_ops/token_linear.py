@@ -12,7 +12,6 @@ import torch
 import torch.nn.functional as F
 
 from .. import _lib, _packcache
-from .fused_norm import _call, _packed_planes
 
 EPI_BIAS, EPI_GELU, EPI_RES = 1, 2, 4        # the bits of `orp_token_linear_pays`' epilogue argument
 ACTS = {None: 0, 'gelu': 1}
@@ -22,9 +21,9 @@ _packed = _packcache.new_cache("token_linear_weight")
 
 def _packed_weight(weight):
     """[N, K] -> the three bf16 planes `orp_token_linear` reads (`orp_token_linear_pack_weight`: 6 bytes per weight), cached on the live
-    parameter as `fused_norm._packed_planes` says (and kept alive for a graph that is being captured)"""
-    return _packed_planes(_packed, weight, "orp_token_linear_packed_bytes", "orp_token_linear_pack_weight",
-                          lambda w: w.float().contiguous())
+    parameter as `_packcache.packed_planes` says (and kept alive for a graph that is being captured)"""
+    return _packcache.packed_planes(_packed, weight, "orp_token_linear_packed_bytes", "orp_token_linear_pack_weight",
+                                    lambda w: w.float().contiguous())
 
 
 def epilogue_bits(linear, act, residual):
@@ -82,8 +81,8 @@ def token_linear(x, linear, act=None, residual=None, force=False):
     if tokens == 0:
         return y
     planes = _packed_weight(w)
-    _call("orp_token_linear", x.device, _lib.ptr(x), _lib.ptr(planes), _lib.ptr(None if b is None else b.detach()), _lib.ptr(residual),
-          _lib.ptr(y), tokens, K, N, ACTS[act], _lib.stream_of(x))
+    _lib.call("orp_token_linear", x.device, _lib.ptr(x), _lib.ptr(planes), _lib.ptr(None if b is None else b.detach()), _lib.ptr(residual),
+              _lib.ptr(y), tokens, K, N, ACTS[act], _lib.stream_of(x))
     return y
 
 

@@ -154,7 +154,6 @@ def train_images(images, table, plan, out, scratch=None):
                          % (out.size(3), out.size(2), plan.out_shape[3], plan.out_shape[2]))
     if images.device != out.device or table.device != out.device:
         raise ValueError("images, table and out must be on one device")
-    L = _lib.lib()
     if plan.any_rotate:
         if scratch is None:
             scratch = _lib.workspace(out.device, plan.scratch_bytes)
@@ -165,11 +164,8 @@ def train_images(images, table, plan, out, scratch=None):
     at = lambda name: ctypes.c_void_p(base + plan.sections[name][0])                               # noqa: E731
     m = (ctypes.c_float * 3)(*[float(v) for v in plan.mean])
     s = (ctypes.c_float * 3)(*[float(v) for v in plan.std])
-    with torch.cuda.device(out.device):
-        rc = L.orp_train_images(_lib.ptr(images), images.numel(), ctypes.c_void_p(plan.desc.ctypes.data), at('desc'),
-                                plan.num_images, at('inv'), at('axis_i0'), at('axis_w1'), plan.axis_len, m, s, int(plan.to_rgb),
-                                int(plan.pad_before_normalize), _lib.ptr(out), out.size(2), out.size(3),
-                                _lib.ptr(scratch) if plan.any_rotate else None, scratch.numel() if plan.any_rotate else 0,
-                                _lib.stream_of(out))
-    _lib.check(rc, "orp_train_images")
+    _lib.call("orp_train_images", out.device, _lib.ptr(images), images.numel(), ctypes.c_void_p(plan.desc.ctypes.data), at('desc'),
+              plan.num_images, at('inv'), at('axis_i0'), at('axis_w1'), plan.axis_len, m, s, int(plan.to_rgb),
+              int(plan.pad_before_normalize), _lib.ptr(out), out.size(2), out.size(3), _lib.ptr(scratch) if plan.any_rotate else None,
+              scratch.numel() if plan.any_rotate else 0, _lib.stream_of(out))
     return out

@@ -31,9 +31,7 @@ def points_from_offsets(levels, strides, mode=0):
     lv = [t.detach().float().contiguous() for t in levels]
     tab, B, C, N = _level_table(lv, strides)
     out = torch.empty((B, N, C), dtype=torch.float32, device=lv[0].device)
-    with torch.cuda.device(out.device):
-        rc = _lib.lib().orp_points_from_offsets(tab, len(lv), B, C, int(mode), _lib.ptr(out), _lib.stream_of(out))
-    _lib.check(rc, "orp_points_from_offsets")
+    _lib.call("orp_points_from_offsets", out.device, tab, len(lv), B, C, int(mode), _lib.ptr(out), _lib.stream_of(out))
     return out
 
 
@@ -48,10 +46,7 @@ class _GatherLevels(Function):
         out = torch.empty((P, C), dtype=torch.float32, device=lv[0].device)
         idx = index.to(torch.long).contiguous()
         if P:
-            with torch.cuda.device(out.device):
-                rc = _lib.lib().orp_gather_levels(tab, len(lv), B, C, _lib.ptr(idx), P, int(mode), _lib.ptr(out),
-                                                  _lib.stream_of(out))
-            _lib.check(rc, "orp_gather_levels")
+            _lib.call("orp_gather_levels", out.device, tab, len(lv), B, C, _lib.ptr(idx), P, int(mode), _lib.ptr(out), _lib.stream_of(out))
         ctx.save_for_backward(idx)
         ctx.meta = (tuple(float(s) for s in strides), int(mode), [tuple(t.shape) for t in levels], lv[0].device)
         return out
@@ -64,10 +59,8 @@ class _GatherLevels(Function):
         grads = [torch.empty(s, dtype=torch.float32, device=dev) for s in shapes]      # zero-filled by the C entry
         tab, B, C, N = _level_table(grads, strides, grads)
         go = grad_out.detach().float().contiguous()
-        with torch.cuda.device(dev):
-            rc = _lib.lib().orp_gather_levels_backward(tab, len(grads), B, C, _lib.ptr(idx), idx.numel(), mode,
-                                                       _lib.ptr(go), _lib.stream_of(go))
-        _lib.check(rc, "orp_gather_levels_backward")
+        _lib.call("orp_gather_levels_backward", dev, tab, len(grads), B, C, _lib.ptr(idx), idx.numel(), mode, _lib.ptr(go),
+                  _lib.stream_of(go))
         return (None, None, None) + tuple(grads)
 
 
@@ -101,13 +94,9 @@ def pointset_target(gt_inds, valid, gt_boxes, gt_labels, gt_offset, pos_weight=-
     counts = torch.empty((B, 2), dtype=torch.int32, device=dev) if want_counts else None
     if counts is not None:
         out['counts'] = counts
-    with torch.cuda.device(dev):
-        rc = _lib.lib().orp_pointset_target(_lib.ptr(gi), _lib.ptr(v), B, N, _lib.ptr(gb), _lib.ptr(gl), _lib.ptr(go),
-                                            _lib.ptr(prop), D, float(pos_weight), _lib.ptr(out['labels']),
-                                            _lib.ptr(out['label_weights']), _lib.ptr(out['rbbox_gt']), _lib.ptr(pp),
-                                            _lib.ptr(out['proposal_weights']), _lib.ptr(out['gt_inds']), _lib.ptr(counts),
-                                            _lib.stream_of(gi))
-    _lib.check(rc, "orp_pointset_target")
+    _lib.call("orp_pointset_target", dev, _lib.ptr(gi), _lib.ptr(v), B, N, _lib.ptr(gb), _lib.ptr(gl), _lib.ptr(go), _lib.ptr(prop), D,
+              float(pos_weight), _lib.ptr(out['labels']), _lib.ptr(out['label_weights']), _lib.ptr(out['rbbox_gt']), _lib.ptr(pp),
+              _lib.ptr(out['proposal_weights']), _lib.ptr(out['gt_inds']), _lib.ptr(counts), _lib.stream_of(gi))
     return out
 
 
@@ -137,13 +126,11 @@ class _SegmentGIoULoss(Function):
         d = denom.detach().float().reshape(nseg).contiguous()
         contrib = torch.empty((P,), dtype=torch.float32, device=dev)
         gsave = torch.empty((P, 18), dtype=torch.float32, device=dev)
-        L = _lib.lib()
-        with torch.cuda.device(dev):
-            st = _lib.stream_of(gious)
-            _lib.check(L.orp_giou_rows(_lib.ptr(gious), _lib.ptr(grad), _lib.ptr(w), _lib.ptr(sg), _lib.ptr(d), P,
-                                       float(loss_weight), _lib.ptr(contrib), _lib.ptr(gsave), st), "orp_giou_rows")
-            _lib.check(L.orp_segment_finish(_lib.ptr(contrib), None, _lib.ptr(sg), P, int(nseg), _lib.ptr(d),
-                                            float(loss_weight), 0, _lib.ptr(loss), None, st), "orp_segment_finish")
+        st = _lib.stream_of(gious)
+        _lib.call("orp_giou_rows", dev, _lib.ptr(gious), _lib.ptr(grad), _lib.ptr(w), _lib.ptr(sg), _lib.ptr(d), P, float(loss_weight),
+                  _lib.ptr(contrib), _lib.ptr(gsave), st)
+        _lib.call("orp_segment_finish", dev, _lib.ptr(contrib), None, _lib.ptr(sg), P, int(nseg), _lib.ptr(d), float(loss_weight), 0,
+                  _lib.ptr(loss), None, st)
         ctx.save_for_backward(gsave.reshape(pred.shape), sg)
         return loss
 
@@ -185,13 +172,10 @@ class _SegmentBorderLoss(Function):
         row_cnt = torch.empty((P,), dtype=torch.float32, device=dev)
         gdir = torch.empty((P, 18), dtype=torch.float32, device=dev)
         scale = torch.empty((nseg,), dtype=torch.float32, device=dev)
-        L = _lib.lib()
-        with torch.cuda.device(dev):
-            st = _lib.stream_of(p)
-            _lib.check(L.orp_border_rows(_lib.ptr(p), _lib.ptr(g), _lib.ptr(w), P, _lib.ptr(row_sum), _lib.ptr(row_cnt),
-                                         _lib.ptr(gdir), st), "orp_border_rows")
-            _lib.check(L.orp_segment_finish(_lib.ptr(row_sum), _lib.ptr(row_cnt), _lib.ptr(sg), P, int(nseg), _lib.ptr(d),
-                                            float(loss_weight), 1, _lib.ptr(loss), _lib.ptr(scale), st), "orp_segment_finish")
+        st = _lib.stream_of(p)
+        _lib.call("orp_border_rows", dev, _lib.ptr(p), _lib.ptr(g), _lib.ptr(w), P, _lib.ptr(row_sum), _lib.ptr(row_cnt), _lib.ptr(gdir), st)
+        _lib.call("orp_segment_finish", dev, _lib.ptr(row_sum), _lib.ptr(row_cnt), _lib.ptr(sg), P, int(nseg), _lib.ptr(d),
+                  float(loss_weight), 1, _lib.ptr(loss), _lib.ptr(scale), st)
         ctx.save_for_backward(gdir, scale, sg)
         ctx.shape = tuple(pts.shape)
         return loss
@@ -222,7 +206,5 @@ def outline_samples(corners, n):
         r = _ratios.get(key)
         if r is None:
             r = _ratios[key] = torch.linspace(0, 1, int(n), device=c.device)     # the reference's own ratios, built once
-        with torch.cuda.device(c.device):
-            rc = _lib.lib().orp_outline_samples(_lib.ptr(c), P, int(n), _lib.ptr(r), _lib.ptr(out), _lib.stream_of(c))
-        _lib.check(rc, "orp_outline_samples")
+        _lib.call("orp_outline_samples", c.device, _lib.ptr(c), P, int(n), _lib.ptr(r), _lib.ptr(out), _lib.stream_of(c))
     return out

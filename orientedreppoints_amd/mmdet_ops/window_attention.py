@@ -79,11 +79,8 @@ def _forward(half, keep_lse, qkv, qkv_bias, bias_table, H, W, heads, window, shi
         name, last = "orp_window_attention_h", (_lib.ptr(lse), HALF_DTYPES[dt])
     else:
         name, last = ("orp_window_attention_train", (_lib.ptr(lse),)) if keep_lse else ("orp_window_attention", ())
-    with torch.cuda.device(qkv.device):
-        rc = getattr(_lib.lib(), name)(_lib.ptr(qkv.detach()), _lib.ptr(None if qkv_bias is None else qkv_bias.detach()),
-                                       _lib.ptr(bias_table.detach()), B, H, W, heads, hd, window, shift, float(scale), _lib.ptr(out),
-                                       *last, _lib.stream_of(qkv))
-    _lib.check(rc, name)
+    _lib.call(name, qkv.device, _lib.ptr(qkv.detach()), _lib.ptr(None if qkv_bias is None else qkv_bias.detach()),
+              _lib.ptr(bias_table.detach()), B, H, W, heads, hd, window, shift, float(scale), _lib.ptr(out), *last, _lib.stream_of(qkv))
     return out, lse
 
 
@@ -103,15 +100,14 @@ def _backward(half, qkv, qkv_bias, bias_table, out, lse, grad_out, H, W, heads, 
         gb = torch.empty_like(qkv_bias) if gb is None else _shaped(gb, qkv_bias.shape, "grad_qkv_bias")
     name, last = ("orp_window_attention_backward_h", (HALF_DTYPES[dt],)) if half else ("orp_window_attention_backward", ())
     L = _lib.lib()
-    with torch.cuda.device(qkv.device):
-        if workspace is None:
+    if workspace is None:
+        with torch.cuda.device(qkv.device):                # (workspace asks whether the current device's stream is capturing)
             workspace = _lib.workspace(qkv.device, L.orp_window_attention_backward_workspace_bytes(B, H, W, heads, hd, window))
-        elif not (isinstance(workspace, torch.Tensor) and workspace.is_cuda and workspace.dtype == torch.uint8 and workspace.is_contiguous()):
-            raise TypeError("workspace must be a contiguous uint8 CUDA tensor")
-        rc = getattr(L, name)(_lib.ptr(qkv.detach()), _lib.ptr(None if qkv_bias is None else qkv_bias.detach()), _lib.ptr(bias_table.detach()),
-                              _lib.ptr(out.detach()), _lib.ptr(lse), _lib.ptr(grad_out), B, H, W, heads, hd, window, shift, float(scale),
-                              _lib.ptr(gq), _lib.ptr(gb), _lib.ptr(gt), _lib.ptr(workspace), workspace.numel(), *last, _lib.stream_of(qkv))
-    _lib.check(rc, name)
+    elif not (isinstance(workspace, torch.Tensor) and workspace.is_cuda and workspace.dtype == torch.uint8 and workspace.is_contiguous()):
+        raise TypeError("workspace must be a contiguous uint8 CUDA tensor")
+    _lib.call(name, qkv.device, _lib.ptr(qkv.detach()), _lib.ptr(None if qkv_bias is None else qkv_bias.detach()),
+              _lib.ptr(bias_table.detach()), _lib.ptr(out.detach()), _lib.ptr(lse), _lib.ptr(grad_out), B, H, W, heads, hd, window, shift,
+              float(scale), _lib.ptr(gq), _lib.ptr(gb), _lib.ptr(gt), _lib.ptr(workspace), workspace.numel(), *last, _lib.stream_of(qkv))
     return gq, gb, gt
 
 
