@@ -1067,6 +1067,40 @@ int orp_token_linear(const float* x, const void* weight_packed, const float* bia
                      int n, int act, void* stream);
 
 /* ---------------------------------------------------------------------------------------------------------
+ * nn.LayerNorm over the last axis of fp32 tokens with the layout glue beside it in the same launch (csrc/orp_token_layernorm.hip,
+ * inference): what Swin runs as a block's norm1 / norm2, as pad + cat + PatchMerging.norm, as the contiguous copy + PatchEmbed.norm
+ * and as norm<i> + permute(0, 3, 1, 2).contiguous() on the stage outputs.
+ *   y = (x - mean) * rsqrt(var + eps) * gamma + beta     per row of c floats; biased variance, eps inside the root
+ *   layout          source x                        destination y                      rows
+ *   ORP_LN_TOKENS   [batch h w][c]                  [batch h w][c]                     batch * h * w
+ *   ORP_LN_MERGE    [batch][h][w][c/4]              [batch ceil(h/2) ceil(w/2)][c]     a row is its 2 x 2 neighbourhood in the order
+ *                   (even row, even col), (odd, even), (even, odd), (odd, odd); positions past an odd h or w are zeros AND enter the statistics
+ *   ORP_LN_FROM_NCHW [batch][c][h w]                [batch h w][c]
+ *   ORP_LN_TO_NCHW  [batch h w][c]                  [batch][c][h w]
+ *   gamma, beta     [c]
+ * Arithmetic: fp32, two passes over the row held in registers (mean, then sum (x - mean)^2; mean and variance are divisions by c),
+ * ONE summation order per row that depends on c alone: a row's bits do not depend on the row count, on its place in the launch, on the
+ * tile or on the layout.  A row that holds a NaN or an infinity comes out all NaN; no other row is touched.  One launch, no workspace,
+ * no atomics, no host synchronisation: capturable.
+ * Supported (the _ok query): c % 32 == 0 in [32, 4096]; any batch, h, w >= 0 (no rows: ORP_OK, nothing launched).  ORP_EINVAL without
+ * a launch: a NULL pointer, a pointer that is not 16-byte aligned, a width the query refuses, an unknown layout, a negative extent,
+ * y == x.  ORP_ETOOBIG: 2^31 rows or more.
+ * The _plan query: lanes per row, rows per workgroup (TOKENS, MERGE) or tokens per LDS tile (the NCHW variants) and the launch's dynamic
+ * LDS bytes; 0 where the launch would refuse the shape.
+ * The _pays query: 1 where this launch was MEASURED faster than the stock span it replaces on MI355X (closed table over (tokens = output
+ * rows, c, layout), docs/notebook/round32.md; 0 for everything outside it).  The three queries answer without a device.
+ * ------------------------------------------------------------------------------------------------------- */
+#define ORP_LN_TOKENS 0
+#define ORP_LN_MERGE 1
+#define ORP_LN_FROM_NCHW 2
+#define ORP_LN_TO_NCHW 3
+int orp_token_layernorm_ok(int c);
+int orp_token_layernorm_plan(int batch, int h, int w, int c, int layout, int* lanes, int* rows, int* lds_bytes);
+int orp_token_layernorm_pays(long tokens, int c, int layout);
+int orp_token_layernorm(const float* x, const float* gamma, const float* beta, float* y, int batch, int h, int w, int c, float eps,
+                        int layout, void* stream);
+
+/* ---------------------------------------------------------------------------------------------------------
  * Fused test-time post-processing around the rotated NMS: replaces the tensor-op chains of
  * get_bboxes_single (orientedreppoints_head.py:707-779), multiclass_rnms (bbox_nms.py:93-182) and rbbox2result
  * (transforms.py:356-375) with fixed-shape, stream-ordered kernels -- no host synchronisation, hipGraph-capturable.

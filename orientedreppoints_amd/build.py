@@ -60,6 +60,7 @@ SOURCES = [
     ("orp_dcn_bwd_mfma.hip", []),
     ("orp_window_attn.hip", []),
     ("orp_token_linear.hip", []),
+    ("orp_token_layernorm.hip", []),
     ("orp_prof.hip", []),
 ]
 # every header of csrc/ and the C ABI: each object depends on all of them, and build_id() hashes them

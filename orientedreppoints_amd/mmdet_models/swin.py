@@ -15,7 +15,11 @@ on 16-bit operands, fp32 arithmetic (`SwinBlock.fuses_attention_half`; switch OR
 An eval-mode block on the fp32 inference route also runs its four linears -- `attn.qkv`, `attn.proj` with the block input as residual,
 `mlp.fc1` with the GELU, `mlp.fc2` with its residual -- and `PatchMerging` its `reduction` as bf16-pieces launches with the epilogue
 fused, each where measured faster (`SwinBlock.fuses_linears`, mmdet_ops/token_linear.py; switch ORP_SWIN_LINEAR_FUSE /
-`fuse_token_linear`); the LayerNorms stay stock.
+`fuse_token_linear`).  On the same fp32 inference route (no gradients, no autocast, contiguous fp32 device tensors) every LayerNorm is
+one launch of `token_layernorm` together with the copies around it -- a block's `norm1` / `norm2`, pad + cat + `PatchMerging.norm` as a
+gather, the contiguous copy in front of `PatchEmbed.norm`, and `norm<i>` with the permuting copy behind it --, each where measured
+faster (`_norm`, mmdet_ops/token_norm.py; switch ORP_SWIN_NORM_FUSE / `fuse_token_norm`, `force_token_norm` for every supported shape).
+That switch ships OFF: the eager detector, which waits on the host, did not gain (docs/notebook/round32.md); the captured one does.
 
 Parameter / buffer names are the released checkpoints' (`swin_tiny_patch4_window7_224.pth`): patch_embed.{proj,norm},
 layers.<i>.blocks.<j>.{norm1,attn.{relative_position_bias_table,relative_position_index,qkv,proj},norm2,mlp.{fc1,fc2}},
@@ -27,6 +31,7 @@ import torch.utils.checkpoint as cp
 
 from .. import switches
 from ..mmdet_ops.token_linear import token_linear, token_linear_ok, token_linear_routed
+from ..mmdet_ops.token_norm import token_layernorm_if_routed
 from ..mmdet_ops.window_attention import (window_attention, window_attention_half, window_attention_half_ok, window_attention_ok,
                                           window_attention_train, window_attention_train_half, window_attention_train_half_ok,
                                           window_attention_train_ok)
@@ -44,6 +49,29 @@ def _linear(owner, linear, x, act=None, residual=None):
     if act == 'gelu':
         y = F.gelu(y)
     return y if residual is None else residual + y
+
+
+def _norm(owner, ln, x, layout='tokens', hw=None):
+    """the LayerNorm `ln` with the copies beside it, for a module whose norms go through `token_layernorm`: one launch where the switch is
+    on and the routing table says so (`owner.force_token_norm`, tests: at every shape the kernel takes), else the lines as the modules
+    always ran them, with their bits.  'tokens': ln(x).  'merge': x [B, H, W, C] -> pad, cat of the 2 x 2 neighbourhood, ln: [B, L/4, 4C].
+    'from_nchw': x [B, C, L] -> ln(x.transpose(1, 2)): [B, L, C].  'to_nchw': x [B, L, C] -> ln(x) as contiguous [B, C, H, W]."""
+    if switches.of(owner, 'fuse_token_norm', 'SWIN_NORM_FUSE'):
+        y = token_layernorm_if_routed(x, ln, layout, hw, force=bool(getattr(owner, 'force_token_norm', False)))
+        if y is not None:
+            return y
+    if layout == 'merge':
+        B, H, W, C = x.shape
+        if H % 2 or W % 2:
+            x = F.pad(x, (0, 0, 0, W % 2, 0, H % 2))
+        # channel order of the released weights: (even row, even col), (odd, even), (even, odd), (odd, odd)
+        x = torch.cat([x[:, 0::2, 0::2], x[:, 1::2, 0::2], x[:, 0::2, 1::2], x[:, 1::2, 1::2]], -1)
+        return ln(x.view(B, -1, 4 * C))
+    if layout == 'from_nchw':
+        return ln(x.transpose(1, 2))
+    if layout == 'to_nchw':
+        return ln(x).view(-1, hw[0], hw[1], x.size(-1)).permute(0, 3, 1, 2).contiguous()
+    return ln(x)
 
 
 class StochasticDepth(nn.Module):
@@ -122,6 +150,7 @@ class SwinBlock(nn.Module):
         self.drop_path = StochasticDepth(drop_path) if drop_path > 0. else nn.Identity()
         self.norm2 = nn.LayerNorm(dim)
         self.mlp = Mlp(dim, int(dim * mlp_ratio), drop)
+        self.fuse_token_norm, self.force_token_norm = None, False     # (`_norm`: None = the switch)
 
     def fuses_attention(self, x):
         """inference on fp32 device tokens: everything between attn.qkv and attn.proj as one kernel (mmdet_ops/window_attention.py)"""
@@ -156,20 +185,20 @@ class SwinBlock(nn.Module):
     def forward(self, x, H, W, shift_mask):
         if self.fuses_linears(x):
             a, m = self.attn, self.mlp
-            y = window_attention(_linear(self, a.qkv, self.norm1(x)), a.qkv.bias, a.relative_position_bias_table, H, W, a.num_heads,
+            y = window_attention(_linear(self, a.qkv, _norm(self, self.norm1, x)), a.qkv.bias, a.relative_position_bias_table, H, W, a.num_heads,
                                  self.ws, self.shift, a.scale)
             x = _linear(self, a.proj, y, None, x)
-            return _linear(self, m.fc2, _linear(self, m.fc1, self.norm2(x), 'gelu'), None, x)
+            return _linear(self, m.fc2, _linear(self, m.fc1, _norm(self, self.norm2, x), 'gelu'), None, x)
         fused = self.fused_attention(x)
         if fused is not None:
             # qkv and proj are per-token linears: both run on the un-padded, un-rolled tokens, the kernel does the index arithmetic
             a = self.attn
-            y = fused(a.qkv(self.norm1(x)), a.qkv.bias, a.relative_position_bias_table, H, W, a.num_heads, self.ws, self.shift, a.scale)
+            y = fused(a.qkv(_norm(self, self.norm1, x)), a.qkv.bias, a.relative_position_bias_table, H, W, a.num_heads, self.ws, self.shift, a.scale)
             x = x + self.drop_path(a.proj_drop(a.proj(y)))
-            return x + self.drop_path(self.mlp(self.norm2(x)))
+            return x + self.drop_path(self.mlp(_norm(self, self.norm2, x)))
         B, L, C = x.shape
         ws = self.ws
-        y = self.norm1(x).view(B, H, W, C)
+        y = _norm(self, self.norm1, x).view(B, H, W, C)
         pr, pb = (ws - W % ws) % ws, (ws - H % ws) % ws                        # pad to whole windows (bottom / right)
         if pr or pb:
             y = F.pad(y, (0, 0, 0, pr, 0, pb))
@@ -183,7 +212,7 @@ class SwinBlock(nn.Module):
         if pr or pb:
             y = y[:, :H, :W, :]
         x = x + self.drop_path(y.reshape(B, L, C))
-        return x + self.drop_path(self.mlp(self.norm2(x)))
+        return x + self.drop_path(self.mlp(_norm(self, self.norm2, x)))
 
 
 class PatchMerging(nn.Module):
@@ -193,15 +222,11 @@ class PatchMerging(nn.Module):
         super().__init__()
         self.reduction = nn.Linear(4 * dim, 2 * dim, bias=False)
         self.norm = nn.LayerNorm(4 * dim)
+        self.fuse_token_norm, self.force_token_norm = None, False
 
     def forward(self, x, H, W):
         B, L, C = x.shape
-        x = x.view(B, H, W, C)
-        if H % 2 or W % 2:
-            x = F.pad(x, (0, 0, 0, W % 2, 0, H % 2))
-        # channel order of the released weights: (even row, even col), (odd, even), (even, odd), (odd, odd)
-        x = torch.cat([x[:, 0::2, 0::2], x[:, 1::2, 0::2], x[:, 0::2, 1::2], x[:, 1::2, 1::2]], -1)
-        x = self.norm(x.view(B, -1, 4 * C))
+        x = _norm(self, self.norm, x.view(B, H, W, C), 'merge')       # pad, cat of the 2 x 2 neighbourhood, norm: [B, L/4, 4C]
         if not self.training and switches.of(self, 'fuse_token_linear', 'SWIN_LINEAR_FUSE'):
             return _linear(self, self.reduction, x)       # (fp32 inference on CUDA tokens, where routed; else the module as written)
         return self.reduction(x)
@@ -257,6 +282,7 @@ class PatchEmbed(nn.Module):
         self.patch_size = patch_size
         self.proj = nn.Conv2d(in_chans, embed_dim, kernel_size=patch_size, stride=patch_size)
         self.norm = nn.LayerNorm(embed_dim) if norm else None
+        self.fuse_token_norm, self.force_token_norm = None, False
 
     def forward(self, x):
         p = self.patch_size
@@ -266,7 +292,7 @@ class PatchEmbed(nn.Module):
         x = self.proj(x)                                                       # [B, C, Wh, Ww]
         if self.norm is not None:
             Wh, Ww = x.shape[2:]
-            x = self.norm(x.flatten(2).transpose(1, 2)).transpose(1, 2).reshape(x.size(0), -1, Wh, Ww)
+            x = _norm(self, self.norm, x.flatten(2), 'from_nchw').transpose(1, 2).reshape(x.size(0), -1, Wh, Ww)
         return x
 
 
@@ -295,6 +321,7 @@ class SwinTransformer(nn.Module):
         self.num_features = [embed_dim * 2 ** i for i in range(self.num_layers)]
         for i in self.out_indices:
             self.add_module('norm%d' % i, nn.LayerNorm(self.num_features[i]))
+        self.fuse_token_norm, self.force_token_norm = None, False     # (the output norms)
         self._freeze_stages()
 
     def _freeze_stages(self):
@@ -347,8 +374,7 @@ class SwinTransformer(nn.Module):
         for i, layer in enumerate(self.layers):
             out, x, Hn, Wn = layer(x, H, W)
             if i in self.out_indices:
-                y = getattr(self, 'norm%d' % i)(out)
-                outs.append(y.view(-1, H, W, self.num_features[i]).permute(0, 3, 1, 2).contiguous())
+                outs.append(_norm(self, getattr(self, 'norm%d' % i), out, 'to_nchw', (H, W)))
             H, W = Hn, Wn
         return tuple(outs)
 

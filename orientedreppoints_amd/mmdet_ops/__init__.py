@@ -20,3 +20,4 @@ from .window_attention import (window_attention_backward, window_attention_forwa
 from .window_attention import (window_attention_backward_half, window_attention_forward_lse_half, window_attention_half,  # noqa: F401
                                window_attention_half_ok, window_attention_train_half, window_attention_train_half_ok)
 from .token_linear import token_linear, token_linear_ok, token_linear_reference, token_linear_routed  # noqa: F401
+from .token_norm import token_layernorm, token_layernorm_ok, token_layernorm_reference, token_layernorm_routed  # noqa: F401

@@ -32,6 +32,7 @@ SWIN_ATTN_FUSE = _on('ORP_SWIN_ATTN_FUSE')    # Swin inference: pad / roll / win
 SWIN_ATTN_TRAIN_FUSE = _on('ORP_SWIN_ATTN_TRAIN_FUSE')  # Swin training: the same between attn.qkv and attn.proj as one fp32 forward kernel that keeps the rows' log-sum-exp, and one backward call (block.fuse_window_attention_train overrides)
 SWIN_ATTN_HALF_FUSE = _on('ORP_SWIN_ATTN_HALF_FUSE')  # Swin under fp16 / bf16 autocast, inference and training: the same span on 16-bit operands with fp32 arithmetic, one forward kernel (+ one backward call) (block.fuse_window_attention_half overrides)
 SWIN_LINEAR_FUSE = _on('ORP_SWIN_LINEAR_FUSE')  # Swin inference, eval-mode blocks on the fused fp32 attention route: attn.qkv, attn.proj (+ residual), mlp.fc1 (+ GELU), mlp.fc2 (+ residual) and PatchMerging.reduction as bf16-pieces launches with the epilogue fused, each where measured faster than the library's GEMM and its GELU / addition kernels (block.fuse_token_linear / downsample.fuse_token_linear override; force_token_linear routes every supported shape)
+SWIN_NORM_FUSE = _on('ORP_SWIN_NORM_FUSE', '0')  # (ships OFF: docs/notebook/round32.md) Swin inference (fp32 device tensors, no gradients, no autocast): every LayerNorm with the copies beside it as one launch -- norm1 / norm2, pad + cat + PatchMerging.norm, the contiguous copy + PatchEmbed.norm, norm<i> + the permuting copy --, each where measured faster than the framework's kernels (fuse_token_norm on the block, the merge, the embedding and the backbone overrides; force_token_norm routes every supported shape)
 FPN_TOPDOWN_FUSE = _on('ORP_FPN_TOPDOWN_FUSE')  # FPN lateral GroupNorm + top-down sum + transposition as one pass (neck.fuse_topdown overrides)
 TRAIN_SPLIT = _on('ORP_TRAIN_SPLIT')          # training: tower / FPN convolutions as conv_split_train nodes
 DETERMINISTIC = _on('ORP_DETERMINISTIC', '0')  # training: fixed-order DeformConv backward for both branches (head.deterministic_backward overrides)
